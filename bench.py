@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """bench.py -- prove() proofs/s and G1 MSM scalar-muls/s on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W   the headline alone: setup, W warm-up proofs, K timed proofs, the line
+  python bench.py ... --full                      every leg described below in the same line
+  python bench.py ... --dump-outputs DIR          also DIR/proof_words.npy: the last timed proof's bytes as uint32 words (float64)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W     (the driver's form)
   python bench.py --gpus N ...            without RANK in the environment and N > 1: starts those N ranks itself as child processes
                                           (before this process touches the GPU), relays rank 0's JSON line and exits with their code
@@ -13,7 +15,7 @@ A "step" is one pass of the hot path over one batch of synthetic input: one full
 generator at scale), circuit + assignment + SRS already resident in HBM when the timed region starts.
 The K steps are streamed -- one host thread, two prover handles per GPU used in turn (sonic_prover_submit /
 sonic_prover_collect), nothing synchronised between steps, all K proofs complete (and byte-identical to the
-one-at-a-time proofs) at the closing barrier; `value` = K / that time.  Beside it, in the same line: the strictly sequential
+one-at-a-time proofs) at the closing barrier; `value` = K / that time.  Beside it, in the same line (--full): the strictly sequential
 rate (`sequential`), the same stream WITHOUT the per-circuit precomputation (`resident_unprepared`) and the reference's own call
 shape -- circuit, assignment and transcript handed over as host buffers per call (`one_shot`).  Round 6: BASELINE configs[1]
 (`config2`: n = 2^14, d = 2^17), configs[4] (`config5`: 64 proofs at n = 2^16 through sonic_prove_batch) and the reference's own criterion
@@ -77,7 +79,7 @@ def load_profile_json(name):
 
 
 def rocprof_avg_ms(kernel):
-    """average duration of `kernel` in the committed rocprofv3 --kernel-trace --stats summary of `bench.py --msm-only --msm-lanes 0`"""
+    """average duration of `kernel` in the committed rocprofv3 --kernel-trace --stats summary of `bench.py --full --msm-only --msm-lanes 0`"""
     cands = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_msm_only_kernel_stats.csv")))
     if not cands:
         return None, None
@@ -151,7 +153,18 @@ def parse_args(argv=None):
     ap.add_argument("--no-configs", action="store_true", help="skip BASELINE configs[1] (n = 2^14) and configs[4] (64 proofs at n = 2^16) and the reference's criterion shape")
     ap.add_argument("--in-process", action="store_true", help="N > 1 from ONE process through the C ABI (no torch.distributed)")
     ap.add_argument("--devices", default="", help="(--in-process) comma-separated ordinals instead of 0..N-1; an ordinal may repeat (tests on one GPU)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true", help="every leg beside the headline (sequential, unprepared, one-shot and C-ABI batch rates, NTT and MSM legs, "
+                                                        "rooflines, sensitivities, BASELINE configs[1] / configs[4], the criterion shape, the strong-scaling and "
+                                                        "north_star legs, the CPU baseline); without it: setup, warm-up, the timed steps, the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last step computed (its proof) as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if (args.msm_only or args.msm_strong) and not args.full:
+        ap.error("--msm-only / --msm-strong pick legs of the --full run: add --full")
+    if args.dump_outputs and args.in_process:
+        ap.error("--dump-outputs writes the proofs of the streamed prove() path, which --in-process does not run")
+    return args
 
 
 def spawn_ranks(args, argv):
@@ -365,7 +378,7 @@ class Bench:
             log(f"  kernels total {tot:.1f} ms of {dt * 1e3:.1f} ms wall ({K} proofs)")
         # strictly sequential (rank 0): the same K proofs, one finished prove() call after the other, on one handle
         sequential = None
-        if self.rank == 0 and K >= 1 and self.depth > 1:
+        if self.rank == 0 and K >= 1 and self.depth > 1 and a.full:
             L.sonic_device_sync()
             t0 = time.perf_counter()
             for i in range(K):
@@ -377,6 +390,46 @@ class Bench:
         for px in pipe.provers[1:]:
             px.close()
         return sequential
+
+    # ---- what the timed path computed in its last step (--dump-outputs; rank 0) ----
+    # The caller of prove() receives the proof's canonical bytes (include/sonic_hip.h): written as their little-endian uint32 words in
+    # float64, which holds every word exactly, so that two builds can be compared word for word.
+    def dump_outputs(self, out_dir):
+        os.makedirs(out_dir, exist_ok=True)
+        words = np.frombuffer(self.proof, dtype="<u4").astype(np.float64)
+        np.save(os.path.join(out_dir, "proof_words.npy"), words)
+        log(f"dump-outputs: {out_dir}/proof_words.npy ({words.size} words of the last step's {len(self.proof)}-byte proof)")
+
+    def headline(self, t_main):
+        """the fields of the line that the headline alone makes (a plain run prints nothing else)"""
+        a, n, Q, d = self.args, self.n, self.Q, self.d
+        workload = f"prove(): rndCircuit n=2^{a.log2n}, Q={Q}, SRS d=2^{a.log2n + 3} (d=8n >= 7n, Protocol.hs:54)"
+        if a.full:
+            workload += f"; G1 MSM N=2^{a.msm_log2} per GPU; one G1 MSM N=2^{self.strong_n.bit_length() - 1} over all GPUs"
+        return {
+            "metric": "prove() proofs/sec",
+            "value": round(self.proofs_per_s, 4),
+            "unit": "proofs/s",
+            "n_gpus": self.world,
+            "steps": self.K,
+            "warmup": self.W,
+            "ms_per_step": round(1e3 * self.dt_prove / self.K, 2),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u32 limbs (Fq 12x32, Fr 8x32 Montgomery)",
+            "data": "synthetic",
+            "config": {"workload": workload, "n": n, "Q": Q, "d": d,
+                       "sharding": "proof-per-rank (value)" + ("; MSM term-range-sharded (msm, weak); one MSM bucket-range-sharded (msm_strong, strong)" if a.full else ""),
+                       "streaming": "K proofs streamed by one host thread through 2 prover handles per GPU (submit / collect), circuit + assignment resident, constraint rows "
+                                    "committed once per circuit (sonic_prover_prepare); `sequential`, `resident_unprepared` and `one_shot` are beside it (--full)",
+                       "process_group": (f"{a.backend}, {self.world} rank(s)" if self.pg else "none (plain single-process run)"),
+                       "legs": "all (--full)" if a.full else "headline only (the other legs: --full)"},
+            "proof_bytes": len(self.proof),
+            "status": "failed legs: " + ", ".join(sorted(self.leg_errors)) if self.leg_errors else "ok",
+            "leg_errors": self.leg_errors or None,
+            "wall_s": round(time.time() - t_main, 1),       # the whole run, SRS generation (and with --full the CPU legs) included
+        }
 
     # ---- rank 0: the same proofs without the per-circuit precomputation, and as the reference's one-shot call ----
     # `value` streams over handles that hold circuit and assignment and have committed the constraint rows once (sonic_prover_prepare).
@@ -807,7 +860,7 @@ class Bench:
                     "avg_launch_ms": round(accum_ms, 4), "algorithmic_bytes_per_launch": alg_bytes,
                     "rocprof": {"avg_launch_ms": None if rp_ms is None else round(rp_ms, 4), "summary": rp_src,
                                 "frac": None if not rp_ms else round(alg_bytes / (rp_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                                "note": "rocprofv3 --kernel-trace --stats of `bench.py --msm-only --msm-lanes 0 --no-cpu --steps 5 --warmup 1` on another box of the pool "
+                                "note": "rocprofv3 --kernel-trace --stats of `bench.py --full --msm-only --msm-lanes 0 --no-cpu --steps 5 --warmup 1` in a separate run "
                                         "(same launches, nothing else); run-to-run and box-to-box spread of this kernel is a few per cent"},
                     "note": "modular-integer kernel: the binding roof is integer multiply issue, see int_roofline"}
         # integer roof of the same kernel: additions x MADs per addition against the chip's v_mad_u64_u32 issue rate; counts and
@@ -877,6 +930,8 @@ def main(argv=None):
     args = parse_args(argv)
     b = Bench(args, argv)
     rank, world, K, W = b.rank, b.world, b.K, b.W
+    if not args.full and not args.in_process:
+        return plain_run(b, t_main)
 
     # ---------------- BASELINE configs[1] and configs[4], and the reference's own criterion shape (rank 0; round 6) ----------------
     # First, on a process that holds nothing else yet: each leg makes its own SRS and handles and frees them.  (Measured after the headline's
@@ -905,6 +960,8 @@ def main(argv=None):
     if b.do_prove:
         sequential = b.leg_prove()
     b.barrier()
+    if b.do_prove and rank == 0 and args.dump_outputs:
+        b.dump_outputs(args.dump_outputs)
 
     resident_unprepared = one_shot = batch_c_abi = None
     small = rank == 0 and b.do_prove and not args.prove_only and not args.kernel_table
@@ -969,26 +1026,8 @@ def main(argv=None):
         cpu_baseline = b.rank0_leg("cpu_baseline", lambda: cpu_baseline_leg(args, b.sonic_amd, b.srs, b.x, b.alpha, b.circ, b.transcripts, b.proof, b.sc, b.n, b.Q, b.d, b.msm_n,
                                                                              K, W, b.big_circuit, b.rand_fr_array))
 
-    n, Q, d = b.n, b.Q, b.d
-    line = {
-        "metric": "prove() proofs/sec",
-        "value": round(b.proofs_per_s, 4),
-        "unit": "proofs/s",
-        "n_gpus": world,
-        "steps": K,
-        "warmup": W,
-        "ms_per_step": round(1e3 * b.dt_prove / K, 2),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u32 limbs (Fq 12x32, Fr 8x32 Montgomery)",
-        "data": "synthetic",
-        "config": {"workload": f"prove(): rndCircuit n=2^{args.log2n}, Q={Q}, SRS d=2^{args.log2n + 3} (d=8n >= 7n, Protocol.hs:54); "
-                               f"G1 MSM N=2^{args.msm_log2} per GPU; one G1 MSM N=2^{b.strong_n.bit_length() - 1} over all GPUs", "n": n, "Q": Q, "d": d,
-                   "sharding": "proof-per-rank (value); MSM term-range-sharded (msm, weak); one MSM bucket-range-sharded (msm_strong, strong)",
-                   "streaming": "K proofs streamed by one host thread through 2 prover handles per GPU (submit / collect), circuit + assignment resident, constraint rows "
-                                "committed once per circuit (sonic_prover_prepare); `sequential`, `resident_unprepared` and `one_shot` are beside it",
-                   "process_group": (f"{args.backend}, {world} rank(s)" if b.pg else "none (plain single-process run)")},
+    line = b.headline(t_main)
+    line.update({
         "msm": msm,
         "msm_strong": msm_strong,
         "msm_protocol_shaped": msm_protocol,
@@ -1000,7 +1039,6 @@ def main(argv=None):
         "cpu_baseline": cpu_baseline,
         "prove_strong": prove_strong,
         "north_star": north_star,
-        "proof_bytes": len(b.proof),
         "sequential": sequential,
         "resident_unprepared": resident_unprepared,
         "one_shot": one_shot,
@@ -1010,15 +1048,29 @@ def main(argv=None):
         "config5": config5,
         "criterion_shape": criterion,
         "in_process": in_process,
-        "status": "failed legs: " + ", ".join(sorted(b.leg_errors)) if b.leg_errors else "ok",
-        "leg_errors": b.leg_errors or None,
-        "wall_s": round(time.time() - t_main, 1),       # the whole run, SRS generation and the CPU legs included
-    }
+    })
+    for k in ("status", "leg_errors", "wall_s"):          # (last in the line, as before)
+        line[k] = line.pop(k)
     print(json.dumps(line), flush=True)
     if b.pg:
         b.dist.destroy_process_group()
     if b.leg_errors:
         sys.exit(3)
+
+
+def plain_run(b, t_main):
+    """`bench.py --gpus N --steps K --warmup W` without --full: what the headline needs and nothing else -- setup (SRS, circuit resident,
+    rows committed), the warm-up, the K timed streamed proofs, the outputs of the last step (--dump-outputs) and the line"""
+    args = b.args
+    b.setup()
+    b.leg_prove()
+    b.barrier()
+    if b.rank == 0:
+        if args.dump_outputs:
+            b.dump_outputs(args.dump_outputs)
+        print(json.dumps(b.headline(t_main)), flush=True)
+    if b.pg:
+        b.dist.destroy_process_group()
 
 
 # ======================================================================================================================================

@@ -106,3 +106,19 @@ def test_dense_circuit_is_satisfied(ref):
 def test_effective_cores_respects_quota(monkeypatch, tmp_path):
     n = bench.effective_cores()
     assert 1 <= n <= (os.cpu_count() or 1)
+
+
+def test_plain_run_options():
+    """a plain run is the headline alone; the other legs are behind --full; --steps is the number of timed steps and must be >= 1"""
+    import pytest
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert not a.full and a.steps == 7 and a.warmup == 3 and a.dump_outputs == ""
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--warmup", "-1"], ["--msm-only"], ["--msm-strong"], ["--in-process", "--gpus", "2", "--dump-outputs", "out"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+    assert bench.parse_args(["--full", "--msm-only"]).msm_only
+    import inspect
+    src = inspect.getsource(bench.plain_run)
+    assert "setup" in src and "leg_prove" in src and "leg_msm" not in src and "cpu_baseline" not in src

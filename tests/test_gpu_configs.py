@@ -355,7 +355,7 @@ def test_bench_under_the_driver_launch_line_one_rank_rccl():
     all-gathered over RCCL on device tensors and the strong-scaling leg runs"""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--log2n", "12", "--msm-log2", "14", "--no-cpu", "--strong-log2n", "13"]
+           "--log2n", "12", "--msm-log2", "14", "--no-cpu", "--strong-log2n", "13", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -402,6 +402,41 @@ def test_bench_under_the_driver_launch_line_one_rank_rccl():
     assert abs(e["ms_per_share"] - e["ms_per_share_kernels_only"] - e["exchange_model"]["ms"]) < 2e-3      # the modelled exchange is INSIDE the figure
     assert e["speedup_vs_single"] <= e["speedup_without_the_exchange"]
     assert ps["emulated_shares"]["allgather_model_ms"] > 0 and ps["emulated_shares"]["ranks_that_repeat_the_t_product"] >= 1
+
+
+def test_plain_bench_run_and_its_outputs(orc, tmp_path):
+    """bench.py without --full: the headline alone, K timed steps, and --dump-outputs writes the last step's proof -- the same words as
+    the --full run's and the oracle's proof of the bench's own inputs (keys from seed 0, circuit seed 1000, transcripts seed 77)"""
+    K, W, lg, Q = 3, 1, 10, 2
+    small = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W), "--log2n", str(lg)]
+    out = subprocess.run(small + ["--dump-outputs", str(tmp_path / "plain")], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j["metric"] == "prove() proofs/sec" and j["unit"] == "proofs/s" and j["higher_is_better"] is True and j["status"] == "ok"
+    assert j["steps"] == K and j["warmup"] == W and j["ms_per_step"] > 0 and abs(1e3 / j["ms_per_step"] - j["value"]) / j["value"] < 0.01
+    assert "msm" not in j and "sequential" not in j and "cpu_baseline" not in j
+    words = np.load(tmp_path / "plain" / "proof_words.npy")
+    assert words.dtype == np.float64 and words.size * 4 == j["proof_bytes"] == (7 + 4 * Q) * 96 + (5 + 2 * Q) * 32
+    out = subprocess.run(small + ["--full", "--no-cpu", "--no-configs", "--no-sensitivities", "--strong-log2n", "0", "--msm-log2", "12", "--msm-strong-log2", "12",
+                                  "--emulate-world", "0", "--dump-outputs", str(tmp_path / "full")], cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-3000:]
+    jf = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+    assert jf["sequential"]["same_bytes_as_streamed"] is True and jf["msm"]["value"] > 0
+    assert np.array_equal(np.load(tmp_path / "full" / "proof_words.npy"), words)
+    # the bench's inputs, rebuilt here: the last timed step proves transcript W + K - 1
+    n, d = 1 << lg, 8 << lg
+    g = np.random.default_rng(0)
+    x = int.from_bytes(rand_fr_array(g, 1)[0].tobytes(), "little") | 1
+    alpha = int.from_bytes(rand_fr_array(g, 1)[0].tobytes(), "little") | 1
+    g = np.random.default_rng(77)
+    trs = [rand_fr_array(g, 8 + 2 * Q) for _ in range(K + W)]
+    tr = trs[W + K - 1]
+    tr[:, 0] |= 1
+    c = big_circuit(1000, n, Q)
+    want = orc.prove(orc.SRS(d, x, alpha, threads=NCPU), n, Q, c["wL"], c["wR"], c["wO"], c["cs"], c["aL"], c["aR"], c["aO"], tr, True)
+    assert words.astype(np.uint32).tobytes() == want
 
 
 _NTT_ALT = r"""

@@ -163,7 +163,7 @@ def test_bench_two_ranks_one_gpu():
     """the driver's N = 2 launch line, small sizes, gloo: one JSON line from rank 0 with whole-job values"""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2",
-           "--warmup", "1", "--log2n", "10", "--msm-log2", "12", "--no-cpu", "--strong-log2n", "12"]
+           "--warmup", "1", "--log2n", "10", "--msm-log2", "12", "--no-cpu", "--strong-log2n", "12", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -189,7 +189,8 @@ def test_bench_starts_its_own_ranks_and_never_mislabels():
     non-zero status instead of measuring one rank under the label N; the in-process form (one process, the C ABI, a device list)"""
     import torch
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    small = ["--steps", "2", "--warmup", "1", "--log2n", "10", "--msm-log2", "12", "--no-cpu", "--strong-log2n", "11", "--msm-strong-log2", "13", "--no-sensitivities"]
+    small = ["--steps", "2", "--warmup", "1", "--log2n", "10", "--msm-log2", "12", "--no-cpu", "--strong-log2n", "11", "--msm-strong-log2", "13", "--no-sensitivities",
+             "--full"]
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo"] + small, cwd=ROOT, capture_output=True, text=True,
                          timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-2000:]

@@ -5,7 +5,7 @@ LGS=${1:-"14 16"}
 STEPS=${2:-30}
 run() {  # label, log2n, env...
   local label=$1 lg=$2; shift 2
-  env "$@" python3 bench.py --log2n $lg --steps $STEPS --warmup 4 --no-cpu --prove-only --strong-log2n 0 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('n=2^$lg  %-34s streamed %6.2f  sequential %6.2f' % ('$label', d['ms_per_step'], d['sequential']['ms_per_proof']))"
+  env "$@" python3 bench.py --full --log2n $lg --steps $STEPS --warmup 4 --no-cpu --prove-only --strong-log2n 0 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('n=2^$lg  %-34s streamed %6.2f  sequential %6.2f' % ('$label', d['ms_per_step'], d['sequential']['ms_per_proof']))"
 }
 for rep in 1 2; do
 for lg in $LGS; do

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Turns the two rocprofv3 --pmc passes of `bench.py --msm-only` (FETCH_SIZE, WRITE_SIZE; one counter per pass, as
+"""Turns the two rocprofv3 --pmc passes of `bench.py --full --msm-only` (FETCH_SIZE, WRITE_SIZE; one counter per pass, as
 MI355X_MICROARCH.md's HBM section prescribes) into profiles/<round>_pmc_msm.json: HBM bytes per launch of every MSM kernel.
 
     python tools/pmc_summary.py <FETCH_SIZE_counter_collection.csv> <WRITE_SIZE_counter_collection.csv> <msm_n> <c> <W> <sets> > out.json
@@ -25,7 +25,7 @@ def per_kernel(path, counter):
 def main():
     fetch, write = per_kernel(sys.argv[1], "FETCH_SIZE"), per_kernel(sys.argv[2], "WRITE_SIZE")
     msm_n, c, W, sets = (int(x) for x in sys.argv[3:7])
-    out = {"command": "rocprofv3 --pmc FETCH_SIZE (then WRITE_SIZE) --output-format csv -- python3 bench.py --msm-only --msm-lanes 0 --no-cpu --steps 3 "
+    out = {"command": "rocprofv3 --pmc FETCH_SIZE (then WRITE_SIZE) --output-format csv -- python3 bench.py --full --msm-only --msm-lanes 0 --no-cpu --steps 3 "
                       "--warmup 1  (one counter per pass; values = mean over the launches of the 3 timed MSMs)",
            "msm_n": msm_n, "plan": {"window_bits": c, "windows": W, "bucket_sets": sets},
            "method": "MI355X_MICROARCH.md HBM section: FETCH_SIZE/WRITE_SIZE are in KB; on gfx950 FETCH_SIZE counts 128-B requests "
