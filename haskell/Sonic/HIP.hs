@@ -49,10 +49,11 @@ module Sonic.HIP
   , commitPoly, openPoly, pcV
     -- * Sonic.Protocol
   , prove, proveWithTranscript, verify, decodeProof, encodeProof
+  , proveWithTranscriptDense, verifyDense, fsCircuitDigest, verifyFs
     -- * Sonic.Signature
   , hscProve, hscVerify, decodeHscProof, encodeHscProof
     -- * resident handles, many GPUs
-  , Prover, newProver, prepare, setAssignment, proveWith, submit, collect
+  , Prover, newProver, newProverDense, prepare, setAssignment, proveWith, submit, collect
   , proveShared, proveBatch, deviceCount
   ) where
 
@@ -107,12 +108,18 @@ foreign import ccall safe   "sonic_pc_v"              c_pc_v             :: Ptr 
 foreign import ccall unsafe "sonic_proof_size"        c_proof_size       :: Int64 -> IO CSize
 foreign import ccall safe   "sonic_prove"             c_prove            :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_verify"            c_verify           :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> IO CInt
+-- gate weights as CSR (ABI 7): the same calls over the non-zero entries only
+foreign import ccall safe   "sonic_prove_csr"         c_prove_csr        :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_verify_csr"        c_verify_csr       :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> IO CInt
+foreign import ccall safe   "sonic_fs_circuit_digest_csr" c_fs_digest_csr :: Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_verify_fs_csr"     c_verify_fs_csr    :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> IO CInt
 
 foreign import ccall unsafe "sonic_hsc_proof_size"    c_hsc_proof_size   :: Int64 -> IO CSize
 foreign import ccall safe   "sonic_hsc_prove_poly"    c_hsc_prove_poly   :: Ptr SrsHandle -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_hsc_verify_poly"   c_hsc_verify_poly  :: Ptr SrsHandle -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> IO CInt
 
 foreign import ccall safe   "sonic_prover_new"            c_prover_new     :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr (Ptr ProverHandle) -> IO CInt
+foreign import ccall safe   "sonic_prover_new_csr"        c_prover_new_csr :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr (Ptr ProverHandle) -> IO CInt
 foreign import ccall safe   "&sonic_prover_free"          p_prover_free    :: FunPtr (Ptr ProverHandle -> IO ())
 foreign import ccall safe   "sonic_prover_prepare"        c_prover_prepare :: Ptr ProverHandle -> IO CInt
 foreign import ccall safe   "sonic_prover_set_assignment" c_prover_set     :: Ptr ProverHandle -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> IO CInt
@@ -138,7 +145,7 @@ check 4 = lastError >>= \m -> panic ("fromJust: " <> m)             -- inexact d
 check c = lastError >>= \m -> panic ("libsonic_hip status " <> show c <> ": " <> m)
 
 abiExpected :: CInt
-abiExpected = 6
+abiExpected = 7
 
 -- every entry into the library goes through here once: the header this module was written against
 libraryReady :: ()
@@ -392,7 +399,7 @@ encodeProof Proof{..} = BS.concat
 -- ---------------------------------------------------------------------------------------------------------------------
 -- Sonic.Protocol
 -- ---------------------------------------------------------------------------------------------------------------------
--- dense Q x n row-major weights, as include/sonic_hip.h takes them
+-- dense Q x n row-major weights, as include/sonic_hip.h takes them (the *Dense functions)
 withCircuit :: ArithCircuit Fr -> (Int64 -> Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> IO a) -> IO a
 withCircuit ArithCircuit{..} f =
   let GateWeights{..} = weights
@@ -400,6 +407,22 @@ withCircuit ArithCircuit{..} f =
       n = case wL of { (row : _) -> length row; [] -> 0 }
   in withFrs (concat wL) $ \pwl -> withFrs (concat wR) $ \pwr -> withFrs (concat wO) $ \pwo -> withFrs cs $ \pcs ->
        f (fromIntegral n) (fromIntegral q) pwl pwr pwo pcs
+
+-- the same weights as ONE CSR of 3Q rows (include/sonic_hip.h, "gate weights as CSR"): wL's rows, then wR's, then wO's, each walked once
+-- with its zeros dropped -- the reference's circuits are lists of mostly-zero rows (Constraints.hs:34-53), and the library's cost of
+-- the circuit follows the entries instead of Q x n
+withCircuitCsr :: ArithCircuit Fr -> (Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> IO a) -> IO a
+withCircuitCsr ArithCircuit{..} f =
+  let GateWeights{..} = weights
+      q = length wL
+      n = case wL of { (row : _) -> length row; [] -> 0 }
+      rows = [ [ (i, c) | (i, c) <- zip [0 :: Int ..] row, c /= 0 ] | row <- wL ++ wR ++ wO ]
+      rowPtr = scanl (+) 0 (map length rows)
+      entries = concat rows
+  in withArrayLen (map fromIntegral rowPtr :: [Int64]) $ \_ prp ->
+       withArrayLen (map (fromIntegral . fst) entries :: [Int64]) $ \_ pcol ->
+         withFrs (map snd entries) $ \pval -> withFrs cs $ \pcs ->
+           f (fromIntegral n) (fromIntegral q) prp pcol pval pcs
 
 -- | the draws of `prove` + `hscProve` in the reference's order: c_{n+1..n+4}, y, z, y_1..y_Q, z_1..z_Q, u, v
 drawTranscript :: MonadRandom m => Int -> m ([Fr], RndOracle)
@@ -416,6 +439,16 @@ drawTranscript q = do
 -- | prove with the draws supplied by the caller (what makes proofs reproducible; the tests of this repository use it)
 proveWithTranscript :: SRS -> Assignment Fr -> ArithCircuit Fr -> [Fr] -> Proof
 proveWithTranscript (SRS h) Assignment{..} circuit transcript = unsafePerformIO $
+  withForeignPtr h $ \p -> withCircuitCsr circuit $ \_ q prp pcol pval pcs ->
+    withFrs aL $ \pal -> withFrs aR $ \par -> withFrs aO $ \pao -> withFrs transcript $ \ptr -> do
+      sz <- fromIntegral <$> c_proof_size q
+      bytes <- BSI.create sz $ \out ->
+        check =<< c_prove_csr p (fromIntegral (length aL)) q prp pcol pval pcs pal par pao ptr out
+      pure (decodeProof (fromIntegral q) bytes)
+
+-- | proveWithTranscript over the dense Q x n weight arrays (sonic_prove): the same bytes
+proveWithTranscriptDense :: SRS -> Assignment Fr -> ArithCircuit Fr -> [Fr] -> Proof
+proveWithTranscriptDense (SRS h) Assignment{..} circuit transcript = unsafePerformIO $
   withForeignPtr h $ \p -> withCircuit circuit $ \_ q pwl pwr pwo pcs ->
     withFrs aL $ \pal -> withFrs aR $ \par -> withFrs aO $ \pao -> withFrs transcript $ \ptr -> do
       sz <- fromIntegral <$> c_proof_size q
@@ -434,11 +467,34 @@ prove srs assignment circuit = do
 --   host CPU inside the library (its own pairing); the reference's `verify` on the points `decodeProof` returns is equivalent
 verify :: SRS -> ArithCircuit Fr -> Proof -> Fr -> Fr -> [(Fr, Fr)] -> Bool
 verify (SRS h) circuit proof y z yzs = unsafePerformIO $
+  withForeignPtr h $ \p -> withCircuitCsr circuit $ \n q prp pcol pval pcs ->
+    withBytes (encodeProof proof) $ \ppf -> withFr y $ \py -> withFr z $ \pz ->
+      withFrs (concat [ [yj, zj] | (yj, zj) <- yzs ]) $ \pyz -> alloca $ \acc -> do
+        check =<< c_verify_csr p n q prp pcol pval pcs ppf py pz pyz acc
+        (/= 0) <$> peek acc
+
+-- | verify over the dense Q x n weight arrays (sonic_verify): the same answer
+verifyDense :: SRS -> ArithCircuit Fr -> Proof -> Fr -> Fr -> [(Fr, Fr)] -> Bool
+verifyDense (SRS h) circuit proof y z yzs = unsafePerformIO $
   withForeignPtr h $ \p -> withCircuit circuit $ \n q pwl pwr pwo pcs ->
     withBytes (encodeProof proof) $ \ppf -> withFr y $ \py -> withFr z $ \pz ->
       withFrs (concat [ [yj, zj] | (yj, zj) <- yzs ]) $ \pyz -> alloca $ \acc -> do
         check =<< c_verify p n q pwl pwr pwo pcs ppf py pz pyz acc
         (/= 0) <$> peek acc
+
+-- | the opt-in Fiat-Shamir transcript's circuit digest (sonic_fs_circuit_digest_csr: host only, SHA-256 of the dense bytes the rows stand for)
+fsCircuitDigest :: ArithCircuit Fr -> ByteString
+fsCircuitDigest circuit = unsafePerformIO $
+  withCircuitCsr circuit $ \n q prp pcol pval pcs -> BSI.create 32 $ \out ->
+    check =<< c_fs_digest_csr n q prp pcol pval pcs out
+
+-- | verify for a proof made with the Fiat-Shamir transcript (sonic_verify_fs_csr): the challenges are recomputed from circuit and proof
+verifyFs :: SRS -> ArithCircuit Fr -> Proof -> Bool
+verifyFs (SRS h) circuit proof = unsafePerformIO $
+  withForeignPtr h $ \p -> withCircuitCsr circuit $ \n q prp pcol pval pcs ->
+    withBytes (encodeProof proof) $ \ppf -> alloca $ \acc -> do
+      check =<< c_verify_fs_csr p n q prp pcol pval pcs ppf acc
+      (/= 0) <$> peek acc
 
 -- ---------------------------------------------------------------------------------------------------------------------
 -- Sonic.Signature
@@ -473,6 +529,14 @@ data Prover = Prover { proverHandle :: ForeignPtr ProverHandle, proverSrs :: SRS
 
 newProver :: SRS -> ArithCircuit Fr -> IO Prover
 newProver srs@(SRS h) circuit =
+  withForeignPtr h $ \p -> withCircuitCsr circuit $ \n q prp pcol pval pcs -> alloca $ \out -> do
+    check =<< c_prover_new_csr p n q prp pcol pval pcs out
+    fp <- newForeignPtr p_prover_free =<< peek out
+    pure Prover { proverHandle = fp, proverSrs = srs, proverQ = fromIntegral q }
+
+-- | newProver over the dense Q x n weight arrays (sonic_prover_new): a handle that proves the same bytes
+newProverDense :: SRS -> ArithCircuit Fr -> IO Prover
+newProverDense srs@(SRS h) circuit =
   withForeignPtr h $ \p -> withCircuit circuit $ \n q pwl pwr pwo pcs -> alloca $ \out -> do
     check =<< c_prover_new p n q pwl pwr pwo pcs out
     fp <- newForeignPtr p_prover_free =<< peek out

@@ -14,6 +14,18 @@
  *         exponents need not be sorted, repeated exponents are summed, zero coefficients allowed
  *   gate weights wL, wR, wO (Bulletproofs GateWeights, lists of Q rows of n): dense Q x n
  *         row-major Fr
+ *   gate weights as CSR (the `_csr` entry points, round 7): the three matrices stacked as ONE
+ *         compressed-sparse-row matrix of 3Q rows -- rows 0..Q-1 are wL, Q..2Q-1 wR, 2Q..3Q-1 wO --
+ *         over columns 0..n-1 (column i = gate i + 1 of the reference):
+ *           const int64_t* row_ptr   3Q + 1 entries, row_ptr[0] == 0, non-decreasing;
+ *                                    nnz = row_ptr[3Q] <= 2^31 - 1
+ *           const int64_t* col       nnz entries in [0, n), strictly increasing within each row
+ *                                    (canonical CSR: sorted, no duplicates)
+ *           const uint8_t* val       nnz x 32-byte canonical Fr; explicit zeros are allowed
+ *         col / val may be NULL when nnz = 0; cs stays dense (Q Fr).  A structural violation
+ *         returns SONIC_ERR_INVALID_ARG with a message that names the row, a non-canonical value
+ *         SONIC_ERR_BAD_ENCODING.  Every `_csr` call gives the bytes its dense counterpart gives for
+ *         the densified matrices.
  *   transcript: the prover's `rnd` draws made explicit, in draw order (Protocol.hs:58,66,76,
  *         84-85; Signature.hs:48,60):  c_{n+1..n+4}, y, z, y_1..y_Q, z_1..z_Q, u, v  = 8 + 2Q Fr
  *   proof: record order of `Proof` (Protocol.hs:28-38) then `HscProof` (Signature.hs:22-29):
@@ -74,10 +86,12 @@ typedef struct sonic_srs sonic_srs_t;
 typedef struct sonic_prover sonic_prover_t;
 
 /* ---- library ---- */
-#define SONIC_ABI_VERSION 6
+#define SONIC_ABI_VERSION 7
 /* the SONIC_ABI_VERSION the library was built as; no device needed.  History: 5 = round 5 (devices; sonic_msm_submit_dev_v2,
  * sonic_msm_reduce_slices_dev_v2 and sonic_fs_challenges_v2 replace the symbols whose meaning changed in round 4; share format 2);
- * 6 = round 6 (additions only: sonic_prove_batch fuses the proofs of a handle group, sonic_one_shot_trim) */
+ * 6 = round 6 (additions only: sonic_prove_batch fuses the proofs of a handle group, sonic_one_shot_trim);
+ * 7 = round 7 (additions only: gate weights as CSR -- sonic_prover_new_csr, sonic_prove_csr, sonic_fs_circuit_digest_csr,
+ * sonic_verify_csr, sonic_verify_fs_csr) */
 int sonic_abi_version(void);
 int sonic_init(int device_ordinal);                 /* choose the DEFAULT GPU (first call wins) and make it the thread's HIP device; idempotent */
 int sonic_device_count(int* out);                   /* GPUs this process can see; SONIC_ERR_NO_DEVICE (and 0) without one */
@@ -236,6 +250,17 @@ int sonic_one_shot_trim(int device);
 /* the same split so that circuit and assignment stay resident in HBM across proofs */
 int sonic_prover_new(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR,
                      const uint8_t* wO, const uint8_t* cs, sonic_prover_t** out);
+/* the same handle from gate weights as CSR (format above).  The handle keeps the rows and their column-major transpose in HBM
+ * (O(nnz + n), int32 indices): s(X,y), s(u,Y) and sonic_prover_prepare then cost O(nnz + n) per constraint set instead of O(Q n).
+ * Every operation on a prover handle accepts it -- set_assignment, prepare, prove, submit / collect, prove_fs, hsc_prove, set_share /
+ * prove_share, sonic_prove_batch, sonic_prove_shared -- with the bytes a dense handle of the densified circuit gives. */
+int sonic_prover_new_csr(const sonic_srs_t* srs, int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val,
+                         const uint8_t* cs, sonic_prover_t** out);
+/* sonic_prove with gate weights as CSR.  It shares the parked shells of sonic_prove: a shell holds the form of its last call's circuit,
+ * and dense and CSR calls of one (n, Q) may alternate. */
+int sonic_prove_csr(const sonic_srs_t* srs, int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val,
+                    const uint8_t* cs, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO, const uint8_t* transcript,
+                    uint8_t* out_proof);
 int sonic_prover_set_assignment(sonic_prover_t* p, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO);
 /* optional, once per handle: commits the Q constraint-row polynomials of sPoly (Constraints.hs:34-53), after which every
  * S_j = commitPoly(s(X, y_j)) (Signature.hs:42) costs an n-term MSM instead of a 3n-term one.  Same proof bytes. */
@@ -332,6 +357,11 @@ int sonic_prover_device(const sonic_prover_t* p);   /* the GPU a prover handle l
  *   fs_challenges   what a proof determines: y, z, y_1..y_Q, z_1..z_Q, u, v (32 bytes each)
  *   verify_fs       recomputes them, requires the proof's own u, v to match, then verify (Protocol.hs:111-130) */
 int sonic_fs_circuit_digest(int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO, const uint8_t* cs, uint8_t out[32]);
+/* the same digest from gate weights as CSR: host only, no device needed.  The rows are hashed as the dense bytes they stand for
+ * (32 zero bytes per absent entry), so the digest equals sonic_fs_circuit_digest of the densified matrices and a proof made on
+ * either form verifies under either.  This costs O(Q n) hashing, once per circuit. */
+int sonic_fs_circuit_digest_csr(int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val, const uint8_t* cs,
+                                uint8_t out[32]);
 int sonic_prover_prove_fs(sonic_prover_t* p, const uint8_t circuit_digest[32], const uint8_t blinder_seed[32], uint8_t* out_proof,
                           uint8_t* out_transcript);
 int sonic_fs_srs_id(const sonic_srs_t* srs, uint8_t out[32]);
@@ -340,6 +370,8 @@ int sonic_fs_challenges_v2(int64_t n, int64_t Q, int64_t d, const uint8_t circui
 int sonic_fs_challenges(int64_t n, int64_t Q, int64_t d, const uint8_t circuit_digest[32], const uint8_t* proof, uint8_t* out);
 int sonic_verify_fs(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO,
                     const uint8_t* cs, const uint8_t* proof, int* accepted);
+int sonic_verify_fs_csr(const sonic_srs_t* srs, int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val,
+                        const uint8_t* cs, const uint8_t* proof, int* accepted);       /* gate weights as CSR */
 
 /* hscProve :: SRS -> BiVLaurent Fr -> [(Fr, Fr)] -> m HscProof  (Signature.hs:32-72) on its own, for the s(X,Y) of the handle's
  * circuit (Constraints.hs:34-53) and any number m of (y_j, z_j) pairs (yzs: m x 64 bytes); u, v are its two `rnd` draws.
@@ -362,6 +394,9 @@ int sonic_pc_v(const sonic_srs_t* srs, int64_t max, const uint8_t commitment[96]
  * hscVerify (Signature.hs:74-90).  yzs = Q pairs y_j || z_j (64 bytes each), i.e. rndOracleYZs. */
 int sonic_verify(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO,
                  const uint8_t* cs, const uint8_t* proof, const uint8_t y[32], const uint8_t z[32], const uint8_t* yzs, int* accepted);
+/* the same with gate weights as CSR: s(u, v) costs O(nnz + n) on the host instead of O(Q n) */
+int sonic_verify_csr(const sonic_srs_t* srs, int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val,
+                     const uint8_t* cs, const uint8_t* proof, const uint8_t y[32], const uint8_t z[32], const uint8_t* yzs, int* accepted);
 
 /* hscVerify :: SRS -> BiVLaurent Fr -> [(Fr, Fr)] -> HscProof -> Bool  (Signature.hs:74-90) for the s(X,Y) of a circuit */
 int sonic_hsc_verify(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO,

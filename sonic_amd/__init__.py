@@ -27,7 +27,7 @@ from .protocol import prove_fs, verify_fs, fs_challenges, fs_circuit_digest, fs_
 from .protocol import proof_from_shares, share_plan, from_x, from_y, biv_add  # noqa: F401,E402
 from .protocol import prove_shared, prove_batch, prove_many, device_count  # noqa: F401,E402
 from .commitment import msm_g1_srs_multi  # noqa: F401,E402
-from .protocol import prove, verify, hsc_prove, hsc_verify, Proof, HscProof, RndOracle, Prover, ProverPipeline, ArithCircuit, Assignment, GateWeights  # noqa: F401,E402
+from .protocol import prove, verify, hsc_prove, hsc_verify, Proof, HscProof, RndOracle, Prover, ProverPipeline, ArithCircuit, SparseCircuit, Assignment, GateWeights  # noqa: F401,E402
 
 __all__ = ["SRS", "commit_poly", "open_poly", "pc_v", "msm_g1", "MsmLane", "prove", "verify", "prove_fs", "verify_fs", "fs_challenges", "fs_circuit_digest", "hsc_prove", "hsc_verify", "hsc_prove_poly", "hsc_verify_poly", "Proof", "HscProof", "RndOracle", "Prover", "ProverPipeline",
-           "ArithCircuit", "Assignment", "GateWeights", "SonicError"]
+           "ArithCircuit", "SparseCircuit", "Assignment", "GateWeights", "SonicError"]

@@ -111,6 +111,11 @@ def lib() -> C.CDLL:
         "sonic_msm_plan": [vp, i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)],
         "sonic_prove": [vp, i64, i64] + [vp] * 9,
         "sonic_prover_new": [vp, i64, i64, vp, vp, vp, vp, C.POINTER(vp)],
+        "sonic_prover_new_csr": [vp, i64, i64, vp, vp, vp, vp, C.POINTER(vp)],
+        "sonic_prove_csr": [vp, i64, i64] + [vp] * 9,
+        "sonic_fs_circuit_digest_csr": [i64, i64, vp, vp, vp, vp, vp],
+        "sonic_verify_csr": [vp, i64, i64, vp, vp, vp, vp, vp, cp, cp, vp, C.POINTER(i32)],
+        "sonic_verify_fs_csr": [vp, i64, i64, vp, vp, vp, vp, vp, C.POINTER(i32)],
         "sonic_prover_set_assignment": [vp, vp, vp, vp],
         "sonic_prover_prove": [vp, vp, vp],
         "sonic_prover_submit": [vp, vp],
@@ -189,7 +194,7 @@ def lib() -> C.CDLL:
 
 
 HIP_RUNTIME_NOTE = None
-ABI_VERSION = 6          # SONIC_ABI_VERSION of include/sonic_hip.h
+ABI_VERSION = 7          # SONIC_ABI_VERSION of include/sonic_hip.h
 
 
 def _hipver(v: int) -> str:
@@ -210,6 +215,7 @@ EXPORTED = [
     "sonic_prover_set_share", "sonic_proof_share_size", "sonic_prover_prove_share", "sonic_prover_collect_share", "sonic_proof_from_shares", "sonic_prove_share_plan", "sonic_fs_circuit_digest", "sonic_fs_srs_id", "sonic_prover_prove_fs", "sonic_fs_challenges", "sonic_verify_fs", "sonic_prover_hsc_prove", "sonic_hsc_prove_poly", "sonic_hsc_verify_poly", "sonic_hsc_proof_size", "sonic_hsc_verify", "sonic_prover_free", "sonic_pc_v", "sonic_verify", "sonic_dev_alloc", "sonic_dev_free", "sonic_dev_upload",
     "sonic_dev_download", "sonic_profile_enable", "sonic_profile_reset", "sonic_profile_get",
     "sonic_profile_names",
+    "sonic_prover_new_csr", "sonic_prove_csr", "sonic_fs_circuit_digest_csr", "sonic_verify_csr", "sonic_verify_fs_csr",
 ]
 
 

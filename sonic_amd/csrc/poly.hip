@@ -15,6 +15,7 @@
 // more elementwise pass -- no sequential Horner chain.
 #include "internal.hpp"
 #include "poly.hpp"
+#include "csr.hpp"
 
 namespace sonic {
 
@@ -353,6 +354,113 @@ void s_of_u_enqueue(hipStream_t st, const Fr* wL, const Fr* wR, const Fr* wO, co
   tmp.ensure(sizeof(Fr) * (size_t)nblk * Q);
   LAUNCH(k_s_of_u_rows, dim3(nblk, (unsigned)Q), 256, 0, st, wL, wR, wO, upow, n, tmp.as<Fr>());
   LAUNCH(k_s_of_u_finish, ceil_div(Q, 64), 64, 0, st, (const Fr*)tmp.as<Fr>(), nblk, n, Q, s);
+}
+
+// ---- the same two polynomials from sparse gate weights (csr.hpp: ONE CSR of 3Q rows, wL / wR / wO stacked) ----------------------------
+// Work proportional to n + nnz instead of Q n.  Row r is row q = r mod Q of matrix r / Q.
+__device__ __forceinline__ int csr_matrix(int r, int Q) { return r >= 2 * Q ? 2 : (r >= Q ? 1 : 0); }
+
+// s(X,y) as k_s_of_y computes it, walking column i of the column-major copy: one thread per gate i, y^{n+1+q} gathered per entry --
+// from LDS when the Q powers fit (stage != 0: Q * 32 bytes of dynamic LDS), else through L2
+__global__ __launch_bounds__(256) void k_s_of_y_csc(const int32_t* __restrict__ col_ptr, const int32_t* __restrict__ row, const Fr* __restrict__ val,
+                                                    const Fr* __restrict__ ypow, long n, int Q, int stage, Fr* __restrict__ s) {
+  extern __shared__ uint32_t yq_lds[];
+  const Fr* yq = ypow + 2 * n + 1;                           // y^{n+1+q}, q = 0..Q-1
+  if (stage) {
+    Fr* sh = reinterpret_cast<Fr*>(yq_lds);
+    for (int q = threadIdx.x; q < Q; q += 256) sh[q] = yq[q];
+    __syncthreads();
+    yq = sh;
+  }
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x + 1; i <= n + 1; i += (long)gridDim.x * 256) {   // 1..n
+    if (i > n) { s[n] = Fr::zero(); break; }                 // X^0 slot
+    Fr u = Fr::zero(), v = Fr::zero(), w = Fr::zero();     // (three named sums, not an array indexed by the matrix: that would live in scratch)
+    const int k1 = col_ptr[i];
+    for (int k = col_ptr[i - 1]; k < k1; k++) {
+      const int r = row[k], m = csr_matrix(r, Q);
+      const Fr x = fp_mul(val[k], yq[r - m * Q]);
+      if (m == 0) u = fp_add(u, x);
+      else if (m == 1) v = fp_add(v, x);
+      else w = fp_add(w, x);
+    }
+    s[n - i] = u;
+    s[n + i] = v;
+    s[2 * n + i] = fp_sub(fp_sub(w, ypow[n + i]), ypow[n - i]);
+  }
+}
+void s_of_y_csc_enqueue(hipStream_t st, const int32_t* col_ptr, const int32_t* row, const Fr* val, const Fr* ypow, long n, long Q, Fr* s) {
+  const int stage = Q <= 1024 ? 1 : 0;
+  LAUNCH(k_s_of_y_csc, elementwise_grid(n + 1), 256, stage ? (unsigned)(sizeof(Fr) * Q) : 0u, st, col_ptr, row, val, ypow, n, (int)Q, stage, s);
+}
+
+// s(u,Y)'s coefficients of Y^{n+1+q} = sum over rows q, Q + q, 2Q + q of val * u^{-i | i | i+n}.  Rows are as skewed as circuits are
+// (rndCircuit: one row of n entries per matrix, every other row empty), so they are cut into chunks of CSR_CHUNK entries
+// (csr.hpp): one wave per chunk, 8 entries per lane, a shuffle reduction in Fr, one partial per chunk -- and k_s_of_u_csr_finish
+// adds each q's partials in chunk order.  No atomics: the sums are exact and come out the same whatever the schedule.
+__device__ __forceinline__ Fr fr_shfl_xor(const Fr& a, int mask) {
+  Fr o;
+#pragma unroll
+  for (int k = 0; k < 8; k++) o.l[k] = (uint32_t)__shfl_xor((int)a.l[k], mask, 64);
+  return o;
+}
+__global__ __launch_bounds__(256) void k_s_of_u_csr(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col, const Fr* __restrict__ val,
+                                                    const int32_t* __restrict__ chunk_row, const int32_t* __restrict__ chunk_begin, long nchunks,
+                                                    const Fr* __restrict__ upow, long n, int Q, Fr* __restrict__ partial) {
+  const long c = (long)blockIdx.x * 4 + (threadIdx.x >> 6);  // one wave per chunk
+  const int lane = threadIdx.x & 63;
+  if (c >= nchunks) return;                                  // (wave-uniform: no barrier below)
+  const int r = chunk_row[c], m = csr_matrix(r, Q);
+  const int k0 = chunk_begin[c];
+  const int k1 = min(k0 + CSR_CHUNK, row_ptr[r + 1]);
+  // u^-i = upow[n - i], u^i = upow[n + i], u^{i+n} = upow[2n + i], i = column + 1
+  const long base = m == 0 ? n - 1 : (m == 1 ? n + 1 : 2 * n + 1);
+  const long sign = m == 0 ? -1 : 1;
+  Fr acc = Fr::zero();
+  for (int k = k0 + lane; k < k1; k += 64) acc = fp_add(acc, fp_mul(val[k], upow[base + sign * col[k]]));
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) acc = fp_add(acc, fr_shfl_xor(acc, o));
+  if (lane == 0) partial[c] = acc;
+}
+// grid Q: s[2n + 1 + q] = the partials of rows q, Q + q, 2Q + q
+__global__ __launch_bounds__(256) void k_s_of_u_csr_finish(const int32_t* __restrict__ row_chunk, const Fr* __restrict__ partial, long n, int Q, Fr* __restrict__ s) {
+  __shared__ Fr sh[256];
+  const int q = blockIdx.x;
+  Fr acc = Fr::zero();
+  for (int m = 0; m < 3; m++) {
+    const int r = m * Q + q;
+    for (int c = row_chunk[r] + threadIdx.x; c < row_chunk[r + 1]; c += 256) acc = fp_add(acc, partial[c]);
+  }
+  sh[threadIdx.x] = acc;
+  __syncthreads();
+  for (int o = 128; o >= 1; o >>= 1) {
+    if ((int)threadIdx.x < o) sh[threadIdx.x] = fp_add(sh[threadIdx.x], sh[threadIdx.x + o]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) s[2 * n + 1 + q] = sh[0];
+}
+void s_of_u_csr_enqueue(hipStream_t st, const int32_t* row_ptr, const int32_t* col, const Fr* val, const int32_t* chunk_row, const int32_t* chunk_begin,
+                        long nchunks, const int32_t* row_chunk, const Fr* upow, long n, long Q, Fr* s, Fr* partial) {
+  LAUNCH(k_s_of_u_diag, elementwise_grid(n + 1), 256, 0, st, upow, n, s);
+  if (nchunks > 0) LAUNCH(k_s_of_u_csr, ceil_div(nchunks, 4L), 256, 0, st, row_ptr, col, val, chunk_row, chunk_begin, nchunks, upow, n, (int)Q, partial);
+  LAUNCH(k_s_of_u_csr_finish, (unsigned)Q, 256, 0, st, row_chunk, (const Fr*)partial, n, (int)Q, s);
+}
+
+// the terms of P_q (sonic_prover_prepare on a sparse handle): rows q, Q + q, 2Q + q of the CSR at X^{-i}, X^{i}, X^{i+n}, gathered as
+// (alpha-basis point, Montgomery value) pairs for a plain MSM over nnz_q terms.  A: the alpha basis positioned at exponent 0.
+__global__ __launch_bounds__(256) void k_csr_row_terms(const int32_t* __restrict__ col, const Fr* __restrict__ val, int b0, int l0, int b1, int l1, int b2, int l2,
+                                                       long n, PointArray A, G1Affine* __restrict__ pts, Fr* __restrict__ scal) {
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (long)l0 + l1 + l2) return;
+  long k, e;
+  if (t < l0) { k = b0 + t; e = -(long)(col[k] + 1); }
+  else if (t < (long)l0 + l1) { k = b1 + (t - l0); e = col[k] + 1; }
+  else { k = b2 + (t - l0 - l1); e = col[k] + 1 + n; }
+  pts[t] = (A + e)[0];
+  scal[t] = val[k];
+}
+void csr_row_terms_enqueue(hipStream_t st, const int32_t* col, const Fr* val, const int32_t seg[6], long n, PointArray A, G1Affine* pts, Fr* scal) {
+  const long total = (long)seg[1] + seg[3] + seg[5];
+  if (total > 0) LAUNCH(k_csr_row_terms, ceil_div(total, 256L), 256, 0, st, col, val, seg[0], seg[1], seg[2], seg[3], seg[4], seg[5], n, A, pts, scal);
 }
 
 // The two operands of t(X,y)'s product (Constraints.hs:56-65 with Y := y) in ONE launch: fa = r(X,1) and fb = r(X,y) + s(X,y), both over

@@ -11,6 +11,12 @@ void s_of_y_enqueue(hipStream_t st, const Fr* wL, const Fr* wR, const Fr* wO, co
 void weight_row_poly_enqueue(hipStream_t st, const Fr* wL, const Fr* wR, const Fr* wO, long n, long q, Fr* s);
 void s_diag_part_enqueue(hipStream_t st, const Fr* ypow, long n, long Q, Fr* diag, Fr* yq);
 void s_of_u_enqueue(hipStream_t st, const Fr* wL, const Fr* wR, const Fr* wO, const Fr* upow, long n, long Q, Fr* s, DevBuf& tmp);
+// from sparse gate weights (csr.hpp): s(X,y) over the column-major copy, s(u,Y) over the rows cut into chunks (partial: one Fr per chunk),
+// and the (point, scalar) terms of one constraint-row polynomial P_q; seg = {first entry, count} of rows q, Q + q, 2Q + q
+void s_of_y_csc_enqueue(hipStream_t st, const int32_t* col_ptr, const int32_t* row, const Fr* val, const Fr* ypow, long n, long Q, Fr* s);
+void s_of_u_csr_enqueue(hipStream_t st, const int32_t* row_ptr, const int32_t* col, const Fr* val, const int32_t* chunk_row, const int32_t* chunk_begin,
+                        long nchunks, const int32_t* row_chunk, const Fr* upow, long n, long Q, Fr* s, Fr* partial);
+void csr_row_terms_enqueue(hipStream_t st, const int32_t* col, const Fr* val, const int32_t seg[6], long n, PointArray A, G1Affine* pts, Fr* scal);
 void add_into_enqueue(hipStream_t st, Fr* dst, const Fr* src, long n);
 void t_operands_enqueue(hipStream_t st, const Fr* r1, long r_len, long r_lo, const Fr* sy, long s_off, long s_len, const Fr* ypair, Fr* fa, Fr* fb, long M);
 void sub_k_of_y_enqueue(hipStream_t st, Fr* slot, const Fr* cs, const Fr* ypow_nq, long Q, int* flags, int flag_bit);

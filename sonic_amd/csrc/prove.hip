@@ -215,6 +215,50 @@ static int prover_load_circuit(sonic_prover* p, const uint8_t* wL, const uint8_t
   return SONIC_OK;
 }
 
+// the sparse form (csr.hpp), laid out on the host: both orientations and the chunk table, values to Montgomery form on the way
+static void upload_i32(hipStream_t st, DevBuf& dst, const std::vector<int32_t>& src) {
+  dst.ensure(sizeof(int32_t) * (src.empty() ? 1 : src.size()));
+  if (!src.empty()) HIP_OK(hipMemcpyAsync(dst.p, src.data(), sizeof(int32_t) * src.size(), hipMemcpyHostToDevice, st));
+}
+void prover_upload_csr(sonic_prover_t* p, hipStream_t st, const CsrLayout& L, int* d_flags) {
+  sonic_prover::CsrBufs& b = p->sp;
+  upload_i32(st, b.row_ptr, L.row_ptr); upload_i32(st, b.col, L.col);
+  upload_i32(st, b.col_ptr, L.col_ptr); upload_i32(st, b.row, L.row);
+  upload_i32(st, b.chunk_row, L.chunk_row); upload_i32(st, b.chunk_begin, L.chunk_begin); upload_i32(st, b.row_chunk, L.row_chunk);
+  upload_fr_mont(st, b.val, L.val, L.nnz, d_flags);
+  upload_fr_mont(st, b.cval, L.cval.data(), L.nnz, d_flags);
+  upload_fr_mont(st, p->cs, L.cs, L.Q, d_flags);
+  b.nnz = L.nnz;
+  b.nchunks = (long)L.chunk_row.size();
+  b.partial.ensure(sizeof(Fr) * (b.nchunks > 0 ? b.nchunks : 1));
+  b.h_row_ptr = L.row_ptr;
+}
+
+static int prover_load_circuit_csr(sonic_prover* p, const CsrLayout& L) {
+  hipStream_t st = p->st;
+  p->csr = true;
+  p->circuit_has_runs = circuit_runs_hint_csr(L, RUN_TILE);
+  HIP_OK(hipMemsetAsync(p->flags.p, 0, 4, st));
+  prover_upload_csr(p, st, L, p->flags.as<int>());
+  int f = read_flags(st, p->flags);          // (also: the pageable host buffers of L have been read when this returns)
+  if (f) return flags_to_status(f, "sonic_prover_new_csr");
+  return SONIC_OK;
+}
+
+// s(X,y) / s(u,Y) of the handle's circuit, in whichever form it holds it
+static void s_of_y_of(sonic_prover* p, hipStream_t st, const Fr* ypow, Fr* out) {
+  if (p->csr) s_of_y_csc_enqueue(st, p->sp.col_ptr.as<int32_t>(), p->sp.row.as<int32_t>(), p->sp.cval.as<Fr>(), ypow, p->n, p->Q, out);
+  else s_of_y_enqueue(st, p->wL.as<Fr>(), p->wR.as<Fr>(), p->wO.as<Fr>(), ypow, p->n, p->Q, out);
+}
+static void s_of_u_of(sonic_prover* p, hipStream_t st, const Fr* upow, Fr* out) {
+  sonic_prover::CsrBufs& b = p->sp;
+  if (p->csr) s_of_u_csr_enqueue(st, b.row_ptr.as<int32_t>(), b.col.as<int32_t>(), b.val.as<Fr>(), b.chunk_row.as<int32_t>(), b.chunk_begin.as<int32_t>(),
+                                 b.nchunks, b.row_chunk.as<int32_t>(), upow, p->n, p->Q, out, b.partial.as<Fr>());
+  else s_of_u_enqueue(st, p->wL.as<Fr>(), p->wR.as<Fr>(), p->wO.as<Fr>(), upow, p->n, p->Q, out, p->tmp);
+}
+
+static int prover_new_impl(const sonic_srs_t* srs, int64_t n, int64_t Q, const std::function<int(sonic_prover*)>& load_circuit, sonic_prover_t** out);
+
 extern "C" {
 
 int sonic_srs_new(int64_t d, const uint8_t x[32], const uint8_t alpha[32], sonic_srs_t** out) { return sonic_srs_new_on(-1, d, x, alpha, out); }
@@ -243,6 +287,33 @@ int sonic_prover_new(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t
     set_error("Parameter d is not large enough: %ld should be greater than %ld", (long)srs_d(srs), (long)(7 * n));
     return SONIC_ERR_D_TOO_SMALL;
   }
+  return prover_new_impl(srs, n, Q, [&](sonic_prover* p) { return prover_load_circuit(p, wL, wR, wO, cs); }, out);
+  API_END
+}
+
+int sonic_prover_new_csr(const sonic_srs_t* srs, int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val,
+                         const uint8_t* cs, sonic_prover_t** out) {
+  API_BEGIN_ON(srs_device(srs))
+  if (!srs || n < 1 || Q < 1 || !row_ptr || !cs || !out) { set_error("sonic_prover_new_csr: bad argument (need n >= 1, Q >= 1)"); return SONIC_ERR_INVALID_ARG; }
+  if (srs_d(srs) < 7 * n) {                                                   // Protocol.hs:54-55
+    set_error("Parameter d is not large enough: %ld should be greater than %ld", (long)srs_d(srs), (long)(7 * n));
+    return SONIC_ERR_D_TOO_SMALL;
+  }
+  int rc = csr_validate("sonic_prover_new_csr", n, Q, row_ptr, col, val);
+  if (rc) return rc;
+  for (long q = 0; q < Q; q++) {
+    Fr c; memcpy(c.l, cs + 32 * q, 32);
+    if (!fp_is_canonical(c)) { set_error("sonic_prover_new_csr: non-canonical constant cs[%ld]", q); return SONIC_ERR_BAD_ENCODING; }
+  }
+  CsrLayout L;
+  csr_layout(n, Q, row_ptr, col, val, cs, L);
+  return prover_new_impl(srs, n, Q, [&](sonic_prover* p) { return prover_load_circuit_csr(p, L); }, out);
+  API_END
+}
+
+}  // extern "C"
+
+static int prover_new_impl(const sonic_srs_t* srs, int64_t n, int64_t Q, const std::function<int(sonic_prover*)>& load_circuit, sonic_prover_t** out) {
   std::unique_ptr<sonic_prover> p(new sonic_prover());
   p->srs = srs; p->n = n; p->Q = Q;
   p->device = srs_device(srs);
@@ -262,7 +333,7 @@ int sonic_prover_new(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t
   mkstream(&p->ts, prio_high);
   hipStream_t st = p->st;
   p->flags.alloc(8);
-  int rc_c = prover_load_circuit(p.get(), wL, wR, wO, cs);
+  int rc_c = load_circuit(p.get());
   if (rc_c) return rc_c;
   // workspaces
   const long tlen = 7 * n + 9;
@@ -324,8 +395,10 @@ int sonic_prover_new(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t
   }
   HIP_OK(hipStreamSynchronize(st));
   *out = p.release();
-  API_END
+  return SONIC_OK;
 }
+
+extern "C" {
 
 int sonic_prover_set_assignment(sonic_prover_t* p, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO) {
   API_BEGIN_ON(p ? p->device : -1)
@@ -436,7 +509,7 @@ static int prove_enqueue(sonic_prover_t* p, const uint8_t* transcript) {
   const int KS = p->sym_on ? K + (int)Q + 1 : K + ((p->prepared || p->runs_on) ? (int)Q : 0);        // + the second halves of the S_j and of C
   // Launch-bound sizes replay the whole multi-stream enqueue as one hipGraph: captured on the second proof of a handle (the
   // first one grows the workspaces), every address in it is owned by the handle.
-  const bool pending = p->pend_circuit[0] != nullptr || p->pend_asg[0] != nullptr;
+  const bool pending = p->pend_circuit[0] != nullptr || p->pend_csr || p->pend_asg[0] != nullptr;
   const bool want_graph = p->use_graph && p->proofs_done >= 1 && !profiler().on && p->phases == PH_ALL && !pending;
   const bool replay = want_graph && p->graph != nullptr;
   const bool capturing = want_graph && !replay && !p->graph_tried;
@@ -458,7 +531,7 @@ static int prove_enqueue(sonic_prover_t* p, const uint8_t* transcript) {
   MsmSlot* slots = p->slots.as<MsmSlot>();
   Fr* frout = p->frout.as<Fr>();
   Fr *r1 = p->r1.as<Fr>(), *su = p->su.as<Fr>(), *pw = p->pw.as<Fr>(), *fa = p->fa.as<Fr>(), *fb = p->fb.as<Fr>();
-  const Fr *wL = p->wL.as<Fr>(), *wR = p->wR.as<Fr>(), *wO = p->wO.as<Fr>(), *cs = p->cs.as<Fr>();
+  const Fr *cs = p->cs.as<Fr>();
   const long d = srs_d(srs);
   const long r_lo = -2 * n - 4, r_len = 3 * n + 5, s_lo = -n, s_len = 3 * n + 1, t_lo = -4 * n - 8, t_len = 7 * n + 9;
   const long M = 1L << p->log2m;
@@ -614,11 +687,17 @@ static int prove_enqueue(sonic_prover_t* p, const uint8_t* transcript) {
     upload_fr_mont(ms, p->wO, c[2], Q * n, flags + 1);
     upload_fr_mont(ms, p->cs, c[3], Q, flags + 1);
     p->pend_circuit[0] = nullptr;
+    p->csr = false;
+  } else if (p->pend_csr) {                                    // (the same for a sparse circuit: sonic_prove_csr)
+    group0();
+    prover_upload_csr(p, ms, p->pend_csr_layout, flags + 1);
+    p->pend_csr = false;
+    p->csr = true;
   }
   // s(X,y)                                                                           Protocol.hs:69-70
   if (need_T && on(PH_T)) {
     poly_scale_powers_enqueue(ms, nullptr, pw, 2 * n + Q + 1, -n, pY, pY + 1);       // y^e, e in [-n, n+Q]
-    s_of_y_enqueue(ms, wL, wR, wO, pw, n, Q, sy);
+    s_of_y_of(p, ms, pw, sy);
     HIP_OK(hipMemcpyAsync(p->kpow.p, pw + (2 * n + 1), sizeof(Fr) * Q, hipMemcpyDeviceToDevice, ms));   // y^{n+1..n+Q} for k(y); pw is reused below
   }
   ready(p->ev_sy0);
@@ -639,7 +718,7 @@ static int prove_enqueue(sonic_prover_t* p, const uint8_t* transcript) {
     if (need_j[(size_t)j] && on(PH_HSCS)) {
       poly_scale_powers_enqueue(ms, nullptr, pw, 2 * n + Q + 1, -n, pYj(j), pYj(j) + 1);
       // a prepared handle that has only a piece of S_j's diagonal part does not read s(X, y_j) itself
-      if (!p->prepared || own(6 + 2 * j) || own(5 + 2 * Q + 2 * j)) s_of_y_enqueue(ms, wL, wR, wO, pw, n, Q, p->syj[j].as<Fr>());
+      if (!p->prepared || own(6 + 2 * j) || own(5 + 2 * Q + 2 * j)) s_of_y_of(p, ms, pw, p->syj[j].as<Fr>());
       if (p->prepared && own(5 + 2 * j)) s_diag_part_enqueue(ms, pw, n, Q, p->diag[j].as<Fr>(), p->yq[j].as<Fr>());
     }
     ready(p->ev_syj[j]);
@@ -647,7 +726,7 @@ static int prove_enqueue(sonic_prover_t* p, const uint8_t* transcript) {
   const long u_lo = -n, u_len = 2 * n + Q + 1;
   if (need_su && on(PH_HSCW)) {
     poly_scale_powers_enqueue(ms, nullptr, pw, 3 * n + 1, -n, pU, pU + 1);           // u^e, e in [-n, 2n]
-    s_of_u_enqueue(ms, wL, wR, wO, pw, n, Q, su, p->tmp);
+    s_of_u_of(p, ms, pw, su);
   }
   ready(p->ev_su);
 
@@ -1179,9 +1258,35 @@ int sonic_prover_prepare(sonic_prover_t* p) {
   HIP_OK(hipMemsetAsync(flags, 0, 4, p->st));
   HIP_OK(hipStreamSynchronize(p->st));
   DevBuf slots(sizeof(MsmSlot) * Q);
-  std::vector<DevBuf> rows(std::min<long>(Q, N_LANES));
+  std::vector<DevBuf> rows(p->csr ? 0 : std::min<long>(Q, N_LANES));
   for (auto& b : rows) b.alloc(sizeof(Fr) * (3 * n + 1));
-  for (long q = 0; q < Q; q++) {
+  DevBuf terms_pts, terms_scal;
+  if (p->csr) {
+    // P_q's nnz_q terms only: rows q, Q + q, 2Q + q gathered as (alpha-basis point, value) pairs, one plain MSM each -- instead of the
+    // 3n + 1-term MSM over a mostly-zero row.  Their exponents lie in [-n, 2n] without 0, inside [-d, d] (d >= 7n) and off the omitted
+    // g^alpha: where the dense path's index checks never fire, and neither do these.  A row without entries commits to the point at
+    // infinity (its slot stays the empty sum).
+    const std::vector<int32_t>& rp = p->sp.h_row_ptr;
+    const long nnz = p->sp.nnz;
+    terms_pts.alloc(sizeof(G1Affine) * (nnz > 0 ? nnz : 1));
+    terms_scal.alloc(sizeof(Fr) * (nnz > 0 ? nnz : 1));
+    HIP_OK(hipMemsetAsync(slots.p, 0, sizeof(MsmSlot) * Q, p->st));
+    HIP_OK(hipStreamSynchronize(p->st));
+    const PointArray A = srs_basis(p->srs, 1) + d;                   // the alpha basis at exponent 0
+    long at = 0;
+    for (long q = 0; q < Q; q++) {
+      const int32_t seg[6] = {rp[q], rp[q + 1] - rp[q], rp[Q + q], rp[Q + q + 1] - rp[Q + q], rp[2 * Q + q], rp[2 * Q + q + 1] - rp[2 * Q + q]};
+      const long cnt = (long)seg[1] + seg[3] + seg[5];
+      if (cnt == 0) continue;
+      Lane& l = p->lane_at((int)(q % N_LANES));
+      G1Affine* pts = terms_pts.as<G1Affine>() + at;
+      Fr* scal = terms_scal.as<Fr>() + at;
+      csr_row_terms_enqueue(l.st, p->sp.col.as<int32_t>(), p->sp.val.as<Fr>(), seg, n, A, pts, scal);
+      msm_enqueue(l.st, l.ws, msm_plan(cnt), PointArray::packed(pts), scal, cnt, true, slots.as<MsmSlot>() + q);
+      at += cnt;
+    }
+  }
+  for (long q = 0; q < Q && !p->csr; q++) {
     Lane& l = p->lane_at((int)(q % N_LANES));
     Fr* row = rows[q % N_LANES].as<Fr>();
     weight_row_poly_enqueue(l.st, p->wL.as<Fr>(), p->wR.as<Fr>(), p->wO.as<Fr>(), n, q, row);
@@ -1258,7 +1363,6 @@ int sonic_prover_hsc_prove(sonic_prover_t* p, int64_t m, const uint8_t* yzs, con
   if (bytes_are_zero(u, 32) || bytes_are_zero(v, 32)) { set_error("hscProve: u or v is zero"); return SONIC_ERR_INEXACT_DIVISION; }
   hipStream_t st = p->st;
   const sonic_srs* srs = p->srs;
-  const Fr *wL = p->wL.as<Fr>(), *wR = p->wR.as<Fr>(), *wO = p->wO.as<Fr>();
   const long NS = 2 * m + 2;                                   // scalars: y_1..y_m, z_1..z_m, u, v
   const long K = 4 * m + 2;                                    // MSMs
   DevBuf S(sizeof(Fr) * NS), PR(sizeof(Fr) * 2 * NS), slots(sizeof(MsmSlot) * K), frout(sizeof(Fr) * (2 * m + 1)), flags(4);
@@ -1285,7 +1389,7 @@ int sonic_prover_hsc_prove(sonic_prover_t* p, int64_t m, const uint8_t* yzs, con
   // slots: S_j = 3j, W_j = 3j + 1, W'_j = 3j + 2;  Q_j = 3m + j;  Q_v = 4m;  C = 4m + 1.   frout: s_j = j, s'_j = m + j
   for (long j = 0; j < m; j++) {                                                       // Signature.hs:40-45, 54
     poly_scale_powers_enqueue(st, nullptr, pw.as<Fr>(), 2 * n + Q + 1, -n, pY(j), pY(j) + 1);
-    s_of_y_enqueue(st, wL, wR, wO, pw.as<Fr>(), n, Q, sy.as<Fr>());
+    s_of_y_of(p, st, pw.as<Fr>(), sy.as<Fr>());
     MsmJob jobs[3];
     jobs[0] = commit_job(st, srs, sy.as<Fr>(), s_lo, s_len, d, &sl[3 * j], fl);
     jobs[1] = open_job(st, srs, lane.sc[1], sy.as<Fr>(), s_lo, s_len, pZ(j), &fo[j], &sl[3 * j + 1], fl);
@@ -1293,7 +1397,7 @@ int sonic_prover_hsc_prove(sonic_prover_t* p, int64_t m, const uint8_t* yzs, con
     run_jobs(st, srs, lane.ws, jobs, 3);
   }
   poly_scale_powers_enqueue(st, nullptr, pw.as<Fr>(), 3 * n + 1, -n, pU, pU + 1);      // u^e, e in [-n, 2n]       :51
-  s_of_u_enqueue(st, wL, wR, wO, pw.as<Fr>(), n, Q, su.as<Fr>(), p->tmp);
+  s_of_u_of(p, st, pw.as<Fr>(), su.as<Fr>());
   {
     MsmJob jobs[MSM_MAX_JOBS];
     int k = 0;

@@ -16,6 +16,7 @@
 #include "poly.hpp"
 #include "fs.hpp"
 #include "share_plan.hpp"
+#include "csr.hpp"
 
 
 namespace sonic {
@@ -79,6 +80,17 @@ struct sonic_prover {
   hipStream_t ts = nullptr;                  // the t(X,y) product (NTT) runs beside the hscProve polynomials
   bool have_assignment = false;
   DevBuf wL, wR, wO, cs, aL, aR, aO;        // Montgomery, resident across proofs
+  // the circuit in sparse form (sonic_prover_new_csr, sonic_prove_csr; csr.hpp): the 3Q stacked rows and their column-major copy, int32
+  // indices and Montgomery values, plus the chunks of s(u,Y)'s row sums.  `csr` says which form the kernels read (wL, wR, wO or these);
+  // a parked one-shot shell switches with the circuit of each call.
+  bool csr = false;
+  struct CsrBufs {
+    DevBuf row_ptr, col, val, col_ptr, row, cval, chunk_row, chunk_begin, row_chunk, partial;
+    long nnz = 0, nchunks = 0;
+    std::vector<int32_t> h_row_ptr;           // (prepare: the entry ranges of the rows of each P_q)
+  } sp;
+  CsrLayout pend_csr_layout;                 // one-shot: this call's sparse circuit, laid out on the host, uploaded inside the proof
+  bool pend_csr = false;
   Lane lanes[N_LANES];
   // lanes in use: all six by default.  SONIC_FUSED_LANES=k (small-proof handles): k lanes of their own; =0: NO lane of its own
   // (few_streams) -- three streams per handle: main, transform, chain; the groups' openings ride on the streams that are waiting anyway
@@ -239,4 +251,6 @@ int flags_to_status(int f, const char* who);
 // (defined inside prove.hip's extern "C" block, not exported)
 extern "C" int prove_with_assignment(sonic_prover_t* p, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO, const uint8_t* transcript, uint8_t* out_proof);
 bool circuit_runs_hint(const uint8_t* wL, const uint8_t* wR, long n, long Q);
+// (prove.hip) queues the upload of a sparse circuit laid out on the host into the handle's CSR buffers (flags: non-canonical values)
+void prover_upload_csr(sonic_prover_t* p, hipStream_t st, const CsrLayout& L, int* d_flags);
 

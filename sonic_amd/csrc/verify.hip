@@ -19,6 +19,7 @@
 #include "g2.hpp"
 #include "pairing.hpp"
 #include "fs.hpp"
+#include "csr.hpp"
 
 namespace sonic {
 namespace {
@@ -174,6 +175,43 @@ int hsc_checks(const sonic_srs* srs, const VerifierKey& vk, int64_t n, int64_t Q
   return SONIC_OK;
 }
 
+// the same for sparse gate weights (csr.hpp, validated by the caller): s(u, v) in O(nnz + n).  Per row q of each matrix the entries sum
+// val * u^{-i | i | i+n}, scaled by v^{n+q}; the diagonal terms u^{i+n} (-v^i - v^-i) are summed on their own.
+int hsc_checks_csr(const sonic_srs* srs, int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val,
+                   int64_t m, const std::vector<Fr>& ys, const std::vector<Fr>& zs, const std::vector<G1Affine>& Sj, const std::vector<Fr>& sj,
+                   const std::vector<G1Affine>& Wj, const std::vector<Fr>& spj, const std::vector<G1Affine>& Wpj, const std::vector<G1Affine>& Qj,
+                   const G1Affine& Qv, const G1Affine& C, const Fr& u, const Fr& v, std::vector<PcvCheck>& checks) {
+  if (u.is_zero() || v.is_zero()) { set_error("hscVerify: u or v is zero"); return SONIC_ERR_INEXACT_DIVISION; }
+  // upos[e] = u^e (e in [0, 2n]), uneg[i] = u^-i (i in [0, n])
+  std::vector<Fr> upos((size_t)(2 * n + 1)), uneg((size_t)(n + 1));
+  const Fr uinv = fp_inv(u), vinv = fp_inv(v);
+  upos[0] = uneg[0] = Fr::one();
+  for (int64_t e = 1; e <= 2 * n; e++) upos[(size_t)e] = fp_mul(upos[(size_t)e - 1], u);
+  for (int64_t i = 1; i <= n; i++) uneg[(size_t)i] = fp_mul(uneg[(size_t)i - 1], uinv);
+  Fr sv = Fr::zero(), vq = fr_pow(v, (uint64_t)n);
+  for (int64_t q = 0; q < Q; q++) {
+    vq = fp_mul(vq, v);                                              // v^{n+q+1}
+    Fr rowsum = Fr::zero(), c;
+    for (int mat = 0; mat < 3; mat++) {
+      const int64_t r = mat * Q + q;
+      for (int64_t k = row_ptr[r]; k < row_ptr[r + 1]; k++) {
+        if (!load_fr(val + 32 * k, c)) return SONIC_ERR_BAD_ENCODING;
+        const int64_t i = col[k] + 1;
+        const Fr& up = mat == 0 ? uneg[(size_t)i] : upos[(size_t)(mat == 1 ? i : i + n)];
+        rowsum = fp_add(rowsum, fp_mul(c, up));
+      }
+    }
+    sv = fp_add(sv, fp_mul(rowsum, vq));
+  }
+  Fr vp = Fr::one(), vm = Fr::one();
+  for (int64_t i = 1; i <= n; i++) {
+    vp = fp_mul(vp, v); vm = fp_mul(vm, vinv);
+    sv = fp_sub(sv, fp_mul(upos[(size_t)(i + n)], fp_add(vp, vm)));
+  }
+  hsc_push_checks(srs_d(srs), m, ys, zs, Sj, sj, Wj, spj, Wpj, Qj, Qv, C, u, v, sv, checks);
+  return SONIC_OK;
+}
+
 }  // namespace
 }  // namespace sonic
 
@@ -199,11 +237,14 @@ int sonic_pc_v(const sonic_srs_t* srs, int64_t max, const uint8_t commitment[96]
   catch (const std::exception& e) { set_error("%s", e.what()); return SONIC_ERR_HIP; }
 }
 
-// verify srs circuit proof y z yzs  (Protocol.hs:111-130); yzs = Q pairs (y_j, z_j), 64 bytes each
-int sonic_verify(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO,
-                 const uint8_t* cs, const uint8_t* proof, const uint8_t y[32], const uint8_t z[32], const uint8_t* yzs, int* accepted) {
+}  // extern "C"
+
+// verify srs circuit proof y z yzs  (Protocol.hs:111-130) with the circuit's part of hscVerify -- s(u, v) and its checks -- left to
+// `hsc` (dense or sparse gate weights)
+template <class HscChecks>
+static int verify_with(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t* cs, const uint8_t* proof, const uint8_t y[32], const uint8_t z[32],
+                       const uint8_t* yzs, int* accepted, const HscChecks& hsc) {
   try {
-    if (!srs || n < 1 || Q < 1 || !wL || !wR || !wO || !cs || !proof || !y || !z || !yzs || !accepted) return SONIC_ERR_INVALID_ARG;
     *accepted = 0;
     const uint8_t* p = proof;
     auto G = [&](G1Affine& o) { bool k = load_g1(p, o); p += 96; return k; };
@@ -228,7 +269,7 @@ int sonic_verify(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t* wL
     if (rc) return rc;
     const int64_t d = srs_d(srs);
     std::vector<PcvCheck> checks;
-    rc = hsc_checks(srs, vk, n, Q, wL, wR, wO, Q, ys, zs, Sj, sj, Wj, spj, Wpj, Qj, Qv, C, u, v, checks);   // hscVerify, Signature.hs:74-90
+    rc = hsc(vk, ys, zs, Sj, sj, Wj, spj, Wpj, Qj, Qv, C, u, v, checks);   // hscVerify, Signature.hs:74-90
     if (rc) return rc;
     checks.push_back(PcvCheck{n, R, zm, a, Wa});                   // Protocol.hs:123
     checks.push_back(PcvCheck{n, R, fp_mul(ym, zm), b, Wb});       // :124
@@ -240,6 +281,35 @@ int sonic_verify(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t* wL
     return SONIC_OK;
   } catch (const HipFail& f) { return f.code; }
   catch (const std::exception& e) { set_error("%s", e.what()); return SONIC_ERR_HIP; }
+}
+
+extern "C" {
+
+// verify srs circuit proof y z yzs  (Protocol.hs:111-130); yzs = Q pairs (y_j, z_j), 64 bytes each
+int sonic_verify(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO,
+                 const uint8_t* cs, const uint8_t* proof, const uint8_t y[32], const uint8_t z[32], const uint8_t* yzs, int* accepted) {
+  if (!srs || n < 1 || Q < 1 || !wL || !wR || !wO || !cs || !proof || !y || !z || !yzs || !accepted) return SONIC_ERR_INVALID_ARG;
+  return verify_with(srs, n, Q, cs, proof, y, z, yzs, accepted,
+                     [&](const VerifierKey& vk, const std::vector<Fr>& ys, const std::vector<Fr>& zs, const std::vector<G1Affine>& Sj, const std::vector<Fr>& sj,
+                         const std::vector<G1Affine>& Wj, const std::vector<Fr>& spj, const std::vector<G1Affine>& Wpj, const std::vector<G1Affine>& Qj,
+                         const G1Affine& Qv, const G1Affine& C, const Fr& u, const Fr& v, std::vector<PcvCheck>& checks) {
+                       return hsc_checks(srs, vk, n, Q, wL, wR, wO, Q, ys, zs, Sj, sj, Wj, spj, Wpj, Qj, Qv, C, u, v, checks);
+                     });
+}
+
+// the same with sparse gate weights (csr.hpp): s(u, v) in O(nnz + n) instead of O(Q n)
+int sonic_verify_csr(const sonic_srs_t* srs, int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val,
+                     const uint8_t* cs, const uint8_t* proof, const uint8_t y[32], const uint8_t z[32], const uint8_t* yzs, int* accepted) {
+  if (!srs || n < 1 || Q < 1 || !row_ptr || !cs || !proof || !y || !z || !yzs || !accepted) { set_error("sonic_verify_csr: bad argument"); return SONIC_ERR_INVALID_ARG; }
+  *accepted = 0;
+  int rc = csr_validate("sonic_verify_csr", n, Q, row_ptr, col, val);
+  if (rc) return rc;
+  return verify_with(srs, n, Q, cs, proof, y, z, yzs, accepted,
+                     [&](const VerifierKey&, const std::vector<Fr>& ys, const std::vector<Fr>& zs, const std::vector<G1Affine>& Sj, const std::vector<Fr>& sj,
+                         const std::vector<G1Affine>& Wj, const std::vector<Fr>& spj, const std::vector<G1Affine>& Wpj, const std::vector<G1Affine>& Qj,
+                         const G1Affine& Qv, const G1Affine& C, const Fr& u, const Fr& v, std::vector<PcvCheck>& checks) {
+                       return hsc_checks_csr(srs, n, Q, row_ptr, col, val, Q, ys, zs, Sj, sj, Wj, spj, Wpj, Qj, Qv, C, u, v, checks);
+                     });
 }
 
 // what ties a Fiat-Shamir transcript to ONE reference string (fs.hpp): four G1 elements that determine x and alpha
@@ -319,6 +389,55 @@ int sonic_verify_fs(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t*
     std::vector<uint8_t> yzs(64 * (size_t)Q);
     for (int64_t j = 0; j < Q; j++) { memcpy(&yzs[64 * j], &ch[32 * (2 + j)], 32); memcpy(&yzs[64 * j + 32], &ch[32 * (2 + Q + j)], 32); }
     return sonic_verify(srs, n, Q, wL, wR, wO, cs, proof, &ch[0], &ch[32], yzs.data(), accepted);
+  } catch (const HipFail& f) { return f.code; }
+  catch (const std::exception& e) { set_error("%s", e.what()); return SONIC_ERR_HIP; }
+}
+
+// sonic_fs_circuit_digest (prove.hip) from the sparse rows: the 3Q rows streamed in order as the dense bytes they stand for (32 zero bytes per absent entry),
+// so that a proof made on either form verifies under either.  O(Q n) hashing, once per circuit.
+int sonic_fs_circuit_digest_csr(int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val, const uint8_t* cs, uint8_t out[32]) {
+  if (n < 1 || Q < 1 || !row_ptr || !cs || !out) { set_error("sonic_fs_circuit_digest_csr: bad argument (need n >= 1, Q >= 1)"); return SONIC_ERR_INVALID_ARG; }
+  int rc = csr_validate("sonic_fs_circuit_digest_csr", n, Q, row_ptr, col, val);
+  if (rc) return rc;
+  static const uint8_t zeros[32 * 1024] = {0};
+  Sha256 h;
+  h.update("sonic-hip/circuit/v1", 20);
+  FsTranscript::le64(h, n); FsTranscript::le64(h, Q);
+  auto gap = [&](int64_t cnt) {
+    for (; cnt > 0; cnt -= 1024) h.update(zeros, 32 * (size_t)(cnt < 1024 ? cnt : 1024));
+  };
+  for (int64_t r = 0; r < 3 * Q; r++) {
+    int64_t at = 0;
+    for (int64_t k = row_ptr[r]; k < row_ptr[r + 1]; k++) {
+      gap(col[k] - at);
+      h.update(val + 32 * k, 32);
+      at = col[k] + 1;
+    }
+    gap(n - at);
+  }
+  h.update(cs, (size_t)(32 * Q));
+  h.finish(out);
+  return SONIC_OK;
+}
+
+int sonic_verify_fs_csr(const sonic_srs_t* srs, int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val,
+                        const uint8_t* cs, const uint8_t* proof, int* accepted) {
+  try {
+    if (!srs || n < 1 || Q < 1 || !row_ptr || !cs || !proof || !accepted) { set_error("sonic_verify_fs_csr: bad argument"); return SONIC_ERR_INVALID_ARG; }
+    *accepted = 0;
+    uint8_t digest[32];
+    int rc = sonic_fs_circuit_digest_csr(n, Q, row_ptr, col, val, cs, digest);       // (validates the CSR)
+    if (rc) return rc;
+    uint8_t srs_id[32];
+    rc = sonic_fs_srs_id(srs, srs_id);
+    if (rc) return rc;
+    std::vector<uint8_t> ch(32 * (size_t)(4 + 2 * Q));
+    fs_challenges_of_proof(n, Q, srs_d(srs), digest, srs_id, proof, ch.data());
+    const uint8_t* uv = proof + sonic_proof_size(Q) - 64;
+    if (memcmp(uv, &ch[32 * (2 + 2 * Q)], 64) != 0) return SONIC_OK;          // u, v are not this transcript's: rejected
+    std::vector<uint8_t> yzs(64 * (size_t)Q);
+    for (int64_t j = 0; j < Q; j++) { memcpy(&yzs[64 * j], &ch[32 * (2 + j)], 32); memcpy(&yzs[64 * j + 32], &ch[32 * (2 + Q + j)], 32); }
+    return sonic_verify_csr(srs, n, Q, row_ptr, col, val, cs, proof, &ch[0], &ch[32], yzs.data(), accepted);
   } catch (const HipFail& f) { return f.code; }
   catch (const std::exception& e) { set_error("%s", e.what()); return SONIC_ERR_HIP; }
 }

@@ -12,6 +12,7 @@ import numpy as np
 from . import _lib
 from .encoding import R_MODULUS, fr_array, fr_matrix, fr_to_bytes, g1_from_bytes, g1_to_bytes
 from .srs import SRS
+from .workload import csr_from_dense
 
 
 @dataclass
@@ -26,6 +27,68 @@ class ArithCircuit:          # Bulletproofs.ArithmeticCircuit.ArithCircuit (comm
     weights: GateWeights
     cs: list
     commitmentWeights: object = None
+
+
+class SparseCircuit:
+    """ArithCircuit with its gate weights as ONE CSR of 3Q rows (include/sonic_hip.h, "gate weights as CSR"): rows 0..Q-1 are wL, Q..2Q-1
+    wR, 2Q..3Q-1 wO; column i is gate i + 1 of the reference.  row_ptr int64 [3Q + 1], col int64 [nnz] (strictly increasing within a
+    row), val uint8 [nnz, 32] canonical Fr, cs uint8 [Q, 32].  Every entry point that takes an ArithCircuit takes this too, with the same
+    result bytes as for the densified circuit; the cost of the circuit's part of a proof follows nnz + n instead of Q n."""
+
+    def __init__(self, n: int, Q: int, row_ptr, col, val, cs):
+        self.n, self.Q = int(n), int(Q)
+        self.row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64).reshape(-1)
+        self.col = np.ascontiguousarray(col, dtype=np.int64).reshape(-1)
+        self.val = fr_array(val)
+        self.cs = fr_array(cs)
+        if self.n < 1 or self.Q < 1 or self.row_ptr.shape[0] != 3 * self.Q + 1 or self.cs.shape[0] != self.Q:
+            raise ValueError("SparseCircuit: need n >= 1, Q >= 1, 3Q + 1 row pointers and Q constants")
+        if self.col.shape[0] != self.val.shape[0]:
+            raise ValueError("SparseCircuit: col and val differ in length")
+
+    @property
+    def nnz(self) -> int:
+        return int(self.col.shape[0])
+
+    @classmethod
+    def from_dense(cls, n: int, Q: int, wL, wR, wO, cs) -> "SparseCircuit":
+        """from the dense encodings (uint8 [Q * n, 32] or [Q, n, 32] each): every non-zero entry, in row order"""
+        row_ptr, col, val = csr_from_dense(fr_matrix(wL), fr_matrix(wR), fr_matrix(wO), n, Q)
+        return cls(n, Q, row_ptr, col, val, fr_array(cs))
+
+    @classmethod
+    def from_circuit(cls, circuit: "ArithCircuit") -> "SparseCircuit":
+        """the non-zero entries of an ArithCircuit's weights"""
+        wL, wR, wO, cs, n, Q = _circuit_arrays(circuit)
+        return cls.from_dense(n, Q, wL, wR, wO, cs)
+
+    @classmethod
+    def from_rows(cls, n: int, wL_rows, wR_rows, wO_rows, cs) -> "SparseCircuit":
+        """from per-row {gate index (0-based): value} mappings, Q of them per matrix; zero values are kept as explicit entries"""
+        rows = list(wL_rows) + list(wR_rows) + list(wO_rows)
+        Q = len(rows) // 3
+        if len(rows) != 3 * Q or len(list(wL_rows)) != Q:
+            raise ValueError("SparseCircuit.from_rows: wL, wR, wO need the same number of rows")
+        row_ptr = np.zeros(3 * Q + 1, np.int64)
+        cols, vals = [], []
+        for r, row in enumerate(rows):
+            items = sorted((int(k), v) for k, v in dict(row).items())
+            cols.extend(k for k, _ in items)
+            vals.extend(v for _, v in items)
+            row_ptr[r + 1] = row_ptr[r] + len(items)
+        return cls(n, Q, row_ptr, np.array(cols, np.int64), fr_array(vals), fr_array(cs))
+
+    def to_dense(self) -> "ArithCircuit":
+        """the ArithCircuit the rows stand for (weights as uint8 [Q, n, 32] arrays, cs as uint8 [Q, 32])"""
+        W = np.zeros((3 * self.Q, self.n, 32), np.uint8)
+        rows = np.repeat(np.arange(3 * self.Q), np.diff(self.row_ptr))
+        W[rows, self.col] = self.val
+        return ArithCircuit(GateWeights(W[:self.Q], W[self.Q:2 * self.Q], W[2 * self.Q:]), self.cs.copy())
+
+    def _args(self):
+        """(row_ptr, col, val) pointers for the C ABI (NULL col / val when there are no entries)"""
+        ptr = lambda a: a.ctypes.data if a.shape[0] else None      # noqa: E731
+        return self.row_ptr.ctypes.data, ptr(self.col), ptr(self.val)
 
 
 @dataclass
@@ -140,6 +203,14 @@ class Prover:
     """Circuit (and assignment) resident in HBM across proofs: sonic_prover_* of the C ABI."""
 
     def __init__(self, srs: SRS, circuit: ArithCircuit, prepare: bool = True):
+        if isinstance(circuit, SparseCircuit):             # gate weights as CSR (sonic_prover_new_csr)
+            self.Q, self.n = circuit.Q, circuit.n
+            self._srs = srs
+            self._h = C.c_void_p()
+            _lib.check(_lib.lib().sonic_prover_new_csr(srs._h, self.n, self.Q, *circuit._args(), circuit.cs.ctypes.data, C.byref(self._h)))
+            if prepare:
+                _lib.check(_lib.lib().sonic_prover_prepare(self._h))
+            return
         w = circuit.weights
         wL, wR, wO = fr_matrix(w.wL), fr_matrix(w.wR), fr_matrix(w.wO)
         cs = fr_array(circuit.cs)
@@ -375,6 +446,8 @@ class ProverPipeline:
 def prove(srs: SRS, assignment: Assignment, circuit: ArithCircuit, transcript: Optional[list] = None, rng=None):
     """prove :: SRS -> Assignment Fr -> ArithCircuit Fr -> m (Proof, RndOracle) (Protocol.hs:47-52).
     `transcript` makes the MonadRandom draws explicit (reproducible proofs); default: fresh draws."""
+    if isinstance(circuit, SparseCircuit):
+        return _prove_sparse(srs, assignment, circuit, transcript, rng)
     n = len(assignment.aL) if not isinstance(assignment.aL, np.ndarray) else fr_array(assignment.aL).shape[0]
     Q = fr_array(circuit.cs).shape[0]
     if srs.srsD < 7 * n:   # Protocol.hs:54-55 (checked again by the library)
@@ -400,6 +473,27 @@ def prove(srs: SRS, assignment: Assignment, circuit: ArithCircuit, transcript: O
     return Proof.from_bytes(raw, Q), oracle
 
 
+def _prove_sparse(srs: SRS, assignment: Assignment, circuit: SparseCircuit, transcript, rng):
+    """prove for gate weights as CSR (sonic_prove_csr: the one-shot call, sharing sonic_prove's parked shells)"""
+    n, Q = circuit.n, circuit.Q
+    if srs.srsD < 7 * n:   # Protocol.hs:54-55 (checked again by the library)
+        raise _lib.SonicError(1, f"Parameter d is not large enough: {srs.srsD} should be greater than {7 * n}")
+    if transcript is None:
+        transcript = draw_transcript(Q, rng)
+    aL, aR, aO = fr_array(assignment.aL), fr_array(assignment.aR), fr_array(assignment.aO)
+    if aL.shape[0] != n or aR.shape[0] != n or aO.shape[0] != n:
+        raise ValueError("assignment and circuit differ in length")
+    tr = fr_array(transcript)
+    if tr.shape[0] != 8 + 2 * Q:
+        raise ValueError(f"transcript needs 8 + 2Q = {8 + 2 * Q} elements")
+    out = C.create_string_buffer(_lib.lib().sonic_proof_size(Q))
+    _lib.check(_lib.lib().sonic_prove_csr(srs._h, n, Q, *circuit._args(), circuit.cs.ctypes.data,
+                                          aL.ctypes.data, aR.ctypes.data, aO.ctypes.data, tr.ctypes.data, out))
+    t = [int(v) % R_MODULUS for v in transcript]
+    oracle = RndOracle(t[4], t[5], list(zip(t[6:6 + Q], t[6 + Q:6 + 2 * Q])))
+    return Proof.from_bytes(out.raw, Q), oracle
+
+
 def _circuit_arrays(circuit: ArithCircuit):
     w = circuit.weights
     wL, wR, wO = fr_matrix(w.wL), fr_matrix(w.wR), fr_matrix(w.wO)
@@ -412,6 +506,10 @@ def _circuit_arrays(circuit: ArithCircuit):
 
 def fs_circuit_digest(circuit: ArithCircuit) -> bytes:
     """SHA-256 of (n, Q, wL, wR, wO, cs): the statement part of the Fiat-Shamir transcript, once per circuit"""
+    if isinstance(circuit, SparseCircuit):             # the same digest from the rows (sonic_fs_circuit_digest_csr; host only)
+        out = C.create_string_buffer(32)
+        _lib.check(_lib.lib().sonic_fs_circuit_digest_csr(circuit.n, circuit.Q, *circuit._args(), circuit.cs.ctypes.data, out))
+        return out.raw
     wL, wR, wO, cs, n, Q = _circuit_arrays(circuit)
     out = C.create_string_buffer(32)
     _lib.check(_lib.lib().sonic_fs_circuit_digest(n, Q, wL.ctypes.data, wR.ctypes.data, wO.ctypes.data, cs.ctypes.data, out))
@@ -427,7 +525,10 @@ def fs_srs_id(srs: SRS) -> bytes:
 
 def fs_challenges(srs: SRS, circuit: ArithCircuit, proof: Proof) -> RndOracle:
     """the RndOracle a Fiat-Shamir proof determines (sonic_fs_challenges_v2)"""
-    wL, wR, wO, cs, n, Q = _circuit_arrays(circuit)
+    if isinstance(circuit, SparseCircuit):
+        n, Q = circuit.n, circuit.Q
+    else:
+        wL, wR, wO, cs, n, Q = _circuit_arrays(circuit)
     raw = proof.to_bytes()
     if len(raw) != _lib.lib().sonic_proof_size(Q):
         raise ValueError("fs_challenges: the proof does not have Q entries in its hsc lists")
@@ -453,6 +554,13 @@ def prove_fs(srs: SRS, assignment: Assignment, circuit: ArithCircuit, blinder_se
 
 def verify_fs(srs: SRS, circuit: ArithCircuit, proof: Proof) -> bool:
     """verify for a Fiat-Shamir proof: the challenges are recomputed from the circuit and the proof (sonic_verify_fs)"""
+    if isinstance(circuit, SparseCircuit):
+        h = proof.prHscProof
+        if len(h.hscS) != circuit.Q or len(h.hscW) != circuit.Q:
+            return False
+        ok = C.c_int(0)
+        _lib.check(_lib.lib().sonic_verify_fs_csr(srs._h, circuit.n, circuit.Q, *circuit._args(), circuit.cs.ctypes.data, proof.to_bytes(), C.byref(ok)))
+        return bool(ok.value)
     wL, wR, wO, cs, n, Q = _circuit_arrays(circuit)
     h = proof.prHscProof
     if len(h.hscS) != Q or len(h.hscW) != Q:
@@ -559,6 +667,8 @@ def verify(srs: SRS, circuit: ArithCircuit, proof: Proof, y: int, z: int, yzs) -
     hscVerify (Signature.hs:74-90).  Runs on the host CPU (pairings); the SRS needs its G2 half (SRS.new, or a file
     that carries it).  Shapes are checked here because the C side reads 64 Q bytes of yzs and sonic_proof_size(Q)
     bytes of proof; a Proof whose hsc lists do not have Q entries is rejected (False), like any other malformed proof."""
+    if isinstance(circuit, SparseCircuit):
+        return _verify_sparse(srs, circuit, proof, y, z, yzs)
     w = circuit.weights
     wL, wR, wO = fr_matrix(w.wL), fr_matrix(w.wR), fr_matrix(w.wO)
     cs = fr_array(circuit.cs)
@@ -579,4 +689,23 @@ def verify(srs: SRS, circuit: ArithCircuit, proof: Proof, y: int, z: int, yzs) -
     ok = C.c_int(0)
     _lib.check(_lib.lib().sonic_verify(srs._h, n, Q, wL.ctypes.data, wR.ctypes.data, wO.ctypes.data, cs.ctypes.data, raw,
                                        fr_to_bytes(y), fr_to_bytes(z), flat.ctypes.data, C.byref(ok)))
+    return bool(ok.value)
+
+
+def _verify_sparse(srs: SRS, circuit: SparseCircuit, proof: Proof, y: int, z: int, yzs) -> bool:
+    """verify for gate weights as CSR (sonic_verify_csr: s(u, v) in O(nnz + n) on the host)"""
+    Q = circuit.Q
+    yzs = list(yzs)
+    if len(yzs) != Q or any(len(pair) != 2 for pair in yzs):
+        raise ValueError(f"verify: yzs must hold {Q} (y_j, z_j) pairs, got {len(yzs)}")
+    h = proof.prHscProof
+    if len(h.hscS) != Q or len(h.hscW) != Q:
+        return False
+    raw = proof.to_bytes()
+    if len(raw) != _lib.lib().sonic_proof_size(Q):
+        return False
+    flat = fr_array([v for pair in yzs for v in pair])
+    ok = C.c_int(0)
+    _lib.check(_lib.lib().sonic_verify_csr(srs._h, circuit.n, Q, *circuit._args(), circuit.cs.ctypes.data, raw,
+                                           fr_to_bytes(y), fr_to_bytes(z), flat.ctypes.data, C.byref(ok)))
     return bool(ok.value)

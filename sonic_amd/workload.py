@@ -45,6 +45,47 @@ def big_circuit(seed: int, n: int, Q: int, orc=None):
                 rows=[int(r_) for r_ in rows], ints=(la, lb, lo), cs_ints=cs)
 
 
+def csr_from_dense(wL, wR, wO, n: int, Q: int):
+    """the dense weight arrays (uint8 [Q * n, 32] each, as big_circuit returns them) as ONE CSR of 3Q rows (include/sonic_hip.h):
+    (row_ptr int64 [3Q + 1], col int64 [nnz], val uint8 [nnz, 32]) with every non-zero entry, rows in order"""
+    W = np.concatenate([np.asarray(w, np.uint8).reshape(-1, 32) for w in (wL, wR, wO)]).reshape(3 * Q, n, 32)
+    nz = W.any(axis=2)
+    rows, cols = np.nonzero(nz)
+    row_ptr = np.zeros(3 * Q + 1, np.int64)
+    np.cumsum(nz.sum(axis=1), out=row_ptr[1:])
+    return row_ptr, cols.astype(np.int64), np.ascontiguousarray(W[rows, cols])
+
+
+def sparse_circuit(seed: int, n: int, Q: int, nnz_per_row: int = 4):
+    """a SATISFIED random circuit with at most `nnz_per_row` non-zero weights per row of wL, wR, wO (distinct random gates, uniform
+    values), as CSR: aL, aR uniform, aO = aL * aR, and cs_q = sum over row q's entries of wL aL + wR aR + wO aO (what big_circuit does
+    for its rows) -- so that t(X,y) has no constant term.  Every row draws its entry count from 0 .. nnz_per_row, so some rows are
+    empty.  Returns dict(row_ptr, col, val, cs, aL, aR, aO, n, Q, nnz)."""
+    rng = np.random.default_rng(seed)
+    aL = rand_fr_array(rng, n)
+    aR = rand_fr_array(rng, n)
+    counts = rng.integers(0, min(nnz_per_row, n) + 1, size=3 * Q)
+    row_ptr = np.zeros(3 * Q + 1, np.int64)
+    np.cumsum(counts, out=row_ptr[1:])
+    nnz = int(row_ptr[-1])
+    col = np.zeros(nnz, np.int64)
+    for r in range(3 * Q):
+        if counts[r]:
+            col[row_ptr[r]:row_ptr[r + 1]] = np.sort(rng.choice(n, size=int(counts[r]), replace=False))
+    val = rand_fr_array(rng, nnz)
+    la = [int.from_bytes(aL[i].tobytes(), "little") for i in range(n)]
+    lb = [int.from_bytes(aR[i].tobytes(), "little") for i in range(n)]
+    lo = [a * b % R for a, b in zip(la, lb)]
+    aO = fr_bytes(lo)
+    cs = [0] * Q
+    for r in range(3 * Q):
+        m, q = divmod(r, Q)
+        a = (la, lb, lo)[m]
+        for k in range(int(row_ptr[r]), int(row_ptr[r + 1])):
+            cs[q] = (cs[q] + int.from_bytes(val[k].tobytes(), "little") * a[int(col[k])]) % R
+    return dict(row_ptr=row_ptr, col=col, val=val, cs=fr_bytes(cs), aL=aL, aR=aR, aO=aO, n=n, Q=Q, nnz=nnz)
+
+
 def wt_quotient_scalars(sonic, seed: int, n: int, Q: int = 2):
     """The scalars the protocol itself hands to its two largest kinds of MSM, for a rndCircuit statement (bench.py `msm_protocol_shaped`,
     SURVEY 8d "protocol-shaped scalar set"):
