@@ -176,72 +176,54 @@ int flags_to_status(int f, const char* who) {
   return SONIC_OK;
 }
 
-// the circuit of a handle: Q x n weights and Q constants, uploaded and brought to Montgomery form (sonic_prover_new; the one-shot
-// sonic_prove re-uses a cached shell by loading the next call's circuit into it)
-// 32 tiles of RUN_TILE consecutive gate indices, spread over [0, n): a tile counts when every row of wL AND of wR repeats one value across
-// it -- then s(X, y) has a run of equal coefficients there (u_i = sum_q wL[q][i] y^{n+q}, Constraints.hs:39-49) -- and the circuit "has
-// runs" when at least a quarter of the sampled tiles do.  ~0.5 MB read at Q = 2, microseconds.
-bool circuit_runs_hint(const uint8_t* wL, const uint8_t* wR, long n, long Q) {
-  const long ntiles = n / RUN_TILE;
-  if (ntiles < 1) return false;
-  const long samples = ntiles < 32 ? ntiles : 32;
-  long uniform = 0;
-  for (long sidx = 0; sidx < samples; sidx++) {
-    const long t = sidx * ntiles / samples;
-    bool uni = true;
-    for (int m = 0; m < 2 && uni; m++) {
-      const uint8_t* w = m ? wR : wL;
-      for (long q = 0; q < Q && uni; q++) {
-        const uint8_t* row = w + 32 * (q * n + t * RUN_TILE);
-        for (long i = 1; i < RUN_TILE && uni; i++) uni = memcmp(row, row + 32 * i, 32) == 0;
-      }
-    }
-    uniform += uni ? 1 : 0;
-  }
-  return 4 * uniform >= samples;
+// the circuit of a handle: uploaded and brought to Montgomery form -- Q x n weights per matrix, or the sparse form (csr.hpp) laid out on
+// the host: both orientations and the chunk table -- and Q constants.  A call hands its circuit over (prover_hand_over: p->pend), and
+// prover_upload_circuit queues its upload: at once when a handle is made, inside the proof when a one-shot call re-uses a parked shell.
+void prover_hand_over(sonic_prover_t* p, const CircuitView& c) {
+  p->circuit_has_runs = circuit_runs_hint(c, RUN_TILE);
+  p->pend.view = c;
+  if (c.csr) csr_layout(c, p->pend.layout);
+  p->pend.set = true;
 }
 
-static int prover_load_circuit(sonic_prover* p, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO, const uint8_t* cs) {
-  hipStream_t st = p->st;
-  const long n = p->n, Q = p->Q;
-  p->circuit_has_runs = circuit_runs_hint(wL, wR, n, Q);
-  HIP_OK(hipMemsetAsync(p->flags.p, 0, 4, st));
-  upload_fr_mont(st, p->wL, wL, Q * n, p->flags.as<int>());
-  upload_fr_mont(st, p->wR, wR, Q * n, p->flags.as<int>());
-  upload_fr_mont(st, p->wO, wO, Q * n, p->flags.as<int>());
-  upload_fr_mont(st, p->cs, cs, Q, p->flags.as<int>());
-  int f = read_flags(st, p->flags);
-  if (f) return flags_to_status(f, "sonic_prover_new");
-  return SONIC_OK;
-}
-
-// the sparse form (csr.hpp), laid out on the host: both orientations and the chunk table, values to Montgomery form on the way
 static void upload_i32(hipStream_t st, DevBuf& dst, const std::vector<int32_t>& src) {
   dst.ensure(sizeof(int32_t) * (src.empty() ? 1 : src.size()));
   if (!src.empty()) HIP_OK(hipMemcpyAsync(dst.p, src.data(), sizeof(int32_t) * src.size(), hipMemcpyHostToDevice, st));
 }
-void prover_upload_csr(sonic_prover_t* p, hipStream_t st, const CsrLayout& L, int* d_flags) {
-  sonic_prover::CsrBufs& b = p->sp;
-  upload_i32(st, b.row_ptr, L.row_ptr); upload_i32(st, b.col, L.col);
-  upload_i32(st, b.col_ptr, L.col_ptr); upload_i32(st, b.row, L.row);
-  upload_i32(st, b.chunk_row, L.chunk_row); upload_i32(st, b.chunk_begin, L.chunk_begin); upload_i32(st, b.row_chunk, L.row_chunk);
-  upload_fr_mont(st, b.val, L.val, L.nnz, d_flags);
-  upload_fr_mont(st, b.cval, L.cval.data(), L.nnz, d_flags);
-  upload_fr_mont(st, p->cs, L.cs, L.Q, d_flags);
-  b.nnz = L.nnz;
-  b.nchunks = (long)L.chunk_row.size();
-  b.partial.ensure(sizeof(Fr) * (b.nchunks > 0 ? b.nchunks : 1));
-  b.h_row_ptr = L.row_ptr;
+// (flags: non-canonical values.  The host buffers of p->pend are read until `st` has drained: the caller clears it after that)
+static void prover_upload_circuit(sonic_prover_t* p, hipStream_t st, int* d_flags) {
+  const CircuitView& c = p->pend.view;
+  const long n = p->n, Q = p->Q;
+  if (c.csr) {
+    const CsrLayout& L = p->pend.layout;
+    sonic_prover::CsrBufs& b = p->sp;
+    upload_i32(st, b.row_ptr, L.row_ptr); upload_i32(st, b.col, L.col);
+    upload_i32(st, b.col_ptr, L.col_ptr); upload_i32(st, b.row, L.row);
+    upload_i32(st, b.chunk_row, L.chunk_row); upload_i32(st, b.chunk_begin, L.chunk_begin); upload_i32(st, b.row_chunk, L.row_chunk);
+    upload_fr_mont(st, b.val, c.val, L.nnz, d_flags);
+    upload_fr_mont(st, b.cval, L.cval.data(), L.nnz, d_flags);
+    b.nnz = L.nnz;
+    b.nchunks = (long)L.chunk_row.size();
+    b.partial.ensure(sizeof(Fr) * (b.nchunks > 0 ? b.nchunks : 1));
+    b.h_row_ptr = L.row_ptr;
+  } else {
+    upload_fr_mont(st, p->wL, c.wL, Q * n, d_flags);
+    upload_fr_mont(st, p->wR, c.wR, Q * n, d_flags);
+    upload_fr_mont(st, p->wO, c.wO, Q * n, d_flags);
+  }
+  upload_fr_mont(st, p->cs, c.cs, Q, d_flags);
+  p->csr = c.csr;
+  p->pend.set = false;
 }
 
-static int prover_load_circuit_csr(sonic_prover* p, const CsrLayout& L) {
+static int prover_load_circuit(sonic_prover* p, const CircuitView& c) {
   hipStream_t st = p->st;
-  p->csr = true;
-  p->circuit_has_runs = circuit_runs_hint_csr(L, RUN_TILE);
+  prover_hand_over(p, c);
   HIP_OK(hipMemsetAsync(p->flags.p, 0, 4, st));
-  prover_upload_csr(p, st, L, p->flags.as<int>());
-  int f = read_flags(st, p->flags);          // (also: the pageable host buffers of L have been read when this returns)
-  if (f) return flags_to_status(f, "sonic_prover_new_csr");
+  prover_upload_circuit(p, st, p->flags.as<int>());
+  int f = read_flags(st, p->flags);          // (also: the pageable host buffers of the layout have been read when this returns)
+  p->pend = sonic_prover::PendingCircuit();
+  if (f) return flags_to_status(f, c.csr ? "sonic_prover_new_csr" : "sonic_prover_new");
   return SONIC_OK;
 }
 
@@ -256,8 +238,6 @@ static void s_of_u_of(sonic_prover* p, hipStream_t st, const Fr* upow, Fr* out) 
                                  b.nchunks, b.row_chunk.as<int32_t>(), upow, p->n, p->Q, out, b.partial.as<Fr>());
   else s_of_u_enqueue(st, p->wL.as<Fr>(), p->wR.as<Fr>(), p->wO.as<Fr>(), upow, p->n, p->Q, out, p->tmp);
 }
-
-static int prover_new_impl(const sonic_srs_t* srs, int64_t n, int64_t Q, const std::function<int(sonic_prover*)>& load_circuit, sonic_prover_t** out);
 
 extern "C" {
 
@@ -279,41 +259,41 @@ int sonic_srs_new_on(int device, int64_t d, const uint8_t x[32], const uint8_t a
 
 size_t sonic_proof_size(int64_t Q) { return (size_t)((7 + 4 * Q) * 96 + (5 + 2 * Q) * 32); }
 
-int sonic_prover_new(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO,
-                     const uint8_t* cs, sonic_prover_t** out) {
+static int prover_new_entry(const char* who, const sonic_srs_t* srs, const CircuitView& c, sonic_prover_t** out) {
   API_BEGIN_ON(srs_device(srs))
-  if (!srs || n < 1 || Q < 1 || !wL || !wR || !wO || !cs || !out) { set_error("sonic_prover_new: bad argument (need n >= 1, Q >= 1)"); return SONIC_ERR_INVALID_ARG; }
-  if (srs_d(srs) < 7 * n) {                                                   // Protocol.hs:54-55
-    set_error("Parameter d is not large enough: %ld should be greater than %ld", (long)srs_d(srs), (long)(7 * n));
-    return SONIC_ERR_D_TOO_SMALL;
-  }
-  return prover_new_impl(srs, n, Q, [&](sonic_prover* p) { return prover_load_circuit(p, wL, wR, wO, cs); }, out);
+  if (!srs || !c.cs || !out) { set_error("%s: bad argument (need n >= 1, Q >= 1)", who); return SONIC_ERR_INVALID_ARG; }
+  int rc = prover_admits(who, srs, c);
+  if (rc) return rc;
+  return prover_new_impl(srs, c, out);
   API_END
 }
-
+int sonic_prover_new(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO,
+                     const uint8_t* cs, sonic_prover_t** out) {
+  return prover_new_entry("sonic_prover_new", srs, dense_view(n, Q, wL, wR, wO, cs), out);
+}
 int sonic_prover_new_csr(const sonic_srs_t* srs, int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val,
                          const uint8_t* cs, sonic_prover_t** out) {
-  API_BEGIN_ON(srs_device(srs))
-  if (!srs || n < 1 || Q < 1 || !row_ptr || !cs || !out) { set_error("sonic_prover_new_csr: bad argument (need n >= 1, Q >= 1)"); return SONIC_ERR_INVALID_ARG; }
-  if (srs_d(srs) < 7 * n) {                                                   // Protocol.hs:54-55
-    set_error("Parameter d is not large enough: %ld should be greater than %ld", (long)srs_d(srs), (long)(7 * n));
-    return SONIC_ERR_D_TOO_SMALL;
-  }
-  int rc = csr_validate("sonic_prover_new_csr", n, Q, row_ptr, col, val);
-  if (rc) return rc;
-  for (long q = 0; q < Q; q++) {
-    Fr c; memcpy(c.l, cs + 32 * q, 32);
-    if (!fp_is_canonical(c)) { set_error("sonic_prover_new_csr: non-canonical constant cs[%ld]", q); return SONIC_ERR_BAD_ENCODING; }
-  }
-  CsrLayout L;
-  csr_layout(n, Q, row_ptr, col, val, cs, L);
-  return prover_new_impl(srs, n, Q, [&](sonic_prover* p) { return prover_load_circuit_csr(p, L); }, out);
-  API_END
+  return prover_new_entry("sonic_prover_new_csr", srs, csr_view(n, Q, row_ptr, col, val, cs), out);
 }
 
 }  // extern "C"
 
-static int prover_new_impl(const sonic_srs_t* srs, int64_t n, int64_t Q, const std::function<int(sonic_prover*)>& load_circuit, sonic_prover_t** out) {
+// the circuit's arguments, Protocol.hs:54-55, then the circuit's own checks (csr.hpp), in the order the entry points always had them
+int prover_admits(const char* who, const sonic_srs* srs, const CircuitView& c) {
+  if (circuit_args_ok(c) && srs_d(srs) < 7 * c.n) {
+    set_error("Parameter d is not large enough: %ld should be greater than %ld", (long)srs_d(srs), (long)(7 * c.n));
+    return SONIC_ERR_D_TOO_SMALL;
+  }
+  return circuit_validate(who, c);
+}
+
+// (an admitted circuit)
+int prover_new_impl(const sonic_srs_t* srs, const CircuitView& c, sonic_prover_t** out) {
+  const long n = c.n, Q = c.Q;
+  for (long q = 0; c.csr && q < Q; q++) {
+    Fr k; memcpy(k.l, c.cs + 32 * q, 32);
+    if (!fp_is_canonical(k)) { set_error("sonic_prover_new_csr: non-canonical constant cs[%ld]", q); return SONIC_ERR_BAD_ENCODING; }
+  }
   std::unique_ptr<sonic_prover> p(new sonic_prover());
   p->srs = srs; p->n = n; p->Q = Q;
   p->device = srs_device(srs);
@@ -333,7 +313,7 @@ static int prover_new_impl(const sonic_srs_t* srs, int64_t n, int64_t Q, const s
   mkstream(&p->ts, prio_high);
   hipStream_t st = p->st;
   p->flags.alloc(8);
-  int rc_c = load_circuit(p.get());
+  int rc_c = prover_load_circuit(p.get(), c);
   if (rc_c) return rc_c;
   // workspaces
   const long tlen = 7 * n + 9;
@@ -509,7 +489,7 @@ static int prove_enqueue(sonic_prover_t* p, const uint8_t* transcript) {
   const int KS = p->sym_on ? K + (int)Q + 1 : K + ((p->prepared || p->runs_on) ? (int)Q : 0);        // + the second halves of the S_j and of C
   // Launch-bound sizes replay the whole multi-stream enqueue as one hipGraph: captured on the second proof of a handle (the
   // first one grows the workspaces), every address in it is owned by the handle.
-  const bool pending = p->pend_circuit[0] != nullptr || p->pend_csr || p->pend_asg[0] != nullptr;
+  const bool pending = p->pend.set || p->pend_asg[0] != nullptr;
   const bool want_graph = p->use_graph && p->proofs_done >= 1 && !profiler().on && p->phases == PH_ALL && !pending;
   const bool replay = want_graph && p->graph != nullptr;
   const bool capturing = want_graph && !replay && !p->graph_tried;
@@ -679,20 +659,9 @@ static int prove_enqueue(sonic_prover_t* p, const uint8_t* transcript) {
     flush_group(last_group == 0);
   };
   if (p->few_streams && p->fused) group0();          // (its openings go on the transform's stream, ahead of the product's kernels)
-  if (p->pend_circuit[0]) {
+  if (p->pend.set) {
     group0();
-    const uint8_t* const* c = p->pend_circuit;
-    upload_fr_mont(ms, p->wL, c[0], Q * n, flags + 1);
-    upload_fr_mont(ms, p->wR, c[1], Q * n, flags + 1);
-    upload_fr_mont(ms, p->wO, c[2], Q * n, flags + 1);
-    upload_fr_mont(ms, p->cs, c[3], Q, flags + 1);
-    p->pend_circuit[0] = nullptr;
-    p->csr = false;
-  } else if (p->pend_csr) {                                    // (the same for a sparse circuit: sonic_prove_csr)
-    group0();
-    prover_upload_csr(p, ms, p->pend_csr_layout, flags + 1);
-    p->pend_csr = false;
-    p->csr = true;
+    prover_upload_circuit(p, ms, flags + 1);
   }
   // s(X,y)                                                                           Protocol.hs:69-70
   if (need_T && on(PH_T)) {
@@ -976,6 +945,19 @@ extern "C" int sonic_proof_from_shares(int64_t Q, int world, const uint8_t* shar
   return SONIC_OK;
 }
 
+// host tails: with window tables a slot holds ONE window sum and there is nothing to fold; without them the Horner walks over <= 64
+// window sums (255 doublings each) run on up to max_threads threads
+static bool slots_folded(const MsmSlot* hs, long K) {
+  for (long i = 0; i < K; i++) if (hs[i].W > 1 && hs[i].pad1 == 0) return false;
+  return true;
+}
+static void finish_slots_host(const MsmSlot* hs, long K, G1XYZZ* out, int max_threads) {
+  const int nt = slots_folded(hs, K) ? 1 : (int)std::min<long>(K, max_threads);
+  ThreadGroup th;
+  for (int w = 1; w < nt; w++) th.emplace_back([=] { for (long i = w; i < K; i += nt) out[i] = msm_finish_host(hs[i]); });
+  for (long i = 0; i < K; i += nt) out[i] = msm_finish_host(hs[i]);
+}
+
 static int prove_finish(sonic_prover_t* p, uint8_t* out_proof) {
   API_BEGIN_ON(p->device)
   const long Q = p->Q;
@@ -996,8 +978,7 @@ static int prove_finish(sonic_prover_t* p, uint8_t* out_proof) {
   if (hflags) return flags_to_status(hflags, "prove");
   std::vector<uint8_t> pts(96 * (size_t)K);
   {
-    // host tails: with window tables a slot holds ONE window sum and there is nothing to fold; without them the Horner walks
-    // over <= 64 window sums (255 doublings each) run on threads.  One shared inversion normalises all results.
+    // host tails (finish_slots_host).  One shared inversion normalises all results.
     auto t0 = std::chrono::steady_clock::now();
     std::vector<G1XYZZ> sums((size_t)K);
     // S_j = slot 5 + 2j + slot K + j on a prepared handle (sum_q y_j^{n+q} C_q) and on one that takes the runs of equal coefficients
@@ -1005,28 +986,13 @@ static int prove_finish(sonic_prover_t* p, uint8_t* out_proof) {
     // sonic_prover_prove_fs: not tied to this pass's slot_ran; a slot whose MSM never ran is W = 0, the empty sum.
     const bool has_extra = p->prepared || p->runs_on;
     std::vector<G1XYZZ> extra((size_t)(has_extra ? Q : 0));
-    auto is_folded = [&](int i) { return hs[i].W <= 1 || hs[i].pad1 != 0; };
-    bool main_folded = true, extra_folded = true;
-    for (int i = 0; i < K; i++) main_folded = main_folded && is_folded(i);
-    for (int j = 0; has_extra && j < (int)Q; j++) extra_folded = extra_folded && is_folded(K + j);
     ThreadGroup th;
     G1XYZZ extra_c = G1XYZZ::inf();                        // the Q-term half of C (per-window sums: a Horner walk, on a thread of its own)
     if (p->sym_on) th.emplace_back([&] { extra_c = msm_finish_host(hs[K + Q]); });
-    if (has_extra && !extra_folded) {                      // the Horner walks of the extra slots beside the main thread's tails
-      const int nt = (int)std::min<long>(Q, 8);
-      for (int w = 0; w < nt; w++) th.emplace_back([&, w] { for (long j = w; j < Q; j += nt) extra[(size_t)j] = msm_finish_host(hs[K + j]); });
-    } else if (has_extra) {
-      for (long j = 0; j < Q; j++) extra[(size_t)j] = msm_finish_host(hs[K + j]);
-    }
-    if (main_folded) {
-      for (int i = 0; i < K; i++) sums[i] = msm_finish_host(hs[i]);
-    } else {
-      ThreadGroup th2;
-      const int nt = K < 16 ? K : 16;
-      for (int w = 0; w < nt; w++) th2.emplace_back([&, w] { for (int i = w; i < K; i += nt) sums[i] = msm_finish_host(hs[i]); });
-      for (auto& x : th2) x.join();
-    }
-    for (auto& x : th) x.join();
+    if (has_extra && !slots_folded(hs + K, Q)) th.emplace_back([&] { finish_slots_host(hs + K, Q, extra.data(), 8); });      // the Horner walks of the extra slots beside the main thread's tails
+    else if (has_extra) finish_slots_host(hs + K, Q, extra.data(), 1);
+    finish_slots_host(hs, K, sums.data(), 16);
+    th.join();
     for (long j = 0; has_extra && j < Q; j++) sums[(size_t)(5 + 2 * j)] = g1_add(sums[(size_t)(5 + 2 * j)], extra[(size_t)j]);
     if (p->sym_on) sums[(size_t)(6 + 4 * Q)] = g1_add(sums[(size_t)(6 + 4 * Q)], extra_c);
     g1_canonical_bytes_host_batch(sums.data(), K, pts.data());
@@ -1150,14 +1116,9 @@ int sonic_prove_share_plan(int64_t n, int64_t Q, int prepared, int world, int ra
 // that chain in six passes over the same enqueue (prove_enqueue with one phase bit each): every MSM of the proof still runs
 // exactly once and every polynomial is built once, in the pass that first knows its challenge (round 4; it was rebuilt in every pass
 // before); between passes the host waits, reads the new elements' canonical bytes and hashes.  The caller-supplied transcript stays the default and fast path (one pass, no waits).
+// the statement part of the transcript, once per circuit (circuit_digest, csr.hpp; its sparse twin is in verify.hip)
 int sonic_fs_circuit_digest(int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO, const uint8_t* cs, uint8_t out[32]) {
-  if (n < 1 || Q < 1 || !wL || !wR || !wO || !cs || !out) return SONIC_ERR_INVALID_ARG;
-  Sha256 h;
-  h.update("sonic-hip/circuit/v1", 20);
-  FsTranscript::le64(h, n); FsTranscript::le64(h, Q);
-  h.update(wL, (size_t)(32 * Q * n)); h.update(wR, (size_t)(32 * Q * n)); h.update(wO, (size_t)(32 * Q * n)); h.update(cs, (size_t)(32 * Q));
-  h.finish(out);
-  return SONIC_OK;
+  return circuit_digest_checked("sonic_fs_circuit_digest", dense_view(n, Q, wL, wR, wO, cs), out);
 }
 
 int sonic_fs_challenges_v2(int64_t n, int64_t Q, int64_t d, const uint8_t circuit_digest[32], const uint8_t srs_id[32], const uint8_t* proof, uint8_t* out) {
@@ -1302,11 +1263,9 @@ int sonic_prover_prepare(sonic_prover_t* p) {
   if (hflags) return flags_to_status(hflags, "sonic_prover_prepare");
   std::vector<G1Affine> cq(Q);
   {
-    ThreadGroup th;
-    const int nt = (int)std::min<long>(Q, 16);
-    for (int w = 0; w < nt; w++)
-      th.emplace_back([&, w] { for (long q = w; q < Q; q += nt) cq[q] = g1_to_affine(msm_finish_host(hs[q])); });
-    for (auto& x : th) x.join();
+    std::vector<G1XYZZ> sums((size_t)Q);
+    finish_slots_host(hs.data(), Q, sums.data(), 16);
+    g1_batch_affine_host(sums.data(), Q, cq.data());
   }
   p->cq.alloc(sizeof(G1Affine) * Q);
   HIP_OK(hipMemcpy(p->cq.p, cq.data(), sizeof(G1Affine) * Q, hipMemcpyHostToDevice));
@@ -1423,16 +1382,7 @@ int sonic_prover_hsc_prove(sonic_prover_t* p, int64_t m, const uint8_t* yzs, con
   std::vector<uint8_t> pts(96 * (size_t)K);
   {
     std::vector<G1XYZZ> sums((size_t)K);
-    bool folded = true;
-    for (long i = 0; i < K; i++) folded = folded && (hs[i].W == 1 || hs[i].pad1 != 0);
-    if (folded) {
-      for (long i = 0; i < K; i++) sums[i] = msm_finish_host(hs[i]);
-    } else {
-      ThreadGroup th;
-      const int nt = (int)std::min<long>(K, 16);
-      for (int w = 0; w < nt; w++) th.emplace_back([&, w] { for (long i = w; i < K; i += nt) sums[i] = msm_finish_host(hs[i]); });
-      for (auto& x : th) x.join();
-    }
+    finish_slots_host(hs.data(), K, sums.data(), 16);
     g1_canonical_bytes_host_batch(sums.data(), (int)K, pts.data());
   }
   uint8_t* o = out;

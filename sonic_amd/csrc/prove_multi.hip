@@ -46,34 +46,19 @@ int sonic_one_shot_trim(int device) {
   return freed;
 }
 
-int sonic_prove(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO,
-                const uint8_t* cs, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO, const uint8_t* transcript,
-                uint8_t* out_proof) {
-  API_BEGIN_ON(srs_device(srs))
-  if (!srs || n < 1 || Q < 1 || !wL || !wR || !wO || !cs || !aL || !aR || !aO || !transcript || !out_proof) { set_error("sonic_prove: bad argument (need n >= 1, Q >= 1)"); return SONIC_ERR_INVALID_ARG; }
-  DeviceCtx& ctx = current_ctx();
-  OneShotShell* sh = nullptr;
-  {
-    std::lock_guard<std::mutex> g(ctx.one_shot_mu);
-    for (size_t i = ctx.one_shot.size(); i-- > 0;) {                 // newest first
-      OneShotShell* c = static_cast<OneShotShell*>(ctx.one_shot[i]);
-      if (c->srs == srs && c->p->n == n && c->p->Q == Q) { sh = c; ctx.one_shot.erase(ctx.one_shot.begin() + (long)i); break; }
-    }
+}  // extern "C"
+
+// the newest parked shell of this SRS and shape, taken out of the list (nullptr: none)
+static OneShotShell* take_shell(DeviceCtx& ctx, const sonic_srs* srs, long n, long Q) {
+  std::lock_guard<std::mutex> g(ctx.one_shot_mu);
+  for (size_t i = ctx.one_shot.size(); i-- > 0;) {                 // newest first
+    OneShotShell* c = static_cast<OneShotShell*>(ctx.one_shot[i]);
+    if (c->srs == srs && c->p->n == n && c->p->Q == Q) { ctx.one_shot.erase(ctx.one_shot.begin() + (long)i); return c; }
   }
-  int rc = SONIC_OK;
-  if (sh) {   // uploaded inside the proof
-    sh->p->pend_circuit[1] = wR; sh->p->pend_circuit[2] = wO; sh->p->pend_circuit[3] = cs; sh->p->pend_circuit[0] = wL;
-    sh->p->circuit_has_runs = circuit_runs_hint(wL, wR, n, Q);
-  }
-  else {
-    sonic_prover_t* p = nullptr;
-    rc = sonic_prover_new(srs, n, Q, wL, wR, wO, cs, &p);
-    if (rc) return rc;
-    sh = new OneShotShell{srs, p};
-  }
-  if (!rc) rc = prove_with_assignment(sh->p, aL, aR, aO, transcript, out_proof);
-  sh->p->pend_circuit[0] = nullptr;           // (a call that failed before its upload: the caller's buffers end with the call)
-  // park the shell (also after a failed call: the next one loads its own circuit and assignment); the oldest parked shell makes room
+  return nullptr;
+}
+// the oldest parked shell makes room
+static void park_shell(DeviceCtx& ctx, OneShotShell* sh) {
   OneShotShell* evict = nullptr;
   {
     std::lock_guard<std::mutex> g(ctx.one_shot_mu);
@@ -81,56 +66,47 @@ int sonic_prove(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t* wL,
     ctx.one_shot.push_back(sh);
   }
   if (evict) { delete evict->p; delete evict; }
+}
+
+// sonic_prove and sonic_prove_csr.  The parked shells are shared by both: a shell holds whichever form of circuit its last call handed
+// over (sonic_prover::csr) and switches with the upload of the next call's, so dense and sparse calls of one (n, Q) alternate over the
+// same shells.  The circuit is checked before a shell is taken (a sparse one is validated here, once per call); into a parked shell it is
+// handed over on the host (the runs hint; a sparse one's transpose) and uploaded inside the proof, behind the group of MSMs that needs the
+// assignment only.
+static int one_shot_prove(const char* who, const sonic_srs_t* srs, const CircuitView& c, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO,
+                          const uint8_t* transcript, uint8_t* out_proof) {
+  API_BEGIN_ON(srs_device(srs))
+  if (!srs || !c.cs || !aL || !aR || !aO || !transcript || !out_proof) { set_error("%s: bad argument (need n >= 1, Q >= 1)", who); return SONIC_ERR_INVALID_ARG; }
+  int rc = prover_admits(who, srs, c);
+  if (rc) return rc;
+  DeviceCtx& ctx = current_ctx();
+  OneShotShell* sh = take_shell(ctx, srs, c.n, c.Q);
+  if (sh) prover_hand_over(sh->p, c);
+  else {
+    sonic_prover_t* p = nullptr;
+    rc = prover_new_impl(srs, c, &p);
+    if (rc) return rc;
+    sh = new OneShotShell{srs, p};
+  }
+  rc = prove_with_assignment(sh->p, aL, aR, aO, transcript, out_proof);
+  sh->p->pend = sonic_prover::PendingCircuit();       // (a call that failed before its upload: the caller's buffers end with the call)
+  park_shell(ctx, sh);        // (also after a failed call: the next one loads its own circuit and assignment)
   return rc;
   API_END
 }
 
-// the same with sparse gate weights (csr.hpp).  The parked shells are shared with sonic_prove: a shell holds whichever form of circuit its
-// last call handed over (sonic_prover::csr) and switches with the upload of the next call's, so dense and sparse calls of one (n, Q) alternate
-// over the same shells.  The host lays the circuit out (validation, transpose) before it takes a shell; the upload runs inside the proof,
-// behind the group of MSMs that needs the assignment only, like the dense one.
+extern "C" {
+
+int sonic_prove(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO,
+                const uint8_t* cs, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO, const uint8_t* transcript,
+                uint8_t* out_proof) {
+  return one_shot_prove("sonic_prove", srs, dense_view(n, Q, wL, wR, wO, cs), aL, aR, aO, transcript, out_proof);
+}
+
+// the same with sparse gate weights (csr.hpp)
 int sonic_prove_csr(const sonic_srs_t* srs, int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val,
                     const uint8_t* cs, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO, const uint8_t* transcript, uint8_t* out_proof) {
-  API_BEGIN_ON(srs_device(srs))
-  if (!srs || n < 1 || Q < 1 || !row_ptr || !cs || !aL || !aR || !aO || !transcript || !out_proof) { set_error("sonic_prove_csr: bad argument (need n >= 1, Q >= 1)"); return SONIC_ERR_INVALID_ARG; }
-  if (srs_d(srs) < 7 * n) {                                                   // Protocol.hs:54-55
-    set_error("Parameter d is not large enough: %ld should be greater than %ld", (long)srs_d(srs), (long)(7 * n));
-    return SONIC_ERR_D_TOO_SMALL;
-  }
-  int rc = csr_validate("sonic_prove_csr", n, Q, row_ptr, col, val);
-  if (rc) return rc;
-  DeviceCtx& ctx = current_ctx();
-  OneShotShell* sh = nullptr;
-  {
-    std::lock_guard<std::mutex> g(ctx.one_shot_mu);
-    for (size_t i = ctx.one_shot.size(); i-- > 0;) {                 // newest first
-      OneShotShell* c = static_cast<OneShotShell*>(ctx.one_shot[i]);
-      if (c->srs == srs && c->p->n == n && c->p->Q == Q) { sh = c; ctx.one_shot.erase(ctx.one_shot.begin() + (long)i); break; }
-    }
-  }
-  if (sh) {   // uploaded inside the proof
-    csr_layout(n, Q, row_ptr, col, val, cs, sh->p->pend_csr_layout);
-    sh->p->circuit_has_runs = circuit_runs_hint_csr(sh->p->pend_csr_layout, RUN_TILE);
-    sh->p->pend_csr = true;
-  }
-  else {
-    sonic_prover_t* p = nullptr;
-    rc = sonic_prover_new_csr(srs, n, Q, row_ptr, col, val, cs, &p);
-    if (rc) return rc;
-    sh = new OneShotShell{srs, p};
-  }
-  if (!rc) rc = prove_with_assignment(sh->p, aL, aR, aO, transcript, out_proof);
-  sh->p->pend_csr = false;                     // (a call that failed before its upload: the caller's buffers end with the call)
-  sh->p->pend_csr_layout = CsrLayout();
-  OneShotShell* evict = nullptr;
-  {
-    std::lock_guard<std::mutex> g(ctx.one_shot_mu);
-    if (ctx.one_shot.size() >= ONE_SHOT_SHELLS) { evict = static_cast<OneShotShell*>(ctx.one_shot.front()); ctx.one_shot.erase(ctx.one_shot.begin()); }
-    ctx.one_shot.push_back(sh);
-  }
-  if (evict) { delete evict->p; delete evict; }
-  return rc;
-  API_END
+  return one_shot_prove("sonic_prove_csr", srs, csr_view(n, Q, row_ptr, col, val, cs), aL, aR, aO, transcript, out_proof);
 }
 
 // mapM (\(assignment, circuit) -> prove srs assignment circuit) over K INDEPENDENT statements of one shape (n, Q), spread over the SRS

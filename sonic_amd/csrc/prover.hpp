@@ -89,8 +89,6 @@ struct sonic_prover {
     long nnz = 0, nchunks = 0;
     std::vector<int32_t> h_row_ptr;           // (prepare: the entry ranges of the rows of each P_q)
   } sp;
-  CsrLayout pend_csr_layout;                 // one-shot: this call's sparse circuit, laid out on the host, uploaded inside the proof
-  bool pend_csr = false;
   Lane lanes[N_LANES];
   // lanes in use: all six by default.  SONIC_FUSED_LANES=k (small-proof handles): k lanes of their own; =0: NO lane of its own
   // (few_streams) -- three streams per handle: main, transform, chain; the groups' openings ride on the streams that are waiting anyway
@@ -121,11 +119,12 @@ struct sonic_prover {
   Fr* h_pairs = nullptr;         // {v, v^-1} of the evaluation points, computed on the host (prove_enqueue)
   MsmSlot* h_slots = nullptr;
   uint8_t* h_fr = nullptr;
-  int* h_flags = nullptr;                  // [0] the proof's flags, [1] those of a circuit uploaded inside the proof (pend_circuit)
-  // one-shot calls into a parked shell (sonic_prove): the circuit of THIS call, still in the caller's host buffers.  prove_enqueue
-  // uploads it after it has queued the group of MSMs that needs the assignment only (R, W_a, W_b), so the 2 Q n + Q weights cross
-  // PCIe under those kernels instead of in front of the proof
-  const uint8_t* pend_circuit[4] = {nullptr, nullptr, nullptr, nullptr};
+  int* h_flags = nullptr;                  // [0] the proof's flags, [1] those of a circuit uploaded inside the proof (pend)
+  // the circuit of THIS call, still in the caller's host buffers (prover_hand_over; a sparse one laid out on the host beside it).  When a
+  // handle is made it is uploaded at once; a one-shot call into a parked shell (sonic_prove, sonic_prove_csr) leaves it to prove_enqueue,
+  // which uploads it after it has queued the group of MSMs that needs the assignment only (R, W_a, W_b), so the weights cross PCIe
+  // under those kernels instead of in front of the proof
+  struct PendingCircuit { bool set = false; CircuitView view = {}; CsrLayout layout; } pend;
   // the same for the ASSIGNMENT of this call (round 6: sonic_prove_batch with per-proof assignments, sonic_prove): uploaded at the head of
   // the proof's own queue instead of by a sonic_prover_set_assignment that waits for the device before the proof may even be queued -- beside
   // another handle's accumulation that wait was ~1 ms per proof (config5: 99 against 113 proofs/s, profiles/r06_bench.json)
@@ -250,7 +249,9 @@ int read_flags(hipStream_t st, DevBuf& flags);
 int flags_to_status(int f, const char* who);
 // (defined inside prove.hip's extern "C" block, not exported)
 extern "C" int prove_with_assignment(sonic_prover_t* p, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO, const uint8_t* transcript, uint8_t* out_proof);
-bool circuit_runs_hint(const uint8_t* wL, const uint8_t* wR, long n, long Q);
-// (prove.hip) queues the upload of a sparse circuit laid out on the host into the handle's CSR buffers (flags: non-canonical values)
-void prover_upload_csr(sonic_prover_t* p, hipStream_t st, const CsrLayout& L, int* d_flags);
+// (prove.hip) what sonic_prover_new[_csr] and the one-shot calls share: the checks of a circuit against an SRS, a handle for an admitted
+// circuit, and the hand-over of the next call's circuit to a handle that exists (uploaded inside its next proof)
+int prover_admits(const char* who, const sonic_srs* srs, const CircuitView& c);
+int prover_new_impl(const sonic_srs_t* srs, const CircuitView& c, sonic_prover_t** out);
+void prover_hand_over(sonic_prover_t* p, const CircuitView& c);
 

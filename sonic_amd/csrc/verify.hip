@@ -76,6 +76,12 @@ int fetch_g2(const sonic_srs* srs, int basis, int64_t e, G2Affine& out) {
   return SONIC_OK;
 }
 
+int load_verifier_key(const sonic_srs* srs, VerifierKey& vk) {
+  int rc = fetch_g2(srs, 1, 0, vk.h_alpha);
+  if (!rc) rc = fetch_g2(srs, 1, 1, vk.h_alpha_x);
+  return rc;
+}
+
 // pcV srs max F z (v, W)  (CommitmentScheme.hs:51-68), in two steps: the G2 element h^{x^{-d+max}} comes from the SRS handle
 // (device memory, the library's call mutex), the pairing equation itself is pure host arithmetic -- so a verifier's checks
 // fetch their elements first and then run side by side on host threads (a proof with Q constraints has 4 + 3Q of them at
@@ -136,69 +142,82 @@ int run_checks(const sonic_srs* srs, const VerifierKey& vk, const std::vector<Pc
   return SONIC_OK;
 }
 
-// the 3m + 1 pcV checks of hscVerify (Signature.hs:82-89) once s(u,v) is known
-void hsc_push_checks(int64_t d, int64_t m, const std::vector<Fr>& ys, const std::vector<Fr>& zs, const std::vector<G1Affine>& Sj, const std::vector<Fr>& sj,
-                     const std::vector<G1Affine>& Wj, const std::vector<Fr>& spj, const std::vector<G1Affine>& Wpj, const std::vector<G1Affine>& Qj,
-                     const G1Affine& Qv, const G1Affine& C, const Fr& u, const Fr& v, const Fr& sv, std::vector<PcvCheck>& checks) {
-  for (int64_t j = 0; j < m; j++) {                                // Signature.hs:82-88
-    checks.push_back(PcvCheck{d, Sj[j], zs[j], sj[j], Wj[j]});
-    checks.push_back(PcvCheck{d, Sj[j], u, spj[j], Wpj[j]});
-    checks.push_back(PcvCheck{d, C, ys[j], spj[j], Qj[j]});
-  }
-  checks.push_back(PcvCheck{d, C, v, sv, Qv});                     // Signature.hs:89
+// an HscProof (Signature.hs:22-29) with the (y_j, z_j) it is checked at, parsed
+struct HscProofView { std::vector<G1Affine> Sj, Wj, Wpj, Qj; std::vector<Fr> sj, spj, ys, zs; G1Affine Qv, C; Fr u, v; };
+
+// [S_j, s_j, W_j]_j, [s'_j, W'_j, Q_j]_j, Q_v, C, u, v (m entries per list: sonic_hsc_proof_size(m) bytes) and the m pairs of yzs;
+// false: a non-canonical field element, or a point off the curve or outside the order-r subgroup
+bool parse_hsc(const uint8_t* p, int64_t m, const uint8_t* yzs, HscProofView& h) {
+  auto G = [&](G1Affine& o) { bool k = load_g1(p, o); p += 96; return k; };
+  auto F = [&](Fr& o) { bool k = load_fr(p, o); p += 32; return k; };
+  for (auto* g : {&h.Sj, &h.Wj, &h.Wpj, &h.Qj}) g->resize((size_t)m);
+  for (auto* f : {&h.sj, &h.spj, &h.ys, &h.zs}) f->resize((size_t)m);
+  bool enc = true;
+  for (int64_t j = 0; j < m; j++) enc = enc && G(h.Sj[j]) && F(h.sj[j]) && G(h.Wj[j]);
+  for (int64_t j = 0; j < m; j++) enc = enc && F(h.spj[j]) && G(h.Wpj[j]) && G(h.Qj[j]);
+  enc = enc && G(h.Qv) && G(h.C) && F(h.u) && F(h.v);
+  for (int64_t j = 0; j < m; j++) enc = enc && load_fr(yzs + 64 * j, h.ys[j]) && load_fr(yzs + 64 * j + 32, h.zs[j]);
+  return enc;
 }
 
-// hscVerify srs sXY yzs proof (Signature.hs:74-90) for the s(X,Y) of a circuit (Constraints.hs:34-53): s(u,v) on the host,
-// then its 3m + 1 pcV checks are appended to `checks` (run_checks evaluates them).
-int hsc_checks(const sonic_srs* srs, const VerifierKey& vk, int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO,
-               int64_t m, const std::vector<Fr>& ys, const std::vector<Fr>& zs, const std::vector<G1Affine>& Sj, const std::vector<Fr>& sj,
-               const std::vector<G1Affine>& Wj, const std::vector<Fr>& spj, const std::vector<G1Affine>& Wpj, const std::vector<G1Affine>& Qj,
-               const G1Affine& Qv, const G1Affine& C, const Fr& u, const Fr& v, std::vector<PcvCheck>& checks) {
-  // s(u, v): sum_i u^-i U_i(v) + u^i V_i(v) + u^{i+n} W_i(v)   (Signature.hs:81; Constraints.hs:34-53)
-  if (u.is_zero() || v.is_zero()) { set_error("hscVerify: u or v is zero"); return SONIC_ERR_INEXACT_DIVISION; }
-  std::vector<Fr> vq(Q);
-  { Fr x = fr_pow(v, (uint64_t)n); for (int64_t q = 0; q < Q; q++) { x = fp_mul(x, v); vq[q] = x; } }
-  const Fr uinv = fp_inv(u), vinv = fp_inv(v), un = fr_pow(u, (uint64_t)n);
-  Fr up = Fr::one(), um = Fr::one(), vp = Fr::one(), vm = Fr::one(), sv = Fr::zero();
-  for (int64_t i = 1; i <= n; i++) {
-    up = fp_mul(up, u); um = fp_mul(um, uinv); vp = fp_mul(vp, v); vm = fp_mul(vm, vinv);
-    Fr Ui = Fr::zero(), Vi = Fr::zero(), Wi = Fr::zero(), c;
-    for (int64_t q = 0; q < Q; q++) {
-      if (!load_fr(wL + 32 * (q * n + i - 1), c)) return SONIC_ERR_BAD_ENCODING; Ui = fp_add(Ui, fp_mul(c, vq[q]));
-      if (!load_fr(wR + 32 * (q * n + i - 1), c)) return SONIC_ERR_BAD_ENCODING; Vi = fp_add(Vi, fp_mul(c, vq[q]));
-      if (!load_fr(wO + 32 * (q * n + i - 1), c)) return SONIC_ERR_BAD_ENCODING; Wi = fp_add(Wi, fp_mul(c, vq[q]));
-    }
-    Wi = fp_sub(fp_sub(Wi, vp), vm);
-    sv = fp_add(sv, fp_add(fp_add(fp_mul(um, Ui), fp_mul(up, Vi)), fp_mul(fp_mul(up, un), Wi)));
+// the end of hscVerify once s(u,v) is known: its 3m + 1 pcV checks (Signature.hs:82-89), run together with those the caller brings
+int hsc_accepts(const sonic_srs* srs, const VerifierKey& vk, const HscProofView& h, const Fr& sv, std::vector<PcvCheck> checks, int* accepted) {
+  const int64_t d = srs_d(srs);
+  for (size_t j = 0; j < h.Sj.size(); j++) {                       // Signature.hs:82-88
+    checks.push_back(PcvCheck{d, h.Sj[j], h.zs[j], h.sj[j], h.Wj[j]});
+    checks.push_back(PcvCheck{d, h.Sj[j], h.u, h.spj[j], h.Wpj[j]});
+    checks.push_back(PcvCheck{d, h.C, h.ys[j], h.spj[j], h.Qj[j]});
   }
-  hsc_push_checks(srs_d(srs), m, ys, zs, Sj, sj, Wj, spj, Wpj, Qj, Qv, C, u, v, sv, checks);
+  checks.push_back(PcvCheck{d, h.C, h.v, sv, h.Qv});               // Signature.hs:89
+  bool all = true;
+  int rc = run_checks(srs, vk, checks, all);
+  if (rc) return rc;
+  *accepted = all ? 1 : 0;
   return SONIC_OK;
 }
 
-// the same for sparse gate weights (csr.hpp, validated by the caller): s(u, v) in O(nnz + n).  Per row q of each matrix the entries sum
+// s(u, v) for the s(X,Y) of a circuit (Signature.hs:81; Constraints.hs:34-53): sum_i u^-i U_i(v) + u^i V_i(v) + u^{i+n} W_i(v).  Dense
+// weights: O(Q n), gate by gate.  Sparse ones (validated by the caller): O(nnz + n) -- per row q of each matrix the entries sum
 // val * u^{-i | i | i+n}, scaled by v^{n+q}; the diagonal terms u^{i+n} (-v^i - v^-i) are summed on their own.
-int hsc_checks_csr(const sonic_srs* srs, int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val,
-                   int64_t m, const std::vector<Fr>& ys, const std::vector<Fr>& zs, const std::vector<G1Affine>& Sj, const std::vector<Fr>& sj,
-                   const std::vector<G1Affine>& Wj, const std::vector<Fr>& spj, const std::vector<G1Affine>& Wpj, const std::vector<G1Affine>& Qj,
-                   const G1Affine& Qv, const G1Affine& C, const Fr& u, const Fr& v, std::vector<PcvCheck>& checks) {
+int s_of_uv(const CircuitView& c, const Fr& u, const Fr& v, Fr& sv) {
+  const int64_t n = c.n, Q = c.Q;
   if (u.is_zero() || v.is_zero()) { set_error("hscVerify: u or v is zero"); return SONIC_ERR_INEXACT_DIVISION; }
+  const Fr uinv = fp_inv(u), vinv = fp_inv(v);
+  sv = Fr::zero();
+  if (!c.csr) {
+    std::vector<Fr> vq(Q);
+    { Fr x = fr_pow(v, (uint64_t)n); for (int64_t q = 0; q < Q; q++) { x = fp_mul(x, v); vq[q] = x; } }
+    const Fr un = fr_pow(u, (uint64_t)n);
+    Fr up = Fr::one(), um = Fr::one(), vp = Fr::one(), vm = Fr::one();
+    for (int64_t i = 1; i <= n; i++) {
+      up = fp_mul(up, u); um = fp_mul(um, uinv); vp = fp_mul(vp, v); vm = fp_mul(vm, vinv);
+      Fr Ui = Fr::zero(), Vi = Fr::zero(), Wi = Fr::zero(), w;
+      for (int64_t q = 0; q < Q; q++) {
+        if (!load_fr(c.wL + 32 * (q * n + i - 1), w)) return SONIC_ERR_BAD_ENCODING; Ui = fp_add(Ui, fp_mul(w, vq[q]));
+        if (!load_fr(c.wR + 32 * (q * n + i - 1), w)) return SONIC_ERR_BAD_ENCODING; Vi = fp_add(Vi, fp_mul(w, vq[q]));
+        if (!load_fr(c.wO + 32 * (q * n + i - 1), w)) return SONIC_ERR_BAD_ENCODING; Wi = fp_add(Wi, fp_mul(w, vq[q]));
+      }
+      Wi = fp_sub(fp_sub(Wi, vp), vm);
+      sv = fp_add(sv, fp_add(fp_add(fp_mul(um, Ui), fp_mul(up, Vi)), fp_mul(fp_mul(up, un), Wi)));
+    }
+    return SONIC_OK;
+  }
   // upos[e] = u^e (e in [0, 2n]), uneg[i] = u^-i (i in [0, n])
   std::vector<Fr> upos((size_t)(2 * n + 1)), uneg((size_t)(n + 1));
-  const Fr uinv = fp_inv(u), vinv = fp_inv(v);
   upos[0] = uneg[0] = Fr::one();
   for (int64_t e = 1; e <= 2 * n; e++) upos[(size_t)e] = fp_mul(upos[(size_t)e - 1], u);
   for (int64_t i = 1; i <= n; i++) uneg[(size_t)i] = fp_mul(uneg[(size_t)i - 1], uinv);
-  Fr sv = Fr::zero(), vq = fr_pow(v, (uint64_t)n);
+  Fr vq = fr_pow(v, (uint64_t)n);
   for (int64_t q = 0; q < Q; q++) {
     vq = fp_mul(vq, v);                                              // v^{n+q+1}
-    Fr rowsum = Fr::zero(), c;
+    Fr rowsum = Fr::zero(), w;
     for (int mat = 0; mat < 3; mat++) {
       const int64_t r = mat * Q + q;
-      for (int64_t k = row_ptr[r]; k < row_ptr[r + 1]; k++) {
-        if (!load_fr(val + 32 * k, c)) return SONIC_ERR_BAD_ENCODING;
-        const int64_t i = col[k] + 1;
+      for (int64_t k = c.row_ptr[r]; k < c.row_ptr[r + 1]; k++) {
+        if (!load_fr(c.val + 32 * k, w)) return SONIC_ERR_BAD_ENCODING;
+        const int64_t i = c.col[k] + 1;
         const Fr& up = mat == 0 ? uneg[(size_t)i] : upos[(size_t)(mat == 1 ? i : i + n)];
-        rowsum = fp_add(rowsum, fp_mul(c, up));
+        rowsum = fp_add(rowsum, fp_mul(w, up));
       }
     }
     sv = fp_add(sv, fp_mul(rowsum, vq));
@@ -208,8 +227,31 @@ int hsc_checks_csr(const sonic_srs* srs, int64_t n, int64_t Q, const int64_t* ro
     vp = fp_mul(vp, v); vm = fp_mul(vm, vinv);
     sv = fp_sub(sv, fp_mul(upos[(size_t)(i + n)], fp_add(vp, vm)));
   }
-  hsc_push_checks(srs_d(srs), m, ys, zs, Sj, sj, Wj, spj, Wpj, Qj, Qv, C, u, v, sv, checks);
   return SONIC_OK;
+}
+
+// verify srs circuit proof y z yzs  (Protocol.hs:111-130) for a validated circuit in either form; yzs = Q pairs (y_j, z_j), 64 bytes each
+int verify_circuit(const sonic_srs* srs, const CircuitView& c, const uint8_t* proof, const uint8_t y[32], const uint8_t z[32], const uint8_t* yzs, int* accepted) {
+  const int64_t n = c.n, Q = c.Q;
+  const uint8_t* p = proof;
+  auto G = [&](G1Affine& o) { bool k = load_g1(p, o); p += 96; return k; };
+  auto F = [&](Fr& o) { bool k = load_fr(p, o); p += 32; return k; };
+  G1Affine R, T, Wa, Wb, Wt;
+  Fr a, b, s, ym, zm, sv;
+  HscProofView h;
+  const bool enc = G(R) && G(T) && F(a) && G(Wa) && F(b) && G(Wb) && G(Wt) && F(s) && parse_hsc(p, Q, yzs, h) && load_fr(y, ym) && load_fr(z, zm);
+  if (!enc) { set_error("verify: non-canonical field element, or point off the curve or outside the order-r subgroup"); return SONIC_ERR_BAD_ENCODING; }
+  // k(y) = sum_q cs[q] y^{n+q}                                  (Constraints.hs:67-68)
+  Fr ky = Fr::zero(), pw = fr_pow(ym, (uint64_t)n);
+  for (int64_t q = 0; q < Q; q++) { Fr k; if (!load_fr(c.cs + 32 * q, k)) return SONIC_ERR_BAD_ENCODING; pw = fp_mul(pw, ym); ky = fp_add(ky, fp_mul(k, pw)); }
+  const Fr t = fp_sub(fp_mul(a, fp_add(b, s)), ky);              // Protocol.hs:120
+  VerifierKey vk;
+  int rc = load_verifier_key(srs, vk);
+  if (!rc) rc = s_of_uv(c, h.u, h.v, sv);                        // hscVerify, Signature.hs:74-90
+  if (rc) return rc;
+  return hsc_accepts(srs, vk, h, sv, {PcvCheck{n, R, zm, a, Wa},                      // Protocol.hs:123
+                                      PcvCheck{n, R, fp_mul(ym, zm), b, Wb},          // :124
+                                      PcvCheck{srs_d(srs), T, zm, t, Wt}}, accepted);  // :125
 }
 
 }  // namespace
@@ -226,8 +268,7 @@ int sonic_pc_v(const sonic_srs_t* srs, int64_t max, const uint8_t commitment[96]
     G1Affine F, W; Fr zm, vm;
     if (!load_g1(commitment, F) || !load_g1(w, W) || !load_fr(z, zm) || !load_fr(v, vm)) { set_error("pcV: bad encoding"); return SONIC_ERR_BAD_ENCODING; }
     VerifierKey vk;
-    int rc = fetch_g2(srs, 1, 0, vk.h_alpha);
-    if (!rc) rc = fetch_g2(srs, 1, 1, vk.h_alpha_x);
+    int rc = load_verifier_key(srs, vk);
     if (rc) return rc;
     bool ok = false;
     rc = pc_v(srs, vk, max, F, zm, vm, W, ok);
@@ -239,46 +280,15 @@ int sonic_pc_v(const sonic_srs_t* srs, int64_t max, const uint8_t commitment[96]
 
 }  // extern "C"
 
-// verify srs circuit proof y z yzs  (Protocol.hs:111-130) with the circuit's part of hscVerify -- s(u, v) and its checks -- left to
-// `hsc` (dense or sparse gate weights)
-template <class HscChecks>
-static int verify_with(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t* cs, const uint8_t* proof, const uint8_t y[32], const uint8_t z[32],
-                       const uint8_t* yzs, int* accepted, const HscChecks& hsc) {
+// the entry points that take a circuit, in either form: an argument check, a view, one implementation
+static int verify_entry(const char* who, const sonic_srs_t* srs, const CircuitView& c, const uint8_t* proof, const uint8_t y[32], const uint8_t z[32],
+                        const uint8_t* yzs, int* accepted) {
   try {
+    if (!srs || !c.cs || !proof || !y || !z || !yzs || !accepted) { set_error("%s: bad argument", who); return SONIC_ERR_INVALID_ARG; }
     *accepted = 0;
-    const uint8_t* p = proof;
-    auto G = [&](G1Affine& o) { bool k = load_g1(p, o); p += 96; return k; };
-    auto F = [&](Fr& o) { bool k = load_fr(p, o); p += 32; return k; };
-    G1Affine R, T, Wa, Wb, Wt, Qv, C;
-    Fr a, b, s, u, v, ym, zm;
-    bool enc = G(R) && G(T) && F(a) && G(Wa) && F(b) && G(Wb) && G(Wt) && F(s);
-    std::vector<G1Affine> Sj(Q), Wj(Q), Wpj(Q), Qj(Q);
-    std::vector<Fr> sj(Q), spj(Q), ys(Q), zs(Q);
-    for (int64_t j = 0; j < Q; j++) enc = enc && G(Sj[j]) && F(sj[j]) && G(Wj[j]);
-    for (int64_t j = 0; j < Q; j++) enc = enc && F(spj[j]) && G(Wpj[j]) && G(Qj[j]);
-    enc = enc && G(Qv) && G(C) && F(u) && F(v) && load_fr(y, ym) && load_fr(z, zm);
-    for (int64_t j = 0; j < Q; j++) enc = enc && load_fr(yzs + 64 * j, ys[j]) && load_fr(yzs + 64 * j + 32, zs[j]);
-    if (!enc) { set_error("verify: non-canonical field element, or point off the curve or outside the order-r subgroup"); return SONIC_ERR_BAD_ENCODING; }
-    // k(y) = sum_q cs[q] y^{n+q}                                  (Constraints.hs:67-68)
-    Fr ky = Fr::zero(), pw = fr_pow(ym, (uint64_t)n);
-    for (int64_t q = 0; q < Q; q++) { Fr c; if (!load_fr(cs + 32 * q, c)) return SONIC_ERR_BAD_ENCODING; pw = fp_mul(pw, ym); ky = fp_add(ky, fp_mul(c, pw)); }
-    const Fr t = fp_sub(fp_mul(a, fp_add(b, s)), ky);              // Protocol.hs:120
-    VerifierKey vk;
-    int rc = fetch_g2(srs, 1, 0, vk.h_alpha);
-    if (!rc) rc = fetch_g2(srs, 1, 1, vk.h_alpha_x);
+    int rc = circuit_validate(who, c);
     if (rc) return rc;
-    const int64_t d = srs_d(srs);
-    std::vector<PcvCheck> checks;
-    rc = hsc(vk, ys, zs, Sj, sj, Wj, spj, Wpj, Qj, Qv, C, u, v, checks);   // hscVerify, Signature.hs:74-90
-    if (rc) return rc;
-    checks.push_back(PcvCheck{n, R, zm, a, Wa});                   // Protocol.hs:123
-    checks.push_back(PcvCheck{n, R, fp_mul(ym, zm), b, Wb});       // :124
-    checks.push_back(PcvCheck{d, T, zm, t, Wt});                   // :125
-    bool all = true;
-    rc = run_checks(srs, vk, checks, all);
-    if (rc) return rc;
-    *accepted = all ? 1 : 0;
-    return SONIC_OK;
+    return verify_circuit(srs, c, proof, y, z, yzs, accepted);
   } catch (const HipFail& f) { return f.code; }
   catch (const std::exception& e) { set_error("%s", e.what()); return SONIC_ERR_HIP; }
 }
@@ -288,28 +298,13 @@ extern "C" {
 // verify srs circuit proof y z yzs  (Protocol.hs:111-130); yzs = Q pairs (y_j, z_j), 64 bytes each
 int sonic_verify(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO,
                  const uint8_t* cs, const uint8_t* proof, const uint8_t y[32], const uint8_t z[32], const uint8_t* yzs, int* accepted) {
-  if (!srs || n < 1 || Q < 1 || !wL || !wR || !wO || !cs || !proof || !y || !z || !yzs || !accepted) return SONIC_ERR_INVALID_ARG;
-  return verify_with(srs, n, Q, cs, proof, y, z, yzs, accepted,
-                     [&](const VerifierKey& vk, const std::vector<Fr>& ys, const std::vector<Fr>& zs, const std::vector<G1Affine>& Sj, const std::vector<Fr>& sj,
-                         const std::vector<G1Affine>& Wj, const std::vector<Fr>& spj, const std::vector<G1Affine>& Wpj, const std::vector<G1Affine>& Qj,
-                         const G1Affine& Qv, const G1Affine& C, const Fr& u, const Fr& v, std::vector<PcvCheck>& checks) {
-                       return hsc_checks(srs, vk, n, Q, wL, wR, wO, Q, ys, zs, Sj, sj, Wj, spj, Wpj, Qj, Qv, C, u, v, checks);
-                     });
+  return verify_entry("sonic_verify", srs, dense_view(n, Q, wL, wR, wO, cs), proof, y, z, yzs, accepted);
 }
 
 // the same with sparse gate weights (csr.hpp): s(u, v) in O(nnz + n) instead of O(Q n)
 int sonic_verify_csr(const sonic_srs_t* srs, int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val,
                      const uint8_t* cs, const uint8_t* proof, const uint8_t y[32], const uint8_t z[32], const uint8_t* yzs, int* accepted) {
-  if (!srs || n < 1 || Q < 1 || !row_ptr || !cs || !proof || !y || !z || !yzs || !accepted) { set_error("sonic_verify_csr: bad argument"); return SONIC_ERR_INVALID_ARG; }
-  *accepted = 0;
-  int rc = csr_validate("sonic_verify_csr", n, Q, row_ptr, col, val);
-  if (rc) return rc;
-  return verify_with(srs, n, Q, cs, proof, y, z, yzs, accepted,
-                     [&](const VerifierKey&, const std::vector<Fr>& ys, const std::vector<Fr>& zs, const std::vector<G1Affine>& Sj, const std::vector<Fr>& sj,
-                         const std::vector<G1Affine>& Wj, const std::vector<Fr>& spj, const std::vector<G1Affine>& Wpj, const std::vector<G1Affine>& Qj,
-                         const G1Affine& Qv, const G1Affine& C, const Fr& u, const Fr& v, std::vector<PcvCheck>& checks) {
-                       return hsc_checks_csr(srs, n, Q, row_ptr, col, val, Q, ys, zs, Sj, sj, Wj, spj, Wpj, Qj, Qv, C, u, v, checks);
-                     });
+  return verify_entry("sonic_verify_csr", srs, csr_view(n, Q, row_ptr, col, val, cs), proof, y, z, yzs, accepted);
 }
 
 // what ties a Fiat-Shamir transcript to ONE reference string (fs.hpp): four G1 elements that determine x and alpha
@@ -369,77 +364,46 @@ int sonic_srs_pairing(const sonic_srs_t* srs, uint8_t out[576]) {
   catch (const std::exception& e) { set_error("%s", e.what()); return SONIC_ERR_HIP; }
 }
 
+}  // extern "C"
+
 // verify for a proof made by sonic_prover_prove_fs: the challenges y, z, (y_j, z_j) are not handed over (RndOracle) but recomputed from
 // the statement and the proof (fs.hpp), and the proof's u, v must be the ones its own transcript yields
+static int verify_fs_entry(const char* who, const sonic_srs_t* srs, const CircuitView& c, const uint8_t* proof, int* accepted) {
+  try {
+    if (!srs || !c.cs || !proof || !accepted) { set_error("%s: bad argument", who); return SONIC_ERR_INVALID_ARG; }
+    *accepted = 0;
+    int rc = circuit_validate(who, c);
+    if (rc) return rc;
+    const int64_t n = c.n, Q = c.Q;
+    uint8_t digest[32], srs_id[32];
+    circuit_digest(c, digest);
+    rc = sonic_fs_srs_id(srs, srs_id);
+    if (rc) return rc;
+    std::vector<uint8_t> ch(32 * (size_t)(4 + 2 * Q));
+    fs_challenges_of_proof(n, Q, srs_d(srs), digest, srs_id, proof, ch.data());
+    const uint8_t* uv = proof + sonic_proof_size(Q) - 64;
+    if (memcmp(uv, &ch[32 * (2 + 2 * Q)], 64) != 0) return SONIC_OK;          // u, v are not this transcript's: rejected
+    std::vector<uint8_t> yzs(64 * (size_t)Q);
+    for (int64_t j = 0; j < Q; j++) { memcpy(&yzs[64 * j], &ch[32 * (2 + j)], 32); memcpy(&yzs[64 * j + 32], &ch[32 * (2 + Q + j)], 32); }
+    return verify_circuit(srs, c, proof, &ch[0], &ch[32], yzs.data(), accepted);
+  } catch (const HipFail& f) { return f.code; }
+  catch (const std::exception& e) { set_error("%s", e.what()); return SONIC_ERR_HIP; }
+}
+
+extern "C" {
+
 int sonic_verify_fs(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO,
                     const uint8_t* cs, const uint8_t* proof, int* accepted) {
-  try {
-    if (!srs || n < 1 || Q < 1 || !wL || !wR || !wO || !cs || !proof || !accepted) return SONIC_ERR_INVALID_ARG;
-    *accepted = 0;
-    uint8_t digest[32];
-    int rc = sonic_fs_circuit_digest(n, Q, wL, wR, wO, cs, digest);
-    if (rc) return rc;
-    uint8_t srs_id[32];
-    rc = sonic_fs_srs_id(srs, srs_id);
-    if (rc) return rc;
-    std::vector<uint8_t> ch(32 * (size_t)(4 + 2 * Q));
-    fs_challenges_of_proof(n, Q, srs_d(srs), digest, srs_id, proof, ch.data());
-    const uint8_t* uv = proof + sonic_proof_size(Q) - 64;
-    if (memcmp(uv, &ch[32 * (2 + 2 * Q)], 64) != 0) return SONIC_OK;          // u, v are not this transcript's: rejected
-    std::vector<uint8_t> yzs(64 * (size_t)Q);
-    for (int64_t j = 0; j < Q; j++) { memcpy(&yzs[64 * j], &ch[32 * (2 + j)], 32); memcpy(&yzs[64 * j + 32], &ch[32 * (2 + Q + j)], 32); }
-    return sonic_verify(srs, n, Q, wL, wR, wO, cs, proof, &ch[0], &ch[32], yzs.data(), accepted);
-  } catch (const HipFail& f) { return f.code; }
-  catch (const std::exception& e) { set_error("%s", e.what()); return SONIC_ERR_HIP; }
+  return verify_fs_entry("sonic_verify_fs", srs, dense_view(n, Q, wL, wR, wO, cs), proof, accepted);
 }
-
-// sonic_fs_circuit_digest (prove.hip) from the sparse rows: the 3Q rows streamed in order as the dense bytes they stand for (32 zero bytes per absent entry),
-// so that a proof made on either form verifies under either.  O(Q n) hashing, once per circuit.
-int sonic_fs_circuit_digest_csr(int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val, const uint8_t* cs, uint8_t out[32]) {
-  if (n < 1 || Q < 1 || !row_ptr || !cs || !out) { set_error("sonic_fs_circuit_digest_csr: bad argument (need n >= 1, Q >= 1)"); return SONIC_ERR_INVALID_ARG; }
-  int rc = csr_validate("sonic_fs_circuit_digest_csr", n, Q, row_ptr, col, val);
-  if (rc) return rc;
-  static const uint8_t zeros[32 * 1024] = {0};
-  Sha256 h;
-  h.update("sonic-hip/circuit/v1", 20);
-  FsTranscript::le64(h, n); FsTranscript::le64(h, Q);
-  auto gap = [&](int64_t cnt) {
-    for (; cnt > 0; cnt -= 1024) h.update(zeros, 32 * (size_t)(cnt < 1024 ? cnt : 1024));
-  };
-  for (int64_t r = 0; r < 3 * Q; r++) {
-    int64_t at = 0;
-    for (int64_t k = row_ptr[r]; k < row_ptr[r + 1]; k++) {
-      gap(col[k] - at);
-      h.update(val + 32 * k, 32);
-      at = col[k] + 1;
-    }
-    gap(n - at);
-  }
-  h.update(cs, (size_t)(32 * Q));
-  h.finish(out);
-  return SONIC_OK;
-}
-
 int sonic_verify_fs_csr(const sonic_srs_t* srs, int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val,
                         const uint8_t* cs, const uint8_t* proof, int* accepted) {
-  try {
-    if (!srs || n < 1 || Q < 1 || !row_ptr || !cs || !proof || !accepted) { set_error("sonic_verify_fs_csr: bad argument"); return SONIC_ERR_INVALID_ARG; }
-    *accepted = 0;
-    uint8_t digest[32];
-    int rc = sonic_fs_circuit_digest_csr(n, Q, row_ptr, col, val, cs, digest);       // (validates the CSR)
-    if (rc) return rc;
-    uint8_t srs_id[32];
-    rc = sonic_fs_srs_id(srs, srs_id);
-    if (rc) return rc;
-    std::vector<uint8_t> ch(32 * (size_t)(4 + 2 * Q));
-    fs_challenges_of_proof(n, Q, srs_d(srs), digest, srs_id, proof, ch.data());
-    const uint8_t* uv = proof + sonic_proof_size(Q) - 64;
-    if (memcmp(uv, &ch[32 * (2 + 2 * Q)], 64) != 0) return SONIC_OK;          // u, v are not this transcript's: rejected
-    std::vector<uint8_t> yzs(64 * (size_t)Q);
-    for (int64_t j = 0; j < Q; j++) { memcpy(&yzs[64 * j], &ch[32 * (2 + j)], 32); memcpy(&yzs[64 * j + 32], &ch[32 * (2 + Q + j)], 32); }
-    return sonic_verify_csr(srs, n, Q, row_ptr, col, val, cs, proof, &ch[0], &ch[32], yzs.data(), accepted);
-  } catch (const HipFail& f) { return f.code; }
-  catch (const std::exception& e) { set_error("%s", e.what()); return SONIC_ERR_HIP; }
+  return verify_fs_entry("sonic_verify_fs_csr", srs, csr_view(n, Q, row_ptr, col, val, cs), proof, accepted);
+}
+
+// sonic_fs_circuit_digest (prove.hip) from the sparse rows: the same 32 bytes (circuit_digest, csr.hpp)
+int sonic_fs_circuit_digest_csr(int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val, const uint8_t* cs, uint8_t out[32]) {
+  return circuit_digest_checked("sonic_fs_circuit_digest_csr", csr_view(n, Q, row_ptr, col, val, cs), out);
 }
 
 // hscVerify :: SRS -> BiVLaurent Fr -> [(Fr, Fr)] -> HscProof -> Bool (Signature.hs:74-90) for the s(X,Y) of a circuit;
@@ -449,29 +413,14 @@ int sonic_hsc_verify(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t
   try {
     if (!srs || n < 1 || Q < 1 || !wL || !wR || !wO || m < 0 || (m > 0 && !yzs) || !hsc || !accepted) return SONIC_ERR_INVALID_ARG;
     *accepted = 0;
-    const uint8_t* p = hsc;
-    auto G = [&](G1Affine& o) { bool k = load_g1(p, o); p += 96; return k; };
-    auto F = [&](Fr& o) { bool k = load_fr(p, o); p += 32; return k; };
-    std::vector<G1Affine> Sj(m), Wj(m), Wpj(m), Qj(m);
-    std::vector<Fr> sj(m), spj(m), ys(m), zs(m);
-    G1Affine Qv, C; Fr u, v;
-    bool enc = true;
-    for (int64_t j = 0; j < m; j++) enc = enc && G(Sj[j]) && F(sj[j]) && G(Wj[j]);
-    for (int64_t j = 0; j < m; j++) enc = enc && F(spj[j]) && G(Wpj[j]) && G(Qj[j]);
-    enc = enc && G(Qv) && G(C) && F(u) && F(v);
-    for (int64_t j = 0; j < m; j++) enc = enc && load_fr(yzs + 64 * j, ys[j]) && load_fr(yzs + 64 * j + 32, zs[j]);
-    if (!enc) { set_error("hscVerify: non-canonical field element, or point off the curve or outside the order-r subgroup"); return SONIC_ERR_BAD_ENCODING; }
+    HscProofView h;
+    Fr sv;
+    if (!parse_hsc(hsc, m, yzs, h)) { set_error("hscVerify: non-canonical field element, or point off the curve or outside the order-r subgroup"); return SONIC_ERR_BAD_ENCODING; }
     VerifierKey vk;
-    int rc = fetch_g2(srs, 1, 0, vk.h_alpha);
-    if (!rc) rc = fetch_g2(srs, 1, 1, vk.h_alpha_x);
+    int rc = load_verifier_key(srs, vk);
+    if (!rc) rc = s_of_uv(dense_view(n, Q, wL, wR, wO, nullptr), h.u, h.v, sv);
     if (rc) return rc;
-    bool all = true;
-    std::vector<PcvCheck> checks;
-    rc = hsc_checks(srs, vk, n, Q, wL, wR, wO, m, ys, zs, Sj, sj, Wj, spj, Wpj, Qj, Qv, C, u, v, checks);
-    if (!rc) rc = run_checks(srs, vk, checks, all);
-    if (rc) return rc;
-    *accepted = all ? 1 : 0;
-    return SONIC_OK;
+    return hsc_accepts(srs, vk, h, sv, {}, accepted);
   } catch (const HipFail& f) { return f.code; }
   catch (const std::exception& e) { set_error("%s", e.what()); return SONIC_ERR_HIP; }
 }
@@ -484,18 +433,9 @@ int sonic_hsc_verify_poly(const sonic_srs_t* srs, int64_t n_terms, const int64_t
   try {
     if (!srs || n_terms < 0 || (n_terms > 0 && (!x_exps || !y_exps || !coeffs)) || m < 0 || (m > 0 && !yzs) || !hsc || !accepted) return SONIC_ERR_INVALID_ARG;
     *accepted = 0;
-    const uint8_t* p = hsc;
-    auto G = [&](G1Affine& o) { bool k = load_g1(p, o); p += 96; return k; };
-    auto F = [&](Fr& o) { bool k = load_fr(p, o); p += 32; return k; };
-    std::vector<G1Affine> Sj(m), Wj(m), Wpj(m), Qj(m);
-    std::vector<Fr> sj(m), spj(m), ys(m), zs(m);
-    G1Affine Qv, C; Fr u, v;
-    bool enc = true;
-    for (int64_t j = 0; j < m; j++) enc = enc && G(Sj[j]) && F(sj[j]) && G(Wj[j]);
-    for (int64_t j = 0; j < m; j++) enc = enc && F(spj[j]) && G(Wpj[j]) && G(Qj[j]);
-    enc = enc && G(Qv) && G(C) && F(u) && F(v);
-    for (int64_t j = 0; j < m; j++) enc = enc && load_fr(yzs + 64 * j, ys[j]) && load_fr(yzs + 64 * j + 32, zs[j]);
-    if (!enc) { set_error("hscVerify: non-canonical field element, or point off the curve or outside the order-r subgroup"); return SONIC_ERR_BAD_ENCODING; }
+    HscProofView h;
+    if (!parse_hsc(hsc, m, yzs, h)) { set_error("hscVerify: non-canonical field element, or point off the curve or outside the order-r subgroup"); return SONIC_ERR_BAD_ENCODING; }
+    const Fr &u = h.u, &v = h.v;
     Fr sv = Fr::zero();
     const Fr uinv = u.is_zero() ? u : fp_inv(u), vinv = v.is_zero() ? v : fp_inv(v);
     for (int64_t i = 0; i < n_terms; i++) {
@@ -507,16 +447,9 @@ int sonic_hsc_verify_poly(const sonic_srs_t* srs, int64_t n_terms, const int64_t
       sv = fp_add(sv, fp_mul(c, fp_mul(px, py)));
     }
     VerifierKey vk;
-    int rc = fetch_g2(srs, 1, 0, vk.h_alpha);
-    if (!rc) rc = fetch_g2(srs, 1, 1, vk.h_alpha_x);
+    int rc = load_verifier_key(srs, vk);
     if (rc) return rc;
-    bool all = true;
-    std::vector<PcvCheck> checks;
-    hsc_push_checks(srs_d(srs), m, ys, zs, Sj, sj, Wj, spj, Wpj, Qj, Qv, C, u, v, sv, checks);
-    rc = run_checks(srs, vk, checks, all);
-    if (rc) return rc;
-    *accepted = all ? 1 : 0;
-    return SONIC_OK;
+    return hsc_accepts(srs, vk, h, sv, {}, accepted);
   } catch (const HipFail& f) { return f.code; }
   catch (const std::exception& e) { set_error("%s", e.what()); return SONIC_ERR_HIP; }
 }

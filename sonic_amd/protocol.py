@@ -203,26 +203,10 @@ class Prover:
     """Circuit (and assignment) resident in HBM across proofs: sonic_prover_* of the C ABI."""
 
     def __init__(self, srs: SRS, circuit: ArithCircuit, prepare: bool = True):
-        if isinstance(circuit, SparseCircuit):             # gate weights as CSR (sonic_prover_new_csr)
-            self.Q, self.n = circuit.Q, circuit.n
-            self._srs = srs
-            self._h = C.c_void_p()
-            _lib.check(_lib.lib().sonic_prover_new_csr(srs._h, self.n, self.Q, *circuit._args(), circuit.cs.ctypes.data, C.byref(self._h)))
-            if prepare:
-                _lib.check(_lib.lib().sonic_prover_prepare(self._h))
-            return
-        w = circuit.weights
-        wL, wR, wO = fr_matrix(w.wL), fr_matrix(w.wR), fr_matrix(w.wO)
-        cs = fr_array(circuit.cs)
-        self.Q = cs.shape[0]
-        if self.Q < 1 or wL.shape[0] % self.Q:
-            raise ValueError("need Q >= 1 rectangular weight rows")
-        self.n = wL.shape[0] // self.Q
-        assert wR.shape == wL.shape and wO.shape == wL.shape
+        self.n, self.Q, suffix, args, _keep = _circuit_args(circuit)
         self._srs = srs
         self._h = C.c_void_p()
-        _lib.check(_lib.lib().sonic_prover_new(srs._h, self.n, self.Q, wL.ctypes.data, wR.ctypes.data, wO.ctypes.data,
-                                               cs.ctypes.data, C.byref(self._h)))
+        _lib.check(getattr(_lib.lib(), "sonic_prover_new" + suffix)(srs._h, self.n, self.Q, *args, C.byref(self._h)))
         if prepare:     # a handle exists to prove repeatedly: commit the constraint rows once (sonic_prover_prepare)
             _lib.check(_lib.lib().sonic_prover_prepare(self._h))
 
@@ -446,73 +430,52 @@ class ProverPipeline:
 def prove(srs: SRS, assignment: Assignment, circuit: ArithCircuit, transcript: Optional[list] = None, rng=None):
     """prove :: SRS -> Assignment Fr -> ArithCircuit Fr -> m (Proof, RndOracle) (Protocol.hs:47-52).
     `transcript` makes the MonadRandom draws explicit (reproducible proofs); default: fresh draws."""
-    if isinstance(circuit, SparseCircuit):
-        return _prove_sparse(srs, assignment, circuit, transcript, rng)
-    n = len(assignment.aL) if not isinstance(assignment.aL, np.ndarray) else fr_array(assignment.aL).shape[0]
-    Q = fr_array(circuit.cs).shape[0]
+    n, Q, suffix, args, _keep = _circuit_args(circuit)
     if srs.srsD < 7 * n:   # Protocol.hs:54-55 (checked again by the library)
         raise _lib.SonicError(1, f"Parameter d is not large enough: {srs.srsD} should be greater than {7 * n}")
     if transcript is None:
         transcript = draw_transcript(Q, rng)
-    # the one-shot entry point (sonic_prove): circuit, assignment and transcript as host buffers, like the reference's call; the library
-    # parks the handle's shell (streams, workspaces, twiddle tables) for the next call of the same shape -- making and freeing a handle
-    # per call cost ~7 ms of stream / pinned-memory set-up around a 2-ms proof at the reference's own benchmark sizes
-    wL, wR, wO, cs, n_c, Q_c = _circuit_arrays(circuit)
-    aL, aR, aO = fr_array(assignment.aL), fr_array(assignment.aR), fr_array(assignment.aO)
-    if n_c != n or aL.shape[0] != n or aR.shape[0] != n or aO.shape[0] != n:
-        raise ValueError("assignment and weight rows differ in length")
-    tr = fr_array(transcript)
-    if tr.shape[0] != 8 + 2 * Q:
-        raise ValueError(f"transcript needs 8 + 2Q = {8 + 2 * Q} elements")
-    out = C.create_string_buffer(_lib.lib().sonic_proof_size(Q))
-    _lib.check(_lib.lib().sonic_prove(srs._h, n, Q, wL.ctypes.data, wR.ctypes.data, wO.ctypes.data, cs.ctypes.data,
-                                      aL.ctypes.data, aR.ctypes.data, aO.ctypes.data, tr.ctypes.data, out))
-    raw = out.raw
-    t = [int(v) % R_MODULUS for v in transcript]
-    oracle = RndOracle(t[4], t[5], list(zip(t[6:6 + Q], t[6 + Q:6 + 2 * Q])))
-    return Proof.from_bytes(raw, Q), oracle
-
-
-def _prove_sparse(srs: SRS, assignment: Assignment, circuit: SparseCircuit, transcript, rng):
-    """prove for gate weights as CSR (sonic_prove_csr: the one-shot call, sharing sonic_prove's parked shells)"""
-    n, Q = circuit.n, circuit.Q
-    if srs.srsD < 7 * n:   # Protocol.hs:54-55 (checked again by the library)
-        raise _lib.SonicError(1, f"Parameter d is not large enough: {srs.srsD} should be greater than {7 * n}")
-    if transcript is None:
-        transcript = draw_transcript(Q, rng)
+    # the one-shot entry point (sonic_prove, sonic_prove_csr): circuit, assignment and transcript as host buffers, like the reference's
+    # call; the library parks the handle's shell (streams, workspaces, twiddle tables) for the next call of the same shape -- making and
+    # freeing a handle per call cost ~7 ms of stream / pinned-memory set-up around a 2-ms proof at the reference's own benchmark sizes
     aL, aR, aO = fr_array(assignment.aL), fr_array(assignment.aR), fr_array(assignment.aO)
     if aL.shape[0] != n or aR.shape[0] != n or aO.shape[0] != n:
-        raise ValueError("assignment and circuit differ in length")
+        raise ValueError(f"assignment and {'circuit' if suffix else 'weight rows'} differ in length")
     tr = fr_array(transcript)
     if tr.shape[0] != 8 + 2 * Q:
         raise ValueError(f"transcript needs 8 + 2Q = {8 + 2 * Q} elements")
     out = C.create_string_buffer(_lib.lib().sonic_proof_size(Q))
-    _lib.check(_lib.lib().sonic_prove_csr(srs._h, n, Q, *circuit._args(), circuit.cs.ctypes.data,
-                                          aL.ctypes.data, aR.ctypes.data, aO.ctypes.data, tr.ctypes.data, out))
+    _lib.check(getattr(_lib.lib(), "sonic_prove" + suffix)(srs._h, n, Q, *args, aL.ctypes.data, aR.ctypes.data, aO.ctypes.data, tr.ctypes.data, out))
     t = [int(v) % R_MODULUS for v in transcript]
     oracle = RndOracle(t[4], t[5], list(zip(t[6:6 + Q], t[6 + Q:6 + 2 * Q])))
     return Proof.from_bytes(out.raw, Q), oracle
 
 
-def _circuit_arrays(circuit: ArithCircuit):
+def _circuit_arrays(circuit: ArithCircuit, who: str = ""):
     w = circuit.weights
     wL, wR, wO = fr_matrix(w.wL), fr_matrix(w.wR), fr_matrix(w.wO)
     cs = fr_array(circuit.cs)
     Q = cs.shape[0]
     if Q < 1 or wL.shape[0] % Q or wL.shape[0] == 0 or wR.shape != wL.shape or wO.shape != wL.shape:
-        raise ValueError("need Q >= 1 weight rows of equal length n >= 1 in wL, wR, wO")
+        raise ValueError(who + "need Q >= 1 weight rows of equal length n >= 1 in wL, wR, wO")
     return wL, wR, wO, cs, wL.shape[0] // Q, Q
+
+
+def _circuit_args(circuit, who: str = ""):
+    """either circuit type, shapes checked -> (n, Q, suffix, args, keep): the entry points that take a circuit are called
+    `sonic_<name><suffix>` ("" dense, "_csr" sparse) with the pointers `args` (gate weights, then cs) where the circuit goes; `keep`
+    holds the arrays they point into"""
+    if isinstance(circuit, SparseCircuit):
+        return circuit.n, circuit.Q, "_csr", (*circuit._args(), circuit.cs.ctypes.data), circuit
+    wL, wR, wO, cs, n, Q = keep = _circuit_arrays(circuit, who)
+    return n, Q, "", (wL.ctypes.data, wR.ctypes.data, wO.ctypes.data, cs.ctypes.data), keep
 
 
 def fs_circuit_digest(circuit: ArithCircuit) -> bytes:
     """SHA-256 of (n, Q, wL, wR, wO, cs): the statement part of the Fiat-Shamir transcript, once per circuit"""
-    if isinstance(circuit, SparseCircuit):             # the same digest from the rows (sonic_fs_circuit_digest_csr; host only)
-        out = C.create_string_buffer(32)
-        _lib.check(_lib.lib().sonic_fs_circuit_digest_csr(circuit.n, circuit.Q, *circuit._args(), circuit.cs.ctypes.data, out))
-        return out.raw
-    wL, wR, wO, cs, n, Q = _circuit_arrays(circuit)
+    n, Q, suffix, args, _keep = _circuit_args(circuit)         # (sparse: the same digest from the rows; host only)
     out = C.create_string_buffer(32)
-    _lib.check(_lib.lib().sonic_fs_circuit_digest(n, Q, wL.ctypes.data, wR.ctypes.data, wO.ctypes.data, cs.ctypes.data, out))
+    _lib.check(getattr(_lib.lib(), "sonic_fs_circuit_digest" + suffix)(n, Q, *args, out))
     return out.raw
 
 
@@ -525,10 +488,7 @@ def fs_srs_id(srs: SRS) -> bytes:
 
 def fs_challenges(srs: SRS, circuit: ArithCircuit, proof: Proof) -> RndOracle:
     """the RndOracle a Fiat-Shamir proof determines (sonic_fs_challenges_v2)"""
-    if isinstance(circuit, SparseCircuit):
-        n, Q = circuit.n, circuit.Q
-    else:
-        wL, wR, wO, cs, n, Q = _circuit_arrays(circuit)
+    n, Q = _circuit_args(circuit)[:2]
     raw = proof.to_bytes()
     if len(raw) != _lib.lib().sonic_proof_size(Q):
         raise ValueError("fs_challenges: the proof does not have Q entries in its hsc lists")
@@ -554,20 +514,12 @@ def prove_fs(srs: SRS, assignment: Assignment, circuit: ArithCircuit, blinder_se
 
 def verify_fs(srs: SRS, circuit: ArithCircuit, proof: Proof) -> bool:
     """verify for a Fiat-Shamir proof: the challenges are recomputed from the circuit and the proof (sonic_verify_fs)"""
-    if isinstance(circuit, SparseCircuit):
-        h = proof.prHscProof
-        if len(h.hscS) != circuit.Q or len(h.hscW) != circuit.Q:
-            return False
-        ok = C.c_int(0)
-        _lib.check(_lib.lib().sonic_verify_fs_csr(srs._h, circuit.n, circuit.Q, *circuit._args(), circuit.cs.ctypes.data, proof.to_bytes(), C.byref(ok)))
-        return bool(ok.value)
-    wL, wR, wO, cs, n, Q = _circuit_arrays(circuit)
+    n, Q, suffix, args, _keep = _circuit_args(circuit)
     h = proof.prHscProof
     if len(h.hscS) != Q or len(h.hscW) != Q:
         return False
-    raw = proof.to_bytes()
     ok = C.c_int(0)
-    _lib.check(_lib.lib().sonic_verify_fs(srs._h, n, Q, wL.ctypes.data, wR.ctypes.data, wO.ctypes.data, cs.ctypes.data, raw, C.byref(ok)))
+    _lib.check(getattr(_lib.lib(), "sonic_verify_fs" + suffix)(srs._h, n, Q, *args, proof.to_bytes(), C.byref(ok)))
     return bool(ok.value)
 
 
@@ -644,12 +596,7 @@ def hsc_verify_poly(srs: SRS, sXY, yzs, proof: HscProof) -> bool:
 
 def hsc_verify(srs: SRS, circuit: ArithCircuit, yzs, proof: HscProof) -> bool:
     """hscVerify :: SRS -> BiVLaurent Fr -> [(Fr, Fr)] -> HscProof -> Bool (Signature.hs:74-90); host CPU pairings"""
-    w = circuit.weights
-    wL, wR, wO = fr_matrix(w.wL), fr_matrix(w.wR), fr_matrix(w.wO)
-    Q = fr_array(circuit.cs).shape[0]
-    if Q < 1 or wL.shape[0] % Q or wL.shape[0] == 0 or wR.shape != wL.shape or wO.shape != wL.shape:
-        raise ValueError("hsc_verify: need Q >= 1 weight rows of equal length n >= 1 in wL, wR, wO")
-    n = wL.shape[0] // Q
+    wL, wR, wO, _cs, n, Q = _circuit_arrays(circuit, "hsc_verify: ")
     yzs = list(yzs)
     if any(len(pair) != 2 for pair in yzs):
         raise ValueError("hsc_verify: yzs must hold (y_j, z_j) pairs")
@@ -667,15 +614,7 @@ def verify(srs: SRS, circuit: ArithCircuit, proof: Proof, y: int, z: int, yzs) -
     hscVerify (Signature.hs:74-90).  Runs on the host CPU (pairings); the SRS needs its G2 half (SRS.new, or a file
     that carries it).  Shapes are checked here because the C side reads 64 Q bytes of yzs and sonic_proof_size(Q)
     bytes of proof; a Proof whose hsc lists do not have Q entries is rejected (False), like any other malformed proof."""
-    if isinstance(circuit, SparseCircuit):
-        return _verify_sparse(srs, circuit, proof, y, z, yzs)
-    w = circuit.weights
-    wL, wR, wO = fr_matrix(w.wL), fr_matrix(w.wR), fr_matrix(w.wO)
-    cs = fr_array(circuit.cs)
-    Q = cs.shape[0]
-    if Q < 1 or wL.shape[0] % Q or wL.shape[0] == 0 or wR.shape != wL.shape or wO.shape != wL.shape:
-        raise ValueError("verify: need Q >= 1 weight rows of equal length n >= 1 in wL, wR, wO")
-    n = wL.shape[0] // Q
+    n, Q, suffix, args, _keep = _circuit_args(circuit, "verify: ")
     yzs = list(yzs)
     if len(yzs) != Q or any(len(pair) != 2 for pair in yzs):
         raise ValueError(f"verify: yzs must hold {Q} (y_j, z_j) pairs, got {len(yzs)}")
@@ -687,25 +626,5 @@ def verify(srs: SRS, circuit: ArithCircuit, proof: Proof, y: int, z: int, yzs) -
         return False
     flat = fr_array([v for pair in yzs for v in pair])
     ok = C.c_int(0)
-    _lib.check(_lib.lib().sonic_verify(srs._h, n, Q, wL.ctypes.data, wR.ctypes.data, wO.ctypes.data, cs.ctypes.data, raw,
-                                       fr_to_bytes(y), fr_to_bytes(z), flat.ctypes.data, C.byref(ok)))
-    return bool(ok.value)
-
-
-def _verify_sparse(srs: SRS, circuit: SparseCircuit, proof: Proof, y: int, z: int, yzs) -> bool:
-    """verify for gate weights as CSR (sonic_verify_csr: s(u, v) in O(nnz + n) on the host)"""
-    Q = circuit.Q
-    yzs = list(yzs)
-    if len(yzs) != Q or any(len(pair) != 2 for pair in yzs):
-        raise ValueError(f"verify: yzs must hold {Q} (y_j, z_j) pairs, got {len(yzs)}")
-    h = proof.prHscProof
-    if len(h.hscS) != Q or len(h.hscW) != Q:
-        return False
-    raw = proof.to_bytes()
-    if len(raw) != _lib.lib().sonic_proof_size(Q):
-        return False
-    flat = fr_array([v for pair in yzs for v in pair])
-    ok = C.c_int(0)
-    _lib.check(_lib.lib().sonic_verify_csr(srs._h, circuit.n, Q, *circuit._args(), circuit.cs.ctypes.data, raw,
-                                           fr_to_bytes(y), fr_to_bytes(z), flat.ctypes.data, C.byref(ok)))
+    _lib.check(getattr(_lib.lib(), "sonic_verify" + suffix)(srs._h, n, Q, *args, raw, fr_to_bytes(y), fr_to_bytes(z), flat.ctypes.data, C.byref(ok)))
     return bool(ok.value)

@@ -6,7 +6,9 @@
 //       i64 n, Q, d | x, alpha (32 B each) | wL, wR, wO (Q n x 32 B each) | cs (Q x 32) | proof | y, z (32 each) | yzs (Q x 64) |
 //       srsPairing = e(g, h^alpha) as oracle/pairing.py computes it, in sonic_srs_pairing's layout (576 B)
 // Runs sonic_verify on the golden proof (must accept), on proofs with one byte changed in every field (must reject or report a bad
-// encoding), with other challenges, sonic_pc_v on a hand-made opening, and sonic_verify_fs.  Prints "san_verify ok".
+// encoding), with other challenges, sonic_pc_v on a hand-made opening, and sonic_verify_fs -- and the same proofs through
+// sonic_verify_csr / sonic_verify_fs_csr with the circuit turned into CSR by dropping its zeros (same decisions; the two circuit
+// digests must be equal).  Prints "san_verify ok".
 #include <stdarg.h>
 #include <stdio.h>
 #include <map>
@@ -38,14 +40,6 @@ static Fr pow_signed(const Fr& a_mont, int64_t e) { return fp_pow_u64(e >= 0 ? a
 
 extern "C" {
 size_t sonic_proof_size(int64_t Q) { return (size_t)((7 + 4 * Q) * 96 + (5 + 2 * Q) * 32); }
-int sonic_fs_circuit_digest(int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO, const uint8_t* cs, uint8_t out[32]) {
-  Sha256 h;
-  h.update("sonic-hip/circuit/v1", 20);
-  FsTranscript::le64(h, n); FsTranscript::le64(h, Q);
-  h.update(wL, (size_t)(32 * Q * n)); h.update(wR, (size_t)(32 * Q * n)); h.update(wO, (size_t)(32 * Q * n)); h.update(cs, (size_t)(32 * Q));
-  h.finish(out);
-  return 0;
-}
 // g^{alpha^basis x^e} from the trapdoor, canonical bytes (the Fiat-Shamir verifier reads four of them for the srs id, fs.hpp)
 int sonic_srs_get_points(const sonic_srs_t* srs, int basis, int64_t e0, int64_t n, uint8_t* out) {
   constexpr uint32_t gx[12] = G1_GEN_X_MONT, gy[12] = G1_GEN_Y_MONT;
@@ -101,8 +95,26 @@ int main(int argc, char** argv) {
   sonic_srs srs;
   srs.d = d;
   CHECK(load_fr(xb.data(), srs.x) && load_fr(ab.data(), srs.alpha), "trapdoor canonical");
+  // the same circuit as ONE CSR of 3Q rows: the non-zero entries of wL, wR, wO in row order
+  std::vector<int64_t> row_ptr(1, 0), col;
+  std::vector<uint8_t> val;
+  for (const std::vector<uint8_t>* w : {&wL, &wR, &wO})
+    for (int64_t q = 0; q < Q; q++) {
+      for (int64_t i = 0; i < n; i++) {
+        const uint8_t* e = w->data() + 32 * (q * n + i);
+        if (std::all_of(e, e + 32, [](uint8_t b) { return b == 0; })) continue;
+        col.push_back(i);
+        val.insert(val.end(), e, e + 32);
+      }
+      row_ptr.push_back((int64_t)col.size());
+    }
+  auto verify_csr = [&](const uint8_t* pf, int* acc) {
+    return sonic_verify_csr(&srs, n, Q, row_ptr.data(), col.data(), val.data(), cs.data(), pf, y.data(), z.data(), yzs.data(), acc);
+  };
   int ok = -1;
   CHECK(sonic_verify(&srs, n, Q, wL.data(), wR.data(), wO.data(), cs.data(), proof.data(), y.data(), z.data(), yzs.data(), &ok) == 0 && ok == 1, "the golden proof is accepted");
+  ok = -1;
+  CHECK(verify_csr(proof.data(), &ok) == 0 && ok == 1, "the golden proof is accepted with the circuit as CSR");
   // one byte changed in one element of every kind: a field element (low byte: stays canonical), a point (leaves the curve)
   const size_t offs[] = {0, 96, 192, 224, 320, 352, 448, 544, 576, 576 + 96, 576 + 128, (size_t)(576 + 224 * Q), (size_t)(576 + 224 * Q + 32),
                          (size_t)(576 + 448 * Q), (size_t)(576 + 448 * Q + 96), proof.size() - 64, proof.size() - 32};
@@ -112,6 +124,8 @@ int main(int argc, char** argv) {
     ok = -1;
     const int rc = sonic_verify(&srs, n, Q, wL.data(), wR.data(), wO.data(), cs.data(), bad.data(), y.data(), z.data(), yzs.data(), &ok);
     CHECK((rc == 0 && ok == 0) || rc == SONIC_ERR_BAD_ENCODING, "a tampered proof is rejected");
+    ok = -1;
+    CHECK(verify_csr(bad.data(), &ok) == rc && ok == 0, "a tampered proof is rejected alike with the circuit as CSR");
   }
   {
     std::vector<uint8_t> y2 = y; y2[0] ^= 1;
@@ -120,6 +134,8 @@ int main(int argc, char** argv) {
     memset(&bad[192], 0xff, 32);                                        // prA >= r
     CHECK(sonic_verify(&srs, n, Q, wL.data(), wR.data(), wO.data(), cs.data(), bad.data(), y.data(), z.data(), yzs.data(), &ok) == SONIC_ERR_BAD_ENCODING, "non-canonical field element");
     CHECK(sonic_verify(&srs, n, Q, wL.data(), wR.data(), wO.data(), cs.data(), nullptr, y.data(), z.data(), yzs.data(), &ok) == SONIC_ERR_INVALID_ARG, "null proof");
+    CHECK(verify_csr(bad.data(), &ok) == SONIC_ERR_BAD_ENCODING, "non-canonical field element, CSR");
+    CHECK(verify_csr(nullptr, &ok) == SONIC_ERR_INVALID_ARG, "null proof, CSR");
   }
   // pcV on its own (CommitmentScheme.hs:51-68): R and its opening at z from the proof: max = n
   CHECK(sonic_pc_v(&srs, n, &proof[0], z.data(), &proof[192], &proof[224], &ok) == 0 && ok == 1, "pcV accepts (R, z, a, W_a)");
@@ -129,6 +145,13 @@ int main(int argc, char** argv) {
   CHECK(sonic_hsc_verify(&srs, n, Q, wL.data(), wR.data(), wO.data(), Q, yzs.data(), &proof[576], &ok) == 0 && ok == 1, "hscVerify accepts");
   // the Fiat-Shamir verifier on a proof made with drawn challenges: its u, v are not its transcript's -> rejected, no pairing needed
   CHECK(sonic_verify_fs(&srs, n, Q, wL.data(), wR.data(), wO.data(), cs.data(), proof.data(), &ok) == 0 && ok == 0, "verify_fs rejects a proof with foreign challenges");
+  CHECK(sonic_verify_fs_csr(&srs, n, Q, row_ptr.data(), col.data(), val.data(), cs.data(), proof.data(), &ok) == 0 && ok == 0, "verify_fs_csr rejects it too");
+  {
+    uint8_t dd[32], ds[32];
+    CHECK(circuit_digest_checked("sonic_fs_circuit_digest", dense_view(n, Q, wL.data(), wR.data(), wO.data(), cs.data()), dd) == 0, "the dense digest (sonic_fs_circuit_digest's body)");
+    CHECK(sonic_fs_circuit_digest_csr(n, Q, row_ptr.data(), col.data(), val.data(), cs.data(), ds) == 0, "sonic_fs_circuit_digest_csr");
+    CHECK(memcmp(dd, ds, 32) == 0, "the CSR digest equals the dense digest");
+  }
   // srsPairing (SRS.hs:21,42) against the python oracle's pairing of the same two points
   {
     uint8_t got[576];

@@ -1,8 +1,9 @@
 """AddressSanitizer + UndefinedBehaviorSanitizer over the product's HOST code (CPU only -- GPU sanitizers are not
 available on this pool): the limb arithmetic / point formulas as the host compiles them, the shared-inversion normalisations, the
 SHA-256 and Fiat-Shamir transcript code, the SRS file parser on hostile files (tests/host/san_host.cpp); the verifier's whole host
-path -- sonic_pc_v, sonic_hsc_verify, sonic_verify, sonic_verify_fs from sonic_amd/csrc/verify.hip compiled as C++ -- on a golden
-proof and tampered copies of it (tests/host/san_verify.cpp); and the pairing self-test (tests/pairing_selftest.cpp).  Any report
+path -- sonic_pc_v, sonic_hsc_verify, sonic_verify, sonic_verify_fs, their `_csr` forms and both circuit digests from
+sonic_amd/csrc/verify.hip compiled as C++ -- on a golden proof and tampered copies of it, with the circuit dense and as CSR
+(tests/host/san_verify.cpp); and the pairing self-test (tests/pairing_selftest.cpp).  Any report
 aborts the binary (-fno-sanitize-recover=all)."""
 import json
 import os
