@@ -84,6 +84,7 @@ enum {
 
 typedef struct sonic_srs sonic_srs_t;
 typedef struct sonic_prover sonic_prover_t;
+typedef struct sonic_verifier sonic_verifier_t;
 
 /* ---- library ---- */
 #define SONIC_ABI_VERSION 7
@@ -91,7 +92,9 @@ typedef struct sonic_prover sonic_prover_t;
  * sonic_msm_reduce_slices_dev_v2 and sonic_fs_challenges_v2 replace the symbols whose meaning changed in round 4; share format 2);
  * 6 = round 6 (additions only: sonic_prove_batch fuses the proofs of a handle group, sonic_one_shot_trim);
  * 7 = round 7 (additions only: gate weights as CSR -- sonic_prover_new_csr, sonic_prove_csr, sonic_fs_circuit_digest_csr,
- * sonic_verify_csr, sonic_verify_fs_csr) */
+ * sonic_verify_csr, sonic_verify_fs_csr); still 7, additions only: the batched verifier -- sonic_verifier_new[_csr], sonic_verifier_free,
+ * sonic_verifier_device, sonic_verifier_verify_batch, sonic_verifier_verify_fs_batch, sonic_verifier_eval_s, sonic_g1_validate,
+ * sonic_verify_batch_randomizers */
 int sonic_abi_version(void);
 int sonic_init(int device_ordinal);                 /* choose the DEFAULT GPU (first call wins) and make it the thread's HIP device; idempotent */
 int sonic_device_count(int* out);                   /* GPUs this process can see; SONIC_ERR_NO_DEVICE (and 0) without one */
@@ -405,6 +408,42 @@ int sonic_hsc_verify(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t
 /* hscVerify (Signature.hs:74-90) for any sparse bivariate Laurent polynomial, the counterpart of sonic_hsc_prove_poly */
 int sonic_hsc_verify_poly(const sonic_srs_t* srs, int64_t n_terms, const int64_t* x_exps, const int64_t* y_exps, const uint8_t* coeffs,
                           int64_t m, const uint8_t* yzs, const uint8_t* hsc, int* accepted);
+
+/* ---- the batched verifier: K proofs for one circuit folded into ONE pairing product (device: point validation, s(u, v), the G1 sums) ----
+ * A pcV check i = (max_i, F_i, z_i, v_i, W_i) holds iff e(W_i, h^{alpha x}) e(g^{v_i} W_i^{-z_i}, h^alpha) = e(F_i, h^{x^{max_i - d}}).  With
+ * non-zero 128-bit randomizers rho_i, over all 4 + 3Q checks of all K proofs, the fold accepts iff
+ *     e(sum rho_i W_i, h^{alpha x}) e((sum rho_i v_i) g - sum (rho_i z_i) W_i, h^alpha) prod_m e(-sum_{max_i = m} rho_i F_i, h^{x^{m-d}}) = 1
+ * -- four Miller loops and one final exponentiation whatever K and Q are; a batch with a false equation passes with probability <= 2^-128.
+ * rho_i = the first 16 bytes (little-endian) of SHA-256("sonic-hip/batch/v1" || seed || D || le64 i), 0 replaced by 1, where i = k (3Q + 4) +
+ * (the check's index in sonic_verify's order) and D = SHA-256("sonic-hip/batch-digest/v1" || le64 n || le64 Q || le64 d || circuit digest ||
+ * srs id || le64 K || K x (proof bytes || its challenges)): D binds everything the verdict depends on.
+ *
+ * The handle holds the circuit in device memory (as CSR, whichever form it is made from), the four G2 elements, the circuit digest, a
+ * stream and an MSM workspace on the SRS's device.  It borrows the SRS, which must outlive it.  One call at a time per handle (calls on
+ * one handle serialise); any number of handles may share an SRS.  Errors of construction are those of sonic_verify for the same circuit and SRS. */
+int sonic_verifier_new(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO, const uint8_t* cs,
+                       sonic_verifier_t** out);
+int sonic_verifier_new_csr(const sonic_srs_t* srs, int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val,
+                           const uint8_t* cs, sonic_verifier_t** out);
+void sonic_verifier_free(sonic_verifier_t* v);
+int sonic_verifier_device(const sonic_verifier_t* v);
+/* proofs: K x sonic_proof_size(Q) bytes.  challenges: K blocks of (2 + 2Q) Fr: y, z, then Q pairs (y_j, z_j) -- sonic_verify's arguments, proof
+ * by proof.  seed: 32 bytes, or NULL (the library draws them from the operating system).  *all_accepted = 1 iff every proof is well-formed
+ * and the fold over all of them holds.  each (K bytes, or NULL): per-proof verdicts -- all ones when *all_accepted; otherwise every
+ * well-formed proof is folded on its own.  A MALFORMED PROOF (a non-canonical field element, a point off the curve or outside the
+ * subgroup; also u = 0 or v = 0) IS A REJECTED PROOF, NOT A FAILED CALL: SONIC_OK, each[k] = 0, sonic_last_error names the first one --
+ * unlike sonic_verify, so that one hostile proof cannot hide the verdicts of the others.  K < 1 or K (4Q + 7) > 2^26: SONIC_ERR_INVALID_ARG. */
+int sonic_verifier_verify_batch(sonic_verifier_t* v, int64_t K, const uint8_t* proofs, const uint8_t* challenges, const uint8_t seed[32],
+                                int* all_accepted, uint8_t* each);
+/* Fiat-Shamir form: the challenges are recomputed per proof as sonic_verify_fs does; a proof whose own u, v are not its transcript's is rejected */
+int sonic_verifier_verify_fs_batch(sonic_verifier_t* v, int64_t K, const uint8_t* proofs, const uint8_t seed[32], int* all_accepted, uint8_t* each);
+/* the two kernels on their own.  eval_s: s(u_k, v_k) of the handle's circuit for K pairs (uv: K x 64 bytes, out: K x 32); a pair with u = 0 or
+ * v = 0 gets 32 bytes of 0xff and the call returns SONIC_ERR_INEXACT_DIVISION after the other values are written.  g1_validate: flags[i] = 1
+ * iff points[i] is what the host verifier accepts (canonical; infinity, or on the curve and in the order-r subgroup). */
+int sonic_verifier_eval_s(sonic_verifier_t* v, int64_t K, const uint8_t* uv, uint8_t* out);
+int sonic_g1_validate(const uint8_t* points, int64_t n, uint8_t* flags);
+/* host only, no device: rho_0 .. rho_{count-1} of a batch with digest D (out: count x 16 bytes, little-endian) */
+int sonic_verify_batch_randomizers(const uint8_t seed[32], const uint8_t batch_digest[32], int64_t count, uint8_t* out);
 
 /* ---- device memory for callers without a HIP binding ---- */
 int sonic_dev_alloc(size_t bytes, void** out);                       /* on the default device */

@@ -5,7 +5,7 @@ Python host-side mirror of the reference's Haskell modules over the C ABI of
 
     Sonic.SRS               -> sonic_amd.srs          (SRS, SRS.new)
     Sonic.CommitmentScheme  -> sonic_amd.commitment   (commit_poly, open_poly, pc_v)
-    Sonic.Protocol          -> sonic_amd.protocol     (prove, verify, Proof, RndOracle, Prover)
+    Sonic.Protocol          -> sonic_amd.protocol     (prove, verify, Proof, RndOracle, Prover; Verifier / verify_batch: K proofs, one pairing product)
     Sonic.Signature         -> sonic_amd.protocol     (HscProof, hsc_prove, hsc_verify; hscProve also runs inside prove)
 
 All compute happens in hand-written HIP kernels on the GPU; this package is ctypes plumbing.
@@ -28,6 +28,7 @@ from .protocol import proof_from_shares, share_plan, from_x, from_y, biv_add  # 
 from .protocol import prove_shared, prove_batch, prove_many, device_count  # noqa: F401,E402
 from .commitment import msm_g1_srs_multi  # noqa: F401,E402
 from .protocol import prove, verify, hsc_prove, hsc_verify, Proof, HscProof, RndOracle, Prover, ProverPipeline, ArithCircuit, SparseCircuit, Assignment, GateWeights  # noqa: F401,E402
+from .protocol import Verifier, verify_batch  # noqa: F401,E402
 
-__all__ = ["SRS", "commit_poly", "open_poly", "pc_v", "msm_g1", "MsmLane", "prove", "verify", "prove_fs", "verify_fs", "fs_challenges", "fs_circuit_digest", "hsc_prove", "hsc_verify", "hsc_prove_poly", "hsc_verify_poly", "Proof", "HscProof", "RndOracle", "Prover", "ProverPipeline",
+__all__ = ["Verifier", "verify_batch", "SRS", "commit_poly", "open_poly", "pc_v", "msm_g1", "MsmLane", "prove", "verify", "prove_fs", "verify_fs", "fs_challenges", "fs_circuit_digest", "hsc_prove", "hsc_verify", "hsc_prove_poly", "hsc_verify_poly", "Proof", "HscProof", "RndOracle", "Prover", "ProverPipeline",
            "ArithCircuit", "SparseCircuit", "Assignment", "GateWeights", "SonicError"]

@@ -137,6 +137,14 @@ def lib() -> C.CDLL:
         "sonic_hsc_verify": [vp, i64, i64, vp, vp, vp, i64, vp, vp, C.POINTER(i32)],
         "sonic_pc_v": [vp, i64, cp, cp, cp, cp, C.POINTER(i32)],
         "sonic_verify": [vp, i64, i64, vp, vp, vp, vp, vp, cp, cp, vp, C.POINTER(i32)],
+        "sonic_verifier_new": [vp, i64, i64, vp, vp, vp, vp, C.POINTER(vp)],
+        "sonic_verifier_new_csr": [vp, i64, i64, vp, vp, vp, vp, C.POINTER(vp)],
+        "sonic_verifier_device": [vp],
+        "sonic_verifier_verify_batch": [vp, i64, vp, vp, cp, C.POINTER(i32), vp],
+        "sonic_verifier_verify_fs_batch": [vp, i64, vp, cp, C.POINTER(i32), vp],
+        "sonic_verifier_eval_s": [vp, i64, vp, vp],
+        "sonic_g1_validate": [vp, i64, vp],
+        "sonic_verify_batch_randomizers": [cp, cp, i64, vp],
         "sonic_dev_alloc": [C.c_size_t, C.POINTER(vp)],
         "sonic_dev_free": [vp],
         "sonic_dev_upload": [vp, vp, C.c_size_t],
@@ -157,6 +165,8 @@ def lib() -> C.CDLL:
     L.sonic_srs_free.restype = None
     L.sonic_prover_free.argtypes = [vp]
     L.sonic_prover_free.restype = None
+    L.sonic_verifier_free.argtypes = [vp]
+    L.sonic_verifier_free.restype = None
     L.sonic_msm_lane_free.argtypes = [vp]
     L.sonic_msm_lane_free.restype = None
     L.sonic_srs_d.argtypes = [vp]
@@ -216,6 +226,8 @@ EXPORTED = [
     "sonic_dev_download", "sonic_profile_enable", "sonic_profile_reset", "sonic_profile_get",
     "sonic_profile_names",
     "sonic_prover_new_csr", "sonic_prove_csr", "sonic_fs_circuit_digest_csr", "sonic_verify_csr", "sonic_verify_fs_csr",
+    "sonic_verifier_new", "sonic_verifier_new_csr", "sonic_verifier_free", "sonic_verifier_device", "sonic_verifier_verify_batch", "sonic_verifier_verify_fs_batch",
+    "sonic_verifier_eval_s", "sonic_g1_validate", "sonic_verify_batch_randomizers",
 ]
 
 

@@ -1,0 +1,607 @@
+// The batched verifier: K proofs for ONE circuit folded into one pairing product (Sonic's "helped"/batched setting).
+//
+// A pcV check i = (max_i, F_i, z_i, v_i, W_i) holds iff e(W_i, h^{alpha x}) e(g^{v_i} W_i^{-z_i}, h^alpha) = e(F_i, h^{x^{max_i - d}}).  With
+// non-zero 128-bit randomizers rho_i the fold accepts iff
+//
+//     e(sum rho_i W_i, h^{alpha x}) . e((sum rho_i v_i) g - sum (rho_i z_i) W_i, h^alpha) . prod_m e(- sum_{max_i = m} rho_i F_i, h^{x^{m-d}}) = 1
+//
+// over all checks of all proofs: 2 + (distinct m) Miller loops -- 4 for `verify`, m in {n, d} -- and ONE final exponentiation, whatever K
+// and Q are.  What grows with K runs on the device:
+//   k_g1_validate      K (4Q + 7) proof points: canonical, on the curve, r P = O -- exactly what load_g1 accepts (verify_host.hpp)
+//   k_s_of_uv_batch    s(u_k, v_k) for K pairs over the handle's resident circuit (device CSR), O(K (nnz + n)), no K x n table
+//   the G1 sums        the variable-base MSM of msm.hip over the validated points, on the handle's own stream and workspace
+// and the host keeps the list of checks (proof_checks: the same function sonic_verify uses), the scalars rho_i, rho_i z_i (K (3Q + 4) Fr
+// products) and the pairing tail.
+//
+// rho_i = the first 128 bits (little-endian) of SHA-256("sonic-hip/batch/v1" || seed || D || le64 i), 0 replaced by 1, with
+// D = SHA-256("sonic-hip/batch-digest/v1" || le64 n || le64 Q || le64 d || circuit digest || srs id || le64 K || K x (proof bytes || its
+// 2 + 2Q challenges)) and i = k (3Q + 4) + (index of the check in proof_checks' order).  D binds everything the verdict depends on, so even
+// a fixed public seed leaves a cheating prover no rho to aim at.
+#include <string.h>
+#include <sys/random.h>
+#include <algorithm>
+#include <chrono>
+#include <memory>
+#include <system_error>
+#include "verify_host.hpp"
+
+namespace sonic {
+namespace {
+
+// ---- kernels --------------------------------------------------------------------------------------------------------------------
+
+// M points from their 96-byte encodings -> affine Montgomery points for the MSM and one flag per point: 1 = what load_g1 accepts (both
+// coordinates canonical; the encoding of infinity, or on the curve and r P = O by the literal double-and-add over the bits of r).  A
+// refused point is written as infinity, so that nothing downstream ever adds a point outside the subgroup.
+__global__ __launch_bounds__(256) void k_g1_validate(const uint8_t* __restrict__ in, G1Affine* __restrict__ out, uint8_t* __restrict__ flags, long n) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(in + 96 * i);
+  G1Affine p;
+  for (int k = 0; k < 12; k++) { p.x.l[k] = w[k]; p.y.l[k] = w[12 + k]; }
+  if (p.is_inf()) { out[i] = p; flags[i] = 1; return; }
+  bool ok = fp_is_canonical(p.x) && fp_is_canonical(p.y);
+  if (ok) {
+    p.x = fp_to_mont(p.x); p.y = fp_to_mont(p.y);
+    const Fq four = fp_dbl(fp_dbl(Fq::one()));
+    ok = fp_sqr(p.y) == fp_add(fp_mul(fp_sqr(p.x), p.x), four);
+  }
+  if (ok) {
+    constexpr uint32_t rl[8] = FR_P;
+    G1XYZZ acc = G1XYZZ::from_affine(p);       // top bit (254) of r
+#pragma unroll 1
+    for (int b = 253; b >= 0; b--) {
+      acc = g1_dbl(acc);
+      uint32_t wd = 0;                           // constant-index reads keep rl[] out of scratch
+#pragma unroll
+      for (int k = 0; k < 8; k++) if (k == (b >> 5)) wd = rl[k];
+      if ((wd >> (b & 31)) & 1u) acc = g1_add_mixed(acc, p);
+    }
+    ok = acc.is_inf();
+  }
+  out[i] = ok ? p : G1Affine::inf();
+  flags[i] = ok ? 1 : 0;
+}
+
+// The resident circuit: the 3Q rows as CSR (values Montgomery) and the work items the s-kernel's threads take -- at most S_ITEM entries of
+// one row each, then S_ITEM consecutive gates of the diagonal each.
+constexpr int S_ITEM = 32;
+constexpr int S_BLOCK = 256;
+struct CircuitDev {
+  long n, Q, nnz;
+  long row_items, items, nblk;                  // items = row_items + ceil(n / S_ITEM); nblk = ceil(items / S_BLOCK)
+  const int32_t *row_ptr, *col, *item_row, *item_begin;
+  const Fr* val;
+};
+struct UvPair { Fr u, uinv, v, vinv; };          // Montgomery; the inverses of a zero are zero (the proof is refused)
+
+__device__ __forceinline__ Fr block_sum(Fr acc, Fr* sh) {
+  sh[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = S_BLOCK / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) sh[threadIdx.x] = fp_add(sh[threadIdx.x], sh[threadIdx.x + s]);
+    __syncthreads();
+  }
+  return sh[0];
+}
+
+// s(u_k, v_k) = sum_q v^{n+q+1} sum_{entries of rows q, Q+q, 2Q+q} val u^{-i | i | i+n}  -  sum_i u^{i+n} (v^i + v^-i), the sum of s_of_uv
+// (verify_host.hpp).  Grid = (proof, block of S_BLOCK items); a thread gets the power at the start of its item by one exponentiation and
+// steps from there (column gaps inside a sparse row by a short exponentiation); the block's partial sums are reduced in LDS and written
+// to partial[k * nblk + block]; k_s_of_uv_finish adds them per proof.
+__global__ __launch_bounds__(S_BLOCK) void k_s_of_uv_batch(CircuitDev c, const UvPair* __restrict__ uv, long K, Fr* __restrict__ partial) {
+  __shared__ Fr sh[S_BLOCK];
+  const long k = (long)blockIdx.x / c.nblk, blk = (long)blockIdx.x % c.nblk;
+  const UvPair p = uv[k];
+  if (p.u.is_zero() || p.v.is_zero()) return;                  // refused per proof (block-uniform): k_s_of_uv_finish flags it
+  const long t = blk * S_BLOCK + threadIdx.x;
+  Fr acc = Fr::zero();
+  if (t < c.row_items) {
+    const long r = c.item_row[t], b = c.item_begin[t];
+    const long rend = c.row_ptr[r + 1], e = b + S_ITEM < rend ? b + S_ITEM : rend;
+    const int mat = (int)(r / c.Q);
+    const long q = r % c.Q;
+    const Fr base = mat == 0 ? p.uinv : p.u;
+    long iprev = 0;
+    Fr pw = Fr::one();
+    for (long x = b; x < e; x++) {
+      const long i = c.col[x] + 1;
+      const long gap = x == b ? (mat == 2 ? i + c.n : i) : i - iprev;
+      pw = gap == 1 ? fp_mul(pw, base) : fp_mul(pw, fp_pow_u64(base, (uint64_t)gap));
+      iprev = i;
+      acc = fp_add(acc, fp_mul(c.val[x], pw));
+    }
+    acc = fp_mul(acc, fp_pow_u64(p.v, (uint64_t)(c.n + q + 1)));
+  } else if (t < c.items) {
+    const long i0 = 1 + (t - c.row_items) * S_ITEM, i1 = i0 + S_ITEM - 1 < c.n ? i0 + S_ITEM - 1 : c.n;
+    Fr a = fp_pow_u64(p.u, (uint64_t)(i0 + c.n)), vp = fp_pow_u64(p.v, (uint64_t)i0), vm = fp_pow_u64(p.vinv, (uint64_t)i0);
+    for (long i = i0; i <= i1; i++) {
+      acc = fp_sub(acc, fp_mul(a, fp_add(vp, vm)));
+      a = fp_mul(a, p.u); vp = fp_mul(vp, p.v); vm = fp_mul(vm, p.vinv);
+    }
+  }
+  const Fr sum = block_sum(acc, sh);
+  if (threadIdx.x == 0) partial[k * c.nblk + blk] = sum;
+}
+// one block per proof: out[k] = sum of its nblk partial sums (Montgomery), ok[k] = 0 for a refused pair (u = 0 or v = 0; out[k] = 0)
+__global__ __launch_bounds__(S_BLOCK) void k_s_of_uv_finish(const Fr* __restrict__ partial, long nblk, const UvPair* __restrict__ uv, Fr* __restrict__ out,
+                                                            uint8_t* __restrict__ ok) {
+  __shared__ Fr sh[S_BLOCK];
+  const long k = blockIdx.x;
+  const bool refused = uv[k].u.is_zero() || uv[k].v.is_zero();
+  Fr acc = Fr::zero();
+  if (!refused) for (long j = threadIdx.x; j < nblk; j += S_BLOCK) acc = fp_add(acc, partial[k * nblk + j]);
+  const Fr sum = block_sum(acc, sh);
+  if (threadIdx.x == 0) { out[k] = sum; ok[k] = refused ? 0 : 1; }
+}
+
+double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// host phases of a batch, in the kernel profiler's table (sonic_profile_get) under names no kernel has
+void host_phase(const char* name, double ms) {
+  if (!profiler().on) return;
+  std::lock_guard<std::mutex> g(profiler().mu);
+  auto& t = profiler().totals[name];
+  t.first += ms; t.second += 1;
+}
+
+void le64(Sha256& h, int64_t v) { FsTranscript::le64(h, v); }
+
+}  // namespace
+
+// rho_i for i in [i0, i0 + count): 16 bytes each, little-endian
+void batch_randomizers(const uint8_t seed[32], const uint8_t D[32], int64_t i0, int64_t count, uint8_t* out) {
+  for (int64_t i = 0; i < count; i++) {
+    Sha256 h;
+    uint8_t dg[32];
+    h.update("sonic-hip/batch/v1", 18); h.update(seed, 32); h.update(D, 32); le64(h, i0 + i);
+    h.finish(dg);
+    bool zero = true;
+    for (int b = 0; b < 16; b++) zero = zero && dg[b] == 0;
+    if (zero) dg[0] = 1;
+    memcpy(out + 16 * i, dg, 16);
+  }
+}
+
+}  // namespace sonic
+
+using namespace sonic;
+
+struct sonic_verifier {
+  const sonic_srs* srs = nullptr;
+  int device = 0;
+  long n = 0, Q = 0;
+  int64_t d = 0;
+  VerifierKey vk;
+  std::vector<int64_t> ms;              // the distinct max of a proof's checks: n and d (one entry when n == d)
+  std::vector<G2Affine> hm;             // h^{x^{m - d}} for them
+  uint8_t digest[32], srs_id[32];
+  std::vector<uint8_t> cs;
+  std::mutex mu;                        // one call at a time per handle
+  hipStream_t st = nullptr;
+  MsmWorkspace ws;
+  CircuitDev cd;
+  DevBuf row_ptr, col, val, item_row, item_begin;
+  // per call, grown on demand: K (4Q + 7) encodings, points and flags; K pairs, s-values and flags; K nblk partial sums; the scalars
+  DevBuf raw, pts, flags, uv, sv, sok, partial, scalars;
+};
+
+namespace {
+
+struct Sums { G1Affine A, B; std::vector<G1Affine> C; };
+
+// one batch in flight
+struct Batch {
+  sonic_verifier* v;
+  long K, NP, NC;                       // points and checks per proof
+  std::vector<char> good;               // well-formed and not refused (u, v != 0)
+  std::vector<Fr> gv;                   // per proof: sum rho_i v_i (Montgomery)
+  size_t N() const { return (size_t)K * (size_t)NP; }
+  const Fr* scal(int which) const { return v->scalars.as<Fr>() + (size_t)which * N(); }     // 0: rho (on W), 1: rho z (on W), 2 + c: rho on the F's of class c
+};
+
+// sum_{k0 <= k < k1} of one scalar array over the proofs' points
+G1XYZZ range_msm(const Batch& b, int which, long k0, long k1) {
+  sonic_verifier* v = b.v;
+  const long n = (k1 - k0) * b.NP;
+  uint8_t part[192];
+  msm_blocking(v->st, v->ws, msm_plan(n), PointArray::packed(v->pts.as<G1Affine>() + k0 * b.NP), b.scal(which) + k0 * b.NP, n, false, nullptr, part);
+  G1XYZZ s;
+  memcpy(&s, part, sizeof s);
+  return s;
+}
+// the G1 side of the fold over proofs [k0, k1)
+Sums fold_sums(const Batch& b, long k0, long k1) {
+  Sums s;
+  s.A = g1_to_affine(range_msm(b, 0, k0, k1));
+  Fr g = Fr::zero();
+  for (long k = k0; k < k1; k++) if (b.good[(size_t)k]) g = fp_add(g, b.gv[(size_t)k]);
+  s.B = g1_to_affine(g1_add(g1_mul_fr(g1_gen_host(), fp_from_mont(g)), g1_neg(range_msm(b, 1, k0, k1))));
+  for (size_t c = 0; c < b.v->ms.size(); c++) s.C.push_back(g1_neg(g1_to_affine(range_msm(b, 2 + (int)c, k0, k1))));
+  return s;
+}
+// the pairing side: 2 + (distinct m) Miller loops, on host threads when `threads`, one product, one final exponentiation
+bool fold_accepts(const sonic_verifier* v, const Sums& s, bool threads) {
+  using namespace pairing;
+  const size_t L = 2 + s.C.size();
+  std::vector<F12> f(L);
+  auto work = [&](size_t i) { f[i] = i == 0 ? miller_loop(s.A, v->vk.h_alpha_x) : i == 1 ? miller_loop(s.B, v->vk.h_alpha) : miller_loop(s.C[i - 2], v->hm[i - 2]); };
+  {
+    ThreadGroup th;
+    size_t started = 1;
+    if (threads) {
+      try {
+        for (; started < L; started++) th.emplace_back(work, started);
+      } catch (const std::system_error&) {}      // thread limit of the host process: the calling thread takes the rest
+    } else started = L;
+    work(0);
+    if (!threads) for (size_t i = 1; i < L; i++) work(i);
+    else for (size_t i = started; i < L; i++) work(i);
+    th.join();
+  }
+  F12 prod = f[0];
+  for (size_t i = 1; i < L; i++) prod = f12_mul(prod, f[i]);
+  return final_exponentiation(prod).is_one();
+}
+
+// s(u_k, v_k) for K pairs (standard-form pairs on the host, canonical) on the handle's stream: Montgomery values and per-pair flags
+void eval_s_device(sonic_verifier* v, long K, const std::vector<Fr>& us, const std::vector<Fr>& vs, std::vector<Fr>& out, std::vector<uint8_t>& ok) {
+  // inverses by Montgomery's trick: one inversion for the batch (zeros are left out and keep a zero inverse)
+  std::vector<UvPair> h((size_t)K);
+  std::vector<Fr> pre((size_t)(2 * K));
+  Fr run = Fr::one();
+  for (long i = 0; i < 2 * K; i++) {
+    const Fr& x = i & 1 ? vs[(size_t)(i >> 1)] : us[(size_t)(i >> 1)];
+    pre[(size_t)i] = run;
+    if (!x.is_zero()) run = fp_mul(run, x);
+  }
+  Fr inv = fp_inv(run);
+  for (long i = 2 * K - 1; i >= 0; i--) {
+    const Fr& x = i & 1 ? vs[(size_t)(i >> 1)] : us[(size_t)(i >> 1)];
+    Fr xi = Fr::zero();
+    if (!x.is_zero()) { xi = fp_mul(inv, pre[(size_t)i]); inv = fp_mul(inv, x); }
+    UvPair& p = h[(size_t)(i >> 1)];
+    if (i & 1) { p.v = x; p.vinv = xi; } else { p.u = x; p.uinv = xi; }
+  }
+  v->uv.ensure(sizeof(UvPair) * (size_t)K);
+  v->sv.ensure(sizeof(Fr) * (size_t)K);
+  v->sok.ensure((size_t)K);
+  v->partial.ensure(sizeof(Fr) * (size_t)K * (size_t)v->cd.nblk);
+  hipStream_t st = v->st;
+  HIP_OK(hipMemcpyAsync(v->uv.p, h.data(), sizeof(UvPair) * (size_t)K, hipMemcpyHostToDevice, st));
+  LAUNCH(k_s_of_uv_batch, (unsigned)(K * v->cd.nblk), S_BLOCK, 0, st, v->cd, (const UvPair*)v->uv.as<UvPair>(), K, v->partial.as<Fr>());
+  LAUNCH(k_s_of_uv_finish, (unsigned)K, S_BLOCK, 0, st, (const Fr*)v->partial.as<Fr>(), v->cd.nblk, (const UvPair*)v->uv.as<UvPair>(), v->sv.as<Fr>(), v->sok.as<uint8_t>());
+  out.resize((size_t)K); ok.resize((size_t)K);
+  HIP_OK(hipMemcpyAsync(out.data(), v->sv.p, sizeof(Fr) * (size_t)K, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(ok.data(), v->sok.p, (size_t)K, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+}
+
+// points from encodings on the handle's stream: validated points stay in v->pts, the flags come back
+void validate_device(sonic_verifier* v, const uint8_t* enc, long M, std::vector<uint8_t>& flags) {
+  v->raw.ensure(96 * (size_t)M); v->pts.ensure(sizeof(G1Affine) * (size_t)M); v->flags.ensure((size_t)M);
+  hipStream_t st = v->st;
+  HIP_OK(hipMemcpyAsync(v->raw.p, enc, 96 * (size_t)M, hipMemcpyHostToDevice, st));
+  LAUNCH(k_g1_validate, ceil_div(M, 256), 256, 0, st, (const uint8_t*)v->raw.as<uint8_t>(), v->pts.as<G1Affine>(), v->flags.as<uint8_t>(), M);
+  flags.resize((size_t)M);
+  HIP_OK(hipMemcpyAsync(flags.data(), v->flags.p, (size_t)M, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+}
+
+// challenges: K blocks of (2 + 2Q) x 32 bytes (y, z, then the pairs)
+int verify_batch_core(sonic_verifier* v, long K, const uint8_t* proofs, const uint8_t* challenges, const uint8_t* seed_in, int* all_accepted, uint8_t* each) {
+  const long Q = v->Q, NP = 4 * Q + 7, NC = 3 * Q + 4;
+  const size_t psz = sonic_proof_size(Q), csz = 32 * (size_t)(2 + 2 * Q);
+  const size_t N = (size_t)K * (size_t)NP;
+  uint8_t seed[32];
+  if (seed_in) memcpy(seed, seed_in, 32);
+  else if (getrandom(seed, 32, 0) != 32) { set_error("sonic_verifier_verify_batch: the operating system gave no random bytes for the seed"); return SONIC_ERR_INVALID_ARG; }
+  double t0 = now_ms();
+
+  // 1. decode: field elements on the host, point encodings into a staging buffer in proof order (index = position in the proof)
+  Batch b{v, K, NP, NC, std::vector<char>((size_t)K, 0), std::vector<Fr>((size_t)K, Fr::zero())};
+  std::vector<ProofViewT<int32_t>> views((size_t)K);
+  std::vector<Fr> yms((size_t)K), zms((size_t)K);
+  std::vector<uint8_t> stage(96 * N, 0);
+  long first_bad = -1;
+  for (long k = 0; k < K; k++) {
+    int32_t idx = 0;
+    uint8_t* dst = &stage[96 * (size_t)(k * NP)];
+    auto take = [&](const uint8_t* enc, int32_t& o) { o = idx++; memcpy(dst + 96 * (size_t)o, enc, 96); return true; };
+    const uint8_t* ch = challenges + csz * (size_t)k;
+    b.good[(size_t)k] = parse_proof(proofs + psz * (size_t)k, Q, ch, ch + 32, ch + 64, views[(size_t)k], yms[(size_t)k], zms[(size_t)k], take) ? 1 : 0;
+    if (!b.good[(size_t)k] && first_bad < 0) first_bad = k;
+  }
+  host_phase("verify_batch:host_decode", now_ms() - t0);
+
+  // 2. the points: canonical, on the curve, in the subgroup (device)
+  std::vector<uint8_t> flags;
+  validate_device(v, stage.data(), (long)N, flags);
+  for (long k = 0; k < K; k++) {
+    bool ok = true;
+    for (long j = 0; j < NP; j++) ok = ok && flags[(size_t)(k * NP + j)];
+    if (!ok) { b.good[(size_t)k] = 0; if (first_bad < 0 || k < first_bad) first_bad = k; }
+  }
+  const bool any_malformed = first_bad >= 0;
+  if (any_malformed) set_error("verify_batch: proof %ld is malformed (non-canonical field element, or point off the curve or outside the order-r subgroup)", first_bad);
+
+  // 3. s(u_k, v_k) (device); a malformed proof rides along as the pair (1, 1)
+  std::vector<Fr> us((size_t)K), vs((size_t)K), svs;
+  std::vector<uint8_t> sok;
+  for (long k = 0; k < K; k++) {
+    us[(size_t)k] = b.good[(size_t)k] ? views[(size_t)k].h.u : Fr::one();
+    vs[(size_t)k] = b.good[(size_t)k] ? views[(size_t)k].h.v : Fr::one();
+  }
+  eval_s_device(v, K, us, vs, svs, sok);
+  long first_refused = -1;
+  for (long k = 0; k < K; k++) if (b.good[(size_t)k] && !sok[(size_t)k]) { b.good[(size_t)k] = 0; if (first_refused < 0) first_refused = k; }
+  if (first_refused >= 0 && !any_malformed) set_error("verify_batch: proof %ld has u or v zero", first_refused);
+  const bool any_bad = any_malformed || first_refused >= 0;
+
+  // 4. the randomizers and the scalars of the fold (host): rho on W, rho z on W, rho on F by class of max
+  t0 = now_ms();
+  uint8_t D[32];
+  {
+    Sha256 h;
+    h.update("sonic-hip/batch-digest/v1", 25);
+    le64(h, v->n); le64(h, Q); le64(h, v->d);
+    h.update(v->digest, 32); h.update(v->srs_id, 32);
+    le64(h, K);
+    for (long k = 0; k < K; k++) { h.update(proofs + psz * (size_t)k, psz); h.update(challenges + csz * (size_t)k, csz); }
+    h.finish(D);
+  }
+  const size_t nclass = v->ms.size();
+  std::vector<Fr> sc((2 + nclass) * N, Fr::zero());          // Montgomery while they are summed
+  const CircuitView cview{v->n, Q, v->cs.data(), true, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  std::vector<uint8_t> rho((size_t)(16 * NC));
+  long good_count = 0;
+  for (long k = 0; k < K; k++) {
+    if (!b.good[(size_t)k]) continue;
+    good_count++;
+    Fr t;
+    proof_t(cview, views[(size_t)k], yms[(size_t)k], t);      // (cs was checked when the handle was made)
+    const auto checks = proof_checks<int32_t>(v->n, v->d, views[(size_t)k], yms[(size_t)k], zms[(size_t)k], t, svs[(size_t)k]);
+    batch_randomizers(seed, D, (int64_t)k * NC, NC, rho.data());
+    const size_t base = (size_t)(k * NP);
+    for (long i = 0; i < NC; i++) {
+      const auto& c = checks[(size_t)i];
+      Fr r = Fr::zero();
+      memcpy(r.l, &rho[(size_t)(16 * i)], 16);
+      r = fp_to_mont(r);
+      sc[base + (size_t)c.W] = fp_add(sc[base + (size_t)c.W], r);
+      sc[N + base + (size_t)c.W] = fp_add(sc[N + base + (size_t)c.W], fp_mul(r, c.z));
+      b.gv[(size_t)k] = fp_add(b.gv[(size_t)k], fp_mul(r, c.val));
+      size_t cls = 0;
+      while (v->ms[cls] != c.maxm) cls++;
+      sc[(2 + cls) * N + base + (size_t)c.F] = fp_add(sc[(2 + cls) * N + base + (size_t)c.F], r);
+    }
+  }
+  for (auto& x : sc) x = fp_from_mont(x);
+  v->scalars.ensure(sizeof(Fr) * sc.size());
+  HIP_OK(hipMemcpyAsync(v->scalars.p, sc.data(), sizeof(Fr) * sc.size(), hipMemcpyHostToDevice, v->st));
+  HIP_OK(hipStreamSynchronize(v->st));
+  host_phase("verify_batch:host_scalars", now_ms() - t0);
+
+  // 5. the fold over every well-formed proof (a malformed one contributes zero scalars)
+  bool fold_ok = false;
+  if (good_count > 0) {
+    t0 = now_ms();
+    const Sums s = fold_sums(b, 0, K);
+    host_phase("verify_batch:msm", now_ms() - t0);
+    t0 = now_ms();
+    fold_ok = fold_accepts(v, s, true);
+    host_phase("verify_batch:host_pairing", now_ms() - t0);
+  }
+  *all_accepted = (fold_ok && !any_bad) ? 1 : 0;
+  if (!each) return SONIC_OK;
+  // the fold of the well-formed proofs held: each of them is accepted (the soundness of the fold); else every one is folded on its own
+  for (long k = 0; k < K; k++) each[k] = (fold_ok && b.good[(size_t)k]) ? 1 : 0;
+  if (fold_ok || good_count == 0) return SONIC_OK;
+  t0 = now_ms();
+  std::vector<Sums> sums((size_t)K);
+  for (long k = 0; k < K; k++) if (b.good[(size_t)k]) sums[(size_t)k] = fold_sums(b, k, k + 1);
+  const int nt = (int)std::min<long>(K, 16);
+  auto work = [&](int w) { for (long k = w; k < K; k += nt) if (b.good[(size_t)k]) each[k] = fold_accepts(v, sums[(size_t)k], false) ? 1 : 0; };
+  {
+    ThreadGroup th;
+    int started = 1;
+    try {
+      for (; started < nt; started++) th.emplace_back(work, started);
+    } catch (const std::system_error&) {}
+    work(0);
+    for (int w = started; w < nt; w++) work(w);
+    th.join();
+  }
+  host_phase("verify_batch:each", now_ms() - t0);
+  return SONIC_OK;
+}
+
+int verifier_new(const char* who, const sonic_srs_t* srs, const CircuitView& c, sonic_verifier_t** out) {
+  if (!srs || !c.cs || !out) { set_error("%s: bad argument", who); return SONIC_ERR_INVALID_ARG; }
+  *out = nullptr;
+  int rc = circuit_validate(who, c);
+  if (rc) return rc;
+  const long n = c.n, Q = c.Q, R = 3 * Q;
+  std::unique_ptr<sonic_verifier> v(new sonic_verifier());
+  v->srs = srs; v->device = srs_device(srs); v->n = n; v->Q = Q; v->d = srs_d(srs);
+  for (long q = 0; q < Q; q++) { Fr k; if (!load_fr(c.cs + 32 * q, k)) { set_error("%s: cs[%ld] is not a canonical field element", who, q); return SONIC_ERR_BAD_ENCODING; } }
+  v->cs.assign(c.cs, c.cs + 32 * Q);
+  // the G2 elements of every fold, once: the same statuses as sonic_verify when one is at infinity or the SRS is too short
+  rc = load_verifier_key(srs, v->vk);
+  if (rc) return rc;
+  v->ms.push_back(n);
+  if (v->d != n) v->ms.push_back(v->d);
+  v->hm.resize(v->ms.size());
+  for (size_t i = 0; i < v->ms.size(); i++) { rc = pc_v_element(srs, v->ms[i], v->hm[i]); if (rc) return rc; }
+  circuit_digest(c, v->digest);
+  rc = sonic_fs_srs_id(srs, v->srs_id);
+  if (rc) return rc;
+  // the circuit as CSR, whichever form it came in (dense: the non-zero entries), values Montgomery
+  std::vector<int32_t> row_ptr((size_t)R + 1, 0), col, item_row, item_begin;
+  std::vector<Fr> val;
+  if (c.csr) {
+    const long nnz = (long)c.row_ptr[R];
+    col.resize((size_t)nnz); val.resize((size_t)nnz);
+    for (long r = 0; r <= R; r++) row_ptr[(size_t)r] = (int32_t)c.row_ptr[r];
+    for (long k = 0; k < nnz; k++) { col[(size_t)k] = (int32_t)c.col[k]; load_fr(c.val + 32 * k, val[(size_t)k]); }
+  } else {
+    if (n > INT32_MAX - 1 || (double)Q * (double)n * 3 > (double)INT32_MAX) { set_error("%s: the circuit does not fit 32-bit entry indices", who); return SONIC_ERR_INVALID_ARG; }
+    static const uint8_t zero[32] = {0};
+    const uint8_t* mats[3] = {c.wL, c.wR, c.wO};
+    for (long r = 0; r < R; r++) {
+      const uint8_t* row = mats[r / Q] + 32 * ((r % Q) * n);
+      for (long i = 0; i < n; i++) {
+        if (memcmp(row + 32 * i, zero, 32) == 0) continue;
+        Fr w;
+        if (!load_fr(row + 32 * i, w)) { set_error("%s: non-canonical gate weight (row %ld, gate %ld)", who, r, i); return SONIC_ERR_BAD_ENCODING; }
+        col.push_back((int32_t)i); val.push_back(w);
+      }
+      row_ptr[(size_t)r + 1] = (int32_t)col.size();
+    }
+  }
+  for (long r = 0; r < R; r++)
+    for (long k = row_ptr[(size_t)r]; k < row_ptr[(size_t)r + 1]; k += S_ITEM) { item_row.push_back((int32_t)r); item_begin.push_back((int32_t)k); }
+  CircuitDev& cd = v->cd;
+  cd.n = n; cd.Q = Q; cd.nnz = (long)col.size();
+  cd.row_items = (long)item_row.size();
+  cd.items = cd.row_items + (n + S_ITEM - 1) / S_ITEM;
+  cd.nblk = (cd.items + S_BLOCK - 1) / S_BLOCK;
+  HIP_OK(hipStreamCreateWithFlags(&v->st, hipStreamNonBlocking));
+  auto up = [&](DevBuf& b, const void* src, size_t bytes) { b.alloc(bytes); if (bytes) HIP_OK(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, v->st)); };
+  try {
+    up(v->row_ptr, row_ptr.data(), 4 * row_ptr.size()); up(v->col, col.data(), 4 * col.size()); up(v->val, val.data(), sizeof(Fr) * val.size());
+    up(v->item_row, item_row.data(), 4 * item_row.size()); up(v->item_begin, item_begin.data(), 4 * item_begin.size());
+    HIP_OK(hipStreamSynchronize(v->st));
+  } catch (...) { (void)hipStreamDestroy(v->st); throw; }
+  cd.row_ptr = v->row_ptr.as<int32_t>(); cd.col = v->col.as<int32_t>(); cd.val = v->val.as<Fr>();
+  cd.item_row = v->item_row.as<int32_t>(); cd.item_begin = v->item_begin.as<int32_t>();
+  *out = v.release();
+  return SONIC_OK;
+}
+
+// K and the size of its MSMs
+int batch_size_ok(const char* who, const sonic_verifier* v, int64_t K) {
+  if (K < 1 || K > MSM_TABLE_MAX_TERMS / (4 * v->Q + 7)) { set_error("%s: K = %lld outside [1, 2^26 / (4Q + 7)]", who, (long long)K); return SONIC_ERR_INVALID_ARG; }
+  if ((double)K * (double)v->cd.nblk >= 2147483647.0) { set_error("%s: K = %lld times the circuit's %ld blocks exceeds one launch", who, (long long)K, v->cd.nblk); return SONIC_ERR_INVALID_ARG; }
+  return SONIC_OK;
+}
+
+}  // namespace
+
+#define VB_BEGIN(dev) try { ::sonic::DeviceScope _scope(dev);
+#define VB_END                                                         \
+  } catch (const HipFail& f) { return f.code; }                        \
+  catch (const std::exception& e) { set_error("%s", e.what()); return SONIC_ERR_HIP; }
+
+extern "C" {
+
+int sonic_verifier_new(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO, const uint8_t* cs,
+                       sonic_verifier_t** out) {
+  VB_BEGIN(srs_device(srs))
+  return verifier_new("sonic_verifier_new", srs, dense_view(n, Q, wL, wR, wO, cs), out);
+  VB_END
+}
+int sonic_verifier_new_csr(const sonic_srs_t* srs, int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val, const uint8_t* cs,
+                           sonic_verifier_t** out) {
+  VB_BEGIN(srs_device(srs))
+  return verifier_new("sonic_verifier_new_csr", srs, csr_view(n, Q, row_ptr, col, val, cs), out);
+  VB_END
+}
+void sonic_verifier_free(sonic_verifier_t* v) {
+  if (!v) return;
+  try {
+    DeviceScope scope(v->device);
+    (void)hipStreamSynchronize(v->st);
+    (void)hipStreamDestroy(v->st);
+    delete v;                            // (the device buffers go inside the scope)
+  } catch (...) {}
+}
+int sonic_verifier_device(const sonic_verifier_t* v) { return v ? v->device : -1; }
+
+int sonic_verifier_verify_batch(sonic_verifier_t* v, int64_t K, const uint8_t* proofs, const uint8_t* challenges, const uint8_t seed[32], int* all_accepted,
+                                uint8_t* each) {
+  if (!v || !proofs || !challenges || !all_accepted) { set_error("sonic_verifier_verify_batch: bad argument"); return SONIC_ERR_INVALID_ARG; }
+  *all_accepted = 0;
+  VB_BEGIN(v->device)
+  int rc = batch_size_ok("sonic_verifier_verify_batch", v, K);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> g(v->mu);
+  return verify_batch_core(v, (long)K, proofs, challenges, seed, all_accepted, each);
+  VB_END
+}
+
+int sonic_verifier_verify_fs_batch(sonic_verifier_t* v, int64_t K, const uint8_t* proofs, const uint8_t seed[32], int* all_accepted, uint8_t* each) {
+  if (!v || !proofs || !all_accepted) { set_error("sonic_verifier_verify_fs_batch: bad argument"); return SONIC_ERR_INVALID_ARG; }
+  *all_accepted = 0;
+  VB_BEGIN(v->device)
+  int rc = batch_size_ok("sonic_verifier_verify_fs_batch", v, K);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> g(v->mu);
+  // the challenges each proof determines (fs.hpp), in sonic_verify's order; a proof whose own u, v are not its transcript's is rejected
+  const long Q = v->Q;
+  const size_t psz = sonic_proof_size(Q), csz = 32 * (size_t)(2 + 2 * Q);
+  std::vector<uint8_t> chal(csz * (size_t)K), ch(32 * (size_t)(4 + 2 * Q)), mine((size_t)K, 1);
+  bool all_mine = true;
+  for (int64_t k = 0; k < K; k++) {
+    const uint8_t* proof = proofs + psz * (size_t)k;
+    fs_challenges_of_proof(v->n, Q, v->d, v->digest, v->srs_id, proof, ch.data());
+    if (memcmp(proof + psz - 64, &ch[32 * (size_t)(2 + 2 * Q)], 64) != 0) { mine[(size_t)k] = 0; all_mine = false; }
+    uint8_t* o = &chal[csz * (size_t)k];
+    memcpy(o, &ch[0], 64);
+    for (long j = 0; j < Q; j++) { memcpy(o + 64 + 64 * j, &ch[32 * (size_t)(2 + j)], 32); memcpy(o + 96 + 64 * j, &ch[32 * (size_t)(2 + Q + j)], 32); }
+  }
+  if (!all_mine && !each) return SONIC_OK;                      // rejected, and nobody asked which
+  rc = verify_batch_core(v, (long)K, proofs, chal.data(), seed, all_accepted, each);
+  if (rc) return rc;
+  if (!all_mine) {
+    *all_accepted = 0;
+    for (int64_t k = 0; k < K; k++) if (!mine[(size_t)k]) each[k] = 0;
+  }
+  return SONIC_OK;
+  VB_END
+}
+
+int sonic_verifier_eval_s(sonic_verifier_t* v, int64_t K, const uint8_t* uv, uint8_t* out) {
+  if (!v || !uv || !out) { set_error("sonic_verifier_eval_s: bad argument"); return SONIC_ERR_INVALID_ARG; }
+  VB_BEGIN(v->device)
+  int rc = batch_size_ok("sonic_verifier_eval_s", v, K);
+  if (rc) return rc;
+  std::vector<Fr> us((size_t)K), vs((size_t)K), sv;
+  std::vector<uint8_t> ok;
+  for (int64_t k = 0; k < K; k++)
+    if (!load_fr(uv + 64 * k, us[(size_t)k]) || !load_fr(uv + 64 * k + 32, vs[(size_t)k])) { set_error("sonic_verifier_eval_s: pair %lld holds a non-canonical field element", (long long)k); return SONIC_ERR_BAD_ENCODING; }
+  std::lock_guard<std::mutex> g(v->mu);
+  eval_s_device(v, (long)K, us, vs, sv, ok);
+  // a refused pair (u = 0 or v = 0) gets 32 bytes of 0xff -- no field element -- and the call reports the first one
+  int64_t refused = -1;
+  for (int64_t k = 0; k < K; k++) {
+    if (!ok[(size_t)k]) { memset(out + 32 * k, 0xff, 32); if (refused < 0) refused = k; continue; }
+    const Fr s = fp_from_mont(sv[(size_t)k]);
+    memcpy(out + 32 * k, s.l, 32);
+  }
+  if (refused >= 0) { set_error("sonic_verifier_eval_s: u or v is zero in pair %lld", (long long)refused); return SONIC_ERR_INEXACT_DIVISION; }
+  return SONIC_OK;
+  VB_END
+}
+
+int sonic_g1_validate(const uint8_t* points, int64_t n, uint8_t* flags) {
+  if (n < 0 || (n > 0 && (!points || !flags))) { set_error("sonic_g1_validate: bad argument"); return SONIC_ERR_INVALID_ARG; }
+  if (n == 0) return SONIC_OK;
+  VB_BEGIN(-1)
+  CallLease lease;
+  hipStream_t st = lease.st();
+  DevBuf raw(96 * (size_t)n), pts(sizeof(G1Affine) * (size_t)n), fl((size_t)n);
+  HIP_OK(hipMemcpyAsync(raw.p, points, 96 * (size_t)n, hipMemcpyHostToDevice, st));
+  LAUNCH(k_g1_validate, ceil_div(n, 256), 256, 0, st, (const uint8_t*)raw.as<uint8_t>(), pts.as<G1Affine>(), fl.as<uint8_t>(), (long)n);
+  HIP_OK(hipMemcpyAsync(flags, fl.p, (size_t)n, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  return SONIC_OK;
+  VB_END
+}
+
+int sonic_verify_batch_randomizers(const uint8_t seed[32], const uint8_t batch_digest[32], int64_t count, uint8_t* out) {
+  if (!seed || !batch_digest || count < 0 || (count > 0 && !out)) { set_error("sonic_verify_batch_randomizers: bad argument"); return SONIC_ERR_INVALID_ARG; }
+  batch_randomizers(seed, batch_digest, 0, count, out);
+  return SONIC_OK;
+}
+
+}  // extern "C"

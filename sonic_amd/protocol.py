@@ -628,3 +628,84 @@ def verify(srs: SRS, circuit: ArithCircuit, proof: Proof, y: int, z: int, yzs) -
     ok = C.c_int(0)
     _lib.check(getattr(_lib.lib(), "sonic_verify" + suffix)(srs._h, n, Q, *args, raw, fr_to_bytes(y), fr_to_bytes(z), flat.ctypes.data, C.byref(ok)))
     return bool(ok.value)
+
+
+class Verifier:
+    """The batched verifier (sonic_verifier_* of the C ABI): the circuit resident in HBM, K proofs folded into ONE pairing product --
+    four Miller loops and one final exponentiation per batch; point validation, s(u, v) and the G1 sums run on the GPU.  `circuit` is an
+    ArithCircuit or a SparseCircuit.  A malformed proof is a rejected proof (False), never an exception."""
+
+    def __init__(self, srs: SRS, circuit):
+        self.n, self.Q, suffix, args, _keep = _circuit_args(circuit, "Verifier: ")
+        self._srs = srs                  # the handle borrows the SRS
+        self._h = C.c_void_p()
+        _lib.check(getattr(_lib.lib(), "sonic_verifier_new" + suffix)(srs._h, self.n, self.Q, *args, C.byref(self._h)))
+
+    def _proof_bytes(self, proofs) -> bytes:
+        size = _lib.lib().sonic_proof_size(self.Q)
+        raws = [p.to_bytes() if isinstance(p, Proof) else bytes(p) for p in proofs]
+        if not raws or any(len(r) != size for r in raws):
+            raise ValueError(f"Verifier: need at least one proof, each of {size} bytes (Q = {self.Q})")
+        return b"".join(raws)
+
+    @staticmethod
+    def _seed(seed):
+        if seed is not None and len(bytes(seed)) != 32:
+            raise ValueError("Verifier: seed must be 32 bytes (or None: the library draws it)")
+        return None if seed is None else bytes(seed)
+
+    def _result(self, K, call, each):
+        ok = C.c_int(0)
+        flags = C.create_string_buffer(K) if each else None
+        _lib.check(call(C.byref(ok), flags))
+        return (bool(ok.value), [bool(b) for b in flags.raw]) if each else bool(ok.value)
+
+    def verify_batch(self, proofs, transcripts, seed=None, each: bool = False):
+        """proofs: Proof objects or proof bytes; transcripts: one (y, z, yzs) per proof, as for verify().  True iff every proof is
+        accepted; with each=True also the per-proof verdicts."""
+        proofs, transcripts = list(proofs), list(transcripts)
+        if len(transcripts) != len(proofs):
+            raise ValueError("verify_batch: one (y, z, yzs) transcript per proof")
+        fr = lambda v: int(v).to_bytes(32, "little")     # noqa: E731  (as is: a non-canonical challenge rejects its proof)
+        blocks = []
+        for y, z, yzs in transcripts:
+            yzs = list(yzs)
+            if len(yzs) != self.Q or any(len(pair) != 2 for pair in yzs):
+                raise ValueError(f"verify_batch: yzs must hold {self.Q} (y_j, z_j) pairs")
+            blocks.append(fr(y) + fr(z) + b"".join(fr(a) + fr(b) for a, b in yzs))
+        raw, chal, sd, K = self._proof_bytes(proofs), b"".join(blocks), self._seed(seed), len(proofs)
+        return self._result(K, lambda ok, flags: _lib.lib().sonic_verifier_verify_batch(self._h, K, raw, chal, sd, ok, flags), each)
+
+    def verify_fs_batch(self, proofs, seed=None, each: bool = False):
+        """the same for Fiat-Shamir proofs (prove_fs): every proof's challenges are recomputed from the circuit and the proof"""
+        proofs = list(proofs)
+        raw, sd, K = self._proof_bytes(proofs), self._seed(seed), len(proofs)
+        return self._result(K, lambda ok, flags: _lib.lib().sonic_verifier_verify_fs_batch(self._h, K, raw, sd, ok, flags), each)
+
+    def eval_s(self, uvs) -> List[int]:
+        """s(u, v) of the circuit's s(X, Y) for every (u, v) of `uvs`, on the GPU (raises SonicError INEXACT_DIVISION for u = 0 or v = 0)"""
+        uvs = list(uvs)
+        flat = fr_array([x for pair in uvs for x in pair])
+        out = C.create_string_buffer(32 * len(uvs))
+        _lib.check(_lib.lib().sonic_verifier_eval_s(self._h, len(uvs), flat.ctypes.data, out))
+        return [int.from_bytes(out.raw[32 * i:32 * i + 32], "little") for i in range(len(uvs))]
+
+    def close(self):
+        if self._h:
+            _lib.lib().sonic_verifier_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def verify_batch(srs: SRS, circuit, proofs, transcripts, seed=None, each: bool = False):
+    """Verifier(srs, circuit).verify_batch(...) for one batch"""
+    v = Verifier(srs, circuit)
+    try:
+        return v.verify_batch(proofs, transcripts, seed=seed, each=each)
+    finally:
+        v.close()
