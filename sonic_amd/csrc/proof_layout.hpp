@@ -1,0 +1,72 @@
+// The numbering of a proof, in ONE place (host only, no HIP; also compiled by tests/host): the MSM slots of its 7 + 4Q commitments and
+// openings, the side slots whose sums the host adds to S_j and C, the 3 + 2Q evaluations, the 8 + 2Q transcript elements with their
+// {v, v^-1} pairs, and the canonical bytes.  prove.hip and share_plan.hpp use these names only; tests/test_proof_layout_host.py holds
+// them against the Python restatements (sonic_amd/protocol.py, tests/test_share_cpu.py).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+
+namespace sonic {
+
+struct ProofLayout {
+  long Q;
+  // counts
+  constexpr long K() const { return 7 + 4 * Q; }                    // commitments and openings = main MSM slots
+  constexpr long F() const { return 3 + 2 * Q; }                    // evaluations
+  constexpr long slots_total() const { return 7 + 5 * Q + 1; }      // K results, Q second halves of the S_j, 1 second half of C
+  constexpr long transcript_len() const { return 8 + 2 * Q; }
+  constexpr long n_pairs() const { return 5 + 2 * Q; }
+  constexpr size_t proof_bytes() const { return (size_t)(K() * 96 + (F() + 2) * 32); }
+  // MSM slots, the order of a share's pieces: R, T, W_a, W_b, W_t, [S_j, W_j]_j, [W'_j, Q_j]_j, Q_v, C
+  static constexpr long R = 0, T = 1, Wa = 2, Wb = 3, Wt = 4;
+  constexpr long S(long j) const { return 5 + 2 * j; }
+  constexpr long W(long j) const { return 6 + 2 * j; }
+  constexpr long Wp(long j) const { return 5 + 2 * Q + 2 * j; }
+  constexpr long Qj(long j) const { return 6 + 2 * Q + 2 * j; }
+  constexpr long Qv() const { return 5 + 4 * Q; }
+  constexpr long C() const { return 6 + 4 * Q; }
+  // side slots: S_j's second half (sum_q y_j^{n+q} C_q of a prepared handle, or the runs of equal coefficients) and C's Q-term half
+  constexpr long S_extra(long j) const { return K() + j; }
+  constexpr long C_extra() const { return K() + Q; }
+  // evaluations, and the slot whose first piece reports each: a <- W_a, b <- W_b, s <- W_t, s_j <- W_j, s'_j <- Q_j
+  static constexpr long a = 0, b = 1, s = 2;
+  constexpr long s_j(long j) const { return 3 + j; }
+  constexpr long sp_j(long j) const { return 3 + Q + j; }
+  constexpr long eval_owner_slot(long i) const { return i == a ? Wa : i == b ? Wb : i == s ? Wt : i < sp_j(0) ? W(i - s_j(0)) : Qj(i - sp_j(0)); }
+  // transcript: the blinders 0..3, then the challenges in draw order
+  static constexpr long n_blinders = 4, y = 4, z = 5;
+  constexpr long y_j(long j) const { return 6 + j; }
+  constexpr long z_j(long j) const { return 6 + Q + j; }
+  constexpr long u() const { return 6 + 2 * Q; }
+  constexpr long v() const { return 7 + 2 * Q; }
+  // {v, v^-1} pairs of the evaluation points (PAIRS: two field elements each)
+  static constexpr long pY = 0, pZ = 1, pYZ = 2, pU = 3, pV = 4;
+  constexpr long pYj(long j) const { return 5 + j; }
+  constexpr long pZj(long j) const { return 5 + Q + j; }
+};
+
+// canonical proof bytes from the 7 + 4Q points (slot order) and the 3 + 2Q evaluations: record order of `Proof` (Protocol.hs:28-38)
+// then `HscProof` (Signature.hs:22-29)
+inline void proof_layout(long Q, const uint8_t* pts, const uint8_t* frs, const uint8_t* transcript, uint8_t* out_proof) {
+  const ProofLayout L{Q};
+  uint8_t* o = out_proof;
+  auto putG = [&](long slot) { memcpy(o, pts + 96 * (size_t)slot, 96); o += 96; };
+  auto putF = [&](const uint8_t* s) { memcpy(o, s, 32); o += 32; };
+  auto F = [&](long i) { return frs + 32 * (size_t)i; };
+  putG(L.R); putG(L.T); putF(F(L.a)); putG(L.Wa); putF(F(L.b)); putG(L.Wb); putG(L.Wt); putF(F(L.s));
+  for (long j = 0; j < Q; j++) { putG(L.S(j)); putF(F(L.s_j(j))); putG(L.W(j)); }             // hscS
+  for (long j = 0; j < Q; j++) { putF(F(L.sp_j(j))); putG(L.Wp(j)); putG(L.Qj(j)); }          // hscW
+  putG(L.Qv()); putG(L.C());
+  putF(transcript + 32 * L.u()); putF(transcript + 32 * L.v());
+}
+
+// S_j's point is its slot's sum plus its side slot's, C's likewise: `side` holds the sums of the side slots K .. K + Q (the empty sum
+// where none ran), s_extra / c_extra say which of the two rules the proof runs with (prepared or runs; symmetric sums)
+template <class Point, class Add>
+inline void fold_side_slots(const ProofLayout& L, bool s_extra, bool c_extra, Point* sums, const Point* side, Add add) {
+  for (long j = 0; s_extra && j < L.Q; j++) sums[L.S(j)] = add(sums[L.S(j)], side[L.S_extra(j) - L.K()]);
+  if (c_extra) sums[L.C()] = add(sums[L.C()], side[L.C_extra() - L.K()]);
+}
+
+}  // namespace sonic

@@ -80,24 +80,27 @@ static void eval_prefix_enqueue(hipStream_t st, Scratch& sc, const Fr* poly, lon
   HIP_OK(hipMemcpyAsync(d_fz, sc.D.as<Fr>() + (len - 1), sizeof(Fr), hipMemcpyDeviceToDevice, st));
 }
 
+// the MSM of a quotient q over exponents [lo, lo+len-2], plain basis; coefficients outside [-d, d] must be zero (FLAG_SRS_INDEX)
+static MsmJob quotient_job(hipStream_t st, const sonic_srs* srs, const Fr* q, long lo, long len, MsmSlot* slot, int* d_flags) {
+  const long d = srs_d(srs), qn = len - 1;
+  long i0 = -d - lo, i1 = d - lo + 1;
+  if (i0 < 0) i0 = 0;
+  if (i1 > qn) i1 = qn;
+  if (i1 < i0) i1 = i0;
+  flag_nonzero_enqueue(st, q, i0, d_flags, FLAG_SRS_INDEX);
+  flag_nonzero_enqueue(st, q + i1, qn - i1, d_flags, FLAG_SRS_INDEX);
+  return MsmJob{srs_basis(srs, 0) + (lo + i0 + d), q + i0, i1 - i0, slot};
+}
+
 // openPoly (CommitmentScheme.hs:36-48).  Requires lo <= 0 <= lo+len-1 (callers extend the range to
 // contain X^0, where `fX - monomial 0 fz` puts -f(z)).  Quotient exponents [lo, lo+len-2], plain basis.
 // Queues evaluation + quotient and returns the MSM that is left to run (its scalars live in `sc` until then).
 MsmJob open_job(hipStream_t st, const sonic_srs* srs, Scratch& sc, const Fr* poly, long lo, long len,
                        const Fr* zpair, Fr* d_fz, MsmSlot* slot, int* d_flags) {
-  const long d = srs_d(srs);
   sc.reserve(len);
   eval_prefix_enqueue(st, sc, poly, lo, len, zpair, d_fz ? d_fz : sc.fz_discard.as<Fr>());
-  const long qn = len - 1;
   poly_quotient_enqueue(st, sc.D.as<Fr>(), sc.q.as<Fr>(), len, lo, zpair, zpair + 1);
-  long i0 = -d - lo, i1 = d - lo + 1;
-  if (i0 < 0) i0 = 0;
-  if (i1 > qn) i1 = qn;
-  if (i1 < i0) i1 = i0;
-  const Fr* q = sc.q.as<Fr>();
-  flag_nonzero_enqueue(st, q, i0, d_flags, FLAG_SRS_INDEX);
-  flag_nonzero_enqueue(st, q + i1, qn - i1, d_flags, FLAG_SRS_INDEX);
-  return MsmJob{srs_basis(srs, 0) + (lo + i0 + d), q + i0, i1 - i0, slot};
+  return quotient_job(st, srs, sc.q.as<Fr>(), lo, len, slot, d_flags);
 }
 
 // openPoly at z = 0 of a polynomial without negative exponents (lo == 0): f(0) = c_0 and (f - c_0)/X is the coefficient
@@ -117,7 +120,6 @@ MsmJob open_job_at_zero(hipStream_t st, const sonic_srs* srs, const Fr* poly, lo
 // that are left to run come back in jobs_out, in the order of `ops`
 struct PendingOpen { const Fr* poly; long lo, len; const Fr* zp; Fr* fz; MsmSlot* slot; long slot_index; Scratch* sc; };
 static void open_jobs_batched(hipStream_t st, const sonic_srs* srs, const PendingOpen* ops, int k, int* d_flags, MsmJob* jobs_out) {
-  const long d = srs_d(srs);
   for (int at = 0; at < k;) {
     int e = at;
     OpenBatch b;
@@ -135,17 +137,7 @@ static void open_jobs_batched(hipStream_t st, const sonic_srs* srs, const Pendin
     b.k = e - at;
     const long lo = ops[at].lo, len = ops[at].len;
     open_batch_enqueue(st, b, lo, len);
-    for (int i = at; i < e; i++) {
-      const long qn = len - 1;
-      long i0 = -d - lo, i1 = d - lo + 1;
-      if (i0 < 0) i0 = 0;
-      if (i1 > qn) i1 = qn;
-      if (i1 < i0) i1 = i0;
-      const Fr* q = ops[i].sc->q.as<Fr>();
-      flag_nonzero_enqueue(st, q, i0, d_flags, FLAG_SRS_INDEX);
-      flag_nonzero_enqueue(st, q + i1, qn - i1, d_flags, FLAG_SRS_INDEX);
-      jobs_out[i] = MsmJob{srs_basis(srs, 0) + (lo + i0 + d), q + i0, i1 - i0, ops[i].slot};
-    }
+    for (int i = at; i < e; i++) jobs_out[i] = quotient_job(st, srs, ops[i].sc->q.as<Fr>(), lo, len, ops[i].slot, d_flags);
     at = e;
   }
 }
@@ -257,7 +249,7 @@ int sonic_srs_new_on(int device, int64_t d, const uint8_t x[32], const uint8_t a
   API_END
 }
 
-size_t sonic_proof_size(int64_t Q) { return (size_t)((7 + 4 * Q) * 96 + (5 + 2 * Q) * 32); }
+size_t sonic_proof_size(int64_t Q) { return ProofLayout{Q}.proof_bytes(); }
 
 static int prover_new_entry(const char* who, const sonic_srs_t* srs, const CircuitView& c, sonic_prover_t** out) {
   API_BEGIN_ON(srs_device(srs))
@@ -290,6 +282,7 @@ int prover_admits(const char* who, const sonic_srs* srs, const CircuitView& c) {
 // (an admitted circuit)
 int prover_new_impl(const sonic_srs_t* srs, const CircuitView& c, sonic_prover_t** out) {
   const long n = c.n, Q = c.Q;
+  const ProofLayout L{Q};
   for (long q = 0; c.csr && q < Q; q++) {
     Fr k; memcpy(k.l, c.cs + 32 * q, 32);
     if (!fp_is_canonical(k)) { set_error("sonic_prover_new_csr: non-canonical constant cs[%ld]", q); return SONIC_ERR_BAD_ENCODING; }
@@ -330,20 +323,20 @@ int prover_new_impl(const sonic_srs_t* srs, const CircuitView& c, sonic_prover_t
   p->su.alloc(sizeof(Fr) * (2 * n + Q + 1));
   p->pw.alloc(sizeof(Fr) * (3 * n + Q + 2));
   p->kpow.alloc(sizeof(Fr) * Q);
-  p->S.alloc(sizeof(Fr) * (8 + 2 * Q)); p->PAIRS.alloc(sizeof(Fr) * 2 * (5 + 2 * Q));
-  p->slots.alloc(sizeof(MsmSlot) * (7 + 5 * Q + 1));        // 7 + 4Q results, Q second halves of the S_j, 1 second half of C
+  p->S.alloc(sizeof(Fr) * L.transcript_len()); p->PAIRS.alloc(sizeof(Fr) * 2 * L.n_pairs());
+  p->slots.alloc(sizeof(MsmSlot) * L.slots_total());
   p->use_graph = getenv("SONIC_PROVE_GRAPH") && atoi(getenv("SONIC_PROVE_GRAPH")) != 0;
-  HIP_OK(hipHostMalloc((void**)&p->h_tr, 32 * (8 + 2 * Q), hipHostMallocDefault));
-  HIP_OK(hipHostMalloc((void**)&p->h_pairs, sizeof(Fr) * 2 * (5 + 2 * Q), hipHostMallocDefault));
-  HIP_OK(hipHostMalloc((void**)&p->h_slots, sizeof(MsmSlot) * (7 + 5 * Q + 1), hipHostMallocDefault));
-  HIP_OK(hipHostMalloc((void**)&p->h_fr, 32 * (3 + 2 * Q), hipHostMallocDefault));
+  HIP_OK(hipHostMalloc((void**)&p->h_tr, 32 * L.transcript_len(), hipHostMallocDefault));
+  HIP_OK(hipHostMalloc((void**)&p->h_pairs, sizeof(Fr) * 2 * L.n_pairs(), hipHostMallocDefault));
+  HIP_OK(hipHostMalloc((void**)&p->h_slots, sizeof(MsmSlot) * L.slots_total(), hipHostMallocDefault));
+  HIP_OK(hipHostMalloc((void**)&p->h_fr, 32 * L.F(), hipHostMallocDefault));
   HIP_OK(hipHostMalloc((void**)&p->h_flags, 8, hipHostMallocDefault));
   p->h_flags[0] = p->h_flags[1] = 0;
-  p->frout.alloc(sizeof(Fr) * (3 + 2 * Q));
-  p->frstd.alloc(sizeof(Fr) * (3 + 2 * Q));
-  HIP_OK(hipMemsetAsync(p->frout.p, 0, sizeof(Fr) * (3 + 2 * Q), st));
-  HIP_OK(hipMemsetAsync(p->slots.p, 0, sizeof(MsmSlot) * (7 + 5 * Q + 1), st));      // W = 0: an empty sum until the slot's MSM has run
-  memset(p->h_slots, 0, sizeof(MsmSlot) * (7 + 5 * Q + 1));
+  p->frout.alloc(sizeof(Fr) * L.F());
+  p->frstd.alloc(sizeof(Fr) * L.F());
+  HIP_OK(hipMemsetAsync(p->frout.p, 0, sizeof(Fr) * L.F(), st));
+  HIP_OK(hipMemsetAsync(p->slots.p, 0, sizeof(MsmSlot) * L.slots_total(), st));      // W = 0: an empty sum until the slot's MSM has run
+  memset(p->h_slots, 0, sizeof(MsmSlot) * L.slots_total());
   auto mkev = [](hipEvent_t* e) { HIP_OK(hipEventCreateWithFlags(e, hipEventDisableTiming)); };
   mkev(&p->ev_r1); mkev(&p->ev_sy0); mkev(&p->ev_t); mkev(&p->ev_su);
   p->ev_syj.resize(Q, nullptr);
@@ -368,7 +361,7 @@ int prover_new_impl(const sonic_srs_t* srs, const CircuitView& c, sonic_prover_t
   }
   if (p->small_plan) {
     // (the second chain stream is only used by proofs of more than MSM_MAX_JOBS MSMs: Q > 2)
-    for (int c = 0; c < (7 + 4 * Q > MSM_MAX_JOBS ? 2 : 1); c++) {
+    for (int c = 0; c < (L.K() > MSM_MAX_JOBS ? 2 : 1); c++) {
       mkstream(&p->chain[c].st, prio_low);
       mkev(&p->chain[c].done);
     }
@@ -404,60 +397,392 @@ int sonic_prover_set_assignment(sonic_prover_t* p, const uint8_t* aL, const uint
 
 }  // extern "C"
 
-// prove = prove_enqueue (queues the whole proof on the handle's streams, no host synchronisation) + prove_finish (waits, runs
-// the host tails, lays out the bytes).  sonic_prover_prove runs them back to back; sonic_prover_submit / sonic_prover_collect
-// expose the halves, so that ONE host thread can keep two handles busy: while it waits for and finishes proof i on one handle,
-// proof i + 1 is already running on the other (its polynomial building and sorts fill the first proof's reduction tail).
-// Both run under p->mu.
-static int prove_enqueue(sonic_prover_t* p, const uint8_t* transcript) {
-  API_BEGIN_ON(p->device)
-  p->t_begin = std::chrono::steady_clock::now();
-  const long n = p->n, Q = p->Q;
-  const sonic_srs* srs = p->srs;
+// ---- the group queue: how a group of MSMs becomes a batch on a lane or on the proof's one chain ---------------------------------------
+// The commitments / openings that depend on one polynomial form a group: it runs on the next MSM lane as soon as its input exists
+// (event), as ONE batched MSM kernel chain -- or, fused, the lanes only prepare the openings and all jobs of the proof run as one chain
+// (prover.hpp).  Results land in disjoint slots / frout entries.  One queue per enqueue; it also cuts every job down to this rank's
+// piece of a shared proof and records what ran (slot_ran, fr_valid).
+// (packing consecutive groups into ONE batched chain -- fewer, wider chains -- was measured in round 3 and removed in round 5: n = 2^18
+// 35.9 / 38.9 ms streamed / one at a time packed against 35.0 / 35.9: the chains of one proof overlap less)
+struct GroupQueue {
+  sonic_prover_t* const p;
+  const sonic_srs* const srs;
+  const ProofLayout L;
+  int* const flags; MsmSlot* const slots; Fr* const frout;      // the handle's error flags, MSM slots and evaluations (device)
+  const SlotShare* const sh;                            // this rank's pieces of the MSMs (share_plan.hpp); nullptr: everything
+  Lane* cur = nullptr;
+  std::vector<PendingOpen> pend;                        // the openings of the group that is being assembled: evaluated and divided together when the group is flushed
+  std::vector<std::function<void()>> after_flush;       // small MSMs that use the lane's workspace after the batch (stream order)
+  std::vector<std::function<void()>> deferred_small;    // (fused proofs: the same, queued behind the proof's chain)
+  enum Side { BESIDE_GROUP, BEHIND_CHAIN };
+
+  explicit GroupQueue(sonic_prover_t* p_)
+      : p(p_), srs(p_->srs), L{p_->Q}, flags(p_->flags.as<int>()), slots(p_->slots.as<MsmSlot>()), frout(p_->frout.as<Fr>()),
+        sh(p_->share_world > 1 ? p_->share.row(p_->share_rank) : nullptr) {
+    p->next_lane = 0;
+    p->slot_ran.assign((size_t)L.slots_total(), 0);
+    p->fr_valid.assign((size_t)L.F(), 0);
+  }
+  bool on(int ph) const { return ((p->phases >> ph) & 1u) != 0; }
+  bool own(long slot) const { return !sh || sh[slot].hi > sh[slot].lo; }
+  bool first_piece(long slot) const { return !sh || (sh[slot].hi > sh[slot].lo && sh[slot].lo == 0); }
+  // cuts the job down to this rank's term range and adds what is left of it to the group
+  void push(MsmJob job, long slot) {
+    if (sh) {
+      long t0, t1;
+      share_term_range(sh[slot], job.n, &t0, &t1);
+      job.points = job.points + t0; job.scalars += t0; job.n = t1 - t0;
+      if (job.n <= 0) return;
+    }
+    p->slot_ran[(size_t)slot] = 1;
+    cur->jobs[cur->njobs++] = job;
+  }
+  void issue_opens() {
+    if (pend.empty()) return;
+    MsmJob oj[MSM_MAX_JOBS];
+    open_jobs_batched(cur->st, srs, pend.data(), (int)pend.size(), flags, oj);
+    for (size_t i = 0; i < pend.size(); i++) push(oj[i], pend[i].slot_index);
+    pend.clear();
+  }
+  void flush(bool last = false) {
+    if (!cur) return;
+    issue_opens();
+    if (p->fused) p->fused_jobs.insert(p->fused_jobs.end(), cur->jobs, cur->jobs + cur->njobs);      // run at the end, as one chain
+    else run_jobs(cur->st, srs, cur->ws, cur->jobs, cur->njobs, last, /*exposed=*/p->share_world >= 4);
+    cur->njobs = 0;
+    // the small MSMs beside a group (Q-term sums): at once behind the group's chain -- or, when the proof is ONE chain, after that chain has
+    // been queued: they are ~14 launches each whose results are only read at the very end, and on a stream the chain waits for they held its
+    // start back by 0.8 ms (n = 2^16 streamed: profiles/r06_streamed_handover.txt)
+    if (p->fused) deferred_small.insert(deferred_small.end(), after_flush.begin(), after_flush.end());
+    else for (auto& f : after_flush) f();
+    after_flush.clear();
+  }
+  // (few_streams: on_ts = the group rides on the transform's stream -- r(X,1)'s, queued there ahead of the product --, else on the main stream)
+  void begin_group(hipEvent_t e, bool on_ts = false) {
+    flush();
+    if (p->few_streams && on_ts) { cur = &p->ts_lane; HIP_OK(hipStreamWaitEvent(p->ts, e, 0)); }
+    else cur = &p->pick(e);
+    cur->njobs = 0;
+  }
+  // the t group's lane (prover.hpp, t_lane) takes over without a flush; it waits for the product unless it IS the product's stream
+  void begin_t_group(Lane& lane_t) {
+    if (on(PH_T) && lane_t.st != p->ts) HIP_OK(hipStreamWaitEvent(lane_t.st, p->ev_t, 0));
+    cur = &lane_t; cur->njobs = 0;
+  }
+  void make_room() { if (cur->njobs + (int)pend.size() == MSM_MAX_JOBS) flush(); }
+  void commit(int ph, const Fr* poly, long lo, long len, long maxm, long slot) {
+    if (!on(ph) || !own(slot)) return;
+    make_room();
+    push(commit_job(cur->st, srs, poly, lo, len, maxm, &slots[slot], flags), slot);
+  }
+  // commitPoly with the runs of equal coefficients taken out (S_j of a handle that is not prepared): the flag checks read the
+  // coefficients themselves, the large MSM a copy with the uniform tiles zeroed, and a small MSM over gathered running sums -- on the
+  // main stream, beside this lane's batch -- adds c (ps[b] - ps[a - 1]) per run
+  void commit_runs(int ph, const Fr* poly, long lo, long len, long maxm, long j) {
+    const long slot = L.S(j), Q = L.Q;
+    if (!on(ph) || !own(slot)) return;
+    make_room();
+    MsmJob job = commit_job(cur->st, srs, poly, lo, len, maxm, &slots[slot], flags);
+    const long ntiles = job.n / RUN_TILE;
+    if (ntiles > 0) {
+      if ((long)p->runs.size() < Q) p->runs.resize((size_t)Q);
+      sonic_prover::RunBufs& rb = p->runs[(size_t)j];
+      if (!rb.masked_ev) HIP_OK(hipEventCreateWithFlags(&rb.masked_ev, hipEventDisableTiming));
+      rb.masked.ensure(sizeof(Fr) * job.n); rb.val.ensure(sizeof(Fr) * ntiles); rb.uniform.ensure(4 * ntiles);
+      rb.scal.ensure(sizeof(Fr) * 2 * ntiles); rb.pts.ensure(sizeof(G1Affine) * 2 * ntiles);
+      run_tiles_enqueue(cur->st, job.scalars, job.n, rb.masked.as<Fr>(), rb.val.as<Fr>(), rb.uniform.as<uint32_t>());
+      HIP_OK(hipEventRecord(rb.masked_ev, cur->st));
+      const long first = (long)((job.points.p - srs_basis(srs, 1).p) / (long)job.points.stride);
+      sonic_prover::RunBufs* rbp = &rb;
+      side([this, rbp, first, ntiles, j] {
+        hipStream_t ms = p->st;
+        HIP_OK(hipStreamWaitEvent(ms, rbp->masked_ev, 0));
+        run_terms_enqueue(ms, rbp->val.as<Fr>(), rbp->uniform.as<uint32_t>(), ntiles, srs_prefix(srs) + first, first, rbp->scal.as<Fr>(), rbp->pts.as<G1Affine>());
+        msm_enqueue(ms, p->runs_ws, msm_plan(2 * ntiles), PointArray::packed(rbp->pts.as<G1Affine>()), rbp->scal.as<Fr>(), 2 * ntiles, true, &slots[L.S_extra(j)]);
+      }, BEHIND_CHAIN);
+      job.scalars = rb.masked.as<Fr>();
+      p->slot_ran[(size_t)L.S_extra(j)] = 1;
+    }
+    push(job, slot);
+  }
+  // C = commitPoly(s(u,Y)) over the symmetric sums (prover.hpp, sym_on; never a piece of a shared proof): exponents 1 .. n as
+  // c_i (A[i] + A[-i]) in the group, exponents n+1 .. n+Q as a Q-term MSM on the main stream (su was built there)
+  void commit_sym(int ph, const Fr* su, long lo, long len, long n) {
+    if (!on(ph) || !own(L.C())) return;
+    const long d = srs_d(srs);
+    make_room();
+    MsmJob job = commit_job(cur->st, srs, su, lo, len, d, &slots[L.C()], flags);      // (the index checks of the whole range)
+    job.points = srs_sym(srs) + 1; job.scalars = su + (n + 1); job.n = n; job.table_stride = d + 1;
+    push(job, L.C());
+    p->slot_ran[(size_t)L.C_extra()] = 1;
+    side([this, su, d, n] { msm_enqueue(p->st, p->runs_ws, msm_plan(L.Q), srs_basis(srs, 1) + (d + n + 1), su + (2 * n + 1), L.Q, true, &slots[L.C_extra()]); }, BEHIND_CHAIN);
+  }
+  // fr: index of the evaluation in frout (-1: not reported); every rank with a piece of the opening computes it (the quotient
+  // needs the prefix sums anyway), the rank whose piece starts at term 0 reports it
+  void open(int ph, const Fr* poly, long lo, long len, const Fr* zp, long fr, long slot) {
+    if (!on(ph) || !own(slot)) return;
+    make_room();
+    Scratch& sc = p->fused ? p->fused_scratch() : cur->sc[cur->njobs + (int)pend.size()];
+    pend.push_back(PendingOpen{poly, lo, len, zp, fr >= 0 ? &frout[fr] : nullptr, &slots[slot], slot, &sc});
+    if (fr >= 0 && first_piece(slot)) p->fr_valid[(size_t)fr] = 1;
+  }
+  // a small MSM whose result is only read at the very end.  BESIDE_GROUP: at once when the group has been flushed, else behind its batch;
+  // BEHIND_CHAIN: at once, or (fused) once the proof's chain has been queued
+  void side(std::function<void()> fn, Side when) {
+    if (when == BEHIND_CHAIN ? !p->fused : cur->njobs == 0) fn();
+    else (when == BEHIND_CHAIN ? deferred_small : after_flush).push_back(std::move(fn));
+  }
+  MsmPlan chain_plan(const MsmJob* jobs, int k) const {
+    long nmax = 0;
+    for (int j = 0; j < k; j++) nmax = std::max(nmax, jobs[j].n);
+    MsmPlan pl = srs_msm_plan(srs, nmax);
+    pl.tree = true;
+    return pl;
+  }
+  // fused: the current group as a chain of its own on its lane (SONIC_FUSED_SPLIT_T)
+  void flush_as_chain() {
+    issue_opens();
+    if (cur->njobs > 0) msm_enqueue_batch(cur->st, cur->ws, chain_plan(cur->jobs, cur->njobs), cur->jobs, cur->njobs, true);
+    cur->njobs = 0;
+  }
+  // the proof's chain(s): every lane has queued the openings of its groups by now; chunks of at most MSM_MAX_JOBS jobs (one chunk up to
+  // Q = 2) on the two chain streams in turn so that two chunks overlap like two groups did.  ts_used: the transform's stream carries work
+  void run_chains(bool ts_used) {
+    if (!p->fused || p->fused_jobs.empty()) return;
+    for (int i = 0; i < p->n_lanes; i++) HIP_OK(hipEventRecord(p->lanes[i].prep, p->lanes[i].st));
+    if (p->few_streams) { HIP_OK(hipEventRecord(p->main_lane.prep, p->st)); if (ts_used) HIP_OK(hipEventRecord(p->ts_lane.prep, p->ts)); }
+    const int total = (int)p->fused_jobs.size();
+    const int nchunks = (total + MSM_MAX_JOBS - 1) / MSM_MAX_JOBS, per = (total + nchunks - 1) / nchunks;
+    for (int c = 0, at = 0; c < nchunks; c++, at += per) {
+      Lane& cl = p->chain[c & 1];
+      if (c < 2) {
+        for (int i = 0; i < p->n_lanes; i++) HIP_OK(hipStreamWaitEvent(cl.st, p->lanes[i].prep, 0));
+        if (p->few_streams) { HIP_OK(hipStreamWaitEvent(cl.st, p->main_lane.prep, 0)); if (ts_used) HIP_OK(hipStreamWaitEvent(cl.st, p->ts_lane.prep, 0)); }
+      }
+      const int k = std::min(per, total - at);
+      MsmPlan pl = chain_plan(&p->fused_jobs[(size_t)at], k);
+      pl.accum_block = 128;      // (measured for this chain, n = 2^16 streamed: 128 lanes 9.19-9.27 ms, 256 9.46-9.49, 512 9.42-9.46)
+      msm_enqueue_batch(cl.st, cl.ws, pl, &p->fused_jobs[(size_t)at], k, true);
+    }
+    p->fused_jobs.clear();
+  }
+  void drain_deferred() {
+    for (auto& f : deferred_small) f();
+    deferred_small.clear();
+  }
+  // the main stream waits for every stream that carried a part of the proof
+  void join(bool ts_used) {
+    hipStream_t ms = p->st;
+    for (int i = 0; i < p->n_lanes; i++) { Lane& l = p->lanes[i]; HIP_OK(hipEventRecord(l.done, l.st)); HIP_OK(hipStreamWaitEvent(ms, l.done, 0)); }
+    if (p->fused) for (auto& l : p->chain) if (l.st) { HIP_OK(hipEventRecord(l.done, l.st)); HIP_OK(hipStreamWaitEvent(ms, l.done, 0)); }
+    if (p->few_streams && ts_used) { HIP_OK(hipEventRecord(p->ts_lane.done, p->ts_lane.st)); HIP_OK(hipStreamWaitEvent(ms, p->ts_lane.done, 0)); }
+  }
+};
+
+// What one enqueue of a proof works with besides the queue: the exponent ranges of its polynomials, the {v, v^-1} pairs of its
+// evaluation points, and which polynomials and groups this rank has a piece of (all of them unless the proof is shared)
+struct ProofPass {
+  const long n, Q, d;
+  const long r_lo, r_len, s_lo, s_len, t_lo, t_len, u_lo, u_len;
+  const Fr* const PR;
+  bool need_g0, need_T, need_su, need_j_any = false;
+  std::vector<uint8_t> need_j;
+  long last_j = -1;
+  int last_group;                 // the group whose reduction nothing is left to hide under (the t group when this rank has a piece of it)
+  bool g0_queued = false;
+  const Fr* pair(long i) const { return PR + 2 * i; }
+  bool ts_used() const { return need_T || g0_queued; }
+  ProofPass(sonic_prover_t* p, const GroupQueue& q)
+      : n(p->n), Q(p->Q), d(srs_d(p->srs)), r_lo(-2 * n - 4), r_len(3 * n + 5), s_lo(-n), s_len(3 * n + 1), t_lo(-4 * n - 8), t_len(7 * n + 9),
+        u_lo(-n), u_len(2 * n + Q + 1), PR(p->PAIRS.as<Fr>()), need_j((size_t)Q, 0) {
+    const ProofLayout& L = q.L;
+    need_su = q.own(L.C()) || q.own(L.Qv());
+    for (long j = 0; j < Q; j++) {
+      need_j[(size_t)j] = q.own(L.S(j)) || q.own(L.W(j)) || q.own(L.Wp(j));
+      need_j_any = need_j_any || need_j[(size_t)j];
+      if (need_j[(size_t)j]) last_j = j;
+      need_su = need_su || q.own(L.Qj(j));
+    }
+    need_g0 = q.own(L.R) || q.own(L.Wa) || q.own(L.Wb);
+    need_T = q.own(L.T) || q.own(L.Wt);
+    last_group = need_T ? 3 : need_su ? 2 : need_j_any ? 1 : 0;
+  }
+};
+
+// the group that needs nothing but r(X,1): R, (a, W_a), (b, W_b)
+static void enqueue_group0(sonic_prover_t* p, GroupQueue& q, ProofPass& w) {
+  if (!w.need_g0 || w.g0_queued) return;
+  w.g0_queued = true;
+  const ProofLayout& L = q.L;
+  const Fr* r1 = p->r1.as<Fr>();
+  q.begin_group(p->ev_r1, /*on_ts=*/true);
+  q.commit(PH_R, r1, w.r_lo, w.r_len, w.n, L.R);                                       // R            Protocol.hs:63
+  q.open(PH_OPEN, r1, w.r_lo, w.r_len, w.pair(L.pZ), L.a, L.Wa);                       // (a, W_a)     :79
+  q.open(PH_OPEN, r1, w.r_lo, w.r_len, w.pair(L.pYZ), L.b, L.Wb);                      // (b, W_b)     :80
+  q.flush(w.last_group == 0);
+}
+
+// ---- all polynomials first (small kernels; queued behind a bucket accumulation they would each wait ~0.5 ms for CUs) ----
+// (a polynomial is built in the pass that first knows its challenge -- every pass when phases == PH_ALL -- and stays in the
+// handle's buffers for the later passes of sonic_prover_prove_fs: r(X,1) from the blinders, s(X,y) and t(X,y) from y, s(X,y_j)
+// from y_j, s(u,Y) from u)
+static void enqueue_polynomials(sonic_prover_t* p, GroupQueue& q, ProofPass& w) {
+  const ProofLayout& L = q.L;
+  const long n = w.n, Q = w.Q;
+  hipStream_t ms = p->st;
+  int* flags = q.flags;
+  Fr *r1 = p->r1.as<Fr>(), *sy = p->sy0.as<Fr>(), *pw = p->pw.as<Fr>(), *fa = p->fa.as<Fr>(), *fb = p->fb.as<Fr>();
+  auto ready = [&](hipEvent_t e) { HIP_OK(hipEventRecord(e, ms)); };
+  // zkP_1: r'(X,1)                                                                   Protocol.hs:58-63
+  if (p->pend_asg[0]) {
+    upload_fr_mont(ms, p->aL, p->pend_asg[0], n, flags + 1);
+    upload_fr_mont(ms, p->aR, p->pend_asg[1], n, flags + 1);
+    upload_fr_mont(ms, p->aO, p->pend_asg[2], n, flags + 1);
+    p->pend_asg[0] = nullptr;
+    p->have_witness_digest = false;
+  }
+  if ((w.need_g0 || w.need_T) && q.on(PH_R)) build_r1_enqueue(ms, p->aL.as<Fr>(), p->aR.as<Fr>(), p->aO.as<Fr>(), p->S.as<Fr>(), n, r1);
+  ready(p->ev_r1);
+  // the group that needs nothing but r(X,1): queued here, ahead of the other polynomials, when this call's circuit is still on the host
+  if (p->few_streams && p->fused) enqueue_group0(p, q, w);          // (its openings go on the transform's stream, ahead of the product's kernels)
+  if (p->pend.set) {
+    enqueue_group0(p, q, w);
+    prover_upload_circuit(p, ms, flags + 1);
+  }
+  // s(X,y)                                                                           Protocol.hs:69-70
+  if (w.need_T && q.on(PH_T)) {
+    poly_scale_powers_enqueue(ms, nullptr, pw, 2 * n + Q + 1, -n, w.pair(L.pY), w.pair(L.pY) + 1);       // y^e, e in [-n, n+Q]
+    s_of_y_of(p, ms, pw, sy);
+    HIP_OK(hipMemcpyAsync(p->kpow.p, pw + (2 * n + 1), sizeof(Fr) * Q, hipMemcpyDeviceToDevice, ms));   // y^{n+1..n+Q} for k(y); pw is reused below
+  }
+  ready(p->ev_sy0);
+  if (w.need_T && q.on(PH_T)) {
+    // zkP_2: t(X,y) = r(X,1) * (r(X,y) + s(X,y)) - k(y), on its own stream          Protocol.hs:69-73, Constraints.hs:56-68
+    hipStream_t ts = p->ts;
+    const long M = 1L << p->log2m;
+    HIP_OK(hipStreamWaitEvent(ts, p->ev_sy0, 0));          // ev_sy0 follows ev_r1 on the main stream
+    t_operands_enqueue(ts, r1, w.r_len, w.r_lo, sy, w.s_lo - w.r_lo, w.s_len, w.pair(L.pY), fa, fb, M);     // fa = r(X,1), fb = r(X,y) + s(X,y), zero-padded
+    ntt_forward_enqueue(ts, *p->ntt, fa, p->log2m);
+    ntt_forward_enqueue(ts, *p->ntt, fb, p->log2m);
+    ntt_inverse_of_product_enqueue(ts, *p->ntt, fa, fb, p->log2m);
+    sub_k_of_y_enqueue(ts, fa + (0 - w.t_lo), p->cs.as<Fr>(), p->kpow.as<Fr>(), Q, flags, 0);
+    HIP_OK(hipEventRecord(p->ev_t, ts));
+  }
+  // hscProve: s(X, y_j), s(u, Y)                                                     Signature.hs:41,51
+  for (long j = 0; j < Q; j++) {
+    if (w.need_j[(size_t)j] && q.on(PH_HSCS)) {
+      poly_scale_powers_enqueue(ms, nullptr, pw, 2 * n + Q + 1, -n, w.pair(L.pYj(j)), w.pair(L.pYj(j)) + 1);
+      // a prepared handle that has only a piece of S_j's diagonal part does not read s(X, y_j) itself
+      if (!p->prepared || q.own(L.W(j)) || q.own(L.Wp(j))) s_of_y_of(p, ms, pw, p->syj[j].as<Fr>());
+      if (p->prepared && q.own(L.S(j))) s_diag_part_enqueue(ms, pw, n, Q, p->diag[j].as<Fr>(), p->yq[j].as<Fr>());
+    }
+    ready(p->ev_syj[j]);
+  }
+  if (w.need_su && q.on(PH_HSCW)) {
+    poly_scale_powers_enqueue(ms, nullptr, pw, 3 * n + 1, -n, w.pair(L.pU), w.pair(L.pU) + 1);           // u^e, e in [-n, 2n]
+    s_of_u_of(p, ms, pw, p->su.as<Fr>());
+  }
+  ready(p->ev_su);
+}
+
+// T and W_t, as a chain of their own when the rest of a fused proof runs without them (SONIC_FUSED_SPLIT_T)
+static void enqueue_t_group(sonic_prover_t* p, GroupQueue& q, const ProofPass& w, Lane& lane_t, bool own_chain) {
+  const ProofLayout& L = q.L;
+  const Fr* t = p->fa.as<Fr>();                                                        // exponents [t_lo, t_lo + t_len)
+  q.begin_t_group(lane_t);
+  q.commit(PH_T, t, w.t_lo, w.t_len, w.d, L.T);                                        // T            Protocol.hs:73
+  q.open(PH_OPEN, t, w.t_lo, w.t_len, w.pair(L.pZ), -1, L.Wt);                         // W_t          :81
+  if (p->fused && own_chain) q.flush_as_chain();
+  else q.flush(true);
+}
+
+// ---- the MSM groups, largest first where its input allows: what the protocol commits to and opens ----
+static void enqueue_groups(sonic_prover_t* p, GroupQueue& q, ProofPass& w) {
+  const ProofLayout& L = q.L;
+  const long n = w.n, Q = w.Q, d = w.d;
+  MsmSlot* slots = q.slots;
+  Fr* su = p->su.as<Fr>();
+  Lane& lane_t = p->t_lane(p->ev_sy0);
+  if (q.on(PH_OPEN) && q.first_piece(L.Wt)) {                                          // s(z,y)       :83  (reported by the rank that starts W_t)
+    // (few_streams: on the main stream, not behind the transform on its stream -- the evaluation needs s(X,y) only, and everything queued
+    // behind the transform is on the longest dependent chain of a proof)
+    Lane& le = p->few_streams ? p->main_lane : lane_t;
+    Scratch& es = le.sc[MSM_MAX_JOBS - 1];
+    es.reserve(w.s_len);
+    es.scan.ensure(sizeof(Fr) * (w.s_len / 1024 + 2));
+    OpenBatch eb;
+    memset(&eb, 0, sizeof eb);
+    eb.k = 1; eb.poly[0] = p->sy0.as<Fr>(); eb.D[0] = es.D.as<Fr>(); eb.q[0] = es.q.as<Fr>(); eb.tiles[0] = es.scan.as<Fr>(); eb.zpair[0] = w.pair(L.pZ); eb.fz[0] = &q.frout[L.s];
+    open_batch_enqueue(le.st, eb, w.s_lo, w.s_len, /*quotient=*/false);
+    p->fr_valid[(size_t)L.s] = 1;
+  }
+  enqueue_group0(p, q, w);
+  for (long j = 0; j < Q; j++) {
+    if (!w.need_j[(size_t)j]) continue;
+    Fr* syj = p->syj[j].as<Fr>();
+    q.begin_group(p->ev_syj[j]);
+    if (p->prepared) q.commit(PH_HSCS, p->diag[j].as<Fr>(), n + 1, n, d, L.S(j));      // S_j (diagonal part)   Signature.hs:42
+    else if (p->runs_on) q.commit_runs(PH_HSCS, syj, w.s_lo, w.s_len, d, j);           // S_j, runs through the running sums   :42
+    else q.commit(PH_HSCS, syj, w.s_lo, w.s_len, d, L.S(j));                           // S_j                   :42
+    q.open(PH_HSCS, syj, w.s_lo, w.s_len, w.pair(L.pZj(j)), L.s_j(j), L.W(j));         // (s_j, W_j)    :43
+    q.open(PH_HSCW, syj, w.s_lo, w.s_len, w.pair(L.pU), -1, L.Wp(j));                  // W'_j          :54
+    q.flush(w.last_group == 1 && j == w.last_j);
+    if (p->prepared && q.on(PH_HSCS) && q.first_piece(L.S(j))) {                       // sum_q y_j^{n+q} C_q, Q-term MSM
+      Lane* ln = q.cur;
+      p->slot_ran[(size_t)L.S_extra(j)] = 1;
+      q.side([p, ln, j, Q, out = &slots[L.S_extra(j)]] {
+        msm_enqueue(ln->st, ln->ws, p->cq_tab.p ? msm_plan_tables(Q, CQ_TAB_C, CQ_TAB_W, Q) : msm_plan(Q),
+                    PointArray::packed(p->cq_tab.p ? p->cq_tab.as<G1Affine>() : p->cq.as<G1Affine>()), p->yq[j].as<Fr>(), Q, true, out);
+      }, GroupQueue::BESIDE_GROUP);
+    }
+  }
+  if (w.need_su) {
+    q.begin_group(p->ev_su);
+    if (p->sym_on) q.commit_sym(PH_HSCW, su, w.u_lo, w.u_len, n);                      // C             :52, over the symmetric sums
+    else q.commit(PH_HSCW, su, w.u_lo, w.u_len, d, L.C());                             // C             :52
+    for (long j = 0; j < Q; j++) q.open(PH_HSCW, su, w.u_lo, w.u_len, w.pair(L.pYj(j)), L.sp_j(j), L.Qj(j));   // (s'_j, Q_j) :55
+    q.open(PH_QV, su, w.u_lo, w.u_len, w.pair(L.pV), -1, L.Qv());                      // Q_v           :63
+  }
+  q.flush(w.last_group == 2 && q.sh != nullptr);
+  // (SONIC_FUSED_SPLIT_T=1, measured and not the default: T and W_t -- 14n of a proof's 45n terms, and the group whose polynomial is ready
+  // last -- as a SECOND chain on the stream that made the polynomial, so that the chain of the other thirteen MSMs need not wait for the
+  // product.  One at a time it gains 1-3 %; streamed it loses 3-10 % at n = 2^14 .. 2^16: two sorts, two accumulation tails and two
+  // butterflies per proof; profiles/r06_ab_small_final.txt)
+  static const bool split_t = getenv("SONIC_FUSED_SPLIT_T") && atoi(getenv("SONIC_FUSED_SPLIT_T")) != 0;
+  if (w.need_T && !(p->fused && split_t)) enqueue_t_group(p, q, w, lane_t, false);
+  q.run_chains(w.ts_used());
+  if (w.need_T && p->fused && split_t) enqueue_t_group(p, q, w, lane_t, true);
+  q.drain_deferred();
+}
+
+// Everything between "inputs in HBM" and "window-sum slots + evaluations on the host", queued with no host synchronisation: what a
+// captured hipGraph replays
+static void enqueue_proof(sonic_prover_t* p) {
+  const ProofLayout L{p->Q};
   hipStream_t st = p->st;
-  // evaluation points feed `pow x e` with negative e (Utils.hs:18, poly's eval): x = 0 has no inverse
-  for (long k = 4; k < 8 + 2 * Q; k++)
-    if (bytes_are_zero(transcript + 32 * k, 32)) { set_error("prove: transcript element %ld is zero: Laurent evaluation at 0 divides by zero", k); return SONIC_ERR_INEXACT_DIVISION; }
-  if (p->share_world > 1 && (!p->share_planned || p->share_planned_prepared != p->prepared)) {
-    const MsmPlan mp = srs_msm_plan(srs, 3 * n);
-    const ShareCosts costs = ShareCosts::from_env();
-    p->share = share_plan(n, Q, p->prepared, p->share_world, mp.NB, mp.W, costs);
-    // what the plan was computed from, as a 32-bit tag in the share header: the plan is a pure function of these, but NB and W come from
-    // the rank's own SRS handle (window tables or not: free memory at SRS construction) and the cost constants from its environment --
-    // ranks that disagree would report pieces that do not fit together, and sonic_proof_from_shares says so instead of "do not cover"
-    {
-      uint64_t h = 1469598103934665603ull;
-      auto mix = [&](uint64_t v) { for (int i = 0; i < 8; i++) { h ^= (v >> (8 * i)) & 0xff; h *= 1099511628211ull; } };
-      auto mixd = [&](double d) { uint64_t v; memcpy(&v, &d, 8); mix(v); };
-      mix((uint64_t)n); mix((uint64_t)Q); mix(p->prepared ? 1 : 0); mix((uint64_t)p->share_world); mix((uint64_t)mp.NB); mix((uint64_t)mp.W);
-      mixd(costs.per_job_buckets); mixd(costs.r1); mixd(costs.sy); mixd(costs.su); mixd(costs.tprod);
-      p->share_plan_tag = (int32_t)(uint32_t)(h ^ (h >> 32));
-    }
-    p->share_planned = true; p->share_planned_prepared = p->prepared;
-  }
-  if (p->share_world > 1 && p->phases != PH_ALL) { set_error("prove: a shared proof runs with a caller-supplied transcript only"); return SONIC_ERR_INVALID_ARG; }
   int* flags = p->flags.as<int>();
-  memcpy(p->h_tr, transcript, 32 * (8 + 2 * Q));
-  {
-    // {v, v^-1} for v = y, z, yz, u, v, y_1..y_Q, z_1..z_Q (Montgomery form), on the host with one shared inversion: the same
-    // values cost a proof 0.35 ms of single-thread Fermat inversions on the device before its first polynomial could be built.
-    // A non-canonical element is flagged by the device's conversion of the transcript below; its pair here is then irrelevant.
-    const long np = 5 + 2 * Q;
-    std::vector<Fr> v((size_t)np), pre((size_t)np);
-    auto tr = [&](long k) { Fr a; memcpy(a.l, transcript + 32 * k, 32); return fp_to_mont(a); };
-    v[0] = tr(4); v[1] = tr(5); v[2] = fp_mul(v[0], v[1]); v[3] = tr(6 + 2 * Q); v[4] = tr(7 + 2 * Q);
-    for (long t = 0; t < 2 * Q; t++) v[5 + t] = tr(6 + t);
-    Fr acc = Fr::one();
-    for (long i = 0; i < np; i++) { pre[i] = acc; acc = fp_mul(acc, v[i].is_zero() ? Fr::one() : v[i]); }
-    Fr inv = fp_inv(acc);
-    for (long i = np - 1; i >= 0; i--) {
-      p->h_pairs[2 * i] = v[i];
-      if (v[i].is_zero()) { p->h_pairs[2 * i + 1] = v[i]; continue; }
-      p->h_pairs[2 * i + 1] = fp_mul(inv, pre[i]);
-      inv = fp_mul(inv, v[i]);
-    }
-  }
-  const int K = (int)(7 + 4 * Q);
+  HIP_OK(hipMemsetAsync(flags, 0, 8, st));
+  Fr* S = p->S.as<Fr>();
+  HIP_OK(hipMemcpyAsync(S, p->h_tr, 32 * L.transcript_len(), hipMemcpyHostToDevice, st));
+  fr_to_mont_enqueue(st, S, L.transcript_len(), flags);
+  HIP_OK(hipMemcpyAsync(p->PAIRS.p, p->h_pairs, sizeof(Fr) * 2 * L.n_pairs(), hipMemcpyHostToDevice, st));
+  GroupQueue q(p);
+  ProofPass w(p, q);
+  enqueue_polynomials(p, q, w);
+  enqueue_groups(p, q, w);
+  q.join(w.ts_used());
+  Fr* frstd = p->frstd.as<Fr>();
+  HIP_OK(hipMemcpyAsync(frstd, q.frout, sizeof(Fr) * L.F(), hipMemcpyDeviceToDevice, st));
+  fr_from_mont_enqueue(st, frstd, L.F());
+  // (the side slots that this proof's modes fill: the second halves of the S_j, and of C)
+  const long KS = p->sym_on ? L.slots_total() : (p->prepared || p->runs_on) ? L.C_extra() : L.K();
+  HIP_OK(hipMemcpyAsync(p->h_slots, q.slots, sizeof(MsmSlot) * KS, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(p->h_fr, frstd, 32 * L.F(), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(p->h_flags, flags, 8, hipMemcpyDeviceToHost, st));
+}
+
+// ---- the per-proof mode decisions ------------------------------------------------------------------------------------------------
+static void decide_modes(sonic_prover_t* p) {
   // runs of equal coefficients in S_j go through the running sums of the alpha basis: not for a piece of a shared proof (its term
   // ranges cut the runs), and by default from n = 2^16 (measured, unprepared ms per proof with / without: n = 2^18 32.9 / 36.7,
   // 2^17 19.8 / 20.8, 2^16 12.2 / 12.3, 2^14 6.8 / 6.0 -- below, the extra launches cost more than the additions they save;
@@ -479,14 +804,73 @@ static int prove_enqueue(sonic_prover_t* p, const uint8_t* transcript) {
     p->sym_on = mode != 0 && (mode == 1 || p->n >= (1L << 17)) && p->share_world <= 1 && srs_sym(p->srs).p != nullptr;
   }
   {
-    const MsmPlan probe = srs_msm_plan(srs, 3 * n);
+    const MsmPlan probe = srs_msm_plan(p->srs, 3 * p->n);
     const char* fe = getenv("SONIC_PROVE_FUSED");
     const int mode = fe ? atoi(fe) : -1;
     p->fused = mode != 0 && p->small_plan && msm_can_batch(probe) && p->share_world <= 1;
     p->fused_jobs.clear();
     p->fused_sc_next = 0;
   }
-  const int KS = p->sym_on ? K + (int)Q + 1 : K + ((p->prepared || p->runs_on) ? (int)Q : 0);        // + the second halves of the S_j and of C
+}
+
+// a shared proof's plan, computed when the share or the prepared state changed since the last one
+static void share_replan_if_needed(sonic_prover_t* p) {
+  if (p->share_world <= 1 || (p->share_planned && p->share_planned_prepared == p->prepared)) return;
+  const long n = p->n, Q = p->Q;
+  const MsmPlan mp = srs_msm_plan(p->srs, 3 * n);
+  const ShareCosts costs = ShareCosts::from_env();
+  p->share = share_plan(n, Q, p->prepared, p->share_world, mp.NB, mp.W, costs);
+  // what the plan was computed from, as a 32-bit tag in the share header: the plan is a pure function of these, but NB and W come from
+  // the rank's own SRS handle (window tables or not: free memory at SRS construction) and the cost constants from its environment --
+  // ranks that disagree would report pieces that do not fit together, and sonic_proof_from_shares says so instead of "do not cover"
+  uint64_t h = 1469598103934665603ull;
+  auto mix = [&](uint64_t v) { for (int i = 0; i < 8; i++) { h ^= (v >> (8 * i)) & 0xff; h *= 1099511628211ull; } };
+  auto mixd = [&](double d) { uint64_t v; memcpy(&v, &d, 8); mix(v); };
+  mix((uint64_t)n); mix((uint64_t)Q); mix(p->prepared ? 1 : 0); mix((uint64_t)p->share_world); mix((uint64_t)mp.NB); mix((uint64_t)mp.W);
+  mixd(costs.per_job_buckets); mixd(costs.r1); mixd(costs.sy); mixd(costs.su); mixd(costs.tprod);
+  p->share_plan_tag = (int32_t)(uint32_t)(h ^ (h >> 32));
+  p->share_planned = true; p->share_planned_prepared = p->prepared;
+}
+
+// {v, v^-1} for v = y, z, yz, u, v, y_1..y_Q, z_1..z_Q (Montgomery form), on the host with one shared inversion: the same
+// values cost a proof 0.35 ms of single-thread Fermat inversions on the device before its first polynomial could be built.
+// A non-canonical element is flagged by the device's conversion of the transcript; its pair here is then irrelevant.
+static void challenge_pairs_host(sonic_prover_t* p, const uint8_t* transcript) {
+  const ProofLayout L{p->Q};
+  const long np = L.n_pairs();
+  std::vector<Fr> v((size_t)np), pre((size_t)np);
+  auto tr = [&](long k) { Fr a; memcpy(a.l, transcript + 32 * k, 32); return fp_to_mont(a); };
+  v[L.pY] = tr(L.y); v[L.pZ] = tr(L.z); v[L.pYZ] = fp_mul(v[L.pY], v[L.pZ]); v[L.pU] = tr(L.u()); v[L.pV] = tr(L.v());
+  for (long j = 0; j < L.Q; j++) { v[L.pYj(j)] = tr(L.y_j(j)); v[L.pZj(j)] = tr(L.z_j(j)); }
+  Fr acc = Fr::one();
+  for (long i = 0; i < np; i++) { pre[i] = acc; acc = fp_mul(acc, v[i].is_zero() ? Fr::one() : v[i]); }
+  Fr inv = fp_inv(acc);
+  for (long i = np - 1; i >= 0; i--) {
+    p->h_pairs[2 * i] = v[i];
+    if (v[i].is_zero()) { p->h_pairs[2 * i + 1] = v[i]; continue; }
+    p->h_pairs[2 * i + 1] = fp_mul(inv, pre[i]);
+    inv = fp_mul(inv, v[i]);
+  }
+}
+
+// prove = prove_enqueue (queues the whole proof on the handle's streams, no host synchronisation) + prove_finish (waits, runs
+// the host tails, lays out the bytes).  sonic_prover_prove runs them back to back; sonic_prover_submit / sonic_prover_collect
+// expose the halves, so that ONE host thread can keep two handles busy: while it waits for and finishes proof i on one handle,
+// proof i + 1 is already running on the other (its polynomial building and sorts fill the first proof's reduction tail).
+// Both run under p->mu.
+static int prove_enqueue(sonic_prover_t* p, const uint8_t* transcript) {
+  API_BEGIN_ON(p->device)
+  p->t_begin = std::chrono::steady_clock::now();
+  const ProofLayout L{p->Q};
+  hipStream_t st = p->st;
+  // evaluation points feed `pow x e` with negative e (Utils.hs:18, poly's eval): x = 0 has no inverse
+  for (long k = L.n_blinders; k < L.transcript_len(); k++)
+    if (bytes_are_zero(transcript + 32 * k, 32)) { set_error("prove: transcript element %ld is zero: Laurent evaluation at 0 divides by zero", k); return SONIC_ERR_INEXACT_DIVISION; }
+  if (p->share_world > 1 && p->phases != PH_ALL) { set_error("prove: a shared proof runs with a caller-supplied transcript only"); return SONIC_ERR_INVALID_ARG; }
+  decide_modes(p);
+  share_replan_if_needed(p);
+  memcpy(p->h_tr, transcript, 32 * L.transcript_len());
+  challenge_pairs_host(p, transcript);
   // Launch-bound sizes replay the whole multi-stream enqueue as one hipGraph: captured on the second proof of a handle (the
   // first one grows the workspaces), every address in it is owned by the handle.
   const bool pending = p->pend.set || p->pend_asg[0] != nullptr;
@@ -498,320 +882,7 @@ static int prove_enqueue(sonic_prover_t* p, const uint8_t* transcript) {
     ~CaptureGuard() { if (active) { hipGraph_t g = nullptr; (void)hipStreamEndCapture(st, &g); if (g) (void)hipGraphDestroy(g); } }
   } capture{st};
   if (capturing) { p->graph_tried = true; HIP_OK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed)); capture.active = true; }
-  if (!replay) {
-  HIP_OK(hipMemsetAsync(flags, 0, 8, st));
-  Fr* S = p->S.as<Fr>();
-  HIP_OK(hipMemcpyAsync(S, p->h_tr, 32 * (8 + 2 * Q), hipMemcpyHostToDevice, st));
-  fr_to_mont_enqueue(st, S, 8 + 2 * Q, flags);
-  Fr* PR = p->PAIRS.as<Fr>();
-  HIP_OK(hipMemcpyAsync(PR, p->h_pairs, sizeof(Fr) * 2 * (5 + 2 * Q), hipMemcpyHostToDevice, st));
-  const Fr *pY = PR + 0, *pZ = PR + 2, *pYZ = PR + 4, *pU = PR + 6, *pV = PR + 8;
-  auto pYj = [&](long j) { return PR + 2 * (5 + j); };
-  auto pZj = [&](long j) { return PR + 2 * (5 + Q + j); };
-  MsmSlot* slots = p->slots.as<MsmSlot>();
-  Fr* frout = p->frout.as<Fr>();
-  Fr *r1 = p->r1.as<Fr>(), *su = p->su.as<Fr>(), *pw = p->pw.as<Fr>(), *fa = p->fa.as<Fr>(), *fb = p->fb.as<Fr>();
-  const Fr *cs = p->cs.as<Fr>();
-  const long d = srs_d(srs);
-  const long r_lo = -2 * n - 4, r_len = 3 * n + 5, s_lo = -n, s_len = 3 * n + 1, t_lo = -4 * n - 8, t_len = 7 * n + 9;
-  const long M = 1L << p->log2m;
-
-  // The main stream builds the polynomials.  The commitments / openings that depend on one polynomial form a group:
-  // it runs on the next MSM lane as soon as its input exists (event), as ONE batched MSM kernel chain.
-  // Results land in disjoint slots / frout entries.
-  hipStream_t ms = st;
-  p->next_lane = 0;
-  auto ready = [&](hipEvent_t e) { HIP_OK(hipEventRecord(e, ms)); };
-  auto on = [&](int ph) { return ((p->phases >> ph) & 1u) != 0; };
-  // one proof over several GPUs: this rank's pieces of the MSMs (share_plan.hpp); sh == nullptr: everything
-  const SlotShare* sh = p->share_world > 1 ? p->share.row(p->share_rank) : nullptr;
-  auto own = [&](long slot) { return !sh || sh[slot].hi > sh[slot].lo; };
-  auto first_piece = [&](long slot) { return !sh || (sh[slot].hi > sh[slot].lo && sh[slot].lo == 0); };
-  // cuts the job down to this rank's term range; false: nothing of it is left
-  auto my_piece = [&](MsmJob& job, long slot) {
-    if (sh) {
-      long t0, t1;
-      share_term_range(sh[slot], job.n, &t0, &t1);
-      job.points = job.points + t0; job.scalars += t0; job.n = t1 - t0;
-      if (job.n <= 0) return false;
-    }
-    p->slot_ran[(size_t)slot] = 1;
-    return true;
-  };
-  p->slot_ran.assign((size_t)(7 + 5 * Q + 1), 0);
-  p->fr_valid.assign((size_t)(3 + 2 * Q), 0);
-  bool need_j_any = false, need_su = own(6 + 4 * Q) || own(5 + 4 * Q);
-  std::vector<uint8_t> need_j((size_t)Q, 0);
-  for (long j = 0; j < Q; j++) {
-    need_j[(size_t)j] = own(5 + 2 * j) || own(6 + 2 * j) || own(5 + 2 * Q + 2 * j);
-    need_j_any = need_j_any || need_j[(size_t)j];
-    need_su = need_su || own(6 + 2 * Q + 2 * j);
-  }
-  const bool need_g0 = own(0) || own(2) || own(3), need_T = own(1) || own(4);
-  // the group whose reduction nothing is left to hide under (the t group when this rank has a piece of it)
-  long last_j = -1;
-  for (long j = 0; j < Q; j++) if (need_j[(size_t)j]) last_j = j;
-  const int last_group = need_T ? 3 : need_su ? 2 : need_j_any ? 1 : 0;
-  Lane* cur = nullptr;
-  // (packing consecutive groups into ONE batched chain -- fewer, wider chains -- was measured in round 3 and removed in round 5: n = 2^18
-  // 35.9 / 38.9 ms streamed / one at a time packed against 35.0 / 35.9: the chains of one proof overlap less)
-  std::vector<std::function<void()>> after_flush;       // small MSMs that use the lane's workspace after the batch (stream order)
-  std::vector<std::function<void()>> deferred_small;    // (fused proofs: the same, queued behind the proof's chain)
-  // the openings of the group that is being assembled: evaluated and divided together when the group is flushed
-  std::vector<PendingOpen> pend;
-  auto issue_opens = [&] {
-    if (pend.empty()) return;
-    MsmJob oj[MSM_MAX_JOBS];
-    open_jobs_batched(cur->st, srs, pend.data(), (int)pend.size(), flags, oj);
-    for (size_t i = 0; i < pend.size(); i++) if (my_piece(oj[i], pend[i].slot_index)) cur->jobs[cur->njobs++] = oj[i];
-    pend.clear();
-  };
-  auto flush_now = [&](bool last = false) {
-    if (!cur) return;
-    issue_opens();
-    if (p->fused) p->fused_jobs.insert(p->fused_jobs.end(), cur->jobs, cur->jobs + cur->njobs);      // run at the end, as one chain
-    else run_jobs(cur->st, srs, cur->ws, cur->jobs, cur->njobs, last, /*exposed=*/p->share_world >= 4);
-    cur->njobs = 0;
-    // the small MSMs beside a group (Q-term sums): at once behind the group's chain -- or, when the proof is ONE chain, after that chain has
-    // been queued: they are ~14 launches each whose results are only read at the very end, and on a stream the chain waits for they held its
-    // start back by 0.8 ms (n = 2^16 streamed: profiles/r06_streamed_handover.txt)
-    if (p->fused) deferred_small.insert(deferred_small.end(), after_flush.begin(), after_flush.end());
-    else for (auto& f : after_flush) f();
-    after_flush.clear();
-  };
-  // (few_streams: on_ts = the group rides on the transform's stream -- r(X,1)'s, queued there ahead of the product --, else on the main stream)
-  auto begin_group = [&](hipEvent_t e, bool on_ts = false) {
-    flush_now();
-    if (p->few_streams && on_ts) { cur = &p->ts_lane; HIP_OK(hipStreamWaitEvent(p->ts, e, 0)); }
-    else cur = &p->pick(e);
-    cur->njobs = 0;
-  };
-  auto flush_group = [&](bool last = false) { flush_now(last); };
-  auto full = [&] { return cur->njobs + (int)pend.size() == MSM_MAX_JOBS; };
-  auto commit = [&](int ph, const Fr* poly, long lo, long len, long maxm, long slot) {
-    if (!on(ph) || !own(slot)) return;
-    if (full()) flush_now();
-    MsmJob job = commit_job(cur->st, srs, poly, lo, len, maxm, &slots[slot], flags);
-    if (my_piece(job, slot)) cur->jobs[cur->njobs++] = job;
-  };
-  // commitPoly with the runs of equal coefficients taken out (S_j of a handle that is not prepared): the flag checks read the
-  // coefficients themselves, the large MSM a copy with the uniform tiles zeroed, and a small MSM over gathered running sums -- on the
-  // main stream, beside this lane's batch -- adds c (ps[b] - ps[a - 1]) per run
-  auto commit_runs = [&](int ph, const Fr* poly, long lo, long len, long maxm, long slot, long j) {
-    if (!on(ph) || !own(slot)) return;
-    if (full()) flush_now();
-    MsmJob job = commit_job(cur->st, srs, poly, lo, len, maxm, &slots[slot], flags);
-    const long ntiles = job.n / RUN_TILE;
-    if (ntiles > 0) {
-      if ((long)p->runs.size() < Q) p->runs.resize((size_t)Q);
-      sonic_prover::RunBufs& rb = p->runs[(size_t)j];
-      if (!rb.masked_ev) HIP_OK(hipEventCreateWithFlags(&rb.masked_ev, hipEventDisableTiming));
-      rb.masked.ensure(sizeof(Fr) * job.n); rb.val.ensure(sizeof(Fr) * ntiles); rb.uniform.ensure(4 * ntiles);
-      rb.scal.ensure(sizeof(Fr) * 2 * ntiles); rb.pts.ensure(sizeof(G1Affine) * 2 * ntiles);
-      run_tiles_enqueue(cur->st, job.scalars, job.n, rb.masked.as<Fr>(), rb.val.as<Fr>(), rb.uniform.as<uint32_t>());
-      HIP_OK(hipEventRecord(rb.masked_ev, cur->st));
-      const long first = (long)((job.points.p - srs_basis(srs, 1).p) / (long)job.points.stride);
-      sonic_prover::RunBufs* rbp = &rb;
-      auto run_tail = [&, rbp, first, ntiles, j, ms, slots, Q] {
-        HIP_OK(hipStreamWaitEvent(ms, rbp->masked_ev, 0));
-        run_terms_enqueue(ms, rbp->val.as<Fr>(), rbp->uniform.as<uint32_t>(), ntiles, srs_prefix(srs) + first, first, rbp->scal.as<Fr>(), rbp->pts.as<G1Affine>());
-        msm_enqueue(ms, p->runs_ws, msm_plan(2 * ntiles), PointArray::packed(rbp->pts.as<G1Affine>()), rbp->scal.as<Fr>(), 2 * ntiles, true, &slots[(7 + 4 * Q) + j]);
-      };
-      if (p->fused) deferred_small.push_back(run_tail); else run_tail();
-      job.scalars = rb.masked.as<Fr>();
-      p->slot_ran[(size_t)((7 + 4 * Q) + j)] = 1;
-    }
-    if (my_piece(job, slot)) cur->jobs[cur->njobs++] = job;
-  };
-  // fr: index of the evaluation in frout (-1: not reported); every rank with a piece of the opening computes it (the quotient
-  // needs the prefix sums anyway), the rank whose piece starts at term 0 reports it
-  auto open = [&](int ph, const Fr* poly, long lo, long len, const Fr* zp, long fr, long slot) {
-    if (!on(ph) || !own(slot)) return;
-    if (full()) flush_now();
-    Scratch& sc = p->fused ? p->fused_scratch() : cur->sc[cur->njobs + (int)pend.size()];
-    pend.push_back(PendingOpen{poly, lo, len, zp, fr >= 0 ? &frout[fr] : nullptr, &slots[slot], slot, &sc});
-    if (fr >= 0 && first_piece(slot)) p->fr_valid[(size_t)fr] = 1;
-  };
-  Fr* sy = p->sy0.as<Fr>();
-  // ---- all polynomials first (small kernels; queued behind a bucket accumulation they would each wait ~0.5 ms for CUs) ----
-  // zkP_1: r'(X,1)                                                                   Protocol.hs:58-63
-  // (a polynomial is built in the pass that first knows its challenge -- every pass when phases == PH_ALL -- and stays in the
-  // handle's buffers for the later passes of sonic_prover_prove_fs: r(X,1) from the blinders, s(X,y) and t(X,y) from y, s(X,y_j)
-  // from y_j, s(u,Y) from u)
-  if (p->pend_asg[0]) {
-    upload_fr_mont(ms, p->aL, p->pend_asg[0], n, flags + 1);
-    upload_fr_mont(ms, p->aR, p->pend_asg[1], n, flags + 1);
-    upload_fr_mont(ms, p->aO, p->pend_asg[2], n, flags + 1);
-    p->pend_asg[0] = nullptr;
-    p->have_witness_digest = false;
-  }
-  if ((need_g0 || need_T) && on(PH_R)) build_r1_enqueue(ms, p->aL.as<Fr>(), p->aR.as<Fr>(), p->aO.as<Fr>(), S, n, r1);
-  ready(p->ev_r1);
-  // the group that needs nothing but r(X,1): queued here, ahead of the other polynomials, when this call's circuit is still on the host
-  bool g0_queued = false;
-  auto group0 = [&] {
-    if (!need_g0 || g0_queued) return;
-    g0_queued = true;
-    begin_group(p->ev_r1, /*on_ts=*/true);
-    commit(PH_R, r1, r_lo, r_len, n, 0);                                               // R            :63
-    open(PH_OPEN, r1, r_lo, r_len, pZ, 0, 2);                                          // (a, W_a)     :79
-    open(PH_OPEN, r1, r_lo, r_len, pYZ, 1, 3);                                         // (b, W_b)     :80
-    flush_group(last_group == 0);
-  };
-  if (p->few_streams && p->fused) group0();          // (its openings go on the transform's stream, ahead of the product's kernels)
-  if (p->pend.set) {
-    group0();
-    prover_upload_circuit(p, ms, flags + 1);
-  }
-  // s(X,y)                                                                           Protocol.hs:69-70
-  if (need_T && on(PH_T)) {
-    poly_scale_powers_enqueue(ms, nullptr, pw, 2 * n + Q + 1, -n, pY, pY + 1);       // y^e, e in [-n, n+Q]
-    s_of_y_of(p, ms, pw, sy);
-    HIP_OK(hipMemcpyAsync(p->kpow.p, pw + (2 * n + 1), sizeof(Fr) * Q, hipMemcpyDeviceToDevice, ms));   // y^{n+1..n+Q} for k(y); pw is reused below
-  }
-  ready(p->ev_sy0);
-  if (need_T && on(PH_T)) {
-    // zkP_2: t(X,y) = r(X,1) * (r(X,y) + s(X,y)) - k(y), on its own stream          Protocol.hs:69-73, Constraints.hs:56-68
-    hipStream_t ts = p->ts;
-    HIP_OK(hipStreamWaitEvent(ts, p->ev_sy0, 0));          // ev_sy0 follows ev_r1 on the main stream
-    t_operands_enqueue(ts, r1, r_len, r_lo, sy, s_lo - r_lo, s_len, pY, fa, fb, M);     // fa = r(X,1), fb = r(X,y) + s(X,y), zero-padded
-    ntt_forward_enqueue(ts, *p->ntt, fa, p->log2m);
-    ntt_forward_enqueue(ts, *p->ntt, fb, p->log2m);
-    ntt_inverse_of_product_enqueue(ts, *p->ntt, fa, fb, p->log2m);
-    sub_k_of_y_enqueue(ts, fa + (0 - t_lo), cs, p->kpow.as<Fr>(), Q, flags, 0);
-    HIP_OK(hipEventRecord(p->ev_t, ts));
-  }
-  Fr* t = fa;                                                                         // exponents [t_lo, t_lo + t_len)
-  // hscProve: s(X, y_j), s(u, Y)                                                     Signature.hs:41,51
-  for (long j = 0; j < Q; j++) {
-    if (need_j[(size_t)j] && on(PH_HSCS)) {
-      poly_scale_powers_enqueue(ms, nullptr, pw, 2 * n + Q + 1, -n, pYj(j), pYj(j) + 1);
-      // a prepared handle that has only a piece of S_j's diagonal part does not read s(X, y_j) itself
-      if (!p->prepared || own(6 + 2 * j) || own(5 + 2 * Q + 2 * j)) s_of_y_of(p, ms, pw, p->syj[j].as<Fr>());
-      if (p->prepared && own(5 + 2 * j)) s_diag_part_enqueue(ms, pw, n, Q, p->diag[j].as<Fr>(), p->yq[j].as<Fr>());
-    }
-    ready(p->ev_syj[j]);
-  }
-  const long u_lo = -n, u_len = 2 * n + Q + 1;
-  if (need_su && on(PH_HSCW)) {
-    poly_scale_powers_enqueue(ms, nullptr, pw, 3 * n + 1, -n, pU, pU + 1);           // u^e, e in [-n, 2n]
-    s_of_u_of(p, ms, pw, su);
-  }
-  ready(p->ev_su);
-
-  // ---- the MSM groups, largest first where its input allows ----
-  Lane& lane_t = p->t_lane(p->ev_sy0);
-  if (on(PH_OPEN) && first_piece(4)) {                                                 // s(z,y)       :83  (reported by the rank that starts W_t)
-    // (few_streams: on the main stream, not behind the transform on its stream -- the evaluation needs s(X,y) only, and everything queued
-    // behind the transform is on the longest dependent chain of a proof)
-    Lane& le = p->few_streams ? p->main_lane : lane_t;
-    Scratch& es = le.sc[MSM_MAX_JOBS - 1];
-    es.reserve(s_len);
-    es.scan.ensure(sizeof(Fr) * (s_len / 1024 + 2));
-    OpenBatch eb;
-    memset(&eb, 0, sizeof eb);
-    eb.k = 1; eb.poly[0] = sy; eb.D[0] = es.D.as<Fr>(); eb.q[0] = es.q.as<Fr>(); eb.tiles[0] = es.scan.as<Fr>(); eb.zpair[0] = pZ; eb.fz[0] = &frout[2];
-    open_batch_enqueue(le.st, eb, s_lo, s_len, /*quotient=*/false);
-    p->fr_valid[2] = 1;
-  }
-  group0();
-  for (long j = 0; j < Q; j++) {
-    if (!need_j[(size_t)j]) continue;
-    Fr* syj = p->syj[j].as<Fr>();
-    begin_group(p->ev_syj[j]);
-    if (p->prepared) commit(PH_HSCS, p->diag[j].as<Fr>(), n + 1, n, d, 5 + 2 * j);   // S_j (diagonal part)   Signature.hs:42
-    else if (p->runs_on) commit_runs(PH_HSCS, syj, s_lo, s_len, d, 5 + 2 * j, j);    // S_j, runs through the running sums   :42
-    else commit(PH_HSCS, syj, s_lo, s_len, d, 5 + 2 * j);                            // S_j                   :42
-    open(PH_HSCS, syj, s_lo, s_len, pZj(j), 3 + j, 6 + 2 * j);                       // (s_j, W_j)    :43
-    open(PH_HSCW, syj, s_lo, s_len, pU, -1, 5 + 2 * Q + 2 * j);                      // W'_j          :54
-    flush_group(last_group == 1 && j == last_j);
-    if (p->prepared && on(PH_HSCS) && first_piece(5 + 2 * j)) {                       // sum_q y_j^{n+q} C_q, Q-term MSM
-      Lane* ln = cur;
-      p->slot_ran[(size_t)((7 + 4 * Q) + j)] = 1;
-      auto small = [&, ln, j] {
-        msm_enqueue(ln->st, ln->ws, p->cq_tab.p ? msm_plan_tables(Q, CQ_TAB_C, CQ_TAB_W, Q) : msm_plan(Q),
-                    PointArray::packed(p->cq_tab.p ? p->cq_tab.as<G1Affine>() : p->cq.as<G1Affine>()), p->yq[j].as<Fr>(), Q, true, &slots[(7 + 4 * Q) + j]);
-      };
-      if (cur->njobs == 0) small(); else after_flush.push_back(small);
-    }
-  }
-  if (need_su) {
-    begin_group(p->ev_su);
-    if (p->sym_on && on(PH_HSCW) && own(6 + 4 * Q)) {                                  // C             :52, over the symmetric sums
-      if (full()) flush_now();
-      MsmJob job = commit_job(cur->st, srs, su, u_lo, u_len, d, &slots[6 + 4 * Q], flags);      // (the index checks of the whole range)
-      job.points = srs_sym(srs) + 1; job.scalars = su + (n + 1); job.n = n; job.table_stride = d + 1;      // exponents 1 .. n: c_i (A[i] + A[-i])
-      p->slot_ran[(size_t)(6 + 4 * Q)] = 1;
-      cur->jobs[cur->njobs++] = job;
-      p->slot_ran[(size_t)(7 + 5 * Q)] = 1;                                                     // exponents n+1 .. n+Q, on the main stream (su was built there)
-      auto c_tail = [&, su, d, n, Q, slots, ms] { msm_enqueue(ms, p->runs_ws, msm_plan(Q), srs_basis(srs, 1) + (d + n + 1), su + (2 * n + 1), Q, true, &slots[7 + 5 * Q]); };
-      if (p->fused) deferred_small.push_back(c_tail); else c_tail();
-    } else
-      commit(PH_HSCW, su, u_lo, u_len, d, 6 + 4 * Q);                                // C             :52
-    for (long j = 0; j < Q; j++) open(PH_HSCW, su, u_lo, u_len, pYj(j), 3 + Q + j, 6 + 2 * Q + 2 * j);   // (s'_j, Q_j) :55
-    open(PH_QV, su, u_lo, u_len, pV, -1, 5 + 4 * Q);                                 // Q_v           :63
-  }
-  flush_now(last_group == 2 && sh != nullptr);
-  static const bool split_t = getenv("SONIC_FUSED_SPLIT_T") && atoi(getenv("SONIC_FUSED_SPLIT_T")) != 0;
-  auto t_group = [&](bool own_chain) {
-    if (on(PH_T) && lane_t.st != p->ts) HIP_OK(hipStreamWaitEvent(lane_t.st, p->ev_t, 0));
-    cur = &lane_t; cur->njobs = 0;
-    commit(PH_T, t, t_lo, t_len, d, 1);                                                // T            Protocol.hs:73
-    open(PH_OPEN, t, t_lo, t_len, pZ, -1, 4);                                          // W_t          :81
-    if (p->fused && own_chain) {
-      issue_opens();
-      if (cur->njobs > 0) {
-        long nmax = 0;
-        for (int j = 0; j < cur->njobs; j++) nmax = std::max(nmax, cur->jobs[j].n);
-        MsmPlan pl = srs_msm_plan(srs, nmax);
-        pl.tree = true;
-        msm_enqueue_batch(cur->st, cur->ws, pl, cur->jobs, cur->njobs, true);
-        cur->njobs = 0;
-      }
-    } else
-      flush_group(true);
-  };
-  if (need_T && !(p->fused && split_t)) t_group(false);
-  if (p->fused && !p->fused_jobs.empty()) {
-    // the proof's chain(s): every lane has queued the openings of its groups by now; chunks of at most MSM_MAX_JOBS jobs (one chunk up to
-    // Q = 2) on the two chain streams in turn so that two chunks overlap like two groups did
-    for (int i = 0; i < p->n_lanes; i++) HIP_OK(hipEventRecord(p->lanes[i].prep, p->lanes[i].st));
-    if (p->few_streams) { HIP_OK(hipEventRecord(p->main_lane.prep, ms)); if (need_T || g0_queued) HIP_OK(hipEventRecord(p->ts_lane.prep, p->ts)); }
-    const int total = (int)p->fused_jobs.size();
-    const int nchunks = (total + MSM_MAX_JOBS - 1) / MSM_MAX_JOBS, per = (total + nchunks - 1) / nchunks;
-    for (int c = 0, at = 0; c < nchunks; c++, at += per) {
-      Lane& cl = p->chain[c & 1];
-      if (c < 2) {
-        for (int i = 0; i < p->n_lanes; i++) HIP_OK(hipStreamWaitEvent(cl.st, p->lanes[i].prep, 0));
-        if (p->few_streams) { HIP_OK(hipStreamWaitEvent(cl.st, p->main_lane.prep, 0)); if (need_T || g0_queued) HIP_OK(hipStreamWaitEvent(cl.st, p->ts_lane.prep, 0)); }
-      }
-      const int k = std::min(per, total - at);
-      long nmax = 0;
-      for (int j = 0; j < k; j++) nmax = std::max(nmax, p->fused_jobs[(size_t)(at + j)].n);
-      MsmPlan pl = srs_msm_plan(srs, nmax);
-      pl.tree = true;
-      pl.accum_block = 128;      // (measured for this chain, n = 2^16 streamed: 128 lanes 9.19-9.27 ms, 256 9.46-9.49, 512 9.42-9.46)
-      msm_enqueue_batch(cl.st, cl.ws, pl, &p->fused_jobs[(size_t)at], k, true);
-    }
-    p->fused_jobs.clear();
-  }
-  // (SONIC_FUSED_SPLIT_T=1, measured and not the default: T and W_t -- 14n of a proof's 45n terms, and the group whose polynomial is ready
-  // last -- as a SECOND chain on the stream that made the polynomial, so that the chain of the other thirteen MSMs need not wait for the
-  // product.  One at a time it gains 1-3 %; streamed it loses 3-10 % at n = 2^14 .. 2^16: two sorts, two accumulation tails and two
-  // butterflies per proof; profiles/r06_ab_small_final.txt)
-  if (need_T && p->fused && split_t) t_group(true);
-  for (auto& f : deferred_small) f();
-  deferred_small.clear();
-  for (int i = 0; i < p->n_lanes; i++) { Lane& l = p->lanes[i]; HIP_OK(hipEventRecord(l.done, l.st)); HIP_OK(hipStreamWaitEvent(ms, l.done, 0)); }
-  if (p->fused) for (auto& l : p->chain) if (l.st) { HIP_OK(hipEventRecord(l.done, l.st)); HIP_OK(hipStreamWaitEvent(ms, l.done, 0)); }
-  if (p->few_streams && (need_T || g0_queued)) { HIP_OK(hipEventRecord(p->ts_lane.done, p->ts_lane.st)); HIP_OK(hipStreamWaitEvent(ms, p->ts_lane.done, 0)); }
-  Fr* frstd = p->frstd.as<Fr>();
-  HIP_OK(hipMemcpyAsync(frstd, frout, sizeof(Fr) * (3 + 2 * Q), hipMemcpyDeviceToDevice, ms));
-  fr_from_mont_enqueue(ms, frstd, 3 + 2 * Q);
-  HIP_OK(hipMemcpyAsync(p->h_slots, slots, sizeof(MsmSlot) * KS, hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(p->h_fr, frstd, 32 * (3 + 2 * Q), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(p->h_flags, flags, 8, hipMemcpyDeviceToHost, st));
-  }  // !replay
+  if (!replay) enqueue_proof(p);
   if (capturing) {
     hipGraph_t g = nullptr;
     capture.active = false;
@@ -825,21 +896,6 @@ static int prove_enqueue(sonic_prover_t* p, const uint8_t* transcript) {
   API_END
 }
 
-// canonical proof bytes from the 7 + 4Q points (slot order) and the 3 + 2Q evaluations: record order of `Proof` (Protocol.hs:28-38)
-// then `HscProof` (Signature.hs:22-29)
-static void proof_layout(long Q, const uint8_t* pts, const uint8_t* frs, const uint8_t* transcript, uint8_t* out_proof) {
-  auto G = [&](long i) { return pts + 96 * (size_t)i; };
-  auto F = [&](long i) { return frs + 32 * (size_t)i; };
-  uint8_t* o = out_proof;
-  auto putG = [&](long i) { memcpy(o, G(i), 96); o += 96; };
-  auto putF = [&](const uint8_t* s) { memcpy(o, s, 32); o += 32; };
-  putG(0); putG(1); putF(F(0)); putG(2); putF(F(1)); putG(3); putG(4); putF(F(2));      // R T a Wa b Wb Wt s
-  for (long j = 0; j < Q; j++) { putG(5 + 2 * j); putF(F(3 + j)); putG(6 + 2 * j); }     // hscS
-  for (long j = 0; j < Q; j++) { putF(F(3 + Q + j)); putG(5 + 2 * Q + 2 * j); putG(6 + 2 * Q + 2 * j); }   // hscW
-  putG(5 + 4 * Q); putG(6 + 4 * Q);                                                      // Qv, C
-  putF(transcript + 32 * (6 + 2 * Q)); putF(transcript + 32 * (7 + 2 * Q));              // u, v
-}
-
 // ---- one proof over several GPUs: the share a rank reports and how the shares become the proof ---------------------------------
 // share = header (32 B) | K x {lo, hi} pieces (8 B each) | K x 192-B un-normalised partial sums (infinity where the rank has no
 // piece) | (3 + 2Q) x 32-B evaluations a, b, s, s_j, s'_j (standard form; zeros unless reported) | (3 + 2Q) x int32 reported
@@ -847,16 +903,18 @@ namespace {
 struct ShareHeader { uint32_t magic, version; int32_t rank, world; int64_t Q; int32_t flags, plan_tag; };
 constexpr uint32_t SHARE_VERSION = 2;      // 2 (round 5): plan_tag in what was padding
 constexpr uint32_t SHARE_MAGIC = 0x48534e53u;      // "SNSH"
+G1XYZZ g1_sum(const G1XYZZ& a, const G1XYZZ& b) { return g1_add(a, b); }
 }
 extern "C" size_t sonic_proof_share_size(int64_t Q) {
-  const size_t K = (size_t)(7 + 4 * Q), F = (size_t)(3 + 2 * Q);
+  const size_t K = (size_t)ProofLayout{Q}.K(), F = (size_t)ProofLayout{Q}.F();
   return sizeof(ShareHeader) + K * 8 + K * 192 + F * 32 + F * 4;
 }
 
 static int prove_finish_share(sonic_prover_t* p, uint8_t* out_share) {
   API_BEGIN_ON(p->device)
   const long Q = p->Q;
-  const int K = (int)(7 + 4 * Q), F = (int)(3 + 2 * Q);
+  const ProofLayout L{Q};
+  const int K = (int)L.K(), F = (int)L.F();
   HIP_OK(hipStreamSynchronize(p->st));
   p->proofs_done++;
   if (getenv("SONIC_DEBUG_TIMING"))
@@ -873,14 +931,12 @@ static int prove_finish_share(sonic_prover_t* p, uint8_t* out_share) {
     if (p->share_world > 1) s = p->share.row(p->share_rank)[i];
     memcpy(o, &s.lo, 4); memcpy(o + 4, &s.hi, 4); o += 8;
   }
-  for (int i = 0; i < K; i++, o += 192) {
-    G1XYZZ sum = G1XYZZ::inf();
-    if (p->slot_ran[(size_t)i]) sum = msm_finish_host(hs[i]);
-    const int j = (i - 5) / 2;
-    if ((p->prepared || p->runs_on) && i >= 5 && i < 5 + 2 * Q && ((i - 5) & 1) == 0 && p->slot_ran[(size_t)(K + j)]) sum = g1_add(sum, msm_finish_host(hs[K + j]));
-    if (p->sym_on && i == 6 + 4 * Q && p->slot_ran[(size_t)(K + Q)]) sum = g1_add(sum, msm_finish_host(hs[K + Q]));      // C's Q-term half
-    memcpy(o, &sum, 192);
-  }
+  // (a slot that did not run in this enqueue is the empty sum here, whatever an earlier proof left in it)
+  std::vector<G1XYZZ> sums((size_t)L.slots_total());
+  for (long i = 0; i < L.slots_total(); i++) sums[(size_t)i] = p->slot_ran[(size_t)i] ? msm_finish_host(hs[i]) : G1XYZZ::inf();
+  fold_side_slots(L, p->prepared || p->runs_on, p->sym_on, sums.data(), sums.data() + K, g1_sum);
+  memcpy(o, sums.data(), 192 * (size_t)K);
+  o += 192 * (size_t)K;
   for (int i = 0; i < F; i++, o += 32) if (p->fr_valid[(size_t)i]) memcpy(o, p->h_fr + 32 * i, 32);
   for (int i = 0; i < F; i++, o += 4) { const int32_t v = p->fr_valid[(size_t)i]; memcpy(o, &v, 4); }
   API_END
@@ -891,7 +947,7 @@ static int prove_finish_share(sonic_prover_t* p, uint8_t* out_share) {
 extern "C" int sonic_proof_from_shares(int64_t Q, int world, const uint8_t* shares, const uint8_t* transcript, uint8_t* out_proof) {
   try {
   if (Q < 1 || world < 1 || !shares || !transcript || !out_proof) return SONIC_ERR_INVALID_ARG;
-  const int K = (int)(7 + 4 * Q), F = (int)(3 + 2 * Q);
+  const int K = (int)ProofLayout{Q}.K(), F = (int)ProofLayout{Q}.F();
   const size_t sz = sonic_proof_share_size(Q);
   std::vector<const uint8_t*> by_rank((size_t)world, nullptr);
   int flags = 0;
@@ -961,7 +1017,8 @@ static void finish_slots_host(const MsmSlot* hs, long K, G1XYZZ* out, int max_th
 static int prove_finish(sonic_prover_t* p, uint8_t* out_proof) {
   API_BEGIN_ON(p->device)
   const long Q = p->Q;
-  const int K = (int)(7 + 4 * Q);
+  const ProofLayout L{Q};
+  const int K = (int)L.K();
   hipStream_t st = p->st;
   const uint8_t* transcript = p->h_tr;
   const auto t_begin = p->t_begin, t_enq = p->t_enq;
@@ -981,20 +1038,20 @@ static int prove_finish(sonic_prover_t* p, uint8_t* out_proof) {
     // host tails (finish_slots_host).  One shared inversion normalises all results.
     auto t0 = std::chrono::steady_clock::now();
     std::vector<G1XYZZ> sums((size_t)K);
-    // S_j = slot 5 + 2j + slot K + j on a prepared handle (sum_q y_j^{n+q} C_q) and on one that takes the runs of equal coefficients
-    // out (their small MSM over gathered running sums: per-window sums, a Horner walk).  Slot K + j persists over the passes of
+    // S_j = its slot + its side slot on a prepared handle (sum_q y_j^{n+q} C_q) and on one that takes the runs of equal coefficients
+    // out (their small MSM over gathered running sums: per-window sums, a Horner walk).  The side slots persist over the passes of
     // sonic_prover_prove_fs: not tied to this pass's slot_ran; a slot whose MSM never ran is W = 0, the empty sum.
     const bool has_extra = p->prepared || p->runs_on;
-    std::vector<G1XYZZ> extra((size_t)(has_extra ? Q : 0));
+    std::vector<G1XYZZ> side((size_t)(Q + 1), G1XYZZ::inf());      // the sums of the side slots: the S_j's, then C's
+    const MsmSlot* hx = hs + L.S_extra(0);
     ThreadGroup th;
-    G1XYZZ extra_c = G1XYZZ::inf();                        // the Q-term half of C (per-window sums: a Horner walk, on a thread of its own)
-    if (p->sym_on) th.emplace_back([&] { extra_c = msm_finish_host(hs[K + Q]); });
-    if (has_extra && !slots_folded(hs + K, Q)) th.emplace_back([&] { finish_slots_host(hs + K, Q, extra.data(), 8); });      // the Horner walks of the extra slots beside the main thread's tails
-    else if (has_extra) finish_slots_host(hs + K, Q, extra.data(), 1);
+    // (the Q-term half of C is per-window sums: a Horner walk, on a thread of its own; so are the walks of the S_j's side slots, beside the main thread's tails)
+    if (p->sym_on) th.emplace_back([&] { side[(size_t)Q] = msm_finish_host(hs[L.C_extra()]); });
+    if (has_extra && !slots_folded(hx, Q)) th.emplace_back([&] { finish_slots_host(hx, Q, side.data(), 8); });
+    else if (has_extra) finish_slots_host(hx, Q, side.data(), 1);
     finish_slots_host(hs, K, sums.data(), 16);
     th.join();
-    for (long j = 0; has_extra && j < Q; j++) sums[(size_t)(5 + 2 * j)] = g1_add(sums[(size_t)(5 + 2 * j)], extra[(size_t)j]);
-    if (p->sym_on) sums[(size_t)(6 + 4 * Q)] = g1_add(sums[(size_t)(6 + 4 * Q)], extra_c);
+    fold_side_slots(L, has_extra, p->sym_on, sums.data(), side.data(), g1_sum);
     g1_canonical_bytes_host_batch(sums.data(), K, pts.data());
     if (timing) fprintf(stderr, "[sonic] host tails of %d MSMs: %.3f ms\n", K, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
   }
@@ -1075,8 +1132,8 @@ int sonic_prover_set_share(sonic_prover_t* p, int rank, int world) {
   p->share_world = world > 1 ? world : 0;
   p->share_planned = false;
   // slots and evaluations of pieces this rank no longer runs must not survive from an earlier proof
-  HIP_OK(hipMemsetAsync(p->slots.p, 0, sizeof(MsmSlot) * (7 + 5 * p->Q), p->st));
-  HIP_OK(hipMemsetAsync(p->frout.p, 0, sizeof(Fr) * (3 + 2 * p->Q), p->st));
+  HIP_OK(hipMemsetAsync(p->slots.p, 0, sizeof(MsmSlot) * ProofLayout{p->Q}.C_extra(), p->st));      // (all but C's side slot, which a share never fills)
+  HIP_OK(hipMemsetAsync(p->frout.p, 0, sizeof(Fr) * ProofLayout{p->Q}.F(), p->st));
   HIP_OK(hipStreamSynchronize(p->st));
   API_END
 }
@@ -1142,7 +1199,8 @@ int sonic_prover_prove_fs(sonic_prover_t* p, const uint8_t circuit_digest[32], c
   if (!rc) rc = whole_proof_only(p, "sonic_prover_prove_fs");
   if (rc) return rc;
   const long n = p->n, Q = p->Q, d = srs_d(p->srs);
-  std::vector<uint8_t> tr(32 * (size_t)(8 + 2 * Q), 0), pf(sonic_proof_size(Q));
+  const ProofLayout L{Q};
+  std::vector<uint8_t> tr(32 * (size_t)L.transcript_len(), 0), pf(sonic_proof_size(Q));
   uint8_t srs_id[32];
   if ((rc = sonic_fs_srs_id(p->srs, srs_id))) return rc;
   if (!p->have_witness_digest) {
@@ -1165,8 +1223,8 @@ int sonic_prover_prove_fs(sonic_prover_t* p, const uint8_t circuit_digest[32], c
       p->have_witness_digest = true;
     } catch (const HipFail& f) { return f.code; }
   }
-  for (long k = 0; k < 4; k++) fs_blinder(blinder_seed, circuit_digest, srs_id, p->witness_digest, (uint32_t)k, &tr[32 * k]);
-  for (long k = 4; k < 8 + 2 * Q; k++) tr[32 * k] = 1;               // not drawn yet: any invertible value (results that use it are not read)
+  for (long k = 0; k < L.n_blinders; k++) fs_blinder(blinder_seed, circuit_digest, srs_id, p->witness_digest, (uint32_t)k, &tr[32 * k]);
+  for (long k = L.n_blinders; k < L.transcript_len(); k++) tr[32 * k] = 1;               // not drawn yet: any invertible value (results that use it are not read)
   FsTranscript t;
   t.init(n, Q, d, circuit_digest, srs_id);
   auto pass = [&](int ph) {
@@ -1180,23 +1238,23 @@ int sonic_prover_prove_fs(sonic_prover_t* p, const uint8_t circuit_digest[32], c
   const uint8_t* R = pf.data(), * T = R + 96, * open = R + 192, * hscS = R + 576, * hscW = hscS + Q * 224, * Cc = hscW + Q * 224 + 96;
   if ((rc = pass(PH_R))) return rc;
   t.absorb("R", R, 96);
-  t.challenge("y", 0, &tr[32 * 4]);
+  t.challenge("y", 0, &tr[32 * L.y]);
   if ((rc = pass(PH_T))) return rc;
   t.absorb("T", T, 96);
-  t.challenge("z", 0, &tr[32 * 5]);
+  t.challenge("z", 0, &tr[32 * L.z]);
   if ((rc = pass(PH_OPEN))) return rc;
   t.absorb("open", open, 384);
-  for (long j = 0; j < Q; j++) { t.challenge("yj", (uint32_t)j, &tr[32 * (6 + j)]); t.challenge("zj", (uint32_t)j, &tr[32 * (6 + Q + j)]); }
+  for (long j = 0; j < Q; j++) { t.challenge("yj", (uint32_t)j, &tr[32 * L.y_j(j)]); t.challenge("zj", (uint32_t)j, &tr[32 * L.z_j(j)]); }
   if ((rc = pass(PH_HSCS))) return rc;
   t.absorb("hscS", hscS, (size_t)Q * 224);
-  t.challenge("u", 0, &tr[32 * (6 + 2 * Q)]);
+  t.challenge("u", 0, &tr[32 * L.u()]);
   if ((rc = pass(PH_HSCW))) return rc;
   {
     std::string w(reinterpret_cast<const char*>(Cc), 96);
     w.append(reinterpret_cast<const char*>(hscW), (size_t)Q * 224);
     t.absorb("hscW", reinterpret_cast<const uint8_t*>(w.data()), w.size());
   }
-  t.challenge("v", 0, &tr[32 * (7 + 2 * Q)]);
+  t.challenge("v", 0, &tr[32 * L.v()]);
   if ((rc = pass(PH_QV))) return rc;
   memcpy(out_proof, pf.data(), pf.size());
   if (out_transcript) memcpy(out_transcript, tr.data(), tr.size());
@@ -1294,7 +1352,7 @@ int sonic_prover_prepare(sonic_prover_t* p) {
   p->diag.resize(Q); p->yq.resize(Q);
   for (auto& b : p->diag) b.alloc(sizeof(Fr) * n);
   for (auto& b : p->yq) b.alloc(sizeof(Fr) * Q);
-  p->slots.ensure(sizeof(MsmSlot) * (7 + 5 * Q + 1));
+  p->slots.ensure(sizeof(MsmSlot) * ProofLayout{Q}.slots_total());
   p->prepared = true;
   API_END
 }

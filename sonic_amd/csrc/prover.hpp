@@ -130,8 +130,8 @@ struct sonic_prover {
   // another handle's accumulation that wait was ~1 ms per proof (config5: 99 against 113 proofs/s, profiles/r06_bench.json)
   const uint8_t* pend_asg[3] = {nullptr, nullptr, nullptr};
   // runs of equal coefficients in the S_j of a handle that is not prepared (poly.hip, k_run_tiles): per j the masked copy of s(X, y_j),
-  // the tile records and the (scalar, running-sum point) slots of the small MSM that stands for the runs; its sum lands in slot
-  // (7 + 4Q) + j, where a prepared handle keeps sum_q y_j^{n+q} C_q, and the host adds it the same way
+  // the tile records and the (scalar, running-sum point) slots of the small MSM that stands for the runs; its sum lands in the side
+  // slot S_extra(j) (proof_layout.hpp), where a prepared handle keeps sum_q y_j^{n+q} C_q, and the host adds it the same way
   // The small MSM runs on the handle's MAIN stream, which has built all polynomials by then and only waits for the lanes: behind the
   // batch of the lane that reads the masked copy its ~13 short launches and the chained sums of its per-window buckets added 0.6-1.3 ms
   // to a proof's latency; a stream of its own (two more streams per handle than the 8 hardware queues the runtime is given) cost
@@ -149,7 +149,7 @@ struct sonic_prover {
   bool circuit_has_runs = true;
   // C = commitPoly(s(u, Y)) through the SRS's symmetric sums (srs.hip, srs_build_sym): s(u, Y) has the same coefficient at Y^i and Y^-i
   // (i <= n), so n terms over A[i] + A[-i] and a Q-term MSM for Y^{n+1} .. Y^{n+Q} stand for its 2n + Q + 1 terms; the Q-term sum lands
-  // in slot 7 + 5Q and the host adds it
+  // in the side slot C_extra() and the host adds it
   bool sym_on = false;
   // Small proofs (round 6): ALL the MSMs of a proof as ONE batched kernel chain.  With 2^16 shared buckets and fewer (c <= 18: d < 2^20,
   // n <= 2^16) a group of two or three MSMs is 2048-3072 one-thread-per-bucket waves -- one round of the chip's 2048 wave slots, half
@@ -159,7 +159,8 @@ struct sonic_prover {
   // only prepare the openings (evaluation, prefix sums, quotient: they still run side by side); their jobs are collected here and run as
   // one chain of up to MSM_MAX_JOBS jobs on the t lane: one sort, ONE accumulation launch that keeps every wave slot filled until its
   // tail, one butterfly over all bucket sets.  Larger plans (2^19 buckets per set) fill the chip per group and keep the lanes
-  // (packing their groups was measured slower in round 3).  SONIC_PROVE_FUSED=0 / 1: never / whenever the plan batches.
+  // (packing their groups was measured slower in round 3).  SONIC_PROVE_FUSED=0: never; =1 is the same as unset: only handles whose
+  // plan is small (small_plan) have chain streams, so only they fuse.
   bool fused = false;
   std::vector<MsmJob> fused_jobs;
   std::vector<std::unique_ptr<Scratch>> fused_sc;      // one per opening of the proof: a quotient lives until the chain has read it
@@ -198,8 +199,8 @@ struct sonic_prover {
   SharePlan share;
   bool share_planned_prepared = false, share_planned = false;
   int32_t share_plan_tag = 0;                // hash of the plan's inputs (share header: ranks must have planned alike)
-  std::vector<uint8_t> slot_ran;             // per slot (7 + 5Q): the last enqueue queued an MSM for it
-  std::vector<uint8_t> fr_valid;             // per evaluation (3 + 2Q): the last enqueue computed it
+  std::vector<uint8_t> slot_ran;             // per slot, side slots included: the last enqueue queued an MSM for it
+  std::vector<uint8_t> fr_valid;             // per evaluation: the last enqueue computed it
   uint8_t witness_digest[32] = {0};          // SHA-256 of the assignment (Fiat-Shamir blinders, fs.hpp), made on first use
   bool have_witness_digest = false;
   // Lane N_LANES-1 carries the t(X,y) group (the largest, ready last); the other groups alternate over the rest, which

@@ -14,6 +14,7 @@
 #include <stdlib.h>
 #include <algorithm>
 #include <vector>
+#include "proof_layout.hpp"
 
 namespace sonic {
 
@@ -42,7 +43,7 @@ struct ShareCosts {
 struct SharePlan {
   long n = 0, Q = 0;
   int world = 1;
-  int K = 0;                                   // 7 + 4Q slots (proof order of prove.hip: R, T, Wa, Wb, Wt, [S_j, W_j], [W'_j, Q_j], Qv, C)
+  int K = 0;                                   // the main MSM slots, in the order of proof_layout.hpp
   std::vector<SlotShare> rows;                 // world x K
   std::vector<uint32_t> polys;                 // per rank: POLY_* it has to build
   std::vector<double> cost;                    // per rank, modelled (terms)
@@ -58,19 +59,20 @@ struct ShareItem { int slot; long terms; uint32_t polys; };
 inline std::vector<ShareItem> share_line(long n, long Q, bool prepared) {
   std::vector<ShareItem> it;
   auto pj = [](long j) { return (uint32_t)POLY_SYJ0 << (j < 27 ? j : 27); };
-  it.push_back({1, 7 * n + 9, POLY_R1 | POLY_SY0 | POLY_T});                       // T
-  it.push_back({4, 7 * n + 8, POLY_R1 | POLY_SY0 | POLY_T});                       // W_t
-  it.push_back({0, 3 * n + 4, POLY_R1});                                           // R (the X^0 coefficient of r is zero)
-  it.push_back({2, 3 * n + 4, POLY_R1});                                           // W_a
-  it.push_back({3, 3 * n + 4, POLY_R1});                                           // W_b
+  const ProofLayout L{Q};
+  it.push_back({(int)L.T, 7 * n + 9, POLY_R1 | POLY_SY0 | POLY_T});                // T
+  it.push_back({(int)L.Wt, 7 * n + 8, POLY_R1 | POLY_SY0 | POLY_T});               // W_t
+  it.push_back({(int)L.R, 3 * n + 4, POLY_R1});                                    // R (the X^0 coefficient of r is zero)
+  it.push_back({(int)L.Wa, 3 * n + 4, POLY_R1});                                   // W_a
+  it.push_back({(int)L.Wb, 3 * n + 4, POLY_R1});                                   // W_b
   for (long j = 0; j < Q; j++) {
-    it.push_back({(int)(5 + 2 * j), prepared ? n : 3 * n + 1, pj(j)});             // S_j
-    it.push_back({(int)(6 + 2 * j), 3 * n, pj(j)});                                // W_j
-    it.push_back({(int)(5 + 2 * Q + 2 * j), 3 * n, pj(j)});                        // W'_j
+    it.push_back({(int)L.S(j), prepared ? n : 3 * n + 1, pj(j)});                  // S_j
+    it.push_back({(int)L.W(j), 3 * n, pj(j)});                                     // W_j
+    it.push_back({(int)L.Wp(j), 3 * n, pj(j)});                                    // W'_j
   }
-  it.push_back({(int)(6 + 4 * Q), 2 * n + Q + 1, POLY_SU});                        // C
-  for (long j = 0; j < Q; j++) it.push_back({(int)(6 + 2 * Q + 2 * j), 2 * n + Q, POLY_SU});   // Q_j
-  it.push_back({(int)(5 + 4 * Q), 2 * n + Q, POLY_SU});                            // Q_v
+  it.push_back({(int)L.C(), 2 * n + Q + 1, POLY_SU});                              // C
+  for (long j = 0; j < Q; j++) it.push_back({(int)L.Qj(j), 2 * n + Q, POLY_SU});   // Q_j
+  it.push_back({(int)L.Qv(), 2 * n + Q, POLY_SU});                                 // Q_v
   return it;
 }
 
@@ -121,7 +123,7 @@ inline int share_fill(const std::vector<ShareItem>& line, long n, double job_fix
 // full additions against W additions per term)
 inline SharePlan share_plan(long n, long Q, bool prepared, int world, long NB, int W, const ShareCosts& c = ShareCosts()) {
   SharePlan pl;
-  pl.n = n; pl.Q = Q; pl.world = world; pl.K = (int)(7 + 4 * Q);
+  pl.n = n; pl.Q = Q; pl.world = world; pl.K = (int)ProofLayout{Q}.K();
   pl.rows.assign((size_t)world * pl.K, SlotShare());
   pl.polys.assign((size_t)world, 0);
   pl.cost.assign((size_t)world, 0.0);
