@@ -48,7 +48,7 @@ module Sonic.HIP
     -- * Sonic.CommitmentScheme
   , commitPoly, openPoly, pcV
     -- * Sonic.Protocol
-  , prove, proveWithTranscript, verify, decodeProof, encodeProof
+  , prove, proveWithTranscript, verify, decodeProof, encodeProof, proofToCompressed, proofFromCompressed
   , proveWithTranscriptDense, verifyDense, fsCircuitDigest, verifyFs
     -- * Sonic.Signature
   , hscProve, hscVerify, decodeHscProof, encodeHscProof
@@ -113,6 +113,11 @@ foreign import ccall safe   "sonic_prove_csr"         c_prove_csr        :: Ptr 
 foreign import ccall safe   "sonic_verify_csr"        c_verify_csr       :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> IO CInt
 foreign import ccall safe   "sonic_fs_circuit_digest_csr" c_fs_digest_csr :: Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_verify_fs_csr"     c_verify_fs_csr    :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> IO CInt
+
+-- compressed encodings (ABI 7, additions): one proof's re-encoding on the host, no device needed
+foreign import ccall safe   "sonic_proof_size_compressed" c_proof_size_z :: Int64 -> IO CSize
+foreign import ccall safe   "sonic_proof_compress"    c_proof_compress   :: Int64 -> Ptr Word8 -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_proof_decompress"  c_proof_decompress :: Int64 -> Ptr Word8 -> Ptr Word8 -> IO CInt
 
 foreign import ccall unsafe "sonic_hsc_proof_size"    c_hsc_proof_size   :: Int64 -> IO CSize
 foreign import ccall safe   "sonic_hsc_prove_poly"    c_hsc_prove_poly   :: Ptr SrsHandle -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> IO CInt
@@ -395,6 +400,26 @@ encodeProof :: Proof -> ByteString
 encodeProof Proof{..} = BS.concat
   [ g1ToBytes prR, g1ToBytes prT, frToBytes prA, g1ToBytes prWa, frToBytes prB, g1ToBytes prWb, g1ToBytes prWt, frToBytes prS
   , encodeHscProof prHscProof ]
+
+-- | the proof in the compressed wire format of other BLS12-381 libraries (include/sonic_hip.h, "Compressed encodings"): every point as
+--   its 48 bytes, the field elements untouched -- (7 + 4Q) * 48 + (5 + 2Q) * 32 bytes.  The points are validated; a proof the verifier
+--   would refuse as malformed panics here like every other refused input.
+proofToCompressed :: Proof -> ByteString
+proofToCompressed proof = unsafePerformIO $ do
+  let q = fromIntegral (length (hscS (prHscProof proof))) :: Int64
+  sz <- fromIntegral <$> c_proof_size_z q
+  withBytes (encodeProof proof) $ \src ->
+    BSI.create sz $ \out -> check =<< c_proof_compress q src out
+
+-- | the inverse, for a proof of Q linear constraints: malformed, off-curve and out-of-subgroup points and non-canonical field elements panic
+proofFromCompressed :: Int -> ByteString -> Proof
+proofFromCompressed q bytes = unsafePerformIO $ do
+  want <- fromIntegral <$> c_proof_size_z (fromIntegral q)
+  when (BS.length bytes /= want) $ panic ("proofFromCompressed: expected " <> show want <> " bytes, got " <> show (BS.length bytes))
+  sz <- fromIntegral <$> c_proof_size (fromIntegral q)
+  raw <- withBytes bytes $ \src ->
+    BSI.create sz $ \out -> check =<< c_proof_decompress (fromIntegral q) src out
+  pure (decodeProof q raw)
 
 -- ---------------------------------------------------------------------------------------------------------------------
 -- Sonic.Protocol

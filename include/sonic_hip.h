@@ -94,7 +94,9 @@ typedef struct sonic_verifier sonic_verifier_t;
  * 7 = round 7 (additions only: gate weights as CSR -- sonic_prover_new_csr, sonic_prove_csr, sonic_fs_circuit_digest_csr,
  * sonic_verify_csr, sonic_verify_fs_csr); still 7, additions only: the batched verifier -- sonic_verifier_new[_csr], sonic_verifier_free,
  * sonic_verifier_device, sonic_verifier_verify_batch, sonic_verifier_verify_fs_batch, sonic_verifier_eval_s, sonic_g1_validate,
- * sonic_verify_batch_randomizers */
+ * sonic_verify_batch_randomizers; still 7, additions only: the compressed encodings -- sonic_g1_compress, sonic_g1_decompress,
+ * sonic_g2_compress, sonic_g2_decompress, sonic_proof_size_compressed, sonic_proof_compress, sonic_proof_decompress,
+ * sonic_verifier_verify_batch_z, sonic_verifier_verify_fs_batch_z, sonic_srs_save_compressed */
 int sonic_abi_version(void);
 int sonic_init(int device_ordinal);                 /* choose the DEFAULT GPU (first call wins) and make it the thread's HIP device; idempotent */
 int sonic_device_count(int* out);                   /* GPUs this process can see; SONIC_ERR_NO_DEVICE (and 0) without one */
@@ -158,8 +160,15 @@ int sonic_srs_set_g2_points(sonic_srs_t* srs, const uint8_t* basis0, const uint8
 int sonic_srs_save(const sonic_srs_t* srs, const char* path, int with_g2);
 /* 1 if the handle holds the G2 half or can still generate it (made by sonic_srs_new and not yet used), else 0 */
 int sonic_srs_has_g2(const sonic_srs_t* srs);
+/* sonic_srs_load[_on] takes either container, told apart by the magic: the one above, or the compressed one below */
 int sonic_srs_load(const char* path, sonic_srs_t** out);
 int sonic_srs_load_on(int device, const char* path, sonic_srs_t** out);
+/* the compressed container, half the size: "SONICSRZ", u32 version = 1, u32 flags (bit 0: G2 half present), i64 d, the two G1 bases as
+ * (2d+1) x 48 bytes each, then -- with_g2 as for sonic_srs_save -- the two G2 bases as (2d+1) x 96 bytes each, every point in the
+ * compressed encoding ("Compressed encodings" below); slot e = 0 of basis 1 (the omitted g^alpha) is the encoding of infinity.  Loading
+ * decompresses on the GPU and then validates exactly as the uncompressed container's load does.  A container of its own rather than a
+ * version 3 of SONICSRS, so that every reader of that format keeps refusing what it does not know. */
+int sonic_srs_save_compressed(const sonic_srs_t* srs, const char* path, int with_g2);
 
 /* ---- Sonic.CommitmentScheme ---- */
 /* commitPoly :: SRS -> Int -> VLaurent Fr -> G1  (CommitmentScheme.hs:20-33) */
@@ -444,6 +453,45 @@ int sonic_verifier_eval_s(sonic_verifier_t* v, int64_t K, const uint8_t* uv, uin
 int sonic_g1_validate(const uint8_t* points, int64_t n, uint8_t* flags);
 /* host only, no device: rho_0 .. rho_{count-1} of a batch with digest D (out: count x 16 bytes, little-endian) */
 int sonic_verify_batch_randomizers(const uint8_t seed[32], const uint8_t batch_digest[32], int64_t count, uint8_t* out);
+
+/* ---- Compressed encodings ----
+ * The compressed form of the Zcash / IETF pairing-friendly-curves serialization, the default wire format of other BLS12-381 libraries.
+ * Every existing entry point keeps its 96- / 192-byte little-endian encodings; these convert, and the `_z` verifier calls and the
+ * compressed SRS container consume the compressed form directly.
+ *
+ * G1, 48 bytes: x as a 381-bit BIG-endian integer, three flag bits in byte 0:
+ *   0x80  compression bit, always set (clear: malformed)
+ *   0x40  infinity bit: infinity is exactly 0xc0 followed by 47 zero bytes (any other pattern with 0x40 set: malformed)
+ *   0x20  sign bit: 1 iff y > (q - 1)/2 as an integer
+ * Malformed also when, the flags masked, x >= q.  "Not on the curve" when x^3 + 4 is not a square.
+ * G2, 96 bytes: x.c1 first, 48 big-endian bytes carrying the flags, then x.c0, 48 big-endian bytes (its three top bits zero).  Sign bit:
+ * y.c1 > (q - 1)/2 when y.c1 != 0, otherwise y.c0 > (q - 1)/2; infinity and compression bits as for G1.  The uncompressed side is the
+ * 192-byte layout of sonic_srs_get_g2_points: x.c0 || x.c1 || y.c0 || y.c1, little-endian.
+ * The G1 generator is 97f1d3a7 3197d794 2695638c 4fa9ac0f c3688c4f 9774b905 a14e3a3f 171bac58 6c55e83f f97a1aef fb3af00a db22c6bb.
+ *
+ * Bulk conversion on the GPU, one thread per point; n = 0 is SONIC_OK.  decompress: flags[i] = 0 for an accepted point, otherwise the error
+ * bits of the SRS loaders -- 1 malformed, 2 not on the curve, 4 outside the order-r subgroup (tested only when check_subgroup != 0) -- and
+ * the refused point is written as infinity (zeros); the call returns SONIC_OK for well-formed arguments whatever the verdicts are, unless
+ * flags == NULL: then the first refused point makes it SONIC_ERR_BAD_ENCODING.  compress: g1 input is validated as sonic_g1_validate does,
+ * g2 input as sonic_srs_set_g2_points does (infinity allowed); a refused point -> SONIC_ERR_BAD_ENCODING. */
+int sonic_g1_compress(const uint8_t* points96, int64_t n, uint8_t* out48);
+int sonic_g1_decompress(const uint8_t* in48, int64_t n, int check_subgroup, uint8_t* out96, uint8_t* flags);
+int sonic_g2_compress(const uint8_t* points192, int64_t n, uint8_t* out96);
+int sonic_g2_decompress(const uint8_t* in96, int64_t n, int check_subgroup, uint8_t* out192, uint8_t* flags);
+/* one proof, on the host, no device needed.  A compressed proof is the proof's record order with every 96-byte point replaced by its 48
+ * bytes and the field elements untouched: (7 + 4Q) * 48 + (5 + 2Q) * 32 bytes.  compress validates the points as sonic_verify does
+ * (canonical, on the curve, in the subgroup); decompress refuses a malformed, off-curve or out-of-subgroup point and a non-canonical field
+ * element: SONIC_ERR_BAD_ENCODING either way. */
+size_t sonic_proof_size_compressed(int64_t Q);
+int sonic_proof_compress(int64_t Q, const uint8_t* proof, uint8_t* out);
+int sonic_proof_decompress(int64_t Q, const uint8_t* proof_z, uint8_t* out_proof);
+/* the batched verifier over K compressed proofs (K x sonic_proof_size_compressed(Q) bytes): decompression is the validation stage on the
+ * GPU, and everything else -- the batch digest D, the Fiat-Shamir challenges, the checks -- reads the uncompressed bytes rebuilt from it.
+ * A compressed proof is the same proof: for any proofs p and seed, verify_batch_z(compress(p)) gives the all_accepted and each of
+ * verify_batch(p).  A malformed or off-curve compressed point rejects its own proof and changes no other verdict. */
+int sonic_verifier_verify_batch_z(sonic_verifier_t* v, int64_t K, const uint8_t* proofs_z, const uint8_t* challenges, const uint8_t seed[32],
+                                  int* all_accepted, uint8_t* each);
+int sonic_verifier_verify_fs_batch_z(sonic_verifier_t* v, int64_t K, const uint8_t* proofs_z, const uint8_t seed[32], int* all_accepted, uint8_t* each);
 
 /* ---- device memory for callers without a HIP binding ---- */
 int sonic_dev_alloc(size_t bytes, void** out);                       /* on the default device */

@@ -145,6 +145,15 @@ def lib() -> C.CDLL:
         "sonic_verifier_eval_s": [vp, i64, vp, vp],
         "sonic_g1_validate": [vp, i64, vp],
         "sonic_verify_batch_randomizers": [cp, cp, i64, vp],
+        "sonic_g1_compress": [vp, i64, vp],
+        "sonic_g1_decompress": [vp, i64, i32, vp, vp],
+        "sonic_g2_compress": [vp, i64, vp],
+        "sonic_g2_decompress": [vp, i64, i32, vp, vp],
+        "sonic_proof_compress": [i64, cp, cp],
+        "sonic_proof_decompress": [i64, cp, cp],
+        "sonic_verifier_verify_batch_z": [vp, i64, vp, vp, cp, C.POINTER(i32), vp],
+        "sonic_verifier_verify_fs_batch_z": [vp, i64, vp, cp, C.POINTER(i32), vp],
+        "sonic_srs_save_compressed": [vp, cp, i32],
         "sonic_dev_alloc": [C.c_size_t, C.POINTER(vp)],
         "sonic_dev_free": [vp],
         "sonic_dev_upload": [vp, vp, C.c_size_t],
@@ -173,6 +182,8 @@ def lib() -> C.CDLL:
     L.sonic_srs_d.restype = i64
     L.sonic_proof_size.argtypes = [i64]
     L.sonic_proof_size.restype = C.c_size_t
+    L.sonic_proof_size_compressed.argtypes = [i64]
+    L.sonic_proof_size_compressed.restype = C.c_size_t
     L.sonic_hsc_proof_size.argtypes = [i64]
     L.sonic_hsc_proof_size.restype = C.c_size_t
     L.sonic_proof_share_size.argtypes = [i64]
@@ -228,6 +239,8 @@ EXPORTED = [
     "sonic_prover_new_csr", "sonic_prove_csr", "sonic_fs_circuit_digest_csr", "sonic_verify_csr", "sonic_verify_fs_csr",
     "sonic_verifier_new", "sonic_verifier_new_csr", "sonic_verifier_free", "sonic_verifier_device", "sonic_verifier_verify_batch", "sonic_verifier_verify_fs_batch",
     "sonic_verifier_eval_s", "sonic_g1_validate", "sonic_verify_batch_randomizers",
+    "sonic_g1_compress", "sonic_g1_decompress", "sonic_g2_compress", "sonic_g2_decompress", "sonic_proof_size_compressed", "sonic_proof_compress", "sonic_proof_decompress",
+    "sonic_verifier_verify_batch_z", "sonic_verifier_verify_fs_batch_z", "sonic_srs_save_compressed",
 ]
 
 

@@ -3,6 +3,7 @@
 #include <stdarg.h>
 #include <string.h>
 #include <condition_variable>
+#include <functional>
 #include <memory>
 #include <string>
 #include <thread>
@@ -168,17 +169,7 @@ __global__ __launch_bounds__(256) void k_points_subgroup_check(PointArray in, lo
   if (i >= n) return;
   const G1Affine p = in[i];
   if (p.is_inf()) return;
-  constexpr uint32_t rl[8] = FR_P;
-  G1XYZZ acc = G1XYZZ::from_affine(p);       // top bit (254) of r
-#pragma unroll 1
-  for (int b = 253; b >= 0; b--) {
-    acc = g1_dbl(acc);
-    uint32_t w = 0;                            // constant-index reads keep rl[] out of scratch
-#pragma unroll
-    for (int k = 0; k < 8; k++) if (k == (b >> 5)) w = rl[k];
-    if ((w >> (b & 31)) & 1u) acc = g1_add_mixed(acc, p);
-  }
-  if (!acc.is_inf()) atomicOr(err, 4);
+  if (!g1_in_subgroup(p)) atomicOr(err, 4);
 }
 __global__ __launch_bounds__(256) void k_points_to_bytes(PointArray in, uint8_t* __restrict__ out, long n) {
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -415,6 +406,24 @@ int sonic_device_sync(void) { API_BEGIN HIP_OK(hipStreamSynchronize(default_stre
 int sonic_srs_from_points(int64_t d, const uint8_t* basis0, const uint8_t* basis1, sonic_srs_t** out) {
   return sonic_srs_from_points_on(-1, d, basis0, basis1, out);
 }
+// The tail every way of filling a handle's G1 bases shares (caller-supplied points, either file container): r P = O for every point of
+// both bases, the error bits the head and the walk have collected in `err` (1 non-canonical or malformed, 2 off the curve, 4 outside the
+// subgroup, 8 infinity where none may be), then the window tables.  Takes the handle: it is deleted when the points are refused.
+static int srs_finish_g1(const char* who, hipStream_t st, sonic_srs* s, DevBuf& err, sonic_srs_t** out) {
+  const long n = 2 * s->d + 1;
+  for (int b = 0; b < 2; b++) LAUNCH(k_points_subgroup_check, ceil_div(n, 256), 256, 0, st, (PointArray)srs_basis_mut(s, b), n, err.as<int>());
+  int herr = 0;
+  HIP_OK(hipMemcpyAsync(&herr, err.p, 4, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  if (herr) {
+    delete s;
+    set_error("%s: %s", who, (herr & 1) ? "non-canonical coordinate" : (herr & 2) ? "point not on curve" : (herr & 4) ? "point outside the order-r subgroup" : "point at infinity (only the omitted g^alpha, basis 1 slot e = 0, may be empty)");
+    return SONIC_ERR_BAD_ENCODING;
+  }
+  srs_build_tables(st, s);
+  *out = s;
+  return SONIC_OK;
+}
 int sonic_srs_from_points_on(int device, int64_t d, const uint8_t* basis0, const uint8_t* basis1, sonic_srs_t** out) {
   API_BEGIN_ON(device)
   if (d < 1 || !basis0 || !basis1 || !out) { set_error("sonic_srs_from_points: bad argument"); return SONIC_ERR_INVALID_ARG; }
@@ -428,18 +437,8 @@ int sonic_srs_from_points_on(int device, int64_t d, const uint8_t* basis0, const
     HIP_OK(hipMemcpyAsync(raw.p, b ? basis1 : basis0, 96 * n, hipMemcpyHostToDevice, st));
     LAUNCH(k_points_from_bytes, ceil_div(n, 256), 256, 0, st, (const uint8_t*)raw.as<uint8_t>(), srs_basis_mut(s, b), n, err.as<int>(),
            b ? (long)d : -2L);        // basis 1 has the empty slot e = 0 (SRS.hs:38); basis 0 has none
-    LAUNCH(k_points_subgroup_check, ceil_div(n, 256), 256, 0, st, (PointArray)srs_basis_mut(s, b), n, err.as<int>());
   }
-  int herr = 0;
-  HIP_OK(hipMemcpyAsync(&herr, err.p, 4, hipMemcpyDeviceToHost, st));
-  HIP_OK(hipStreamSynchronize(st));
-  if (herr) {
-    delete s;
-    set_error("sonic_srs_from_points: %s", (herr & 1) ? "non-canonical coordinate" : (herr & 2) ? "point not on curve" : (herr & 4) ? "point outside the order-r subgroup" : "point at infinity (only the omitted g^alpha, basis 1 slot e = 0, may be empty)");
-    return SONIC_ERR_BAD_ENCODING;
-  }
-  srs_build_tables(st, s);
-  *out = s;
+  return srs_finish_g1("sonic_srs_from_points", st, s, err, out);
   API_END
 }
 
@@ -520,6 +519,23 @@ int sonic_srs_get_g2_points(const sonic_srs_t* srs, int basis, int64_t e0, int64
   API_END
 }
 
+// the tail of both ways of attaching a G2 half (192-byte points, the compressed container): the error bits its validation has collected
+// in `err`, then the two vectors go to the handle and the trapdoor goes away
+static int srs_attach_g2(const char* who, hipStream_t st, sonic_srs_t* srs, DevBuf& err, DevBuf& h0, DevBuf& h1) {
+  int herr = 0;
+  HIP_OK(hipMemcpyAsync(&herr, err.p, 4, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  if (herr) {
+    set_error("%s: %s", who, (herr & 1) ? "non-canonical coordinate" : (herr & 2) ? "point not on the twist" : (herr & 4) ? "point outside the order-r subgroup" : "point at infinity (h^{x^e}, h^{alpha x^e} are never the identity)");
+    return SONIC_ERR_BAD_ENCODING;
+  }
+  std::lock_guard<std::mutex> g2(srs->g2_mu);
+  srs->h = std::move(h0);
+  srs->ha = std::move(h1);
+  srs->wipe_trapdoor();
+  return SONIC_OK;
+}
+
 int sonic_srs_set_g2_points(sonic_srs_t* srs, const uint8_t* basis0, const uint8_t* basis1) {
   API_BEGIN_ON(srs_device(srs))
   if (!srs || !basis0 || !basis1) return SONIC_ERR_INVALID_ARG;
@@ -532,17 +548,7 @@ int sonic_srs_set_g2_points(sonic_srs_t* srs, const uint8_t* basis0, const uint8
     HIP_OK(hipMemcpyAsync(raw.p, b ? basis1 : basis0, 192 * n, hipMemcpyHostToDevice, st));
     g2_points_from_bytes_enqueue(st, raw.as<uint8_t>(), (b ? h1 : h0).as<G2Affine>(), n, err.as<int>());
   }
-  int herr = 0;
-  HIP_OK(hipMemcpyAsync(&herr, err.p, 4, hipMemcpyDeviceToHost, st));
-  HIP_OK(hipStreamSynchronize(st));
-  if (herr) {
-    set_error("sonic_srs_set_g2_points: %s", (herr & 1) ? "non-canonical coordinate" : (herr & 2) ? "point not on the twist" : (herr & 4) ? "point outside the order-r subgroup" : "point at infinity (h^{x^e}, h^{alpha x^e} are never the identity)");
-    return SONIC_ERR_BAD_ENCODING;
-  }
-  std::lock_guard<std::mutex> g2(srs->g2_mu);
-  srs->h = std::move(h0);
-  srs->ha = std::move(h1);
-  srs->wipe_trapdoor();
+  return srs_attach_g2("sonic_srs_set_g2_points", st, srs, err, h0, h1);
   API_END
 }
 
@@ -583,10 +589,104 @@ int sonic_srs_save(const sonic_srs_t* srs, const char* path, int with_g2) {
   API_END
 }
 
+// ---- the compressed container (srs_file.hpp): "SONICSRZ" | u32 version = 1 | u32 flags | i64 d | the G1 bases as (2d+1) x 48 B | [the G2
+// bases as (2d+1) x 96 B].  Half the bytes; the half that is gone is recomputed on the device when the file is loaded.
+int sonic_srs_save_compressed(const sonic_srs_t* srs, const char* path, int with_g2) {
+  API_BEGIN_ON(srs_device(srs))
+  if (!srs || !path || with_g2 < 0 || with_g2 > 2) return SONIC_ERR_INVALID_ARG;
+  if (with_g2 == 2) with_g2 = sonic_srs_has_g2(srs) ? 1 : 0;
+  std::lock_guard<std::mutex> g(call_mutex());
+  hipStream_t st = default_stream();
+  if (with_g2) {
+    int rc = srs_ensure_g2(srs, st, "sonic_srs_save_compressed");
+    if (rc) return rc;
+  }
+  FILE* f = fopen(path, "wb");
+  if (!f) { set_error("sonic_srs_save_compressed: cannot open %s", path); return SONIC_ERR_INVALID_ARG; }
+  struct Closer { FILE* f; ~Closer() { if (f) fclose(f); } } closer{f};
+  const int64_t d = srs->d, n = 2 * d + 1, CH = 1 << 16;
+  bool ok = srs_zfile_write_header(f, d, with_g2 != 0);
+  std::vector<uint8_t> buf(96 * (size_t)CH);
+  DevBuf z(96 * (size_t)CH);
+  for (int b = 0; b < (with_g2 ? 4 : 2) && ok; b++)
+    for (int64_t i = 0; i < n && ok; i += CH) {
+      const int64_t m = n - i < CH ? n - i : CH;
+      const size_t sz = b < 2 ? 48 : 96;
+      if (b < 2) g1_compress_enqueue(st, srs->basis(b) + i, z.as<uint8_t>(), m);
+      else g2_compress_enqueue(st, (b == 3 ? srs->ha : srs->h).as<G2Affine>() + i, z.as<uint8_t>(), m);
+      HIP_OK(hipMemcpyAsync(buf.data(), z.p, sz * (size_t)m, hipMemcpyDeviceToHost, st));
+      HIP_OK(hipStreamSynchronize(st));
+      ok = fwrite(buf.data(), sz, (size_t)m, f) == (size_t)m;
+    }
+  closer.f = nullptr;
+  ok = (fclose(f) == 0) && ok;
+  if (!ok) { set_error("sonic_srs_save_compressed: write to %s failed", path); return SONIC_ERR_INVALID_ARG; }
+  API_END
+}
+
+// decompresses one vector of a compressed container on the device, in chunks, straight into its array; the verdicts and the infinity
+// rule (inf_ok: the one slot that may hold infinity, or -2) are folded into the loaders' error bits in *herr
+static void srs_zload_vector(hipStream_t st, const std::vector<uint8_t>& src, size_t zsz, long n, long inf_ok, int* herr,
+                             const std::function<void(const uint8_t*, uint8_t*, long, long)>& enqueue) {
+  const long CH = 1L << 18;
+  const long cap = n < CH ? n : CH;
+  DevBuf raw(zsz * (size_t)cap), fl((size_t)cap);
+  std::vector<uint8_t> hfl((size_t)cap);
+  for (long i = 0; i < n; i += CH) {
+    const long m = n - i < CH ? n - i : CH;
+    HIP_OK(hipMemcpyAsync(raw.p, &src[zsz * (size_t)i], zsz * (size_t)m, hipMemcpyHostToDevice, st));
+    enqueue((const uint8_t*)raw.as<uint8_t>(), fl.as<uint8_t>(), i, m);
+    HIP_OK(hipMemcpyAsync(hfl.data(), fl.p, (size_t)m, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    for (long k = 0; k < m; k++) {
+      *herr |= hfl[(size_t)k];
+      if (!hfl[(size_t)k] && (src[zsz * (size_t)(i + k)] & 0x40) && i + k != inf_ok) *herr |= 8;      // an accepted encoding of infinity
+    }
+  }
+}
+static int srs_load_compressed(const char* path, sonic_srs_t** out) {
+  SrsFile file;
+  std::string why;
+  const int frc = srs_zfile_read(path, file, why);
+  if (frc) { set_error("sonic_srs_load: %s", why.c_str()); return frc == 1 ? SONIC_ERR_INVALID_ARG : SONIC_ERR_BAD_ENCODING; }
+  std::lock_guard<std::mutex> g(call_mutex());
+  hipStream_t st = default_stream();
+  const int64_t d = file.d;
+  const long n = 2 * d + 1;
+  sonic_srs* s = srs_alloc(d);
+  DevBuf err(4);
+  int herr = 0;
+  try {
+    for (int b = 0; b < 2; b++)
+      srs_zload_vector(st, b ? file.g1 : file.g0, 48, n, b ? (long)d : -2L, &herr, [&](const uint8_t* in, uint8_t* fl, long i, long m) {
+        g1_decompress_enqueue(st, in, srs_basis_mut(s, b) + i, nullptr, fl, m, false);          // (the subgroup walk is the shared tail's)
+      });
+    HIP_OK(hipMemcpyAsync(err.p, &herr, 4, hipMemcpyHostToDevice, st));
+  } catch (...) { delete s; throw; }
+  int rc = srs_finish_g1("sonic_srs_load", st, s, err, &s);
+  if (rc) return rc;
+  if (file.has_g2()) {
+    DevBuf h0(sizeof(G2Affine) * n), h1(sizeof(G2Affine) * n);
+    herr = 0;
+    try {
+      for (int b = 0; b < 2; b++)
+        srs_zload_vector(st, b ? file.h1 : file.h0, 96, n, -2L, &herr, [&](const uint8_t* in, uint8_t* fl, long i, long m) {
+          g2_decompress_enqueue(st, in, (b ? h1 : h0).as<G2Affine>() + i, nullptr, fl, m, true);
+        });
+      HIP_OK(hipMemcpyAsync(err.p, &herr, 4, hipMemcpyHostToDevice, st));
+      rc = srs_attach_g2("sonic_srs_load", st, s, err, h0, h1);
+    } catch (...) { delete s; throw; }
+    if (rc) { delete s; return rc; }
+  }
+  *out = s;
+  return SONIC_OK;
+}
+
 int sonic_srs_load(const char* path, sonic_srs_t** out) { return sonic_srs_load_on(-1, path, out); }
 int sonic_srs_load_on(int device, const char* path, sonic_srs_t** out) {
   API_BEGIN_ON(device)
   if (!path || !out) return SONIC_ERR_INVALID_ARG;
+  if (srs_file_is_compressed(path)) return srs_load_compressed(path, out);      // by its magic; everything else is srs_file_read's to judge
   SrsFile file;
   std::string why;
   const int frc = srs_file_read(path, file, why);             // header against the real file size before anything is allocated (srs_file.hpp)

@@ -407,4 +407,35 @@ HD bool fp_is_canonical(const Fp<P>& a) {
 typedef Fp<FqParams> Fq;
 typedef Fp<FrParams> Fr;
 
+// A square root in Fq (Montgomery in, Montgomery out): q = 3 mod 4, so a^((q+1)/4) squares to a whenever a is a square; *ok says
+// whether it did.  Left-to-right square-and-multiply over the constant exponent -- ~378 squarings and ~190 products, no window table
+// (sixteen Fq values would be 192 VGPRs); the exponent is read by a constant-index limb select, which keeps it out of scratch memory.
+// Which of the two roots comes back is decided by the caller (fq_is_high).
+HD Fq fq_sqrt(const Fq& a, bool* ok) {
+  constexpr uint32_t el[FQ_LIMBS] = FQ_SQRT_EXP;
+  Fq acc = a;                                  // top bit of the exponent
+#pragma unroll 1
+  for (int b = FQ_SQRT_EXP_BITS - 2; b >= 0; b--) {
+    acc = fp_sqr(acc);
+    uint32_t wd = 0;
+#pragma unroll
+    for (int k = 0; k < FQ_LIMBS; k++) if (k == (b >> 5)) wd = el[k];
+    if ((wd >> (b & 31)) & 1u) acc = fp_mul(acc, a);
+  }
+  *ok = fp_sqr(acc) == a;
+  return acc;
+}
+
+// the sign of the compressed encodings: y > (q-1)/2 as an integer (y in standard form, below q)
+HD bool fq_is_high(const Fq& y_std) {
+  constexpr uint32_t h[FQ_LIMBS] = FQ_HALF;
+  uint64_t br = 0;                             // (q-1)/2 - y borrows iff y > (q-1)/2
+#pragma unroll
+  for (int i = 0; i < FQ_LIMBS; i++) {
+    uint64_t d = (uint64_t)h[i] - y_std.l[i] - br;
+    br = (d >> 32) & 1;
+  }
+  return br != 0;
+}
+
 }  // namespace sonic

@@ -117,6 +117,23 @@ HD G1XYZZ g1_add_mixed(const G1XYZZ& acc, const G1Affine& q) {
   return r;
 }
 
+// r P == O for a finite affine point, by the literal double-and-add over the bits of r: the membership test of every G1 input (E(Fq) has
+// cofactor points, e.g. (0, 2) of order 3).  ONE copy, shared by the kernels that validate points (k_points_subgroup_check, k_g1_validate,
+// k_g1_decompress).
+HD bool g1_in_subgroup(const G1Affine& p) {
+  constexpr uint32_t rl[8] = FR_P;
+  G1XYZZ acc = G1XYZZ::from_affine(p);       // top bit (254) of r
+#pragma unroll 1
+  for (int b = 253; b >= 0; b--) {
+    acc = g1_dbl(acc);
+    uint32_t wd = 0;                           // constant-index reads keep rl[] out of scratch
+#pragma unroll
+    for (int k = 0; k < 8; k++) if (k == (b >> 5)) wd = rl[k];
+    if ((wd >> (b & 31)) & 1u) acc = g1_add_mixed(acc, p);
+  }
+  return acc.is_inf();
+}
+
 // The same addition for the bucket walks: on the device the whole formula is one generated asm statement around ten calls of
 // the product core (mont_asm.hpp, sonic_g1_madd_asm); lanes in an exceptional position come back flagged and unchanged and are
 // redone by the general function above.

@@ -42,6 +42,32 @@ HD Fq2 f2_inv(const Fq2& a) {
   return r;
 }
 
+// A square root in Fq2 = Fq[u]/(u^2 + 1) from square roots in Fq (fq_sqrt), *ok = whether a is a square.  a1 = 0: sqrt(a0) when a0 is a
+// square, else sqrt(-a0) u (-1 is a non-residue).  Otherwise with s = sqrt(a0^2 + a1^2) (the norm of a square is a square) and
+// t = (a0 + s)/2 -- or (a0 - s)/2 when that is no square -- x0 = sqrt(t), x1 = a1 / (2 x0): x0^2 - x1^2 = a0 and 2 x0 x1 = a1.  The result
+// is checked by squaring it.  Which of the two roots comes back is decided by the caller (fq2_is_high).
+HD Fq2 fq2_sqrt(const Fq2& a, bool* ok) {
+  Fq2 r = Fq2::zero();
+  bool k;
+  if (a.c1.is_zero()) {
+    r.c0 = fq_sqrt(a.c0, &k);
+    if (!k) { r.c1 = fq_sqrt(fp_neg(a.c0), &k); r.c0 = Fq::zero(); }
+  } else {
+    const Fq s = fq_sqrt(fp_add(fp_sqr(a.c0), fp_sqr(a.c1)), &k);
+    if (!k) { *ok = false; return Fq2::zero(); }
+    constexpr uint32_t h[FQ_LIMBS] = FQ_INV2_MONT;
+    Fq half;
+    for (int i = 0; i < FQ_LIMBS; i++) half.l[i] = h[i];
+    r.c0 = fq_sqrt(fp_mul(fp_add(a.c0, s), half), &k);
+    if (!k) r.c0 = fq_sqrt(fp_mul(fp_sub(a.c0, s), half), &k);
+    r.c1 = fp_mul(fp_mul(a.c1, half), fp_inv(r.c0));
+  }
+  *ok = f2_sqr(r) == a;
+  return r;
+}
+// the sign of a compressed G2 encoding: y.c1 > (q-1)/2 when y.c1 != 0, else y.c0 > (q-1)/2 (standard form, below q)
+HD bool fq2_is_high(const Fq& c0_std, const Fq& c1_std) { return c1_std.is_zero_strict() ? fq_is_high(c0_std) : fq_is_high(c1_std); }
+
 struct G2Affine {
   Fq2 x, y;
   HD bool is_inf() const { return x.is_zero() && y.is_zero(); }
@@ -82,6 +108,27 @@ HD G2Jac g2_add_mixed(const G2Jac& p, const G2Affine& q) {   // madd-2007-bl
   r.z = f2_sub(f2_sub(f2_sqr(f2_add(p.z, H)), Z1Z1), HH);
   return r;
 }
+// r P == O for a finite point of the twist (E'(Fq2) has a large cofactor and the pairing is bilinear only on the order-r subgroup): the
+// literal double-and-add over the bits of r, shared by k_g2_points_from_bytes and k_g2_decompress
+HD bool g2_in_subgroup(const G2Affine& p) {
+  constexpr uint32_t rl[8] = FR_P;
+  G2Jac acc; acc.x = p.x; acc.y = p.y; acc.z = Fq2::one();       // top bit (254) of r
+#pragma unroll 1
+  for (int bit = 253; bit >= 0; bit--) {
+    acc = g2_dbl(acc);
+    uint32_t word = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) if (k == (bit >> 5)) word = rl[k];
+    if ((word >> (bit & 31)) & 1u) acc = g2_add_mixed(acc, p);
+  }
+  return acc.is_inf();
+}
+// on the twist y^2 = x^3 + 4 (u + 1): the right-hand side for an x (Montgomery)
+HD Fq2 g2_curve_rhs(const Fq2& x) {
+  Fq2 b; b.c0 = fp_dbl(fp_dbl(Fq::one())); b.c1 = b.c0;
+  return f2_add(f2_mul(f2_sqr(x), x), b);
+}
+
 HD G2Affine g2_to_affine(const G2Jac& p) {
   if (p.is_inf()) return G2Affine::inf();
   Fq2 zi = f2_inv(p.z), zi2 = f2_sqr(zi);

@@ -110,6 +110,17 @@ void srs_generate_g2(hipStream_t st, long d, const Fr& x_std, const Fr& alpha_st
 void g2_points_to_bytes_enqueue(hipStream_t st, const G2Affine* in, uint8_t* d_out, long n);
 void g2_points_from_bytes_enqueue(hipStream_t st, const uint8_t* d_in, G2Affine* out, long n, int* d_err);
 
+// compressed point encodings (compress.hip; the format: compress.hpp).  One thread per point; d_in at multiples of 48 / 96 bytes.
+// decompress: out (may be {nullptr}) gets the Montgomery affine point, d_bytes (may be null) its canonical 96 / 192 bytes, d_flags one
+// verdict per point: 0 accepted, else bits 1 malformed, 2 off the curve, 4 outside the subgroup (only with check_subgroup); a refused
+// point is written as infinity.
+void g1_decompress_enqueue(hipStream_t st, const uint8_t* d_in48, PointArrayMut out, uint8_t* d_bytes96, uint8_t* d_flags, long n, bool check_subgroup);
+void g2_decompress_enqueue(hipStream_t st, const uint8_t* d_in96, G2Affine* out, uint8_t* d_bytes192, uint8_t* d_flags, long n, bool check_subgroup);
+void g1_compress_enqueue(hipStream_t st, PointArray in, uint8_t* d_out48, long n);
+void g2_compress_enqueue(hipStream_t st, const G2Affine* in, uint8_t* d_out96, long n);
+// k_g1_validate (verify_batch.hip): 96-byte encodings -> affine points and flags, 1 = what load_g1 accepts
+void g1_validate_enqueue(hipStream_t st, const uint8_t* d_in96, G1Affine* out, uint8_t* d_flags, long n);
+
 // SRS generation (srs.hip): fills both bases of `s` from x, alpha (standard-form Fr on the host)
 void srs_generate(hipStream_t st, sonic_srs* s, const Fr& x_std, const Fr& alpha_std);
 

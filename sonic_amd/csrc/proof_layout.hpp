@@ -18,6 +18,7 @@ struct ProofLayout {
   constexpr long transcript_len() const { return 8 + 2 * Q; }
   constexpr long n_pairs() const { return 5 + 2 * Q; }
   constexpr size_t proof_bytes() const { return (size_t)(K() * 96 + (F() + 2) * 32); }
+  constexpr size_t proof_bytes_compressed() const { return (size_t)(K() * 48 + (F() + 2) * 32); }      // every point as its 48 bytes
   // MSM slots, the order of a share's pieces: R, T, W_a, W_b, W_t, [S_j, W_j]_j, [W'_j, Q_j]_j, Q_v, C
   static constexpr long R = 0, T = 1, Wa = 2, Wb = 3, Wt = 4;
   constexpr long S(long j) const { return 5 + 2 * j; }
@@ -48,17 +49,30 @@ struct ProofLayout {
 
 // canonical proof bytes from the 7 + 4Q points (slot order) and the 3 + 2Q evaluations: record order of `Proof` (Protocol.hs:28-38)
 // then `HscProof` (Signature.hs:22-29)
+// the record order itself: onG(slot) for a point, onF(i) for evaluation i, then onF(-1), onF(-2) for u and v
+template <class OnG, class OnF>
+inline void proof_record_order(long Q, OnG&& onG, OnF&& onF) {
+  const ProofLayout L{Q};
+  onG(L.R); onG(L.T); onF(L.a); onG(L.Wa); onF(L.b); onG(L.Wb); onG(L.Wt); onF(L.s);
+  for (long j = 0; j < Q; j++) { onG(L.S(j)); onF(L.s_j(j)); onG(L.W(j)); }             // hscS
+  for (long j = 0; j < Q; j++) { onF(L.sp_j(j)); onG(L.Wp(j)); onG(L.Qj(j)); }          // hscW
+  onG(L.Qv()); onG(L.C());
+  onF(-1); onF(-2);
+}
 inline void proof_layout(long Q, const uint8_t* pts, const uint8_t* frs, const uint8_t* transcript, uint8_t* out_proof) {
   const ProofLayout L{Q};
   uint8_t* o = out_proof;
-  auto putG = [&](long slot) { memcpy(o, pts + 96 * (size_t)slot, 96); o += 96; };
-  auto putF = [&](const uint8_t* s) { memcpy(o, s, 32); o += 32; };
-  auto F = [&](long i) { return frs + 32 * (size_t)i; };
-  putG(L.R); putG(L.T); putF(F(L.a)); putG(L.Wa); putF(F(L.b)); putG(L.Wb); putG(L.Wt); putF(F(L.s));
-  for (long j = 0; j < Q; j++) { putG(L.S(j)); putF(F(L.s_j(j))); putG(L.W(j)); }             // hscS
-  for (long j = 0; j < Q; j++) { putF(F(L.sp_j(j))); putG(L.Wp(j)); putG(L.Qj(j)); }          // hscW
-  putG(L.Qv()); putG(L.C());
-  putF(transcript + 32 * L.u()); putF(transcript + 32 * L.v());
+  proof_record_order(Q, [&](long slot) { memcpy(o, pts + 96 * (size_t)slot, 96); o += 96; },
+                     [&](long i) { memcpy(o, i >= 0 ? frs + 32 * (size_t)i : transcript + 32 * (size_t)(i == -1 ? L.u() : L.v()), 32); o += 32; });
+}
+// The same proof with every point in another encoding -- 96 <-> 48 bytes (compress.hpp): `in` is walked in record order with points of
+// in_pt bytes, `out` gets points of out_pt bytes made by point(in, out) (false: refused, the walk goes on and the result is false) and
+// the field elements as they are.
+template <class Point>
+inline bool proof_repack(long Q, const uint8_t* in, size_t in_pt, uint8_t* out, size_t out_pt, Point&& point) {
+  bool ok = true;
+  proof_record_order(Q, [&](long) { ok = point(in, out) && ok; in += in_pt; out += out_pt; }, [&](long) { memcpy(out, in, 32); in += 32; out += 32; });
+  return ok;
 }
 
 // S_j's point is its slot's sum plus its side slot's, C's likewise: `side` holds the sums of the side slots K .. K + Q (the empty sum

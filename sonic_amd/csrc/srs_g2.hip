@@ -114,19 +114,8 @@ __global__ __launch_bounds__(64, 1) void k_g2_points_from_bytes(const uint8_t* _
   // pairing with a G2 element at infinity is 1, and with all three at infinity it would accept every proof
   if (!nz) { atomicOr(err, 8); out[i] = G2Affine::inf(); return; }
   p.x.c0 = fp_to_mont(p.x.c0); p.x.c1 = fp_to_mont(p.x.c1); p.y.c0 = fp_to_mont(p.y.c0); p.y.c1 = fp_to_mont(p.y.c1);
-  Fq2 b; b.c0 = fp_dbl(fp_dbl(Fq::one())); b.c1 = b.c0;
-  if (!(f2_sqr(p.y) == f2_add(f2_mul(f2_sqr(p.x), p.x), b))) { atomicOr(err, 2); out[i] = G2Affine::inf(); return; }
-  constexpr uint32_t rl[8] = FR_P;
-  G2Jac acc; acc.x = p.x; acc.y = p.y; acc.z = Fq2::one();       // top bit (254) of r
-#pragma unroll 1
-  for (int bit = 253; bit >= 0; bit--) {
-    acc = g2_dbl(acc);
-    uint32_t word = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) if (k == (bit >> 5)) word = rl[k];
-    if ((word >> (bit & 31)) & 1u) acc = g2_add_mixed(acc, p);
-  }
-  if (!acc.is_inf()) { atomicOr(err, 4); out[i] = G2Affine::inf(); return; }
+  if (!(f2_sqr(p.y) == g2_curve_rhs(p.x))) { atomicOr(err, 2); out[i] = G2Affine::inf(); return; }
+  if (!g2_in_subgroup(p)) { atomicOr(err, 4); out[i] = G2Affine::inf(); return; }
   out[i] = p;
 }
 void g2_points_from_bytes_enqueue(hipStream_t st, const uint8_t* d_in, G2Affine* out, long n, int* d_err) {

@@ -24,6 +24,7 @@
 #include <memory>
 #include <system_error>
 #include "verify_host.hpp"
+#include "proof_layout.hpp"
 
 namespace sonic {
 namespace {
@@ -46,19 +47,7 @@ __global__ __launch_bounds__(256) void k_g1_validate(const uint8_t* __restrict__
     const Fq four = fp_dbl(fp_dbl(Fq::one()));
     ok = fp_sqr(p.y) == fp_add(fp_mul(fp_sqr(p.x), p.x), four);
   }
-  if (ok) {
-    constexpr uint32_t rl[8] = FR_P;
-    G1XYZZ acc = G1XYZZ::from_affine(p);       // top bit (254) of r
-#pragma unroll 1
-    for (int b = 253; b >= 0; b--) {
-      acc = g1_dbl(acc);
-      uint32_t wd = 0;                           // constant-index reads keep rl[] out of scratch
-#pragma unroll
-      for (int k = 0; k < 8; k++) if (k == (b >> 5)) wd = rl[k];
-      if ((wd >> (b & 31)) & 1u) acc = g1_add_mixed(acc, p);
-    }
-    ok = acc.is_inf();
-  }
+  ok = ok && g1_in_subgroup(p);
   out[i] = ok ? p : G1Affine::inf();
   flags[i] = ok ? 1 : 0;
 }
@@ -135,6 +124,12 @@ __global__ __launch_bounds__(S_BLOCK) void k_s_of_uv_finish(const Fr* __restrict
   if (threadIdx.x == 0) { out[k] = sum; ok[k] = refused ? 0 : 1; }
 }
 
+}  // namespace
+void g1_validate_enqueue(hipStream_t st, const uint8_t* d_in96, G1Affine* out, uint8_t* d_flags, long n) {
+  if (n > 0) LAUNCH(k_g1_validate, ceil_div(n, 256), 256, 0, st, d_in96, out, d_flags, n);
+}
+namespace {
+
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 // host phases of a batch, in the kernel profiler's table (sonic_profile_get) under names no kernel has
 void host_phase(const char* name, double ms) {
@@ -182,7 +177,7 @@ struct sonic_verifier {
   CircuitDev cd;
   DevBuf row_ptr, col, val, item_row, item_begin;
   // per call, grown on demand: K (4Q + 7) encodings, points and flags; K pairs, s-values and flags; K nblk partial sums; the scalars
-  DevBuf raw, pts, flags, uv, sv, sok, partial, scalars;
+  DevBuf raw, zraw, pts, flags, uv, sv, sok, partial, scalars;      // (zraw: the compressed encodings of the `_z` calls)
 };
 
 namespace {
@@ -281,14 +276,42 @@ void validate_device(sonic_verifier* v, const uint8_t* enc, long M, std::vector<
   v->raw.ensure(96 * (size_t)M); v->pts.ensure(sizeof(G1Affine) * (size_t)M); v->flags.ensure((size_t)M);
   hipStream_t st = v->st;
   HIP_OK(hipMemcpyAsync(v->raw.p, enc, 96 * (size_t)M, hipMemcpyHostToDevice, st));
-  LAUNCH(k_g1_validate, ceil_div(M, 256), 256, 0, st, (const uint8_t*)v->raw.as<uint8_t>(), v->pts.as<G1Affine>(), v->flags.as<uint8_t>(), M);
+  g1_validate_enqueue(st, v->raw.as<uint8_t>(), v->pts.as<G1Affine>(), v->flags.as<uint8_t>(), M);
   flags.resize((size_t)M);
   HIP_OK(hipMemcpyAsync(flags.data(), v->flags.p, (size_t)M, hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));
 }
 
-// challenges: K blocks of (2 + 2Q) x 32 bytes (y, z, then the pairs)
-int verify_batch_core(sonic_verifier* v, long K, const uint8_t* proofs, const uint8_t* challenges, const uint8_t* seed_in, int* all_accepted, uint8_t* each) {
+// K compressed proofs (the `_z` entry points): k_g1_decompress is the validation stage -- the affine points stay in v->pts for the MSMs as
+// after validate_device, and the canonical 96-byte encodings come back, from which the host rebuilds the uncompressed proof bytes: those
+// are what the batch digest, the Fiat-Shamir challenges and proof_checks read, so a compressed proof is the same proof.  accepted[i] = 1
+// as k_g1_validate's flags; a refused point stands in the rebuilt proof as infinity and rejects its proof through accepted.
+void decompress_device(sonic_verifier* v, long K, const uint8_t* proofs_z, std::vector<uint8_t>& proofs, std::vector<uint8_t>& accepted) {
+  const long Q = v->Q, NP = 4 * Q + 7;
+  const size_t psz = sonic_proof_size(Q), zsz = sonic_proof_size_compressed(Q), M = (size_t)K * (size_t)NP;
+  std::vector<uint8_t> stage(48 * M), canon(96 * M);
+  proofs.resize(psz * (size_t)K);
+  uint8_t* s = stage.data();
+  for (long k = 0; k < K; k++)
+    proof_repack(Q, proofs_z + zsz * (size_t)k, 48, &proofs[psz * (size_t)k], 96, [&](const uint8_t* in, uint8_t*) { memcpy(s, in, 48); s += 48; return true; });
+  v->raw.ensure(96 * M); v->zraw.ensure(48 * M); v->pts.ensure(sizeof(G1Affine) * M); v->flags.ensure(M);
+  hipStream_t st = v->st;
+  HIP_OK(hipMemcpyAsync(v->zraw.p, stage.data(), 48 * M, hipMemcpyHostToDevice, st));
+  g1_decompress_enqueue(st, v->zraw.as<uint8_t>(), PointArrayMut{v->pts.as<char>(), (uint32_t)sizeof(G1Affine)}, v->raw.as<uint8_t>(), v->flags.as<uint8_t>(), (long)M, true);
+  accepted.resize(M);
+  HIP_OK(hipMemcpyAsync(canon.data(), v->raw.p, 96 * M, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(accepted.data(), v->flags.p, M, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  for (auto& f : accepted) f = f ? 0 : 1;                       // the kernel's verdict is 0 = accepted
+  const uint8_t* c = canon.data();
+  for (long k = 0; k < K; k++)
+    proof_repack(Q, proofs_z + zsz * (size_t)k, 48, &proofs[psz * (size_t)k], 96, [&](const uint8_t*, uint8_t* out) { memcpy(out, c, 96); c += 96; return true; });
+}
+
+// challenges: K blocks of (2 + 2Q) x 32 bytes (y, z, then the pairs).  accepted: null, or the per-point flags of a batch that decompress_device
+// has already validated into v->pts
+int verify_batch_core(sonic_verifier* v, long K, const uint8_t* proofs, const uint8_t* challenges, const uint8_t* seed_in, int* all_accepted, uint8_t* each,
+                      const std::vector<uint8_t>* accepted = nullptr) {
   const long Q = v->Q, NP = 4 * Q + 7, NC = 3 * Q + 4;
   const size_t psz = sonic_proof_size(Q), csz = 32 * (size_t)(2 + 2 * Q);
   const size_t N = (size_t)K * (size_t)NP;
@@ -301,12 +324,12 @@ int verify_batch_core(sonic_verifier* v, long K, const uint8_t* proofs, const ui
   Batch b{v, K, NP, NC, std::vector<char>((size_t)K, 0), std::vector<Fr>((size_t)K, Fr::zero())};
   std::vector<ProofViewT<int32_t>> views((size_t)K);
   std::vector<Fr> yms((size_t)K), zms((size_t)K);
-  std::vector<uint8_t> stage(96 * N, 0);
+  std::vector<uint8_t> stage(accepted ? 0 : 96 * N, 0);
   long first_bad = -1;
   for (long k = 0; k < K; k++) {
     int32_t idx = 0;
-    uint8_t* dst = &stage[96 * (size_t)(k * NP)];
-    auto take = [&](const uint8_t* enc, int32_t& o) { o = idx++; memcpy(dst + 96 * (size_t)o, enc, 96); return true; };
+    uint8_t* dst = accepted ? nullptr : &stage[96 * (size_t)(k * NP)];
+    auto take = [&](const uint8_t* enc, int32_t& o) { o = idx++; if (!accepted) memcpy(dst + 96 * (size_t)o, enc, 96); return true; };
     const uint8_t* ch = challenges + csz * (size_t)k;
     b.good[(size_t)k] = parse_proof(proofs + psz * (size_t)k, Q, ch, ch + 32, ch + 64, views[(size_t)k], yms[(size_t)k], zms[(size_t)k], take) ? 1 : 0;
     if (!b.good[(size_t)k] && first_bad < 0) first_bad = k;
@@ -315,7 +338,8 @@ int verify_batch_core(sonic_verifier* v, long K, const uint8_t* proofs, const ui
 
   // 2. the points: canonical, on the curve, in the subgroup (device)
   std::vector<uint8_t> flags;
-  validate_device(v, stage.data(), (long)N, flags);
+  if (accepted) flags = *accepted;
+  else validate_device(v, stage.data(), (long)N, flags);
   for (long k = 0; k < K; k++) {
     bool ok = true;
     for (long j = 0; j < NP; j++) ok = ok && flags[(size_t)(k * NP + j)];
@@ -412,6 +436,31 @@ int verify_batch_core(sonic_verifier* v, long K, const uint8_t* proofs, const ui
     th.join();
   }
   host_phase("verify_batch:each", now_ms() - t0);
+  return SONIC_OK;
+}
+
+// the Fiat-Shamir form: the challenges each proof determines (fs.hpp), in sonic_verify's order; a proof whose own u, v are not its
+// transcript's is rejected
+int verify_fs_batch_core(sonic_verifier* v, long K, const uint8_t* proofs, const uint8_t* seed, int* all_accepted, uint8_t* each, const std::vector<uint8_t>* accepted) {
+  const long Q = v->Q;
+  const size_t psz = sonic_proof_size(Q), csz = 32 * (size_t)(2 + 2 * Q);
+  std::vector<uint8_t> chal(csz * (size_t)K), ch(32 * (size_t)(4 + 2 * Q)), mine((size_t)K, 1);
+  bool all_mine = true;
+  for (int64_t k = 0; k < K; k++) {
+    const uint8_t* proof = proofs + psz * (size_t)k;
+    fs_challenges_of_proof(v->n, Q, v->d, v->digest, v->srs_id, proof, ch.data());
+    if (memcmp(proof + psz - 64, &ch[32 * (size_t)(2 + 2 * Q)], 64) != 0) { mine[(size_t)k] = 0; all_mine = false; }
+    uint8_t* o = &chal[csz * (size_t)k];
+    memcpy(o, &ch[0], 64);
+    for (long j = 0; j < Q; j++) { memcpy(o + 64 + 64 * j, &ch[32 * (size_t)(2 + j)], 32); memcpy(o + 96 + 64 * j, &ch[32 * (size_t)(2 + Q + j)], 32); }
+  }
+  if (!all_mine && !each) return SONIC_OK;                      // rejected, and nobody asked which
+  const int rc = verify_batch_core(v, K, proofs, chal.data(), seed, all_accepted, each, accepted);
+  if (rc) return rc;
+  if (!all_mine) {
+    *all_accepted = 0;
+    for (int64_t k = 0; k < K; k++) if (!mine[(size_t)k]) each[k] = 0;
+  }
   return SONIC_OK;
 }
 
@@ -536,27 +585,34 @@ int sonic_verifier_verify_fs_batch(sonic_verifier_t* v, int64_t K, const uint8_t
   int rc = batch_size_ok("sonic_verifier_verify_fs_batch", v, K);
   if (rc) return rc;
   std::lock_guard<std::mutex> g(v->mu);
-  // the challenges each proof determines (fs.hpp), in sonic_verify's order; a proof whose own u, v are not its transcript's is rejected
-  const long Q = v->Q;
-  const size_t psz = sonic_proof_size(Q), csz = 32 * (size_t)(2 + 2 * Q);
-  std::vector<uint8_t> chal(csz * (size_t)K), ch(32 * (size_t)(4 + 2 * Q)), mine((size_t)K, 1);
-  bool all_mine = true;
-  for (int64_t k = 0; k < K; k++) {
-    const uint8_t* proof = proofs + psz * (size_t)k;
-    fs_challenges_of_proof(v->n, Q, v->d, v->digest, v->srs_id, proof, ch.data());
-    if (memcmp(proof + psz - 64, &ch[32 * (size_t)(2 + 2 * Q)], 64) != 0) { mine[(size_t)k] = 0; all_mine = false; }
-    uint8_t* o = &chal[csz * (size_t)k];
-    memcpy(o, &ch[0], 64);
-    for (long j = 0; j < Q; j++) { memcpy(o + 64 + 64 * j, &ch[32 * (size_t)(2 + j)], 32); memcpy(o + 96 + 64 * j, &ch[32 * (size_t)(2 + Q + j)], 32); }
-  }
-  if (!all_mine && !each) return SONIC_OK;                      // rejected, and nobody asked which
-  rc = verify_batch_core(v, (long)K, proofs, chal.data(), seed, all_accepted, each);
+  return verify_fs_batch_core(v, (long)K, proofs, seed, all_accepted, each, nullptr);
+  VB_END
+}
+
+// the compressed forms: decompress on the device, then the very same verifier over the rebuilt proof bytes
+int sonic_verifier_verify_batch_z(sonic_verifier_t* v, int64_t K, const uint8_t* proofs_z, const uint8_t* challenges, const uint8_t seed[32], int* all_accepted,
+                                  uint8_t* each) {
+  if (!v || !proofs_z || !challenges || !all_accepted) { set_error("sonic_verifier_verify_batch_z: bad argument"); return SONIC_ERR_INVALID_ARG; }
+  *all_accepted = 0;
+  VB_BEGIN(v->device)
+  int rc = batch_size_ok("sonic_verifier_verify_batch_z", v, K);
   if (rc) return rc;
-  if (!all_mine) {
-    *all_accepted = 0;
-    for (int64_t k = 0; k < K; k++) if (!mine[(size_t)k]) each[k] = 0;
-  }
-  return SONIC_OK;
+  std::lock_guard<std::mutex> g(v->mu);
+  std::vector<uint8_t> proofs, accepted;
+  decompress_device(v, (long)K, proofs_z, proofs, accepted);
+  return verify_batch_core(v, (long)K, proofs.data(), challenges, seed, all_accepted, each, &accepted);
+  VB_END
+}
+int sonic_verifier_verify_fs_batch_z(sonic_verifier_t* v, int64_t K, const uint8_t* proofs_z, const uint8_t seed[32], int* all_accepted, uint8_t* each) {
+  if (!v || !proofs_z || !all_accepted) { set_error("sonic_verifier_verify_fs_batch_z: bad argument"); return SONIC_ERR_INVALID_ARG; }
+  *all_accepted = 0;
+  VB_BEGIN(v->device)
+  int rc = batch_size_ok("sonic_verifier_verify_fs_batch_z", v, K);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> g(v->mu);
+  std::vector<uint8_t> proofs, accepted;
+  decompress_device(v, (long)K, proofs_z, proofs, accepted);
+  return verify_fs_batch_core(v, (long)K, proofs.data(), seed, all_accepted, each, &accepted);
   VB_END
 }
 
@@ -591,7 +647,7 @@ int sonic_g1_validate(const uint8_t* points, int64_t n, uint8_t* flags) {
   hipStream_t st = lease.st();
   DevBuf raw(96 * (size_t)n), pts(sizeof(G1Affine) * (size_t)n), fl((size_t)n);
   HIP_OK(hipMemcpyAsync(raw.p, points, 96 * (size_t)n, hipMemcpyHostToDevice, st));
-  LAUNCH(k_g1_validate, ceil_div(n, 256), 256, 0, st, (const uint8_t*)raw.as<uint8_t>(), pts.as<G1Affine>(), fl.as<uint8_t>(), (long)n);
+  g1_validate_enqueue(st, raw.as<uint8_t>(), pts.as<G1Affine>(), fl.as<uint8_t>(), (long)n);
   HIP_OK(hipMemcpyAsync(flags, fl.p, (size_t)n, hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));
   return SONIC_OK;

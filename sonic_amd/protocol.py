@@ -161,9 +161,13 @@ class Proof:                 # Protocol.hs:28-38
     prS: int
     prHscProof: HscProof
 
-    def to_bytes(self) -> bytes:
+    def to_bytes(self, compressed: bool = False) -> bytes:
         """canonical proof bytes (include/sonic_hip.h): the record order of `Proof` then `HscProof`, serialised from the
-        fields -- an edited or hand-built Proof is what gets verified, never a cached copy of the prover's output"""
+        fields -- an edited or hand-built Proof is what gets verified, never a cached copy of the prover's output.
+        compressed=True: the same record with every point as its 48 compressed bytes (sonic_proof_compress, which validates the points)"""
+        if compressed:
+            from .compressed import proof_compress
+            return proof_compress(self.to_bytes(), len(self.prHscProof.hscS))
         def fr(v):               # as is: a non-canonical field element must reach the verifier (which rejects it) unreduced
             return int(v).to_bytes(32, "little")
         head = [g1_to_bytes(self.prR), g1_to_bytes(self.prT), fr(self.prA), g1_to_bytes(self.prWa), fr(self.prB),
@@ -173,8 +177,11 @@ class Proof:                 # Protocol.hs:28-38
     @classmethod
     def from_bytes(cls, b: bytes, Q: int) -> "Proof":
         b = bytes(b)
+        if len(b) == (7 + 4 * Q) * 48 + (5 + 2 * Q) * 32:         # the compressed form (the two lengths never coincide for one Q)
+            from .compressed import proof_decompress
+            b = proof_decompress(b, Q)
         if len(b) != (7 + 4 * Q) * 96 + (5 + 2 * Q) * 32:
-            raise ValueError(f"proof for Q = {Q} is {(7 + 4 * Q) * 96 + (5 + 2 * Q) * 32} bytes, got {len(b)}")
+            raise ValueError(f"proof for Q = {Q} is {(7 + 4 * Q) * 96 + (5 + 2 * Q) * 32} bytes ({(7 + 4 * Q) * 48 + (5 + 2 * Q) * 32} compressed), got {len(b)}")
         g = lambda o: g1_from_bytes(b[o:o + 96])                  # noqa: E731
         f = lambda o: int.from_bytes(b[o:o + 32], "little")       # noqa: E731
         # R T a Wa b Wb Wt s
@@ -641,12 +648,16 @@ class Verifier:
         self._h = C.c_void_p()
         _lib.check(getattr(_lib.lib(), "sonic_verifier_new" + suffix)(srs._h, self.n, self.Q, *args, C.byref(self._h)))
 
-    def _proof_bytes(self, proofs) -> bytes:
-        size = _lib.lib().sonic_proof_size(self.Q)
+    def _proof_bytes(self, proofs):
+        """the batch as one buffer, and the suffix of the entry point that reads it: "" for proof bytes / Proof objects, "_z" when every
+        proof is given as compressed bytes (told apart by length)"""
+        size, zsize = _lib.lib().sonic_proof_size(self.Q), _lib.lib().sonic_proof_size_compressed(self.Q)
         raws = [p.to_bytes() if isinstance(p, Proof) else bytes(p) for p in proofs]
+        if raws and all(len(r) == zsize for r in raws):
+            return b"".join(raws), "_z"
         if not raws or any(len(r) != size for r in raws):
-            raise ValueError(f"Verifier: need at least one proof, each of {size} bytes (Q = {self.Q})")
-        return b"".join(raws)
+            raise ValueError(f"Verifier: need at least one proof, each of {size} bytes, or each of {zsize} compressed (Q = {self.Q})")
+        return b"".join(raws), ""
 
     @staticmethod
     def _seed(seed):
@@ -661,7 +672,7 @@ class Verifier:
         return (bool(ok.value), [bool(b) for b in flags.raw]) if each else bool(ok.value)
 
     def verify_batch(self, proofs, transcripts, seed=None, each: bool = False):
-        """proofs: Proof objects or proof bytes; transcripts: one (y, z, yzs) per proof, as for verify().  True iff every proof is
+        """proofs: Proof objects, proof bytes, or compressed proof bytes (all of them: the `_z` entry point); transcripts: one (y, z, yzs) per proof, as for verify().  True iff every proof is
         accepted; with each=True also the per-proof verdicts."""
         proofs, transcripts = list(proofs), list(transcripts)
         if len(transcripts) != len(proofs):
@@ -673,14 +684,16 @@ class Verifier:
             if len(yzs) != self.Q or any(len(pair) != 2 for pair in yzs):
                 raise ValueError(f"verify_batch: yzs must hold {self.Q} (y_j, z_j) pairs")
             blocks.append(fr(y) + fr(z) + b"".join(fr(a) + fr(b) for a, b in yzs))
-        raw, chal, sd, K = self._proof_bytes(proofs), b"".join(blocks), self._seed(seed), len(proofs)
-        return self._result(K, lambda ok, flags: _lib.lib().sonic_verifier_verify_batch(self._h, K, raw, chal, sd, ok, flags), each)
+        (raw, z), chal, sd, K = self._proof_bytes(proofs), b"".join(blocks), self._seed(seed), len(proofs)
+        call = getattr(_lib.lib(), "sonic_verifier_verify_batch" + z)
+        return self._result(K, lambda ok, flags: call(self._h, K, raw, chal, sd, ok, flags), each)
 
     def verify_fs_batch(self, proofs, seed=None, each: bool = False):
         """the same for Fiat-Shamir proofs (prove_fs): every proof's challenges are recomputed from the circuit and the proof"""
         proofs = list(proofs)
-        raw, sd, K = self._proof_bytes(proofs), self._seed(seed), len(proofs)
-        return self._result(K, lambda ok, flags: _lib.lib().sonic_verifier_verify_fs_batch(self._h, K, raw, sd, ok, flags), each)
+        (raw, z), sd, K = self._proof_bytes(proofs), self._seed(seed), len(proofs)
+        call = getattr(_lib.lib(), "sonic_verifier_verify_fs_batch" + z)
+        return self._result(K, lambda ok, flags: call(self._h, K, raw, sd, ok, flags), each)
 
     def eval_s(self, uvs) -> List[int]:
         """s(u, v) of the circuit's s(X, Y) for every (u, v) of `uvs`, on the GPU (raises SonicError INEXACT_DIVISION for u = 0 or v = 0)"""

@@ -68,11 +68,13 @@ class SRS:
         """whether the handle holds the verifier half or can still generate it (sonic_srs_has_g2)"""
         return bool(_lib.lib().sonic_srs_has_g2(self._h))
 
-    def save(self, path: str, g2=None) -> None:
+    def save(self, path: str, g2=None, compressed: bool = False) -> None:
         """write the SRS to disk (format in include/sonic_hip.h): the G1 bases and, with g2, the G2 bases, so that the
         loaded handle can verify as well as prove.  g2=None (default): include the G2 half if the handle has it -- handles made
-        from G1 points only, or loaded from a version-1 file, save as they are.  The file never holds the trapdoor."""
-        _lib.check(_lib.lib().sonic_srs_save(self._h, str(path).encode(), 2 if g2 is None else (1 if g2 else 0)))
+        from G1 points only, or loaded from a version-1 file, save as they are.  The file never holds the trapdoor.
+        compressed=True writes the "SONICSRZ" container instead: every point in its compressed encoding, half the size; load() takes either."""
+        save = _lib.lib().sonic_srs_save_compressed if compressed else _lib.lib().sonic_srs_save
+        _lib.check(save(self._h, str(path).encode(), 2 if g2 is None else (1 if g2 else 0)))
 
     @classmethod
     def load(cls, path: str, device: int = -1) -> "SRS":
