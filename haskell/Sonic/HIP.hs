@@ -55,6 +55,9 @@ module Sonic.HIP
     -- * resident handles, many GPUs
   , Prover, newProver, newProverDense, prepare, setAssignment, proveWith, submit, collect
   , proveShared, proveBatch, deviceCount
+    -- * one circuit, many statements
+  , setConstants, evalConstraints, proveBatchStatements, fsCircuitMidstate, fsCircuitDigestResume
+  , Verifier, newVerifier, verifyBatchStatements, verifyFsBatchStatements
   ) where
 
 import Protolude hiding (check)
@@ -69,7 +72,7 @@ import Data.Pairing.BLS12381 (BLS12381, Fq, Fq12, Fr, G1, G2, GT)
 import Data.Poly.Sparse.Laurent (VLaurent)
 import Bulletproofs.ArithmeticCircuit (ArithCircuit(..), Assignment(..), GateWeights(..))
 import Foreign (FunPtr, ForeignPtr, Ptr, alloca, allocaArray, allocaBytes, castPtr, newForeignPtr, nullPtr,
-                peek, pokeArray, withArrayLen, withForeignPtr)
+                peek, peekElemOff, pokeArray, withArrayLen, withForeignPtr)
 import Foreign.C.String (CString, peekCString, withCString)
 import Foreign.C.Types (CChar, CInt(..), CSize(..))
 import System.IO.Unsafe (unsafePerformIO)
@@ -133,6 +136,18 @@ foreign import ccall safe   "sonic_prover_submit"         c_prover_submit  :: Pt
 foreign import ccall safe   "sonic_prover_collect"        c_prover_collect :: Ptr ProverHandle -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_prove_shared"          c_prove_shared   :: Ptr (Ptr ProverHandle) -> CInt -> Ptr Word8 -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_prove_batch"           c_prove_batch    :: Ptr (Ptr ProverHandle) -> CInt -> Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> IO CInt
+
+-- one circuit, many statements (ABI 7, additions): per-proof constants on a resident circuit, prover and batched verifier
+data VerifierHandle
+foreign import ccall safe   "sonic_prover_eval_constraints" c_eval_constraints :: Ptr ProverHandle -> Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Int64 -> IO CInt
+foreign import ccall safe   "sonic_prover_set_constants"  c_set_constants  :: Ptr ProverHandle -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_prove_batch_statements" c_prove_batch_st :: Ptr (Ptr ProverHandle) -> CInt -> Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> IO CInt
+foreign import ccall safe   "sonic_fs_circuit_midstate_csr" c_fs_midstate_csr :: Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_fs_circuit_digest_resume" c_fs_resume   :: Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_verifier_new_csr"      c_verifier_new_csr :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr (Ptr VerifierHandle) -> IO CInt
+foreign import ccall safe   "&sonic_verifier_free"        p_verifier_free  :: FunPtr (Ptr VerifierHandle -> IO ())
+foreign import ccall safe   "sonic_verifier_verify_batch_cs" c_verify_batch_cs :: Ptr VerifierHandle -> Int64 -> Ptr Word8 -> CInt -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_verifier_verify_fs_batch_cs" c_verify_fs_batch_cs :: Ptr VerifierHandle -> Int64 -> Ptr Word8 -> CInt -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> Ptr Word8 -> IO CInt
 
 -- ---------------------------------------------------------------------------------------------------------------------
 -- status codes -> the reference's failure behaviour (it panics: Protocol.hs:55, CommitmentScheme.hs:70-73, :44)
@@ -633,6 +648,95 @@ proveBatch ps@(p0 : _) asgs = do
         BSI.create (psz * k) $ \out ->
           check =<< c_prove_batch arr np (fromIntegral k) pal par pao ptr out nullPtr
   pure (zip (map (decodeProof q) (chunks psz bytes)) (map snd drawn))
+
+-- ---------------------------------------------------------------------------------------------------------------------
+-- one circuit, many statements: the weights are the program and stay resident, the constants cs = wL.aL + wR.aR + wO.aO
+-- (test/Test/Reference.hs:138) are the public inputs and change with every proof
+-- ---------------------------------------------------------------------------------------------------------------------
+-- | the constants of the handle's next statement, overwritten in place (sonic_prover_set_constants): assignment and prepared rows stay
+setConstants :: Prover -> [Fr] -> IO ()
+setConstants Prover{..} cs
+  | length cs /= proverQ = panic "setConstants: need Q constants"
+  | otherwise = withForeignPtr proverHandle $ \p -> withFrs cs (check <=< c_set_constants p)
+
+-- | per assignment: the constants it satisfies under the handle's weights, and (broken multiplication gates, the first one or -1), on the
+--   GPU (sonic_prover_eval_constraints)
+evalConstraints :: Prover -> [Assignment Fr] -> IO [([Fr], (Int, Int))]
+evalConstraints _ [] = pure []
+evalConstraints Prover{..} asgs = do
+  let b = length asgs
+  withForeignPtr proverHandle $ \p ->
+    withFrs (concatMap aL asgs) $ \pal -> withFrs (concatMap aR asgs) $ \par -> withFrs (concatMap aO asgs) $ \pao ->
+      allocaArray (2 * b) $ \gates -> do
+        bytes <- BSI.create (32 * proverQ * b) $ \out ->
+          check =<< c_eval_constraints p (fromIntegral b) pal par pao out gates
+        gs <- forM [0 .. b - 1] $ \i -> (,) <$> peekElemOff gates (2 * i) <*> peekElemOff gates (2 * i + 1)
+        pure [ (map frFromBytes (chunks 32 one), (fromIntegral c, fromIntegral f)) | (one, (c, f)) <- zip (chunks (32 * proverQ) bytes) gs ]
+
+-- | proveBatch with one statement per proof (sonic_prove_batch_statements): proof i's constants ride at the head of its own queue as its
+--   assignment does.  Afterwards each handle holds the constants and the assignment of the last proof it ran.
+proveBatchStatements :: [Prover] -> [(Assignment Fr, [Fr])] -> IO [(Proof, RndOracle)]
+proveBatchStatements [] _ = panic "proveBatchStatements: no handles"
+proveBatchStatements ps@(p0 : _) sts = do
+  let q = proverQ p0
+      k = length sts
+      asgs = map fst sts
+  when (any ((/= q) . length . snd) sts) $ panic "proveBatchStatements: need Q constants per statement"
+  drawn <- replicateM k (drawTranscript q)
+  psz <- fromIntegral <$> c_proof_size (fromIntegral q)
+  bytes <- withProvers ps $ \arr np ->
+    withFrs (concatMap aL asgs) $ \pal -> withFrs (concatMap aR asgs) $ \par -> withFrs (concatMap aO asgs) $ \pao ->
+      withFrs (concatMap snd sts) $ \pcs -> withFrs (concatMap fst drawn) $ \ptr ->
+        BSI.create (psz * k) $ \out ->
+          check =<< c_prove_batch_st arr np (fromIntegral k) pal par pao pcs ptr out nullPtr
+  pure (zip (map (decodeProof q) (chunks psz bytes)) (map snd drawn))
+
+-- | the SHA-256 state of the circuit digest after the gate weights (sonic_fs_circuit_midstate_csr; host only): 112 bytes
+fsCircuitMidstate :: ArithCircuit Fr -> ByteString
+fsCircuitMidstate circuit = unsafePerformIO $
+  withCircuitCsr circuit $ \n q prp pcol pval _ -> BSI.create 112 $ \out ->
+    check =<< c_fs_midstate_csr n q prp pcol pval out
+
+-- | fsCircuitDigest of the circuit behind the midstate with these constants, from Q x 32 bytes of hashing
+fsCircuitDigestResume :: ByteString -> [Fr] -> ByteString
+fsCircuitDigestResume mid cs = unsafePerformIO $
+  withBytes mid $ \pm -> withFrs cs $ \pcs -> BSI.create 32 $ \out ->
+    check =<< c_fs_resume pm pcs out
+
+-- | the batched verifier's handle (sonic_verifier_new_csr): the circuit resident on the GPU; keeps the SRS alive as long as the handle
+data Verifier = Verifier { verifierHandle :: ForeignPtr VerifierHandle, verifierSrs :: SRS, verifierQ :: Int }
+
+newVerifier :: SRS -> ArithCircuit Fr -> IO Verifier
+newVerifier srs@(SRS h) circuit =
+  withForeignPtr h $ \p -> withCircuitCsr circuit $ \n q prp pcol pval pcs -> alloca $ \out -> do
+    check =<< c_verifier_new_csr p n q prp pcol pval pcs out
+    fp <- newForeignPtr p_verifier_free =<< peek out
+    pure Verifier { verifierHandle = fp, verifierSrs = srs, verifierQ = fromIntegral q }
+
+-- | K proofs of K statements of the handle's circuit in one pairing product (sonic_verifier_verify_batch_cs): proof k against cs_k with
+--   its RndOracle; the per-proof verdicts (a malformed proof is a rejected proof).  The library draws the seed of the randomizers.
+verifyBatchStatements :: Verifier -> [(Proof, RndOracle, [Fr])] -> IO [Bool]
+verifyBatchStatements _ [] = pure []
+verifyBatchStatements Verifier{..} sts = do
+  let k = length sts
+      chal RndOracle{..} = rndOracleY : rndOracleZ : concat [ [yj, zj] | (yj, zj) <- rndOracleYZs ]
+  withForeignPtr verifierHandle $ \v ->
+    withBytes (BS.concat [ encodeProof pf | (pf, _, _) <- sts ]) $ \ppf ->
+      withFrs (concat [ chal o | (_, o, _) <- sts ]) $ \pch -> withFrs (concat [ cs | (_, _, cs) <- sts ]) $ \pcs ->
+        alloca $ \acc -> do
+          each <- BSI.create k $ \out -> check =<< c_verify_batch_cs v (fromIntegral k) ppf 0 pch pcs nullPtr acc out
+          pure (map (/= 0) (BS.unpack each))
+
+-- | the same for Fiat-Shamir proofs (sonic_verifier_verify_fs_batch_cs): proof k's challenges come from the digest of its own statement
+verifyFsBatchStatements :: Verifier -> [(Proof, [Fr])] -> IO [Bool]
+verifyFsBatchStatements _ [] = pure []
+verifyFsBatchStatements Verifier{..} sts = do
+  let k = length sts
+  withForeignPtr verifierHandle $ \v ->
+    withBytes (BS.concat (map (encodeProof . fst) sts)) $ \ppf -> withFrs (concatMap snd sts) $ \pcs ->
+      alloca $ \acc -> do
+        each <- BSI.create k $ \out -> check =<< c_verify_fs_batch_cs v (fromIntegral k) ppf 0 pcs nullPtr acc out
+        pure (map (/= 0) (BS.unpack each))
 
 deviceCount :: IO Int
 deviceCount = alloca $ \out -> do

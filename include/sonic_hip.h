@@ -96,7 +96,9 @@ typedef struct sonic_verifier sonic_verifier_t;
  * sonic_verifier_device, sonic_verifier_verify_batch, sonic_verifier_verify_fs_batch, sonic_verifier_eval_s, sonic_g1_validate,
  * sonic_verify_batch_randomizers; still 7, additions only: the compressed encodings -- sonic_g1_compress, sonic_g1_decompress,
  * sonic_g2_compress, sonic_g2_decompress, sonic_proof_size_compressed, sonic_proof_compress, sonic_proof_decompress,
- * sonic_verifier_verify_batch_z, sonic_verifier_verify_fs_batch_z, sonic_srs_save_compressed */
+ * sonic_verifier_verify_batch_z, sonic_verifier_verify_fs_batch_z, sonic_srs_save_compressed; still 7, additions only: one circuit, many
+ * statements -- sonic_prover_eval_constraints, sonic_prover_set_constants, sonic_prove_batch_statements, sonic_fs_circuit_midstate[_csr],
+ * sonic_fs_circuit_digest_resume, sonic_verifier_verify_batch_cs, sonic_verifier_verify_fs_batch_cs, sonic_verify_batch_digest_v2 */
 int sonic_abi_version(void);
 int sonic_init(int device_ordinal);                 /* choose the DEFAULT GPU (first call wins) and make it the thread's HIP device; idempotent */
 int sonic_device_count(int* out);                   /* GPUs this process can see; SONIC_ERR_NO_DEVICE (and 0) without one */
@@ -492,6 +494,63 @@ int sonic_proof_decompress(int64_t Q, const uint8_t* proof_z, uint8_t* out_proof
 int sonic_verifier_verify_batch_z(sonic_verifier_t* v, int64_t K, const uint8_t* proofs_z, const uint8_t* challenges, const uint8_t seed[32],
                                   int* all_accepted, uint8_t* each);
 int sonic_verifier_verify_fs_batch_z(sonic_verifier_t* v, int64_t K, const uint8_t* proofs_z, const uint8_t seed[32], int* all_accepted, uint8_t* each);
+
+/* ---- One circuit, many statements ----
+ * In the reference a statement is (ArithCircuit, Assignment) with cs = wL.aL + wR.aR + wO.aO (test/Test/Reference.hs:138): the gate weights
+ * are the program, the constants are the public inputs and change with every proof.  A prover handle and a verifier handle take cs when they
+ * are made; these calls let ONE resident circuit -- its device layout, its prepared rows (sonic_prover_prepare), s(X,y), s(u,Y): all functions
+ * of the weights only -- serve proofs of many statements.  cs enters the prover in one Q-term sum (k(y)), the verifier in the same sum, and
+ * the Fiat-Shamir circuit digest as its last bytes.
+ *
+ * eval_constraints  the constants B assignments satisfy under the handle's weights, on the GPU (dense handle: three Q x n matrix-vector
+ *                   products over Fr; CSR handle: one sparse product over the 3Q stacked rows), and the multiplication gates they break.
+ *                   aL, aR, aO: B x n x 32 canonical bytes each; all three NULL: B must be 1 and the handle's resident assignment is read
+ *                   (none set: SONIC_ERR_INVALID_ARG, as sonic_prover_prove).  out_cs: B x Q x 32 bytes, out_cs[b][q] = sum_i wL[q,i] aL_b[i]
+ *                   + wR[q,i] aR_b[i] + wO[q,i] aO_b[i].  out_gates (may be NULL): B x 2 int64, {the number of i with aL_b[i] aR_b[i] !=
+ *                   aO_b[i], the smallest such i (0-based) or -1}.  A non-canonical input: SONIC_ERR_BAD_ENCODING (the outputs are then
+ *                   undefined); B < 1 or B n > 2^26: SONIC_ERR_INVALID_ARG; a handle with a proof in flight: SONIC_ERR_INVALID_ARG, as
+ *                   sonic_prover_set_assignment.  The handle's own assignment and constants are left as they are.  Assignments are staged
+ *                   through the device in chunks, so B is not bounded by device memory.
+ * set_constants     overwrites the handle's cs (Q x 32 canonical bytes) in place: the assignment, the prepared rows, the share mode, parked
+ *                   state and a proof graph captured under SONIC_PROVE_GRAPH=1 all stay.  A proof in flight: SONIC_ERR_INVALID_ARG, as
+ *                   sonic_prover_set_assignment; a non-canonical cs: SONIC_ERR_BAD_ENCODING and the old constants stay.
+ * prove_batch_statements   sonic_prove_batch with proof i's constants (cs: K x Q x 32) uploaded at the head of proof i's own queue, as its
+ *                   assignment is: no device wait of its own.  Everything else as sonic_prove_batch: proof i on handle i % n_provers, all
+ *                   proofs attempted, the first non-zero status returned; a proof whose assignment does not satisfy its constants gets
+ *                   SONIC_ERR_SRS_INDEX, one with a non-canonical constant SONIC_ERR_BAD_ENCODING before anything of it is queued.  AFTER
+ *                   THE CALL EACH HANDLE HOLDS THE CONSTANTS (and, when assignments are given, the assignment) OF THE LAST PROOF IT RAN.
+ * fs_circuit_midstate[_csr], fs_circuit_digest_resume   host only, no device.  The midstate is the SHA-256 state after
+ *                   "sonic-hip/circuit/v1" || le64 n || le64 Q || wL || wR || wO: SONIC_FS_MIDSTATE_SIZE bytes -- the chaining value (8 x le32),
+ *                   the 64 bytes of the pending block (zero behind the pending ones), le64 length, le64 Q (sonic_amd/csrc/fs.hpp).
+ *                   resume(midstate(W), cs) == sonic_fs_circuit_digest[_csr](W, cs) byte for byte, for every cs, at Q x 32 bytes of hashing;
+ *                   dense and CSR midstates of the same matrices are equal.  resume refuses a midstate whose length is not 36 + 96 Q n for
+ *                   its Q (SONIC_ERR_INVALID_ARG) and a non-canonical cs (SONIC_ERR_BAD_ENCODING).  sonic_prover_prove_fs takes the digest
+ *                   from its caller: after set_constants, pass the resumed one. */
+#define SONIC_FS_MIDSTATE_SIZE 112
+int sonic_prover_eval_constraints(sonic_prover_t* p, int64_t B, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO, uint8_t* out_cs,
+                                  int64_t* out_gates);
+int sonic_prover_set_constants(sonic_prover_t* p, const uint8_t* cs);
+int sonic_prove_batch_statements(sonic_prover_t* const* provers, int n_provers, int64_t K, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO,
+                                 const uint8_t* cs, const uint8_t* transcripts, uint8_t* out_proofs, int* out_status);
+int sonic_fs_circuit_midstate(int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO, uint8_t out[SONIC_FS_MIDSTATE_SIZE]);
+int sonic_fs_circuit_midstate_csr(int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val,
+                                  uint8_t out[SONIC_FS_MIDSTATE_SIZE]);
+int sonic_fs_circuit_digest_resume(const uint8_t midstate[SONIC_FS_MIDSTATE_SIZE], const uint8_t* cs, uint8_t out[32]);
+/* The batched verifier with proof k checked against the handle's weights and ITS OWN constants cs_k (cs: K x Q x 32 bytes).  compressed: 0 =
+ * proofs of sonic_proof_size(Q) bytes, 1 = of sonic_proof_size_compressed(Q) bytes (the `_z` forms' input).  Everything else -- challenges,
+ * seed, all_accepted, each, the size limits -- as sonic_verifier_verify_batch / _fs_batch; the Fiat-Shamir form derives proof k's challenges
+ * from resume(the handle's midstate, cs_k).  A non-canonical cs_k makes proof k a rejected, malformed proof, not a failed call.  The
+ * randomizers bind the constants: rho_i is derived as above from
+ *     D = SHA-256("sonic-hip/batch-digest/v2" || le64 n || le64 Q || le64 d || the handle's circuit digest || srs id || le64 K ||
+ *                 K x (proof bytes || its challenges || cs_k))
+ * (for compressed = 1 the rebuilt uncompressed proof bytes).  With every cs_k equal to the handle's constants the verdicts are those of
+ * sonic_verifier_verify_batch.  sonic_verify_batch_digest_v2 is D on its own: host only, no device (challenges: K blocks of 2 + 2Q). */
+int sonic_verifier_verify_batch_cs(sonic_verifier_t* v, int64_t K, const uint8_t* proofs, int compressed, const uint8_t* challenges,
+                                   const uint8_t* cs, const uint8_t seed[32], int* all_accepted, uint8_t* each);
+int sonic_verifier_verify_fs_batch_cs(sonic_verifier_t* v, int64_t K, const uint8_t* proofs, int compressed, const uint8_t* cs,
+                                      const uint8_t seed[32], int* all_accepted, uint8_t* each);
+int sonic_verify_batch_digest_v2(int64_t n, int64_t Q, int64_t d, const uint8_t circuit_digest[32], const uint8_t srs_id[32], int64_t K,
+                                 const uint8_t* proofs, const uint8_t* challenges, const uint8_t* cs, uint8_t out[32]);
 
 /* ---- device memory for callers without a HIP binding ---- */
 int sonic_dev_alloc(size_t bytes, void** out);                       /* on the default device */

@@ -154,6 +154,15 @@ def lib() -> C.CDLL:
         "sonic_verifier_verify_batch_z": [vp, i64, vp, vp, cp, C.POINTER(i32), vp],
         "sonic_verifier_verify_fs_batch_z": [vp, i64, vp, cp, C.POINTER(i32), vp],
         "sonic_srs_save_compressed": [vp, cp, i32],
+        "sonic_prover_eval_constraints": [vp, i64, vp, vp, vp, vp, vp],
+        "sonic_prover_set_constants": [vp, vp],
+        "sonic_prove_batch_statements": [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp],
+        "sonic_fs_circuit_midstate": [i64, i64, vp, vp, vp, vp],
+        "sonic_fs_circuit_midstate_csr": [i64, i64, vp, vp, vp, vp],
+        "sonic_fs_circuit_digest_resume": [vp, vp, vp],
+        "sonic_verifier_verify_batch_cs": [vp, i64, vp, i32, vp, vp, cp, C.POINTER(i32), vp],
+        "sonic_verifier_verify_fs_batch_cs": [vp, i64, vp, i32, vp, cp, C.POINTER(i32), vp],
+        "sonic_verify_batch_digest_v2": [i64, i64, i64, cp, cp, i64, vp, vp, vp, vp],
         "sonic_dev_alloc": [C.c_size_t, C.POINTER(vp)],
         "sonic_dev_free": [vp],
         "sonic_dev_upload": [vp, vp, C.c_size_t],
@@ -216,6 +225,7 @@ def lib() -> C.CDLL:
 
 HIP_RUNTIME_NOTE = None
 ABI_VERSION = 7          # SONIC_ABI_VERSION of include/sonic_hip.h
+FS_MIDSTATE_SIZE = 112   # SONIC_FS_MIDSTATE_SIZE
 
 
 def _hipver(v: int) -> str:
@@ -241,6 +251,8 @@ EXPORTED = [
     "sonic_verifier_eval_s", "sonic_g1_validate", "sonic_verify_batch_randomizers",
     "sonic_g1_compress", "sonic_g1_decompress", "sonic_g2_compress", "sonic_g2_decompress", "sonic_proof_size_compressed", "sonic_proof_compress", "sonic_proof_decompress",
     "sonic_verifier_verify_batch_z", "sonic_verifier_verify_fs_batch_z", "sonic_srs_save_compressed",
+    "sonic_prover_eval_constraints", "sonic_prover_set_constants", "sonic_prove_batch_statements", "sonic_fs_circuit_midstate", "sonic_fs_circuit_midstate_csr",
+    "sonic_fs_circuit_digest_resume", "sonic_verifier_verify_batch_cs", "sonic_verifier_verify_fs_batch_cs", "sonic_verify_batch_digest_v2",
 ]
 
 

@@ -157,39 +157,33 @@ inline bool circuit_runs_hint(const CircuitView& c, long tile) {
   return 4 * uniform >= samples;
 }
 
-// The statement part of the Fiat-Shamir transcript (fs.hpp): SHA-256 of (n, Q, wL, wR, wO, cs).  Sparse rows are streamed in order as the
-// dense bytes they stand for (32 zero bytes per absent entry), so that a proof made on either form verifies under either; O(Q n) hashing,
-// once per circuit.
-inline void circuit_digest(const CircuitView& c, uint8_t out[32]) {
-  const long n = c.n, Q = c.Q;
+// The statement part of the Fiat-Shamir transcript (fs.hpp): SHA-256 of (n, Q, wL, wR, wO, cs), in two halves.  circuit_midstate hashes
+// the weights -- sparse rows streamed in order as the dense bytes they stand for (32 zero bytes per absent entry), so that a proof made on
+// either form verifies under either; O(Q n) hashing, once per circuit -- and fs_circuit_digest_resume adds one statement's constants.
+inline void circuit_midstate(const CircuitView& c, uint8_t out[FS_MIDSTATE_SIZE]) {
   Sha256 h;
-  h.update("sonic-hip/circuit/v1", 20);
-  FsTranscript::le64(h, n); FsTranscript::le64(h, Q);
-  if (!c.csr) {
-    h.update(c.wL, (size_t)(32 * Q * n)); h.update(c.wR, (size_t)(32 * Q * n)); h.update(c.wO, (size_t)(32 * Q * n));
-  } else {
-    static const uint8_t zeros[32 * 1024] = {0};
-    auto gap = [&](int64_t cnt) {
-      for (; cnt > 0; cnt -= 1024) h.update(zeros, 32 * (size_t)(cnt < 1024 ? cnt : 1024));
-    };
-    for (long r = 0; r < 3 * Q; r++) {
-      int64_t at = 0;
-      for (int64_t k = c.row_ptr[r]; k < c.row_ptr[r + 1]; k++) {
-        gap(c.col[k] - at);
-        h.update(c.val + 32 * k, 32);
-        at = c.col[k] + 1;
-      }
-      gap(n - at);
-    }
-  }
-  h.update(c.cs, (size_t)(32 * Q));
-  h.finish(out);
+  fs_circuit_begin(h, c.n, c.Q);
+  if (!c.csr) fs_circuit_absorb_dense(h, c.n, c.Q, c.wL, c.wR, c.wO);
+  else fs_circuit_absorb_csr(h, c.n, c.Q, c.row_ptr, c.col, c.val);
+  fs_midstate_save(h, c.Q, out);
+}
+// (the digest hashes cs as the bytes they are: whether they are canonical is the caller's check, as it always was)
+inline void circuit_digest(const CircuitView& c, uint8_t out[32]) {
+  uint8_t mid[FS_MIDSTATE_SIZE];
+  circuit_midstate(c, mid);
+  fs_circuit_digest_resume(mid, c.cs, out, nullptr, /*check_cs=*/false);
 }
 // (the two exported digests: the argument checks first)
 inline int circuit_digest_checked(const char* who, const CircuitView& c, uint8_t out[32]) {
   if (!c.cs || !out) { set_error("%s: bad argument", who); return SONIC_ERR_INVALID_ARG; }
   int rc = circuit_validate(who, c);
   if (!rc) circuit_digest(c, out);
+  return rc;
+}
+inline int circuit_midstate_checked(const char* who, const CircuitView& c, uint8_t out[FS_MIDSTATE_SIZE]) {
+  if (!out) { set_error("%s: bad argument", who); return SONIC_ERR_INVALID_ARG; }
+  int rc = circuit_validate(who, c);
+  if (!rc) circuit_midstate(c, out);
   return rc;
 }
 

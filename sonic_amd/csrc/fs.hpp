@@ -125,4 +125,92 @@ inline void fs_challenges_of_proof(int64_t n, int64_t Q, int64_t d, const uint8_
   t.challenge("v", 0, out + 32 * (3 + 2 * Q));
 }
 
+// ---- the circuit digest in two halves: one circuit, many statements ----------------------------------------------------------------
+// The constants cs are the LAST bytes of the circuit digest, and they are what changes from statement to statement (the reference's
+// cs = wL.aL + wR.aR + wO.aO, test/Test/Reference.hs:138); the weights are the program.  The midstate is the SHA-256 state after
+// "sonic-hip/circuit/v1" || le64 n || le64 Q || wL || wR || wO, from which every statement's digest costs Q x 32 more bytes of hashing.
+// Layout, FS_MIDSTATE_SIZE = 112 bytes, every integer little-endian, the same on every host:
+//     0 ..  31   the chaining value: eight 32-bit words h0 .. h7
+//    32 ..  95   the bytes of the block that is not full yet: (length mod 64) of them, then zeros
+//    96 .. 103   length: the number of bytes hashed so far, 64 bits; = 36 + 96 Q n
+//   104 .. 111   Q, 64 bits
+// resume refuses a midstate whose fields disagree: Q < 1, a length that is not 36 + 96 Q n for an integer n >= 1, a non-zero byte behind
+// the pending ones.  There is ONE code path: the whole digest (csr.hpp, circuit_digest) is midstate + resume.
+constexpr size_t FS_MIDSTATE_SIZE = 112;
+constexpr uint64_t FS_CIRCUIT_HEAD = 36;      // the label and the two le64
+
+inline void fs_circuit_begin(Sha256& h, int64_t n, int64_t Q) {
+  h.update("sonic-hip/circuit/v1", 20);
+  FsTranscript::le64(h, n); FsTranscript::le64(h, Q);
+}
+inline void fs_circuit_absorb_dense(Sha256& h, int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO) {
+  h.update(wL, (size_t)(32 * Q * n)); h.update(wR, (size_t)(32 * Q * n)); h.update(wO, (size_t)(32 * Q * n));
+}
+// sparse rows are streamed in order as the dense bytes they stand for (32 zero bytes per absent entry); of a validated CSR (csr.hpp)
+inline void fs_circuit_absorb_csr(Sha256& h, int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val) {
+  static const uint8_t zeros[32 * 1024] = {0};
+  auto gap = [&](int64_t cnt) {
+    for (; cnt > 0; cnt -= 1024) h.update(zeros, 32 * (size_t)(cnt < 1024 ? cnt : 1024));
+  };
+  for (int64_t r = 0; r < 3 * Q; r++) {
+    int64_t at = 0;
+    for (int64_t k = row_ptr[r]; k < row_ptr[r + 1]; k++) {
+      gap(col[k] - at);
+      h.update(val + 32 * k, 32);
+      at = col[k] + 1;
+    }
+    gap(n - at);
+  }
+}
+inline void fs_midstate_save(const Sha256& h, int64_t Q, uint8_t out[FS_MIDSTATE_SIZE]) {
+  uint32_t chain[8];
+  uint64_t len;
+  h.get_state(chain, out + 32, &len);
+  for (int i = 0; i < 8; i++) for (int b = 0; b < 4; b++) out[4 * i + b] = (uint8_t)(chain[i] >> (8 * b));
+  for (int b = 0; b < 8; b++) { out[96 + b] = (uint8_t)(len >> (8 * b)); out[104 + b] = (uint8_t)((uint64_t)Q >> (8 * b)); }
+}
+// the Q a midstate holds (0 when its fields disagree)
+inline int64_t fs_midstate_Q(const uint8_t mid[FS_MIDSTATE_SIZE]) {
+  uint64_t len = 0, Q = 0;
+  for (int b = 0; b < 8; b++) { len |= (uint64_t)mid[96 + b] << (8 * b); Q |= (uint64_t)mid[104 + b] << (8 * b); }
+  if (Q < 1 || Q > (uint64_t)1 << 40 || len < FS_CIRCUIT_HEAD + 96 * Q || (len - FS_CIRCUIT_HEAD) % (96 * Q) != 0) return 0;
+  for (size_t i = (size_t)(len % 64); i < 64; i++) if (mid[32 + i]) return 0;
+  return (int64_t)Q;
+}
+// 0 = done; 1 = the midstate's fields disagree; 2 = cs[q] is not canonical (*bad_q = q)
+inline int fs_circuit_digest_resume(const uint8_t mid[FS_MIDSTATE_SIZE], const uint8_t* cs, uint8_t out[32], int64_t* bad_q = nullptr, bool check_cs = true) {
+  const int64_t Q = fs_midstate_Q(mid);
+  if (Q < 1) return 1;
+  for (int64_t q = 0; check_cs && q < Q; q++) {
+    Fr k;
+    memcpy(k.l, cs + 32 * q, 32);
+    if (!fp_is_canonical(k)) { if (bad_q) *bad_q = q; return 2; }
+  }
+  uint32_t chain[8];
+  uint64_t len = 0;
+  for (int i = 0; i < 8; i++) chain[i] = (uint32_t)mid[4 * i] | (uint32_t)mid[4 * i + 1] << 8 | (uint32_t)mid[4 * i + 2] << 16 | (uint32_t)mid[4 * i + 3] << 24;
+  for (int b = 0; b < 8; b++) len |= (uint64_t)mid[96 + b] << (8 * b);
+  Sha256 h;
+  h.put_state(chain, mid + 32, len);
+  h.update(cs, (size_t)(32 * Q));
+  h.finish(out);
+  return 0;
+}
+
+// The digest of a batch whose proofs carry their OWN constants (sonic_verifier_verify_batch_cs; verify_batch.hip): v1 with cs_k behind
+// proof k's challenges, under a label of its own, so that the randomizers bind the constants each proof is checked against.
+//   D = SHA-256("sonic-hip/batch-digest/v2" || le64 n || le64 Q || le64 d || the handle's circuit digest || srs id || le64 K ||
+//               K x (proof bytes || its 2 + 2Q challenges || cs_k))
+inline void fs_batch_digest_v2(int64_t n, int64_t Q, int64_t d, const uint8_t digest[32], const uint8_t srs_id[32], int64_t K, const uint8_t* proofs,
+                               size_t proof_bytes, const uint8_t* challenges, const uint8_t* cs, uint8_t out[32]) {
+  const size_t csz = 32 * (size_t)(2 + 2 * Q), ksz = 32 * (size_t)Q;
+  Sha256 h;
+  h.update("sonic-hip/batch-digest/v2", 25);
+  FsTranscript::le64(h, n); FsTranscript::le64(h, Q); FsTranscript::le64(h, d);
+  h.update(digest, 32); h.update(srs_id, 32);
+  FsTranscript::le64(h, K);
+  for (int64_t k = 0; k < K; k++) { h.update(proofs + proof_bytes * (size_t)k, proof_bytes); h.update(challenges + csz * (size_t)k, csz); h.update(cs + ksz * (size_t)k, ksz); }
+  h.finish(out);
+}
+
 }  // namespace sonic

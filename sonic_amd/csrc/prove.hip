@@ -641,6 +641,10 @@ static void enqueue_polynomials(sonic_prover_t* p, GroupQueue& q, ProofPass& w) 
     p->pend_asg[0] = nullptr;
     p->have_witness_digest = false;
   }
+  if (p->pend_cs) {
+    upload_fr_mont(ms, p->cs, p->pend_cs, Q, flags + 1);
+    p->pend_cs = nullptr;
+  }
   if ((w.need_g0 || w.need_T) && q.on(PH_R)) build_r1_enqueue(ms, p->aL.as<Fr>(), p->aR.as<Fr>(), p->aO.as<Fr>(), p->S.as<Fr>(), n, r1);
   ready(p->ev_r1);
   // the group that needs nothing but r(X,1): queued here, ahead of the other polynomials, when this call's circuit is still on the host
@@ -873,7 +877,7 @@ static int prove_enqueue(sonic_prover_t* p, const uint8_t* transcript) {
   challenge_pairs_host(p, transcript);
   // Launch-bound sizes replay the whole multi-stream enqueue as one hipGraph: captured on the second proof of a handle (the
   // first one grows the workspaces), every address in it is owned by the handle.
-  const bool pending = p->pend.set || p->pend_asg[0] != nullptr;
+  const bool pending = p->pend.set || p->pend_asg[0] != nullptr || p->pend_cs != nullptr;
   const bool want_graph = p->use_graph && p->proofs_done >= 1 && !profiler().on && p->phases == PH_ALL && !pending;
   const bool replay = want_graph && p->graph != nullptr;
   const bool capturing = want_graph && !replay && !p->graph_tried;
@@ -1085,16 +1089,24 @@ int sonic_prover_prove(sonic_prover_t* p, const uint8_t* transcript, uint8_t* ou
 
 // prove with the assignment of THIS call still in the caller's host buffers (uploaded inside the proof's queue: pend_asg)
 int prove_with_assignment(sonic_prover_t* p, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO, const uint8_t* transcript, uint8_t* out_proof) {
+  return prove_with_statement(p, aL, aR, aO, nullptr, transcript, out_proof);
+}
+// ... and its constants (pend_cs), either or both
+int prove_with_statement(sonic_prover_t* p, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO, const uint8_t* cs, const uint8_t* transcript,
+                         uint8_t* out_proof) {
   std::lock_guard<std::mutex> g(p->mu);
   if (p->in_flight) { set_error("prove: a submitted proof has not been collected yet"); return SONIC_ERR_INVALID_ARG; }
   int rc = whole_proof_only(p, "prove");
   if (rc) return rc;
-  p->pend_asg[1] = aR; p->pend_asg[2] = aO; p->pend_asg[0] = aL;
+  if (!aL && !p->have_assignment) { set_error("prove: no assignment set"); return SONIC_ERR_INVALID_ARG; }
+  if (aL) { p->pend_asg[1] = aR; p->pend_asg[2] = aO; p->pend_asg[0] = aL; }
+  p->pend_cs = cs;
   rc = prove_enqueue(p, transcript);
   if (!rc) rc = prove_finish(p, out_proof);
   else if (p->st) (void)hipStreamSynchronize(p->st);
   p->pend_asg[0] = nullptr;
-  p->have_assignment = rc == SONIC_OK;          // (a failed call may have left a partly converted assignment behind)
+  p->pend_cs = nullptr;
+  if (aL) p->have_assignment = rc == SONIC_OK;          // (a failed call may have left a partly converted assignment behind)
   return rc;
 }
 

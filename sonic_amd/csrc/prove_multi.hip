@@ -193,19 +193,20 @@ int sonic_prove_shared(sonic_prover_t* const* provers, int world, const uint8_t*
   return sonic_proof_from_shares(Q, world, shares.data(), transcript, out_proof);
 }
 
-int sonic_prove_batch(sonic_prover_t* const* provers, int n_provers, int64_t K, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO,
-                      const uint8_t* transcripts, uint8_t* out_proofs, int* out_status) {
+// sonic_prove_batch (cs == null) and sonic_prove_batch_statements (cs: K x Q constants, proof i's uploaded at the head of its own queue)
+static int prove_batch_impl(const char* who, sonic_prover_t* const* provers, int n_provers, int64_t K, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO,
+                            const uint8_t* cs, const uint8_t* transcripts, uint8_t* out_proofs, int* out_status) {
   if (!provers || n_provers < 1 || n_provers > 1024 || K < 0 || (K > 0 && (!transcripts || !out_proofs))) return SONIC_ERR_INVALID_ARG;
   const bool per_proof = aL || aR || aO;
-  if (per_proof && !(aL && aR && aO)) { set_error("sonic_prove_batch: aL, aR, aO must be given together (or all NULL: the handles' resident assignments)"); return SONIC_ERR_INVALID_ARG; }
+  if (per_proof && !(aL && aR && aO)) { set_error("%s: aL, aR, aO must be given together (or all NULL: the handles' resident assignments)", who); return SONIC_ERR_INVALID_ARG; }
   for (int i = 0; i < n_provers; i++) {
     if (!provers[i]) return SONIC_ERR_INVALID_ARG;
-    if (provers[i]->n != provers[0]->n || provers[i]->Q != provers[0]->Q) { set_error("sonic_prove_batch: handle %d proves another circuit shape (n, Q) than handle 0", i); return SONIC_ERR_INVALID_ARG; }
-    if (provers[i]->share_world > 1) { set_error("sonic_prove_batch: handle %d runs one rank's share of a proof (sonic_prover_set_share)", i); return SONIC_ERR_INVALID_ARG; }
-    for (int q = 0; q < i; q++) if (provers[q] == provers[i]) { set_error("sonic_prove_batch: handle %d appears twice", i); return SONIC_ERR_INVALID_ARG; }
+    if (provers[i]->n != provers[0]->n || provers[i]->Q != provers[0]->Q) { set_error("%s: handle %d proves another circuit shape (n, Q) than handle 0", who, i); return SONIC_ERR_INVALID_ARG; }
+    if (provers[i]->share_world > 1) { set_error("%s: handle %d runs one rank's share of a proof (sonic_prover_set_share)", who, i); return SONIC_ERR_INVALID_ARG; }
+    for (int q = 0; q < i; q++) if (provers[q] == provers[i]) { set_error("%s: handle %d appears twice", who, i); return SONIC_ERR_INVALID_ARG; }
   }
   const long n = provers[0]->n, Q = provers[0]->Q;
-  const size_t psz = sonic_proof_size(Q), tsz = 32 * (size_t)(8 + 2 * Q), asz = 32 * (size_t)n;
+  const size_t psz = sonic_proof_size(Q), tsz = 32 * (size_t)(8 + 2 * Q), asz = 32 * (size_t)n, ksz = 32 * (size_t)Q;
   std::vector<int> status((size_t)K, SONIC_OK);
   std::vector<std::string> errs((size_t)n_provers);
   std::vector<int64_t> first_bad((size_t)n_provers, -1);
@@ -213,7 +214,16 @@ int sonic_prove_batch(sonic_prover_t* const* provers, int n_provers, int64_t K, 
     for (int64_t i = h; i < K; i += n_provers) {
       int rc = SONIC_OK;
       try {
-        if (per_proof) rc = prove_with_assignment(provers[h], aL + asz * (size_t)i, aR + asz * (size_t)i, aO + asz * (size_t)i, transcripts + tsz * (size_t)i, out_proofs + psz * (size_t)i);
+        if (cs) {
+          // (checked here, before anything of proof i is queued: its status, and the handle keeps the constants it has)
+          for (long q = 0; q < Q && !rc; q++) {
+            Fr k;
+            memcpy(k.l, cs + ksz * (size_t)i + 32 * (size_t)q, 32);
+            if (!fp_is_canonical(k)) { set_error("%s: cs[%ld] of proof %ld is not a canonical field element", who, q, (long)i); rc = SONIC_ERR_BAD_ENCODING; }
+          }
+          if (!rc) rc = prove_with_statement(provers[h], per_proof ? aL + asz * (size_t)i : nullptr, per_proof ? aR + asz * (size_t)i : nullptr,
+                                             per_proof ? aO + asz * (size_t)i : nullptr, cs + ksz * (size_t)i, transcripts + tsz * (size_t)i, out_proofs + psz * (size_t)i);
+        } else if (per_proof) rc = prove_with_assignment(provers[h], aL + asz * (size_t)i, aR + asz * (size_t)i, aO + asz * (size_t)i, transcripts + tsz * (size_t)i, out_proofs + psz * (size_t)i);
         else rc = sonic_prover_prove(provers[h], transcripts + tsz * (size_t)i, out_proofs + psz * (size_t)i);
         if (rc && first_bad[(size_t)h] < 0) { first_bad[(size_t)h] = i; char b[512]; sonic_last_error(b, sizeof b); errs[(size_t)h] = b; }
       } catch (...) { rc = SONIC_ERR_HIP; }                          // (nothing may leave a thread's body: std::terminate)
@@ -230,10 +240,23 @@ int sonic_prove_batch(sonic_prover_t* const* provers, int n_provers, int64_t K, 
   for (int64_t i = 0; i < K; i++)
     if (status[(size_t)i]) {
       const int h = (int)(i % n_provers);
-      set_error("sonic_prove_batch, proof %ld (handle %d, device %d): %s", (long)i, h, provers[h]->device, errs[(size_t)h].c_str());
+      set_error("%s, proof %ld (handle %d, device %d): %s", who, (long)i, h, provers[h]->device, errs[(size_t)h].c_str());
       return status[(size_t)i];
     }
   return SONIC_OK;
+}
+
+
+int sonic_prove_batch(sonic_prover_t* const* provers, int n_provers, int64_t K, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO,
+                      const uint8_t* transcripts, uint8_t* out_proofs, int* out_status) {
+  return prove_batch_impl("sonic_prove_batch", provers, n_provers, K, aL, aR, aO, nullptr, transcripts, out_proofs, out_status);
+}
+
+int sonic_prove_batch_statements(sonic_prover_t* const* provers, int n_provers, int64_t K, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO,
+                                 const uint8_t* cs, const uint8_t* transcripts, uint8_t* out_proofs, int* out_status) {
+  try { DeviceScope probe(-1); } catch (const HipFail& f) { return f.code; }      // (no device: SONIC_ERR_NO_DEVICE whatever the arguments are)
+  if (K > 0 && !cs) { set_error("sonic_prove_batch_statements: cs is NULL (sonic_prove_batch proves with the handles' constants)"); return SONIC_ERR_INVALID_ARG; }
+  return prove_batch_impl("sonic_prove_batch_statements", provers, n_provers, K, aL, aR, aO, cs, transcripts, out_proofs, out_status);
 }
 
 }  // extern "C"

@@ -129,6 +129,12 @@ struct sonic_prover {
   // the proof's own queue instead of by a sonic_prover_set_assignment that waits for the device before the proof may even be queued -- beside
   // another handle's accumulation that wait was ~1 ms per proof (config5: 99 against 113 proofs/s, profiles/r06_bench.json)
   const uint8_t* pend_asg[3] = {nullptr, nullptr, nullptr};
+  // and for the CONSTANTS of this call (sonic_prove_batch_statements: one statement per proof): Q canonical field elements, checked by the
+  // caller, uploaded into `cs` in place at the same point of the queue -- k(y) reads them on the transform's stream, which waits for the
+  // main stream's polynomials anyway
+  const uint8_t* pend_cs = nullptr;
+  // sonic_prover_eval_constraints (statement.hip): the staging buffer of the assignments of one chunk, the partial sums, the results
+  struct StatementBufs { DevBuf stage, partial, out, gates; } stm;
   // runs of equal coefficients in the S_j of a handle that is not prepared (poly.hip, k_run_tiles): per j the masked copy of s(X, y_j),
   // the tile records and the (scalar, running-sum point) slots of the small MSM that stands for the runs; its sum lands in the side
   // slot S_extra(j) (proof_layout.hpp), where a prepared handle keeps sum_q y_j^{n+q} C_q, and the host adds it the same way
@@ -250,6 +256,10 @@ int read_flags(hipStream_t st, DevBuf& flags);
 int flags_to_status(int f, const char* who);
 // (defined inside prove.hip's extern "C" block, not exported)
 extern "C" int prove_with_assignment(sonic_prover_t* p, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO, const uint8_t* transcript, uint8_t* out_proof);
+// the same with the constants of this call as well (cs: Q canonical field elements, or null: the handle's; aL, aR, aO all null: the
+// resident assignment)
+extern "C" int prove_with_statement(sonic_prover_t* p, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO, const uint8_t* cs, const uint8_t* transcript,
+                                    uint8_t* out_proof);
 // (prove.hip) what sonic_prover_new[_csr] and the one-shot calls share: the checks of a circuit against an SRS, a handle for an admitted
 // circuit, and the hand-over of the next call's circuit to a handle that exists (uploaded inside its next proof)
 int prover_admits(const char* who, const sonic_srs* srs, const CircuitView& c);

@@ -37,6 +37,19 @@ class Sha256 {
     update(pad, padlen + 8);
     for (int i = 0; i < 8; i++) { out[4 * i] = (uint8_t)(h_[i] >> 24); out[4 * i + 1] = (uint8_t)(h_[i] >> 16); out[4 * i + 2] = (uint8_t)(h_[i] >> 8); out[4 * i + 3] = (uint8_t)h_[i]; }
   }
+  // the state between two updates (fs.hpp, the circuit midstate): the chaining value, the bytes of the block that is not full yet (the
+  // rest of `pending` zero) and the number of bytes hashed so far; put_state continues from it.  pending holds length % 64 bytes.
+  void get_state(uint32_t chain[8], uint8_t pending[64], uint64_t* length) const {
+    memcpy(chain, h_, sizeof h_);
+    memset(pending, 0, 64);
+    memcpy(pending, buf_, fill_);
+    *length = len_;
+  }
+  void put_state(const uint32_t chain[8], const uint8_t pending[64], uint64_t length) {
+    memcpy(h_, chain, sizeof h_);
+    len_ = length; fill_ = (size_t)(length % 64);
+    memcpy(buf_, pending, fill_);
+  }
 
  private:
   static uint32_t rotr(uint32_t x, int k) { return (x >> k) | (x << (32 - k)); }

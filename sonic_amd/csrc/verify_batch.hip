@@ -170,6 +170,7 @@ struct sonic_verifier {
   std::vector<int64_t> ms;              // the distinct max of a proof's checks: n and d (one entry when n == d)
   std::vector<G2Affine> hm;             // h^{x^{m - d}} for them
   uint8_t digest[32], srs_id[32];
+  uint8_t midstate[FS_MIDSTATE_SIZE];   // the circuit digest before the constants (fs.hpp): each statement's digest from it (the `_cs` calls)
   std::vector<uint8_t> cs;
   std::mutex mu;                        // one call at a time per handle
   hipStream_t st = nullptr;
@@ -309,9 +310,11 @@ void decompress_device(sonic_verifier* v, long K, const uint8_t* proofs_z, std::
 }
 
 // challenges: K blocks of (2 + 2Q) x 32 bytes (y, z, then the pairs).  accepted: null, or the per-point flags of a batch that decompress_device
-// has already validated into v->pts
+// has already validated into v->pts.  cs_each: null -- every proof is checked against the handle's constants, batch digest v1 -- or K x Q
+// constants, proof k's own: k(y) of proof k is summed over cs_k (Q more field products per proof, on the host beside the K (3Q + 4) of the
+// scalars), a non-canonical cs_k makes proof k malformed, and the batch digest is v2, which hashes cs_k behind proof k's challenges.
 int verify_batch_core(sonic_verifier* v, long K, const uint8_t* proofs, const uint8_t* challenges, const uint8_t* seed_in, int* all_accepted, uint8_t* each,
-                      const std::vector<uint8_t>* accepted = nullptr) {
+                      const std::vector<uint8_t>* accepted = nullptr, const uint8_t* cs_each = nullptr) {
   const long Q = v->Q, NP = 4 * Q + 7, NC = 3 * Q + 4;
   const size_t psz = sonic_proof_size(Q), csz = 32 * (size_t)(2 + 2 * Q);
   const size_t N = (size_t)K * (size_t)NP;
@@ -332,6 +335,7 @@ int verify_batch_core(sonic_verifier* v, long K, const uint8_t* proofs, const ui
     auto take = [&](const uint8_t* enc, int32_t& o) { o = idx++; if (!accepted) memcpy(dst + 96 * (size_t)o, enc, 96); return true; };
     const uint8_t* ch = challenges + csz * (size_t)k;
     b.good[(size_t)k] = parse_proof(proofs + psz * (size_t)k, Q, ch, ch + 32, ch + 64, views[(size_t)k], yms[(size_t)k], zms[(size_t)k], take) ? 1 : 0;
+    for (long q = 0; cs_each && q < Q && b.good[(size_t)k]; q++) { Fr c; if (!load_fr(cs_each + 32 * (size_t)(k * Q + q), c)) b.good[(size_t)k] = 0; }
     if (!b.good[(size_t)k] && first_bad < 0) first_bad = k;
   }
   host_phase("verify_batch:host_decode", now_ms() - t0);
@@ -346,7 +350,8 @@ int verify_batch_core(sonic_verifier* v, long K, const uint8_t* proofs, const ui
     if (!ok) { b.good[(size_t)k] = 0; if (first_bad < 0 || k < first_bad) first_bad = k; }
   }
   const bool any_malformed = first_bad >= 0;
-  if (any_malformed) set_error("verify_batch: proof %ld is malformed (non-canonical field element, or point off the curve or outside the order-r subgroup)", first_bad);
+  if (any_malformed) set_error("verify_batch: proof %ld is malformed (non-canonical field element%s, or point off the curve or outside the order-r subgroup)", first_bad,
+                               cs_each ? " in the proof or its constants" : "");
 
   // 3. s(u_k, v_k) (device); a malformed proof rides along as the pair (1, 1)
   std::vector<Fr> us((size_t)K), vs((size_t)K), svs;
@@ -364,7 +369,8 @@ int verify_batch_core(sonic_verifier* v, long K, const uint8_t* proofs, const ui
   // 4. the randomizers and the scalars of the fold (host): rho on W, rho z on W, rho on F by class of max
   t0 = now_ms();
   uint8_t D[32];
-  {
+  if (cs_each) fs_batch_digest_v2(v->n, Q, v->d, v->digest, v->srs_id, K, proofs, psz, challenges, cs_each, D);
+  else {
     Sha256 h;
     h.update("sonic-hip/batch-digest/v1", 25);
     le64(h, v->n); le64(h, Q); le64(h, v->d);
@@ -375,14 +381,15 @@ int verify_batch_core(sonic_verifier* v, long K, const uint8_t* proofs, const ui
   }
   const size_t nclass = v->ms.size();
   std::vector<Fr> sc((2 + nclass) * N, Fr::zero());          // Montgomery while they are summed
-  const CircuitView cview{v->n, Q, v->cs.data(), true, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  CircuitView cview{v->n, Q, v->cs.data(), true, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   std::vector<uint8_t> rho((size_t)(16 * NC));
   long good_count = 0;
   for (long k = 0; k < K; k++) {
     if (!b.good[(size_t)k]) continue;
     good_count++;
     Fr t;
-    proof_t(cview, views[(size_t)k], yms[(size_t)k], t);      // (cs was checked when the handle was made)
+    if (cs_each) cview.cs = cs_each + 32 * (size_t)(k * Q);
+    proof_t(cview, views[(size_t)k], yms[(size_t)k], t);      // (cs was checked when the handle was made, cs_k in step 1)
     const auto checks = proof_checks<int32_t>(v->n, v->d, views[(size_t)k], yms[(size_t)k], zms[(size_t)k], t, svs[(size_t)k]);
     batch_randomizers(seed, D, (int64_t)k * NC, NC, rho.data());
     const size_t base = (size_t)(k * NP);
@@ -441,21 +448,27 @@ int verify_batch_core(sonic_verifier* v, long K, const uint8_t* proofs, const ui
 
 // the Fiat-Shamir form: the challenges each proof determines (fs.hpp), in sonic_verify's order; a proof whose own u, v are not its
 // transcript's is rejected
-int verify_fs_batch_core(sonic_verifier* v, long K, const uint8_t* proofs, const uint8_t* seed, int* all_accepted, uint8_t* each, const std::vector<uint8_t>* accepted) {
+// cs_each (the `_cs` form): proof k's transcript starts from the digest of ITS statement, resume(midstate, cs_k); a cs_k that is not canonical has
+// no digest -- the proof rides along under the handle's and verify_batch_core refuses it as malformed
+int verify_fs_batch_core(sonic_verifier* v, long K, const uint8_t* proofs, const uint8_t* seed, int* all_accepted, uint8_t* each, const std::vector<uint8_t>* accepted,
+                         const uint8_t* cs_each = nullptr) {
   const long Q = v->Q;
   const size_t psz = sonic_proof_size(Q), csz = 32 * (size_t)(2 + 2 * Q);
   std::vector<uint8_t> chal(csz * (size_t)K), ch(32 * (size_t)(4 + 2 * Q)), mine((size_t)K, 1);
   bool all_mine = true;
   for (int64_t k = 0; k < K; k++) {
     const uint8_t* proof = proofs + psz * (size_t)k;
-    fs_challenges_of_proof(v->n, Q, v->d, v->digest, v->srs_id, proof, ch.data());
+    uint8_t dk[32];
+    memcpy(dk, v->digest, 32);
+    if (cs_each && fs_circuit_digest_resume(v->midstate, cs_each + 32 * (size_t)(k * Q), dk) != 0) memcpy(dk, v->digest, 32);
+    fs_challenges_of_proof(v->n, Q, v->d, dk, v->srs_id, proof, ch.data());
     if (memcmp(proof + psz - 64, &ch[32 * (size_t)(2 + 2 * Q)], 64) != 0) { mine[(size_t)k] = 0; all_mine = false; }
     uint8_t* o = &chal[csz * (size_t)k];
     memcpy(o, &ch[0], 64);
     for (long j = 0; j < Q; j++) { memcpy(o + 64 + 64 * j, &ch[32 * (size_t)(2 + j)], 32); memcpy(o + 96 + 64 * j, &ch[32 * (size_t)(2 + Q + j)], 32); }
   }
   if (!all_mine && !each) return SONIC_OK;                      // rejected, and nobody asked which
-  const int rc = verify_batch_core(v, K, proofs, chal.data(), seed, all_accepted, each, accepted);
+  const int rc = verify_batch_core(v, K, proofs, chal.data(), seed, all_accepted, each, accepted, cs_each);
   if (rc) return rc;
   if (!all_mine) {
     *all_accepted = 0;
@@ -481,7 +494,8 @@ int verifier_new(const char* who, const sonic_srs_t* srs, const CircuitView& c, 
   if (v->d != n) v->ms.push_back(v->d);
   v->hm.resize(v->ms.size());
   for (size_t i = 0; i < v->ms.size(); i++) { rc = pc_v_element(srs, v->ms[i], v->hm[i]); if (rc) return rc; }
-  circuit_digest(c, v->digest);
+  circuit_midstate(c, v->midstate);
+  fs_circuit_digest_resume(v->midstate, c.cs, v->digest);
   rc = sonic_fs_srs_id(srs, v->srs_id);
   if (rc) return rc;
   // the circuit as CSR, whichever form it came in (dense: the non-zero entries), values Montgomery
@@ -613,6 +627,36 @@ int sonic_verifier_verify_fs_batch_z(sonic_verifier_t* v, int64_t K, const uint8
   std::vector<uint8_t> proofs, accepted;
   decompress_device(v, (long)K, proofs_z, proofs, accepted);
   return verify_fs_batch_core(v, (long)K, proofs.data(), seed, all_accepted, each, &accepted);
+  VB_END
+}
+
+// one statement per proof: proof k against the handle's weights and cs_k (compressed: 0 = 96-byte points, 1 = 48-byte points)
+int sonic_verifier_verify_batch_cs(sonic_verifier_t* v, int64_t K, const uint8_t* proofs, int compressed, const uint8_t* challenges, const uint8_t* cs,
+                                   const uint8_t seed[32], int* all_accepted, uint8_t* each) {
+  if (all_accepted) *all_accepted = 0;
+  VB_BEGIN(v ? v->device : -1)                      // (first: without a device the answer is SONIC_ERR_NO_DEVICE whatever the arguments are)
+  if (!v || !proofs || !challenges || !cs || !all_accepted || (compressed != 0 && compressed != 1)) { set_error("sonic_verifier_verify_batch_cs: bad argument"); return SONIC_ERR_INVALID_ARG; }
+  int rc = batch_size_ok("sonic_verifier_verify_batch_cs", v, K);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> g(v->mu);
+  if (!compressed) return verify_batch_core(v, (long)K, proofs, challenges, seed, all_accepted, each, nullptr, cs);
+  std::vector<uint8_t> full, accepted;
+  decompress_device(v, (long)K, proofs, full, accepted);
+  return verify_batch_core(v, (long)K, full.data(), challenges, seed, all_accepted, each, &accepted, cs);
+  VB_END
+}
+int sonic_verifier_verify_fs_batch_cs(sonic_verifier_t* v, int64_t K, const uint8_t* proofs, int compressed, const uint8_t* cs, const uint8_t seed[32],
+                                      int* all_accepted, uint8_t* each) {
+  if (all_accepted) *all_accepted = 0;
+  VB_BEGIN(v ? v->device : -1)                      // (first: without a device the answer is SONIC_ERR_NO_DEVICE whatever the arguments are)
+  if (!v || !proofs || !cs || !all_accepted || (compressed != 0 && compressed != 1)) { set_error("sonic_verifier_verify_fs_batch_cs: bad argument"); return SONIC_ERR_INVALID_ARG; }
+  int rc = batch_size_ok("sonic_verifier_verify_fs_batch_cs", v, K);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> g(v->mu);
+  if (!compressed) return verify_fs_batch_core(v, (long)K, proofs, seed, all_accepted, each, nullptr, cs);
+  std::vector<uint8_t> full, accepted;
+  decompress_device(v, (long)K, proofs, full, accepted);
+  return verify_fs_batch_core(v, (long)K, full.data(), seed, all_accepted, each, &accepted, cs);
   VB_END
 }
 

@@ -222,6 +222,35 @@ class Prover:
         assert aL.shape[0] == self.n and aR.shape[0] == self.n and aO.shape[0] == self.n
         _lib.check(_lib.lib().sonic_prover_set_assignment(self._h, aL.ctypes.data, aR.ctypes.data, aO.ctypes.data))
 
+    def set_constants(self, cs) -> None:
+        """the constants of the next statement (sonic_prover_set_constants): the handle's cs overwritten in place -- the assignment, the
+        prepared rows, the share mode and a captured proof graph stay.  cs: Q ints, or Q x 32 canonical bytes (passed as they are)"""
+        raw = _constants_bytes(cs, self.Q, "set_constants")
+        _lib.check(_lib.lib().sonic_prover_set_constants(self._h, raw))
+
+    def eval_constraints(self, assignments=None):
+        """the constants the assignments satisfy under this handle's weights, and the multiplication gates they break, on the GPU
+        (sonic_prover_eval_constraints): ([cs of assignment b as Q ints], [(bad_count, first_bad or -1)]).  assignments: Assignment
+        objects, or None for the handle's resident assignment (one entry)."""
+        n, Q = self.n, self.Q
+        if assignments is None:
+            B, ptrs = 1, (None, None, None)
+        else:
+            assignments = list(assignments)
+            B = len(assignments)
+            if B < 1:
+                raise ValueError("eval_constraints: need at least one assignment (or None: the resident one)")
+            keep = [np.ascontiguousarray(np.stack([fr_array(getattr(a, k)) for a in assignments])) for k in ("aL", "aR", "aO")]
+            if any(a.shape != (B, n, 32) for a in keep):
+                raise ValueError(f"eval_constraints: every assignment needs n = {n} values in aL, aR, aO")
+            ptrs = tuple(a.ctypes.data for a in keep)
+        out = np.zeros((B, Q, 32), np.uint8)
+        gates = np.zeros((B, 2), np.int64)
+        _lib.check(_lib.lib().sonic_prover_eval_constraints(self._h, B, *ptrs, out.ctypes.data, gates.ctypes.data))
+        raw = out.tobytes()
+        cs = [[int.from_bytes(raw[32 * (b * Q + q):32 * (b * Q + q) + 32], "little") for q in range(Q)] for b in range(B)]
+        return cs, [(int(c), int(f)) for c, f in gates]
+
     def prove_bytes(self, transcript) -> bytes:
         tr = fr_array(transcript)
         assert tr.shape[0] == transcript_len(self.Q)
@@ -338,11 +367,21 @@ def prove_shared(provers, transcript) -> bytes:
     return out.raw
 
 
-def prove_batch(provers, transcripts, assignments=None) -> List[bytes]:
+def _constants_bytes(cs, Q: int, who: str) -> bytes:
+    """one statement's constants as Q x 32 bytes: bytes as they are (a non-canonical value must reach the library, which refuses it),
+    ints little-endian without reduction"""
+    raw = bytes(cs) if isinstance(cs, (bytes, bytearray, memoryview)) else b"".join(int(c).to_bytes(32, "little") for c in cs)
+    if len(raw) != 32 * Q:
+        raise ValueError(f"{who}: need Q = {Q} constants (32 bytes each)")
+    return raw
+
+
+def prove_batch(provers, transcripts, assignments=None, constants=None) -> List[bytes]:
     """`mapM prove` over K statements of one circuit, spread over several prover handles (sonic_prove_batch: proof i on handle
     i % len(provers), one host thread per handle, no collective): the throughput mode of BASELINE's "batch of 64 independent proofs
     streamed over 8 GPUs".  assignments: K Assignment objects, or None to prove every statement with the handles' resident
-    assignment (then only the transcripts differ)."""
+    assignment (then only the transcripts differ).  constants: None, or one cs (Q ints or Q x 32 bytes) per proof -- one statement
+    per proof (sonic_prove_batch_statements); afterwards each handle holds the constants of the last proof it ran."""
     provers = list(provers)
     Q, n = provers[0].Q, provers[0].n
     K = len(transcripts)
@@ -359,6 +398,13 @@ def prove_batch(provers, transcripts, assignments=None) -> List[bytes]:
         aO = np.ascontiguousarray(np.stack([fr_array(a.aO) for a in assignments]))
         assert aL.shape[1] == n and aR.shape == aL.shape and aO.shape == aL.shape
     ptr = lambda a: None if a is None else a.ctypes.data       # noqa: E731
+    if constants is not None:
+        constants = list(constants)
+        if len(constants) != K:
+            raise ValueError("prove_batch: one set of constants per proof")
+        cs = b"".join(_constants_bytes(c, Q, "prove_batch") for c in constants) or bytes(32)
+        _lib.check(_lib.lib().sonic_prove_batch_statements(_handle_array(provers), len(provers), K, ptr(aL), ptr(aR), ptr(aO), cs, tr.ctypes.data, out.ctypes.data, status))
+        return [out[i].tobytes() for i in range(K)]
     _lib.check(_lib.lib().sonic_prove_batch(_handle_array(provers), len(provers), K, ptr(aL), ptr(aR), ptr(aO), tr.ctypes.data, out.ctypes.data, status))
     return [out[i].tobytes() for i in range(K)]
 
@@ -483,6 +529,27 @@ def fs_circuit_digest(circuit: ArithCircuit) -> bytes:
     n, Q, suffix, args, _keep = _circuit_args(circuit)         # (sparse: the same digest from the rows; host only)
     out = C.create_string_buffer(32)
     _lib.check(getattr(_lib.lib(), "sonic_fs_circuit_digest" + suffix)(n, Q, *args, out))
+    return out.raw
+
+
+def fs_circuit_midstate(circuit) -> bytes:
+    """the SHA-256 state of the circuit digest after the gate weights (sonic_fs_circuit_midstate[_csr]; the circuit's cs is not read):
+    O(Q n) hashing once per circuit, after which fs_circuit_digest_resume gives each statement's digest from Q x 32 bytes"""
+    n, Q, suffix, args, _keep = _circuit_args(circuit)
+    out = C.create_string_buffer(_lib.FS_MIDSTATE_SIZE)
+    _lib.check(getattr(_lib.lib(), "sonic_fs_circuit_midstate" + suffix)(n, Q, *args[:-1], out))
+    return out.raw
+
+
+def fs_circuit_digest_resume(state: bytes, cs) -> bytes:
+    """fs_circuit_digest of the circuit behind `state` with the constants cs (Q ints or Q x 32 bytes), byte for byte"""
+    state = bytes(state)
+    if len(state) != _lib.FS_MIDSTATE_SIZE:
+        raise ValueError(f"fs_circuit_digest_resume: a midstate is {_lib.FS_MIDSTATE_SIZE} bytes")
+    Q = int.from_bytes(state[104:112], "little")
+    raw = _constants_bytes(cs, Q, "fs_circuit_digest_resume") if 0 < Q < 1 << 40 else bytes(32)      # (a bad Q: the library refuses the midstate)
+    out = C.create_string_buffer(32)
+    _lib.check(_lib.lib().sonic_fs_circuit_digest_resume(state, raw, out))
     return out.raw
 
 
@@ -671,9 +738,16 @@ class Verifier:
         _lib.check(call(C.byref(ok), flags))
         return (bool(ok.value), [bool(b) for b in flags.raw]) if each else bool(ok.value)
 
-    def verify_batch(self, proofs, transcripts, seed=None, each: bool = False):
+    def _constants(self, constants, K):
+        constants = list(constants)
+        if len(constants) != K:
+            raise ValueError("Verifier: one set of constants per proof")
+        return b"".join(_constants_bytes(c, self.Q, "Verifier") for c in constants)
+
+    def verify_batch(self, proofs, transcripts, seed=None, each: bool = False, constants=None):
         """proofs: Proof objects, proof bytes, or compressed proof bytes (all of them: the `_z` entry point); transcripts: one (y, z, yzs) per proof, as for verify().  True iff every proof is
-        accepted; with each=True also the per-proof verdicts."""
+        accepted; with each=True also the per-proof verdicts.  constants: None -- every proof against the circuit's cs -- or one cs per
+        proof (Q ints or Q x 32 bytes): proof k against the handle's weights and ITS constants (sonic_verifier_verify_batch_cs)."""
         proofs, transcripts = list(proofs), list(transcripts)
         if len(transcripts) != len(proofs):
             raise ValueError("verify_batch: one (y, z, yzs) transcript per proof")
@@ -685,13 +759,20 @@ class Verifier:
                 raise ValueError(f"verify_batch: yzs must hold {self.Q} (y_j, z_j) pairs")
             blocks.append(fr(y) + fr(z) + b"".join(fr(a) + fr(b) for a, b in yzs))
         (raw, z), chal, sd, K = self._proof_bytes(proofs), b"".join(blocks), self._seed(seed), len(proofs)
+        if constants is not None:
+            cs, call = self._constants(constants, K), _lib.lib().sonic_verifier_verify_batch_cs
+            return self._result(K, lambda ok, flags: call(self._h, K, raw, int(z == "_z"), chal, cs, sd, ok, flags), each)
         call = getattr(_lib.lib(), "sonic_verifier_verify_batch" + z)
         return self._result(K, lambda ok, flags: call(self._h, K, raw, chal, sd, ok, flags), each)
 
-    def verify_fs_batch(self, proofs, seed=None, each: bool = False):
-        """the same for Fiat-Shamir proofs (prove_fs): every proof's challenges are recomputed from the circuit and the proof"""
+    def verify_fs_batch(self, proofs, seed=None, each: bool = False, constants=None):
+        """the same for Fiat-Shamir proofs (prove_fs): every proof's challenges are recomputed from the circuit and the proof -- with
+        constants (one cs per proof), from the digest of that proof's own statement (sonic_verifier_verify_fs_batch_cs)"""
         proofs = list(proofs)
         (raw, z), sd, K = self._proof_bytes(proofs), self._seed(seed), len(proofs)
+        if constants is not None:
+            cs, call = self._constants(constants, K), _lib.lib().sonic_verifier_verify_fs_batch_cs
+            return self._result(K, lambda ok, flags: call(self._h, K, raw, int(z == "_z"), cs, sd, ok, flags), each)
         call = getattr(_lib.lib(), "sonic_verifier_verify_fs_batch" + z)
         return self._result(K, lambda ok, flags: call(self._h, K, raw, sd, ok, flags), each)
 
