@@ -1,6 +1,6 @@
 // Compressed point encodings (include/sonic_hip.h, "Compressed encodings"; point-level code: compress.hpp): the four bulk kernels, one
 // thread per point, their C entry points, and one proof's re-encoding on the host.  The batched verifier (verify_batch.hip) and the
-// compressed SRS container (api.hip) run the same kernels through the *_enqueue functions.
+// compressed SRS container (srs_api.hip) run the same kernels through the *_enqueue functions.
 #include <string.h>
 #include "verify_host.hpp"
 #include "compress.hpp"
@@ -64,11 +64,6 @@ void g2_compress_enqueue(hipStream_t st, const G2Affine* in, uint8_t* d_out96, l
 
 using namespace sonic;
 
-#define Z_BEGIN try { ::sonic::DeviceScope _scope(-1);
-#define Z_END                                                          \
-  } catch (const HipFail& f) { return f.code; }                        \
-  catch (const std::exception& e) { set_error("%s", e.what()); return SONIC_ERR_HIP; }
-
 namespace {
 
 // the verdicts of a bulk decompression: into the caller's array, or (flags == NULL) the first refused point fails the call
@@ -89,7 +84,7 @@ extern "C" {
 int sonic_g1_decompress(const uint8_t* in48, int64_t n, int check_subgroup, uint8_t* out96, uint8_t* flags) {
   if (n < 0 || (n > 0 && (!in48 || !out96))) { set_error("sonic_g1_decompress: bad argument"); return SONIC_ERR_INVALID_ARG; }
   if (n == 0) return SONIC_OK;
-  Z_BEGIN
+  API_BEGIN
   CallLease lease;
   hipStream_t st = lease.st();
   DevBuf raw(48 * (size_t)n), bytes(96 * (size_t)n), fl((size_t)n);
@@ -100,13 +95,13 @@ int sonic_g1_decompress(const uint8_t* in48, int64_t n, int check_subgroup, uint
   HIP_OK(hipMemcpyAsync(hfl.data(), fl.p, (size_t)n, hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));
   return report_flags("sonic_g1_decompress", hfl, flags);
-  Z_END
+  API_CATCH
 }
 
 int sonic_g2_decompress(const uint8_t* in96, int64_t n, int check_subgroup, uint8_t* out192, uint8_t* flags) {
   if (n < 0 || (n > 0 && (!in96 || !out192))) { set_error("sonic_g2_decompress: bad argument"); return SONIC_ERR_INVALID_ARG; }
   if (n == 0) return SONIC_OK;
-  Z_BEGIN
+  API_BEGIN
   CallLease lease;
   hipStream_t st = lease.st();
   DevBuf raw(96 * (size_t)n), bytes(192 * (size_t)n), fl((size_t)n);
@@ -117,13 +112,13 @@ int sonic_g2_decompress(const uint8_t* in96, int64_t n, int check_subgroup, uint
   HIP_OK(hipMemcpyAsync(hfl.data(), fl.p, (size_t)n, hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));
   return report_flags("sonic_g2_decompress", hfl, flags);
-  Z_END
+  API_CATCH
 }
 
 int sonic_g1_compress(const uint8_t* points96, int64_t n, uint8_t* out48) {
   if (n < 0 || (n > 0 && (!points96 || !out48))) { set_error("sonic_g1_compress: bad argument"); return SONIC_ERR_INVALID_ARG; }
   if (n == 0) return SONIC_OK;
-  Z_BEGIN
+  API_BEGIN
   CallLease lease;
   hipStream_t st = lease.st();
   DevBuf raw(96 * (size_t)n), pts(sizeof(G1Affine) * (size_t)n), fl((size_t)n), z(48 * (size_t)n);
@@ -137,13 +132,13 @@ int sonic_g1_compress(const uint8_t* points96, int64_t n, uint8_t* out48) {
   for (int64_t i = 0; i < n; i++)
     if (!hfl[(size_t)i]) { set_error("sonic_g1_compress: point %lld is non-canonical, off the curve or outside the order-r subgroup", (long long)i); return SONIC_ERR_BAD_ENCODING; }
   return SONIC_OK;
-  Z_END
+  API_CATCH
 }
 
 int sonic_g2_compress(const uint8_t* points192, int64_t n, uint8_t* out96) {
   if (n < 0 || (n > 0 && (!points192 || !out96))) { set_error("sonic_g2_compress: bad argument"); return SONIC_ERR_INVALID_ARG; }
   if (n == 0) return SONIC_OK;
-  Z_BEGIN
+  API_BEGIN
   CallLease lease;
   hipStream_t st = lease.st();
   DevBuf raw(192 * (size_t)n), pts(sizeof(G2Affine) * (size_t)n), err(4), z(96 * (size_t)n);
@@ -158,7 +153,7 @@ int sonic_g2_compress(const uint8_t* points192, int64_t n, uint8_t* out96) {
   // (bit 8, the point at infinity, is an SRS rule: here infinity has an encoding like every other point)
   if (herr & 7) { set_error("sonic_g2_compress: %s", (herr & 1) ? "non-canonical coordinate" : (herr & 2) ? "point not on the twist" : "point outside the order-r subgroup"); return SONIC_ERR_BAD_ENCODING; }
   return SONIC_OK;
-  Z_END
+  API_CATCH
 }
 
 // ---- one proof, on the host ----

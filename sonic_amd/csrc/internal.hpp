@@ -1,6 +1,7 @@
 // Cross-translation-unit declarations inside libsonic_hip.so.
 #pragma once
 #include <atomic>
+#include <exception>
 #include "common.hpp"
 #include "g1.hpp"
 #include "msm.hpp"
@@ -12,7 +13,7 @@ namespace sonic {
 
 struct NttTables;
 
-// ---- devices (api.hip) ------------------------------------------------------------------------------------------------------------
+// ---- devices (device.hip) ---------------------------------------------------------------------------------------------------------
 // One host process may drive every GPU of the node (round 5): each handle -- SRS, prover, MSM lane -- is bound to the device it was
 // made on, and what used to be process-wide state (the default stream, the mutex of the state-changing calls, the leased call
 // contexts, the pool of blocking-MSM lanes, the twiddle tables and scratch of the stand-alone NTT entry points, per-device kernel
@@ -78,32 +79,38 @@ class CallLease {
   DeviceCtx* owner_;
 };
 
-// SRS handle internals (api.hip)
-PointArray srs_basis(const sonic_srs* s, int b);            // table 0 of a basis, slot e + d; window table w follows at + w (2d+1)
-PointArrayMut srs_basis_mut(sonic_srs* s, int b);
+// ---- the entry-point wrapper ------------------------------------------------------------------------------------------------------
+// Every entry point that touches a device runs inside a DeviceScope: API_BEGIN on the default device, API_BEGIN_ON(dev) on a handle's.
+// Host-only entry points open with API_HOST_BEGIN: the same tail, no scope (it names nothing of the device: verify.hip is also built as
+// plain C++).  API_END closes either with `return SONIC_OK`; API_CATCH is the tail alone, for bodies whose every path returns.
+#define API_BEGIN_ON(dev) try { ::sonic::DeviceScope _scope(dev);
+#define API_BEGIN API_BEGIN_ON(-1)
+#define API_HOST_BEGIN try {
+#define API_CATCH                                                               \
+  } catch (const ::sonic::HipFail& f) { return f.code; }                        \
+  catch (const std::exception& e) { ::sonic::set_error("%s", e.what()); return SONIC_ERR_HIP; }
+#define API_END API_CATCH return SONIC_OK;
+
+// ---- the SRS handle, opaque (srs_api.hip) -----------------------------------------------------------------------------------------
+// The handle is a type in srs_handle.hpp for the code that works on its device side.  These two stay functions over the forward
+// declaration because the verifier's host path (verify.hip, verify_host.hpp, and this header with them) is also compiled as plain C++
+// under ASan / UBSan against a stand-in `struct sonic_srs` that supplies its own pair (tests/host/san_verify.cpp).
 int64_t srs_d(const sonic_srs* s);
-int srs_device(const sonic_srs* s);          // -1 for a null handle (= the default device: the null check then reports the argument)
-sonic_srs* srs_alloc(int64_t d);
 // the handle's Fiat-Shamir id (fs.hpp), made once by `make` and kept in the handle
 int srs_cached_id(const sonic_srs* s, int (*make)(const sonic_srs*, uint8_t*), uint8_t out[32]);
 
-// encodings (api.hip)
+// ---- encodings at the boundary (encoding.hip) -------------------------------------------------------------------------------------
 void fr_to_mont_enqueue(hipStream_t st, Fr* d, long n, int* d_err);
 void fr_from_mont_enqueue(hipStream_t st, Fr* d, long n);
 void fr_check_enqueue(hipStream_t st, const Fr* d, long n, int* d_err);
+// 96-byte canonical encodings -> Montgomery affine points; *d_err collects bits 1 non-canonical, 2 off the curve, 8 infinity at an index
+// other than inf_ok (-1: accepted everywhere, -2: nowhere)
+void points_from_bytes_enqueue(hipStream_t st, const uint8_t* d_in96, PointArrayMut out, long n, int* d_err, long inf_ok);
+void points_subgroup_check_enqueue(hipStream_t st, PointArray in, long n, int* d_err);      // bit 4: a point outside the order-r subgroup
+void points_to_bytes_enqueue(hipStream_t st, PointArray in, uint8_t* d_out96, long n);
+int read_flags(hipStream_t st, DevBuf& flags);      // the error bits the stream's kernels have collected in a device word; waits for the stream
 void msm_blocking(hipStream_t st, MsmWorkspace& ws, const MsmPlan& pl, PointArray d_pts, const Fr* d_sc, long n, bool mont,
                   uint8_t* out96, uint8_t* out_partial192);
-int srs_tab_c(const sonic_srs* s);
-int srs_tab_W(const sonic_srs* s);
-bool srs_tab_endo(const sonic_srs* s);
-MsmPlan srs_msm_plan(const sonic_srs* s, long n);
-// fills window tables 1 .. W-1 of both bases from table 0 (srs.hip)
-void srs_build_tables(hipStream_t st, sonic_srs* s);
-PointArrayMut srs_prefix_mut(sonic_srs* s);      // running sums of the alpha basis (p == nullptr: not held)
-PointArray srs_prefix(const sonic_srs* s);
-PointArrayMut srs_sym_mut(sonic_srs* s);         // symmetric sums A[e] + A[-e] of the alpha basis, laid out like a basis with its window tables
-PointArray srs_sym(const sonic_srs* s);
-void srs_set_trapdoor(sonic_srs* s, const Fr& x_std, const Fr& alpha_std);
 struct G2Affine;
 // G2 half (srs_g2.hip)
 void srs_generate_g2(hipStream_t st, long d, const Fr& x_std, const Fr& alpha_std, G2Affine* h0, G2Affine* h1);
@@ -120,9 +127,6 @@ void g1_compress_enqueue(hipStream_t st, PointArray in, uint8_t* d_out48, long n
 void g2_compress_enqueue(hipStream_t st, const G2Affine* in, uint8_t* d_out96, long n);
 // k_g1_validate (verify_batch.hip): 96-byte encodings -> affine points and flags, 1 = what load_g1 accepts
 void g1_validate_enqueue(hipStream_t st, const uint8_t* d_in96, G1Affine* out, uint8_t* d_flags, long n);
-
-// SRS generation (srs.hip): fills both bases of `s` from x, alpha (standard-form Fr on the host)
-void srs_generate(hipStream_t st, sonic_srs* s, const Fr& x_std, const Fr& alpha_std);
 
 // NTT (ntt.hip).  Data in Montgomery form, in place.  forward: natural -> bit-reversed;
 // inverse: bit-reversed -> natural, scaled by 1/n.

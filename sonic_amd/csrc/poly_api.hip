@@ -48,7 +48,7 @@ int sonic_hsc_prove_poly(const sonic_srs_t* srs, int64_t n_terms, const int64_t*
   if (!srs || n_terms < 0 || (n_terms > 0 && (!x_exps || !y_exps || !coeffs)) || m < 0 || (m > 0 && !yzs) || !u || !v || !out) return SONIC_ERR_INVALID_ARG;
   CallLease lease;
   hipStream_t st = lease.st();
-  const long d = srs_d(srs);
+  const long d = srs->d;
   bool neg_x = false, neg_y = false;
   for (int64_t i = 0; i < n_terms; i++) {
     neg_x = neg_x || x_exps[i] < 0; neg_y = neg_y || y_exps[i] < 0;
@@ -148,7 +148,7 @@ static int densify(hipStream_t st, const sonic_srs* srs, int64_t nt, const int64
                    DensePoly& out, int* d_flags) {
   long lo = include_zero ? 0 : (nt ? exps[0] : 0), hi = lo;
   for (int64_t i = 0; i < nt; i++) { if (exps[i] < lo) lo = exps[i]; if (exps[i] > hi) hi = exps[i]; }
-  const long d = srs_d(srs);
+  const long d = srs->d;
   if (hi - lo + 1 > 8 * (2 * d + 1) + 64) { set_error("polynomial exponent range [%ld, %ld] is far outside the SRS", lo, hi); return SONIC_ERR_SRS_INDEX; }
   out.lo = lo; out.len = hi - lo + 1;
   out.c.alloc(sizeof(Fr) * out.len);

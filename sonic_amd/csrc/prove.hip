@@ -27,7 +27,7 @@ static int prove_segment(const MsmPlan& pl, int k, bool last) {
 // would not contain them); otherwise FLAG_SRS_INDEX (`index` panics, CommitmentScheme.hs:70-73).
 // Queues the checks and returns the MSM that is left to run.
 MsmJob commit_job(hipStream_t st, const sonic_srs* srs, const Fr* poly, long lo, long len, long maxm, MsmSlot* slot, int* d_flags) {
-  const long d = srs_d(srs), shift = d - maxm;
+  const long d = srs->d, shift = d - maxm;
   long i0 = -d - shift - lo, i1 = d - shift - lo + 1;     // in-range i: lo + i + shift in [-d, d]
   if (i0 < 0) i0 = 0;
   if (i1 > len) i1 = len;
@@ -36,7 +36,7 @@ MsmJob commit_job(hipStream_t st, const sonic_srs* srs, const Fr* poly, long lo,
   flag_nonzero_enqueue(st, poly + i1, len - i1, d_flags, FLAG_SRS_INDEX);
   const long ih = -shift - lo;
   if (ih >= i0 && ih < i1) flag_nonzero_enqueue(st, poly + ih, 1, d_flags, FLAG_SRS_INDEX);
-  return MsmJob{srs_basis(srs, 1) + (lo + i0 + shift + d), poly + i0, i1 - i0, slot};
+  return MsmJob{srs->basis(1) + (lo + i0 + shift + d), poly + i0, i1 - i0, slot};
 }
 
 // The MSMs that become ready together run as one batched kernel chain when the SRS has window tables (msm.hpp);
@@ -82,14 +82,14 @@ static void eval_prefix_enqueue(hipStream_t st, Scratch& sc, const Fr* poly, lon
 
 // the MSM of a quotient q over exponents [lo, lo+len-2], plain basis; coefficients outside [-d, d] must be zero (FLAG_SRS_INDEX)
 static MsmJob quotient_job(hipStream_t st, const sonic_srs* srs, const Fr* q, long lo, long len, MsmSlot* slot, int* d_flags) {
-  const long d = srs_d(srs), qn = len - 1;
+  const long d = srs->d, qn = len - 1;
   long i0 = -d - lo, i1 = d - lo + 1;
   if (i0 < 0) i0 = 0;
   if (i1 > qn) i1 = qn;
   if (i1 < i0) i1 = i0;
   flag_nonzero_enqueue(st, q, i0, d_flags, FLAG_SRS_INDEX);
   flag_nonzero_enqueue(st, q + i1, qn - i1, d_flags, FLAG_SRS_INDEX);
-  return MsmJob{srs_basis(srs, 0) + (lo + i0 + d), q + i0, i1 - i0, slot};
+  return MsmJob{srs->basis(0) + (lo + i0 + d), q + i0, i1 - i0, slot};
 }
 
 // openPoly (CommitmentScheme.hs:36-48).  Requires lo <= 0 <= lo+len-1 (callers extend the range to
@@ -107,13 +107,13 @@ MsmJob open_job(hipStream_t st, const sonic_srs* srs, Scratch& sc, const Fr* pol
 // array shifted down by one (CommitmentScheme.hs:43-44 with z = 0).  The prefix-sum form above multiplies by z^{-1-j} and
 // cannot express it (0^-1 is not defined; k_fr_with_inverse returns 0 for it).
 MsmJob open_job_at_zero(hipStream_t st, const sonic_srs* srs, const Fr* poly, long len, Fr* d_fz, MsmSlot* slot, int* d_flags) {
-  const long d = srs_d(srs);
+  const long d = srs->d;
   HIP_OK(hipMemcpyAsync(d_fz, poly, sizeof(Fr), hipMemcpyDeviceToDevice, st));
   const long qn = len - 1;                 // quotient exponents [0, len - 2]
   long i1 = d + 1;
   if (i1 > qn) i1 = qn;
   flag_nonzero_enqueue(st, poly + 1 + i1, qn - i1, d_flags, FLAG_SRS_INDEX);
-  return MsmJob{srs_basis(srs, 0) + d, poly + 1, i1, slot};
+  return MsmJob{srs->basis(0) + d, poly + 1, i1, slot};
 }
 
 // openPoly for several openings over one exponent range as one batched set of launches (poly.hip, open_batch_enqueue); the jobs
@@ -153,13 +153,6 @@ int upload_fr_mont(hipStream_t st, DevBuf& dst, const uint8_t* src, long count, 
     fr_to_mont_enqueue(st, dst.as<Fr>(), count, d_flags);
   }
   return 0;
-}
-
-int read_flags(hipStream_t st, DevBuf& flags) {
-  int h = 0;
-  HIP_OK(hipMemcpyAsync(&h, flags.p, 4, hipMemcpyDeviceToHost, st));
-  HIP_OK(hipStreamSynchronize(st));
-  return h;
 }
 
 int flags_to_status(int f, const char* who) {
@@ -244,7 +237,7 @@ int sonic_srs_new_on(int device, int64_t d, const uint8_t x[32], const uint8_t a
   std::lock_guard<std::mutex> g(call_mutex());
   sonic_srs* s = srs_alloc(d);
   try { srs_generate(default_stream(), s, xs, as); } catch (...) { sonic_srs_free(s); throw; }
-  srs_set_trapdoor(s, xs, as);
+  s->have_trapdoor = true; s->x_std = xs; s->alpha_std = as;
   *out = s;
   API_END
 }
@@ -272,8 +265,8 @@ int sonic_prover_new_csr(const sonic_srs_t* srs, int64_t n, int64_t Q, const int
 
 // the circuit's arguments, Protocol.hs:54-55, then the circuit's own checks (csr.hpp), in the order the entry points always had them
 int prover_admits(const char* who, const sonic_srs* srs, const CircuitView& c) {
-  if (circuit_args_ok(c) && srs_d(srs) < 7 * c.n) {
-    set_error("Parameter d is not large enough: %ld should be greater than %ld", (long)srs_d(srs), (long)(7 * c.n));
+  if (circuit_args_ok(c) && srs->d < 7 * c.n) {
+    set_error("Parameter d is not large enough: %ld should be greater than %ld", (long)srs->d, (long)(7 * c.n));
     return SONIC_ERR_D_TOO_SMALL;
   }
   return circuit_validate(who, c);
@@ -492,12 +485,12 @@ struct GroupQueue {
       rb.scal.ensure(sizeof(Fr) * 2 * ntiles); rb.pts.ensure(sizeof(G1Affine) * 2 * ntiles);
       run_tiles_enqueue(cur->st, job.scalars, job.n, rb.masked.as<Fr>(), rb.val.as<Fr>(), rb.uniform.as<uint32_t>());
       HIP_OK(hipEventRecord(rb.masked_ev, cur->st));
-      const long first = (long)((job.points.p - srs_basis(srs, 1).p) / (long)job.points.stride);
+      const long first = (long)((job.points.p - srs->basis(1).p) / (long)job.points.stride);
       sonic_prover::RunBufs* rbp = &rb;
       side([this, rbp, first, ntiles, j] {
         hipStream_t ms = p->st;
         HIP_OK(hipStreamWaitEvent(ms, rbp->masked_ev, 0));
-        run_terms_enqueue(ms, rbp->val.as<Fr>(), rbp->uniform.as<uint32_t>(), ntiles, srs_prefix(srs) + first, first, rbp->scal.as<Fr>(), rbp->pts.as<G1Affine>());
+        run_terms_enqueue(ms, rbp->val.as<Fr>(), rbp->uniform.as<uint32_t>(), ntiles, srs->prefix() + first, first, rbp->scal.as<Fr>(), rbp->pts.as<G1Affine>());
         msm_enqueue(ms, p->runs_ws, msm_plan(2 * ntiles), PointArray::packed(rbp->pts.as<G1Affine>()), rbp->scal.as<Fr>(), 2 * ntiles, true, &slots[L.S_extra(j)]);
       }, BEHIND_CHAIN);
       job.scalars = rb.masked.as<Fr>();
@@ -509,13 +502,13 @@ struct GroupQueue {
   // c_i (A[i] + A[-i]) in the group, exponents n+1 .. n+Q as a Q-term MSM on the main stream (su was built there)
   void commit_sym(int ph, const Fr* su, long lo, long len, long n) {
     if (!on(ph) || !own(L.C())) return;
-    const long d = srs_d(srs);
+    const long d = srs->d;
     make_room();
     MsmJob job = commit_job(cur->st, srs, su, lo, len, d, &slots[L.C()], flags);      // (the index checks of the whole range)
-    job.points = srs_sym(srs) + 1; job.scalars = su + (n + 1); job.n = n; job.table_stride = d + 1;
+    job.points = srs->sym() + 1; job.scalars = su + (n + 1); job.n = n; job.table_stride = d + 1;
     push(job, L.C());
     p->slot_ran[(size_t)L.C_extra()] = 1;
-    side([this, su, d, n] { msm_enqueue(p->st, p->runs_ws, msm_plan(L.Q), srs_basis(srs, 1) + (d + n + 1), su + (2 * n + 1), L.Q, true, &slots[L.C_extra()]); }, BEHIND_CHAIN);
+    side([this, su, d, n] { msm_enqueue(p->st, p->runs_ws, msm_plan(L.Q), srs->basis(1) + (d + n + 1), su + (2 * n + 1), L.Q, true, &slots[L.C_extra()]); }, BEHIND_CHAIN);
   }
   // fr: index of the evaluation in frout (-1: not reported); every rank with a piece of the opening computes it (the quotient
   // needs the prefix sums anyway), the rank whose piece starts at term 0 reports it
@@ -593,7 +586,7 @@ struct ProofPass {
   const Fr* pair(long i) const { return PR + 2 * i; }
   bool ts_used() const { return need_T || g0_queued; }
   ProofPass(sonic_prover_t* p, const GroupQueue& q)
-      : n(p->n), Q(p->Q), d(srs_d(p->srs)), r_lo(-2 * n - 4), r_len(3 * n + 5), s_lo(-n), s_len(3 * n + 1), t_lo(-4 * n - 8), t_len(7 * n + 9),
+      : n(p->n), Q(p->Q), d(p->srs->d), r_lo(-2 * n - 4), r_len(3 * n + 5), s_lo(-n), s_len(3 * n + 1), t_lo(-4 * n - 8), t_len(7 * n + 9),
         u_lo(-n), u_len(2 * n + Q + 1), PR(p->PAIRS.as<Fr>()), need_j((size_t)Q, 0) {
     const ProofLayout& L = q.L;
     need_su = q.own(L.C()) || q.own(L.Qv());
@@ -795,7 +788,7 @@ static void decide_modes(sonic_prover_t* p) {
     const char* re = getenv("SONIC_PROVE_RUNS");
     const int mode = re ? atoi(re) : -1;
     const bool size_ok = mode == 1 ? 3 * p->n + 1 >= 8 * RUN_TILE : p->n >= (1L << 16);
-    p->runs_on = mode != 0 && size_ok && (mode == 1 || p->circuit_has_runs) && !p->prepared && p->share_world <= 1 && srs_prefix(p->srs).p != nullptr;
+    p->runs_on = mode != 0 && size_ok && (mode == 1 || p->circuit_has_runs) && !p->prepared && p->share_world <= 1 && p->srs->prefix().p != nullptr;
   }
   {
     // by default from n = 2^17: the Q-term MSM's launches cost a small proof more than n additions save it (ms per proof streamed with /
@@ -805,7 +798,7 @@ static void decide_modes(sonic_prover_t* p) {
     const int mode = se ? atoi(se) : -1;
     // (round 6, n = 2^16 again, where a proof is one chain now: with / without 9.20-9.25 / 9.08-9.15 ms streamed, 10.44-10.51 / 10.49-10.80
     // one at a time -- still no gain below 2^17; profiles/r06_ab_small_final.txt)
-    p->sym_on = mode != 0 && (mode == 1 || p->n >= (1L << 17)) && p->share_world <= 1 && srs_sym(p->srs).p != nullptr;
+    p->sym_on = mode != 0 && (mode == 1 || p->n >= (1L << 17)) && p->share_world <= 1 && p->srs->sym().p != nullptr;
   }
   {
     const MsmPlan probe = srs_msm_plan(p->srs, 3 * p->n);
@@ -1210,7 +1203,7 @@ int sonic_prover_prove_fs(sonic_prover_t* p, const uint8_t circuit_digest[32], c
   int rc = prove_args_ok(p, "sonic_prover_prove_fs");
   if (!rc) rc = whole_proof_only(p, "sonic_prover_prove_fs");
   if (rc) return rc;
-  const long n = p->n, Q = p->Q, d = srs_d(p->srs);
+  const long n = p->n, Q = p->Q, d = p->srs->d;
   const ProofLayout L{Q};
   std::vector<uint8_t> tr(32 * (size_t)L.transcript_len(), 0), pf(sonic_proof_size(Q));
   uint8_t srs_id[32];
@@ -1218,22 +1211,20 @@ int sonic_prover_prove_fs(sonic_prover_t* p, const uint8_t circuit_digest[32], c
   if (!p->have_witness_digest) {
     // SHA-256 of the assignment's canonical bytes, once per set_assignment: the device copy is Montgomery, so a scratch copy is
     // converted back and brought to the host
-    try {
-      DevBuf tmp(sizeof(Fr) * 3 * n);
-      Fr* t3 = tmp.as<Fr>();
-      HIP_OK(hipMemcpyAsync(t3, p->aL.p, sizeof(Fr) * n, hipMemcpyDeviceToDevice, p->st));
-      HIP_OK(hipMemcpyAsync(t3 + n, p->aR.p, sizeof(Fr) * n, hipMemcpyDeviceToDevice, p->st));
-      HIP_OK(hipMemcpyAsync(t3 + 2 * n, p->aO.p, sizeof(Fr) * n, hipMemcpyDeviceToDevice, p->st));
-      fr_from_mont_enqueue(p->st, t3, 3 * n);
-      std::vector<uint8_t> host(96 * (size_t)n);
-      HIP_OK(hipMemcpyAsync(host.data(), t3, host.size(), hipMemcpyDeviceToHost, p->st));
-      HIP_OK(hipStreamSynchronize(p->st));
-      Sha256 h;
-      h.update("sonic-hip/witness/v1", 20);
-      h.update(host.data(), host.size());
-      h.finish(p->witness_digest);
-      p->have_witness_digest = true;
-    } catch (const HipFail& f) { return f.code; }
+    DevBuf tmp(sizeof(Fr) * 3 * n);
+    Fr* t3 = tmp.as<Fr>();
+    HIP_OK(hipMemcpyAsync(t3, p->aL.p, sizeof(Fr) * n, hipMemcpyDeviceToDevice, p->st));
+    HIP_OK(hipMemcpyAsync(t3 + n, p->aR.p, sizeof(Fr) * n, hipMemcpyDeviceToDevice, p->st));
+    HIP_OK(hipMemcpyAsync(t3 + 2 * n, p->aO.p, sizeof(Fr) * n, hipMemcpyDeviceToDevice, p->st));
+    fr_from_mont_enqueue(p->st, t3, 3 * n);
+    std::vector<uint8_t> host(96 * (size_t)n);
+    HIP_OK(hipMemcpyAsync(host.data(), t3, host.size(), hipMemcpyDeviceToHost, p->st));
+    HIP_OK(hipStreamSynchronize(p->st));
+    Sha256 h;
+    h.update("sonic-hip/witness/v1", 20);
+    h.update(host.data(), host.size());
+    h.finish(p->witness_digest);
+    p->have_witness_digest = true;
   }
   for (long k = 0; k < L.n_blinders; k++) fs_blinder(blinder_seed, circuit_digest, srs_id, p->witness_digest, (uint32_t)k, &tr[32 * k]);
   for (long k = L.n_blinders; k < L.transcript_len(); k++) tr[32 * k] = 1;               // not drawn yet: any invertible value (results that use it are not read)
@@ -1284,7 +1275,7 @@ int sonic_prover_prepare(sonic_prover_t* p) {
   if (p->in_flight) { set_error("sonic_prover_prepare: a submitted proof has not been collected yet"); return SONIC_ERR_INVALID_ARG; }
   if (p->graph) { (void)hipGraphExecDestroy(p->graph); p->graph = nullptr; }     // a captured proof would not know the prepared path
   p->graph_tried = false;
-  const long n = p->n, Q = p->Q, d = srs_d(p->srs);
+  const long n = p->n, Q = p->Q, d = p->srs->d;
   int* flags = p->flags.as<int>();
   HIP_OK(hipMemsetAsync(flags, 0, 4, p->st));
   HIP_OK(hipStreamSynchronize(p->st));
@@ -1303,7 +1294,7 @@ int sonic_prover_prepare(sonic_prover_t* p) {
     terms_scal.alloc(sizeof(Fr) * (nnz > 0 ? nnz : 1));
     HIP_OK(hipMemsetAsync(slots.p, 0, sizeof(MsmSlot) * Q, p->st));
     HIP_OK(hipStreamSynchronize(p->st));
-    const PointArray A = srs_basis(p->srs, 1) + d;                   // the alpha basis at exponent 0
+    const PointArray A = p->srs->basis(1) + d;                   // the alpha basis at exponent 0
     long at = 0;
     for (long q = 0; q < Q; q++) {
       const int32_t seg[6] = {rp[q], rp[q + 1] - rp[q], rp[Q + q], rp[Q + q + 1] - rp[Q + q], rp[2 * Q + q], rp[2 * Q + q + 1] - rp[2 * Q + q]};
@@ -1386,7 +1377,7 @@ int sonic_prover_hsc_prove(sonic_prover_t* p, int64_t m, const uint8_t* yzs, con
   if (!p || m < 0 || (m > 0 && !yzs) || !u || !v || !out) return SONIC_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> g(p->mu);
   if (p->in_flight) { set_error("sonic_prover_hsc_prove: a submitted proof has not been collected yet"); return SONIC_ERR_INVALID_ARG; }
-  const long n = p->n, Q = p->Q, d = srs_d(p->srs);
+  const long n = p->n, Q = p->Q, d = p->srs->d;
   for (long k = 0; k < 2 * m; k++)
     if (bytes_are_zero(yzs + 32 * k, 32)) { set_error("hscProve: y_j / z_j number %ld is zero: Laurent evaluation at 0 divides by zero", k); return SONIC_ERR_INEXACT_DIVISION; }
   if (bytes_are_zero(u, 32) || bytes_are_zero(v, 32)) { set_error("hscProve: u or v is zero"); return SONIC_ERR_INEXACT_DIVISION; }

@@ -12,7 +12,7 @@
 #include <numeric>
 #include <string>
 #include <vector>
-#include "internal.hpp"
+#include "srs_handle.hpp"
 #include "poly.hpp"
 #include "fs.hpp"
 #include "share_plan.hpp"
@@ -243,16 +243,8 @@ struct sonic_prover {
   }
 };
 
-#define API_BEGIN_ON(dev) try { ::sonic::DeviceScope _scope(dev);
-#define API_BEGIN API_BEGIN_ON(-1)
-#define API_END                                                        \
-  } catch (const HipFail& f) { return f.code; }                        \
-  catch (const std::exception& e) { set_error("%s", e.what()); return SONIC_ERR_HIP; } \
-  return SONIC_OK;
-
 // (prove.hip)
 int upload_fr_mont(hipStream_t st, DevBuf& dst, const uint8_t* src, long count, int* d_flags);
-int read_flags(hipStream_t st, DevBuf& flags);
 int flags_to_status(int f, const char* who);
 // (defined inside prove.hip's extern "C" block, not exported)
 extern "C" int prove_with_assignment(sonic_prover_t* p, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO, const uint8_t* transcript, uint8_t* out_proof);

@@ -4,7 +4,7 @@
 // a 32 x 256 table of byte multiples of the generator (j * 2^(8w) * G), one thread per exponent
 // doing 2 x 32 table additions into XYZZ accumulators, then a batched (Montgomery-trick)
 // normalisation to affine, 64 points per inversion.
-#include "internal.hpp"
+#include "srs_handle.hpp"
 #include "endo.hpp"
 
 namespace sonic {
@@ -120,14 +120,14 @@ __global__ __launch_bounds__(256) void k_ps_apply(G1XYZZ* __restrict__ x, const 
 }
 
 void srs_build_prefix(hipStream_t st, sonic_srs* s) {
-  PointArrayMut ps = srs_prefix_mut(s);
+  PointArrayMut ps = s->prefix_mut();
   if (!ps.p) return;
-  const long n = 2 * srs_d(s) + 1;
+  const long n = 2 * s->d + 1;
   const long SLAB = 1L << 20;
   const long cap = n < SLAB ? n : SLAB, ccap = ceil_div(cap, PS_CHUNK);
   DevBuf x(sizeof(G1XYZZ) * cap), pref(sizeof(Fq) * cap), t0(sizeof(G1XYZZ) * ccap), t1(sizeof(G1XYZZ) * ccap), carry(sizeof(G1XYZZ));
   HIP_OK(hipMemsetAsync(carry.p, 0, sizeof(G1XYZZ), st));            // the point at infinity
-  const PointArray src = srs_basis(s, 1);
+  const PointArray src = s->basis(1);
   for (long base = 0; base < n; base += SLAB) {
     const long m = n - base < SLAB ? n - base : SLAB, nc = ceil_div(m, PS_CHUNK);
     LAUNCH(k_ps_chunk, ceil_div(nc, 64), 64, 0, st, src + base, x.as<G1XYZZ>(), t0.as<G1XYZZ>(), m);
@@ -157,15 +157,15 @@ __global__ __launch_bounds__(256) void k_sym_sum(PointArray A, long d, long e0, 
   out[i] = g1_add_mixed(G1XYZZ::from_affine(A[(size_t)(d + e)]), A[(size_t)(d - e)]);
 }
 void srs_build_sym(hipStream_t st, sonic_srs* s) {
-  PointArrayMut sym = srs_sym_mut(s);
+  PointArrayMut sym = s->sym_mut();
   if (!sym.p) return;
-  const int W = srs_tab_W(s);
-  const long d = srs_d(s), n = d + 1;                          // points per table: exponents 0 .. d
+  const int W = s->tab_W;
+  const long d = s->d, n = d + 1;                          // points per table: exponents 0 .. d
   for (int w = 0; w < W; w++) HIP_OK(hipMemsetAsync((sym + (long)((size_t)w * n)).p, 0, sym.stride, st));      // slot 0 of every table: infinity
   const long SLAB = 1L << 20;
   const long cap = d < SLAB ? d : SLAB;
   DevBuf x(sizeof(G1XYZZ) * cap), pref(sizeof(Fq) * cap);
-  const PointArray A = srs_basis(s, 1);
+  const PointArray A = s->basis(1);
   for (long base = 0; base < d; base += SLAB) {              // exponents e = 1 + base ...
     const long m = d - base < SLAB ? d - base : SLAB;
     LAUNCH(k_sym_sum, ceil_div(m, 256), 256, 0, st, A, d, 1 + base, m, x.as<G1XYZZ>());
@@ -175,7 +175,7 @@ void srs_build_sym(hipStream_t st, sonic_srs* s) {
     for (long base = 0; base < d; base += SLAB) {
       const long m = d - base < SLAB ? d - base : SLAB;
       LAUNCH(k_table_step, ceil_div(m, 256), 256, 0, st, (PointArray)(sym + (long)((size_t)(w - 1) * n + 1 + base)), x.as<G1XYZZ>(), m,
-             msm_even_width(W, w - 1, srs_tab_endo(s) ? ENDO_BITS : 255));
+             msm_even_width(W, w - 1, s->tab_endo ? ENDO_BITS : 255));
       LAUNCH(k_batch_affine, ceil_div(ceil_div(m, 64), 64), 64, 0, st, (const G1XYZZ*)x.as<G1XYZZ>(), sym + (long)((size_t)w * n + 1 + base), pref.as<Fq>(), m);
     }
   HIP_OK(hipStreamSynchronize(st));
@@ -184,20 +184,20 @@ void srs_build_sym(hipStream_t st, sonic_srs* s) {
 void srs_build_tables(hipStream_t st, sonic_srs* s) {
   srs_build_prefix(st, s);
   srs_build_sym(st, s);
-  const int W = srs_tab_W(s), c = srs_tab_c(s);
-  if (getenv("SONIC_DEBUG_TIMING")) fprintf(stderr, "[sonic] window tables: c=%d W=%d d=%ld\n", c, W, (long)srs_d(s));
+  const int W = s->tab_W, c = s->tab_c;
+  if (getenv("SONIC_DEBUG_TIMING")) fprintf(stderr, "[sonic] window tables: c=%d W=%d d=%ld\n", c, W, (long)s->d);
   if (W <= 1) return;
-  const long n = 2 * srs_d(s) + 1;
+  const long n = 2 * s->d + 1;
   const long SLAB = 1L << 20;
   const long cap = n < SLAB ? n : SLAB;
   DevBuf x(sizeof(G1XYZZ) * cap), pref(sizeof(Fq) * cap);
   for (int b = 0; b < 2; b++) {
-    const PointArrayMut tab = srs_basis_mut(s, b);
+    const PointArrayMut tab = s->basis_mut(b);
     for (int w = 1; w < W; w++) {
       for (long base = 0; base < n; base += SLAB) {
         const long m = n - base < SLAB ? n - base : SLAB;
         LAUNCH(k_table_step, ceil_div(m, 256), 256, 0, st, (PointArray)(tab + (long)((size_t)(w - 1) * n + base)), x.as<G1XYZZ>(), m,
-               msm_even_width(W, w - 1, srs_tab_endo(s) ? ENDO_BITS : 255));
+               msm_even_width(W, w - 1, s->tab_endo ? ENDO_BITS : 255));
         LAUNCH(k_batch_affine, ceil_div(ceil_div(m, 64), 64), 64, 0, st, (const G1XYZZ*)x.as<G1XYZZ>(), tab + (size_t)w * n + base, pref.as<Fq>(), m);
       }
     }
@@ -211,7 +211,7 @@ __global__ void k_fr_setup_x(const Fr* in_std, Fr* out) {  // out = {x, x^-1, al
 }
 
 void srs_generate(hipStream_t st, sonic_srs* s, const Fr& x_std, const Fr& alpha_std) {
-  const long d = srs_d(s), n = 2 * d + 1;
+  const long d = s->d, n = 2 * d + 1;
   DevBuf tabx(sizeof(G1XYZZ) * 8192), tab(sizeof(G1Affine) * 8192);
   LAUNCH(k_fb_table, 1, 64, 0, st, tabx.as<G1XYZZ>());
   LAUNCH(k_xyzz_to_affine, ceil_div(8192, 64), 64, 0, st, (const G1XYZZ*)tabx.as<G1XYZZ>(), tab.as<G1Affine>(), 8192L);
@@ -229,8 +229,8 @@ void srs_generate(hipStream_t st, sonic_srs* s, const Fr& x_std, const Fr& alpha
     long m = n - base < SLAB ? n - base : SLAB;
     LAUNCH(k_srs_points, ceil_div(m, 256), 256, 0, st, (const G1Affine*)tab.as<G1Affine>(), d - base, m, hp[0], hp[1], hp[2],
            x0.as<G1XYZZ>(), x1.as<G1XYZZ>());
-    LAUNCH(k_batch_affine, ceil_div(ceil_div(m, 64), 64), 64, 0, st, (const G1XYZZ*)x0.as<G1XYZZ>(), srs_basis_mut(s, 0) + base, pref.as<Fq>(), m);
-    LAUNCH(k_batch_affine, ceil_div(ceil_div(m, 64), 64), 64, 0, st, (const G1XYZZ*)x1.as<G1XYZZ>(), srs_basis_mut(s, 1) + base, pref.as<Fq>(), m);
+    LAUNCH(k_batch_affine, ceil_div(ceil_div(m, 64), 64), 64, 0, st, (const G1XYZZ*)x0.as<G1XYZZ>(), s->basis_mut(0) + base, pref.as<Fq>(), m);
+    LAUNCH(k_batch_affine, ceil_div(ceil_div(m, 64), 64), 64, 0, st, (const G1XYZZ*)x1.as<G1XYZZ>(), s->basis_mut(1) + base, pref.as<Fq>(), m);
   }
   HIP_OK(hipStreamSynchronize(st));
   srs_build_tables(st, s);

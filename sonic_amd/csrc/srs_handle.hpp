@@ -1,0 +1,67 @@
+// The SRS handle (sonic_srs_t of include/sonic_hip.h) as a type, for the translation units that work on its device side: construction and
+// the C entry points (srs_api.hip), generation and the table builders (srs.hip), the MSM entry points (msm_api.hip), the prover and the
+// batched verifier.  NOT for verify.hip, verify_host.hpp or internal.hpp: the verifier's host path is also built as plain C++ with a
+// stand-in handle (tests/host/san_verify.cpp) and sees the handle only through srs_d and srs_cached_id (internal.hpp).
+#pragma once
+#include "internal.hpp"
+
+struct sonic_srs {
+  int64_t d;
+  int device = 0;             // the GPU that holds the handle's memory: every call that takes the handle runs there (DeviceScope)
+  // Fiat-Shamir id of the reference string (fs.hpp): constant for an SRS, made on first use (four point fetches) and cached
+  mutable std::mutex id_mu;
+  mutable bool have_id = false;
+  mutable uint8_t id[32] = {0};
+  // basis b, window table w, exponent e  ->  tab[b][w * (2d+1) + e + d] = 2^(msm_even_shift(tab_W, w)) * g^{(alpha^b) x^e}
+  // (w = 0 is the basis itself; tab_W = 1 when the window tables are switched off)
+  int tab_c = 0, tab_W = 1;
+  // endomorphism tables (endo.hpp): tab_W windows over 130 bits instead of 255 -- 7 tables instead of 13 at c = 19 / 20 -- for SRS
+  // sizes whose full tables do not fit; every MSM then runs as two half-scalar MSMs (msm_enqueue_batch)
+  bool tab_endo = false;
+  sonic::DevBuf g, ga;
+  sonic::DevBuf ps;          // running sums of the alpha basis (srs.hip, srs_build_prefix); empty when memory was short
+  sonic::DevBuf gs;          // symmetric sums A[e] + A[-e] of the alpha basis with their window tables (srs_build_sym); empty when memory was short
+  // verifier half: generated on first use from the trapdoor SRS.new was given -- which is wiped as soon as that has
+  // happened -- or attached by sonic_srs_set_g2_points / read from a version-2 file
+  mutable bool have_trapdoor = false;
+  mutable sonic::Fr x_std, alpha_std;
+  mutable std::mutex g2_mu;
+  mutable sonic::DevBuf h, ha;        // G2Affine[2d+1] each
+  ~sonic_srs() { wipe_trapdoor(); }
+  void wipe_trapdoor() const {
+    volatile uint32_t* a = x_std.l; volatile uint32_t* b = alpha_std.l;
+    for (int i = 0; i < 8; i++) { a[i] = 0; b[i] = 0; }
+    have_trapdoor = false;
+  }
+  // table 0 of a basis, slot e + d; window table w follows at + w (2d+1)
+  sonic::PointArray basis(int b) const { return sonic::PointArray{(b ? ga : g).as<char>(), SONIC_SRS_POINT_BYTES}; }
+  sonic::PointArrayMut basis_mut(int b) { return sonic::PointArrayMut{(b ? ga : g).as<char>(), SONIC_SRS_POINT_BYTES}; }
+  // running sums of the alpha basis (p == nullptr: not held)
+  sonic::PointArray prefix() const { return sonic::PointArray{ps.as<char>(), SONIC_SRS_POINT_BYTES}; }
+  sonic::PointArrayMut prefix_mut() { return sonic::PointArrayMut{ps.as<char>(), SONIC_SRS_POINT_BYTES}; }
+  // symmetric sums of the alpha basis: d + 1 slots per window table, slot e for exponent e (p == nullptr: not held)
+  sonic::PointArray sym() const { return sonic::PointArray{gs.as<char>(), SONIC_SRS_POINT_BYTES}; }
+  sonic::PointArrayMut sym_mut() { return sonic::PointArrayMut{gs.as<char>(), SONIC_SRS_POINT_BYTES}; }
+};
+
+namespace sonic {
+
+// what API_BEGIN_ON takes for an entry point over a handle: -1 for a null handle (= the default device: the null check then reports the argument)
+inline int srs_device(const sonic_srs* s) { return s ? s->device : -1; }
+// exponents [e0, e0 + n) must lie inside the handle's [-d, d]; `who` opens the message
+inline bool srs_range_ok(const char* who, const sonic_srs* s, int64_t e0, int64_t n) {
+  if (e0 >= -s->d && e0 + n - 1 <= s->d) return true;
+  set_error("%s: exponent range [%ld, %ld] outside [-%ld, %ld]", who, (long)e0, (long)(e0 + n - 1), (long)s->d, (long)s->d);
+  return false;
+}
+
+// an empty handle on the current device, sized by srs_policy.hpp (srs_api.hip)
+sonic_srs* srs_alloc(int64_t d);
+// plan for an MSM over n consecutive points of the handle (srs_api.hip)
+MsmPlan srs_msm_plan(const sonic_srs* s, long n);
+// SRS generation (srs.hip): fills both bases of `s` from x, alpha (standard-form Fr on the host), then its tables
+void srs_generate(hipStream_t st, sonic_srs* s, const Fr& x_std, const Fr& alpha_std);
+// fills window tables 1 .. W-1 of both bases from table 0, the running sums and the symmetric sums (srs.hip)
+void srs_build_tables(hipStream_t st, sonic_srs* s);
+
+}  // namespace sonic

@@ -99,7 +99,7 @@ extern "C" {
 
 int sonic_pc_v(const sonic_srs_t* srs, int64_t max, const uint8_t commitment[96], const uint8_t z[32], const uint8_t v[32],
                const uint8_t w[96], int* accepted) {
-  try {
+  API_HOST_BEGIN
     if (!srs || !commitment || !z || !v || !w || !accepted) return SONIC_ERR_INVALID_ARG;
     G1Affine F, W; Fr zm, vm;
     if (!load_g1(commitment, F) || !load_g1(w, W) || !load_fr(z, zm) || !load_fr(v, vm)) { set_error("pcV: bad encoding"); return SONIC_ERR_BAD_ENCODING; }
@@ -110,8 +110,7 @@ int sonic_pc_v(const sonic_srs_t* srs, int64_t max, const uint8_t commitment[96]
     rc = pc_v(srs, vk, max, F, zm, vm, W, ok);
     *accepted = ok ? 1 : 0;
     return rc;
-  } catch (const HipFail& f) { return f.code; }
-  catch (const std::exception& e) { set_error("%s", e.what()); return SONIC_ERR_HIP; }
+  API_CATCH
 }
 
 }  // extern "C"
@@ -119,14 +118,13 @@ int sonic_pc_v(const sonic_srs_t* srs, int64_t max, const uint8_t commitment[96]
 // the entry points that take a circuit, in either form: an argument check, a view, one implementation
 static int verify_entry(const char* who, const sonic_srs_t* srs, const CircuitView& c, const uint8_t* proof, const uint8_t y[32], const uint8_t z[32],
                         const uint8_t* yzs, int* accepted) {
-  try {
+  API_HOST_BEGIN
     if (!srs || !c.cs || !proof || !y || !z || !yzs || !accepted) { set_error("%s: bad argument", who); return SONIC_ERR_INVALID_ARG; }
     *accepted = 0;
     int rc = circuit_validate(who, c);
     if (rc) return rc;
     return verify_circuit(srs, c, proof, y, z, yzs, accepted);
-  } catch (const HipFail& f) { return f.code; }
-  catch (const std::exception& e) { set_error("%s", e.what()); return SONIC_ERR_HIP; }
+  API_CATCH
 }
 
 extern "C" {
@@ -146,7 +144,7 @@ int sonic_verify_csr(const sonic_srs_t* srs, int64_t n, int64_t Q, const int64_t
 // what ties a Fiat-Shamir transcript to ONE reference string (fs.hpp): four G1 elements that determine x and alpha
 // (constant for a handle: computed on first use -- four point fetches from the device -- and cached in the handle, srs_cached_id)
 static int make_srs_id(const sonic_srs* srs, uint8_t out[32]) {
-  try {
+  API_HOST_BEGIN
     uint8_t pts[4 * 96];
     int rc = sonic_srs_get_points(srs, 0, 1, 1, pts);                 // g^x            gPositiveX[1]
     if (!rc) rc = sonic_srs_get_points(srs, 1, 1, 1, pts + 96);       // g^{alpha x}    gPositiveAlphaX[0]
@@ -155,8 +153,7 @@ static int make_srs_id(const sonic_srs* srs, uint8_t out[32]) {
     if (rc) return rc;
     fs_srs_id_of_points(srs_d(srs), pts, out);
     return SONIC_OK;
-  } catch (const HipFail& f) { return f.code; }
-  catch (const std::exception& e) { set_error("%s", e.what()); return SONIC_ERR_HIP; }
+  API_CATCH
 }
 int sonic_fs_srs_id(const sonic_srs_t* srs, uint8_t out[32]) {
   if (!srs || !out) return SONIC_ERR_INVALID_ARG;
@@ -170,7 +167,7 @@ int sonic_fs_srs_id(const sonic_srs_t* srs, uint8_t out[32]) {
 // inverse, which in the cyclotomic subgroup is the conjugate.  (Which representative pairing-1.0.0 itself returns is [dep, unverified]:
 // the package is not in the reference tree; this is the textbook definition.)
 int sonic_srs_pairing(const sonic_srs_t* srs, uint8_t out[576]) {
-  try {
+  API_HOST_BEGIN
     if (!srs || !out) return SONIC_ERR_INVALID_ARG;
     G2Affine ha;
     int rc = fetch_g2(srs, 1, 0, ha);                                  // hPositiveAlphaX[0] = h^alpha
@@ -196,8 +193,7 @@ int sonic_srs_pairing(const sonic_srs_t* srs, uint8_t out[576]) {
       }
     }
     return SONIC_OK;
-  } catch (const HipFail& f) { return f.code; }
-  catch (const std::exception& e) { set_error("%s", e.what()); return SONIC_ERR_HIP; }
+  API_CATCH
 }
 
 }  // extern "C"
@@ -205,7 +201,7 @@ int sonic_srs_pairing(const sonic_srs_t* srs, uint8_t out[576]) {
 // verify for a proof made by sonic_prover_prove_fs: the challenges y, z, (y_j, z_j) are not handed over (RndOracle) but recomputed from
 // the statement and the proof (fs.hpp), and the proof's u, v must be the ones its own transcript yields
 static int verify_fs_entry(const char* who, const sonic_srs_t* srs, const CircuitView& c, const uint8_t* proof, int* accepted) {
-  try {
+  API_HOST_BEGIN
     if (!srs || !c.cs || !proof || !accepted) { set_error("%s: bad argument", who); return SONIC_ERR_INVALID_ARG; }
     *accepted = 0;
     int rc = circuit_validate(who, c);
@@ -222,8 +218,7 @@ static int verify_fs_entry(const char* who, const sonic_srs_t* srs, const Circui
     std::vector<uint8_t> yzs(64 * (size_t)Q);
     for (int64_t j = 0; j < Q; j++) { memcpy(&yzs[64 * j], &ch[32 * (2 + j)], 32); memcpy(&yzs[64 * j + 32], &ch[32 * (2 + Q + j)], 32); }
     return verify_circuit(srs, c, proof, &ch[0], &ch[32], yzs.data(), accepted);
-  } catch (const HipFail& f) { return f.code; }
-  catch (const std::exception& e) { set_error("%s", e.what()); return SONIC_ERR_HIP; }
+  API_CATCH
 }
 
 extern "C" {
@@ -246,7 +241,7 @@ int sonic_fs_circuit_digest_csr(int64_t n, int64_t Q, const int64_t* row_ptr, co
 // hsc = the bytes sonic_prover_hsc_prove wrote (m pairs)
 int sonic_hsc_verify(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO,
                      int64_t m, const uint8_t* yzs, const uint8_t* hsc, int* accepted) {
-  try {
+  API_HOST_BEGIN
     if (!srs || n < 1 || Q < 1 || !wL || !wR || !wO || m < 0 || (m > 0 && !yzs) || !hsc || !accepted) return SONIC_ERR_INVALID_ARG;
     *accepted = 0;
     HscProofView h;
@@ -257,8 +252,7 @@ int sonic_hsc_verify(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t
     if (!rc) rc = s_of_uv(dense_view(n, Q, wL, wR, wO, nullptr), h.u, h.v, sv);
     if (rc) return rc;
     return hsc_accepts(srs, vk, h, sv, accepted);
-  } catch (const HipFail& f) { return f.code; }
-  catch (const std::exception& e) { set_error("%s", e.what()); return SONIC_ERR_HIP; }
+  API_CATCH
 }
 
 
@@ -266,7 +260,7 @@ int sonic_hsc_verify(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t
 // (the counterpart of sonic_hsc_prove_poly): s(u,v) = eval (evalY v sXY) u on the host, then the 3m + 1 pcV checks
 int sonic_hsc_verify_poly(const sonic_srs_t* srs, int64_t n_terms, const int64_t* x_exps, const int64_t* y_exps, const uint8_t* coeffs,
                           int64_t m, const uint8_t* yzs, const uint8_t* hsc, int* accepted) {
-  try {
+  API_HOST_BEGIN
     if (!srs || n_terms < 0 || (n_terms > 0 && (!x_exps || !y_exps || !coeffs)) || m < 0 || (m > 0 && !yzs) || !hsc || !accepted) return SONIC_ERR_INVALID_ARG;
     *accepted = 0;
     HscProofView h;
@@ -286,8 +280,7 @@ int sonic_hsc_verify_poly(const sonic_srs_t* srs, int64_t n_terms, const int64_t
     int rc = load_verifier_key(srs, vk);
     if (rc) return rc;
     return hsc_accepts(srs, vk, h, sv, accepted);
-  } catch (const HipFail& f) { return f.code; }
-  catch (const std::exception& e) { set_error("%s", e.what()); return SONIC_ERR_HIP; }
+  API_CATCH
 }
 
 }  // extern "C"

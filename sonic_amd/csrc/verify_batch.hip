@@ -24,6 +24,7 @@
 #include <memory>
 #include <system_error>
 #include "verify_host.hpp"
+#include "srs_handle.hpp"
 #include "proof_layout.hpp"
 
 namespace sonic {
@@ -484,7 +485,7 @@ int verifier_new(const char* who, const sonic_srs_t* srs, const CircuitView& c, 
   if (rc) return rc;
   const long n = c.n, Q = c.Q, R = 3 * Q;
   std::unique_ptr<sonic_verifier> v(new sonic_verifier());
-  v->srs = srs; v->device = srs_device(srs); v->n = n; v->Q = Q; v->d = srs_d(srs);
+  v->srs = srs; v->device = srs_device(srs); v->n = n; v->Q = Q; v->d = srs->d;
   for (long q = 0; q < Q; q++) { Fr k; if (!load_fr(c.cs + 32 * q, k)) { set_error("%s: cs[%ld] is not a canonical field element", who, q); return SONIC_ERR_BAD_ENCODING; } }
   v->cs.assign(c.cs, c.cs + 32 * Q);
   // the G2 elements of every fold, once: the same statuses as sonic_verify when one is at infinity or the SRS is too short
@@ -550,24 +551,19 @@ int batch_size_ok(const char* who, const sonic_verifier* v, int64_t K) {
 
 }  // namespace
 
-#define VB_BEGIN(dev) try { ::sonic::DeviceScope _scope(dev);
-#define VB_END                                                         \
-  } catch (const HipFail& f) { return f.code; }                        \
-  catch (const std::exception& e) { set_error("%s", e.what()); return SONIC_ERR_HIP; }
-
 extern "C" {
 
 int sonic_verifier_new(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO, const uint8_t* cs,
                        sonic_verifier_t** out) {
-  VB_BEGIN(srs_device(srs))
+  API_BEGIN_ON(srs_device(srs))
   return verifier_new("sonic_verifier_new", srs, dense_view(n, Q, wL, wR, wO, cs), out);
-  VB_END
+  API_CATCH
 }
 int sonic_verifier_new_csr(const sonic_srs_t* srs, int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val, const uint8_t* cs,
                            sonic_verifier_t** out) {
-  VB_BEGIN(srs_device(srs))
+  API_BEGIN_ON(srs_device(srs))
   return verifier_new("sonic_verifier_new_csr", srs, csr_view(n, Q, row_ptr, col, val, cs), out);
-  VB_END
+  API_CATCH
 }
 void sonic_verifier_free(sonic_verifier_t* v) {
   if (!v) return;
@@ -584,23 +580,23 @@ int sonic_verifier_verify_batch(sonic_verifier_t* v, int64_t K, const uint8_t* p
                                 uint8_t* each) {
   if (!v || !proofs || !challenges || !all_accepted) { set_error("sonic_verifier_verify_batch: bad argument"); return SONIC_ERR_INVALID_ARG; }
   *all_accepted = 0;
-  VB_BEGIN(v->device)
+  API_BEGIN_ON(v->device)
   int rc = batch_size_ok("sonic_verifier_verify_batch", v, K);
   if (rc) return rc;
   std::lock_guard<std::mutex> g(v->mu);
   return verify_batch_core(v, (long)K, proofs, challenges, seed, all_accepted, each);
-  VB_END
+  API_CATCH
 }
 
 int sonic_verifier_verify_fs_batch(sonic_verifier_t* v, int64_t K, const uint8_t* proofs, const uint8_t seed[32], int* all_accepted, uint8_t* each) {
   if (!v || !proofs || !all_accepted) { set_error("sonic_verifier_verify_fs_batch: bad argument"); return SONIC_ERR_INVALID_ARG; }
   *all_accepted = 0;
-  VB_BEGIN(v->device)
+  API_BEGIN_ON(v->device)
   int rc = batch_size_ok("sonic_verifier_verify_fs_batch", v, K);
   if (rc) return rc;
   std::lock_guard<std::mutex> g(v->mu);
   return verify_fs_batch_core(v, (long)K, proofs, seed, all_accepted, each, nullptr);
-  VB_END
+  API_CATCH
 }
 
 // the compressed forms: decompress on the device, then the very same verifier over the rebuilt proof bytes
@@ -608,33 +604,33 @@ int sonic_verifier_verify_batch_z(sonic_verifier_t* v, int64_t K, const uint8_t*
                                   uint8_t* each) {
   if (!v || !proofs_z || !challenges || !all_accepted) { set_error("sonic_verifier_verify_batch_z: bad argument"); return SONIC_ERR_INVALID_ARG; }
   *all_accepted = 0;
-  VB_BEGIN(v->device)
+  API_BEGIN_ON(v->device)
   int rc = batch_size_ok("sonic_verifier_verify_batch_z", v, K);
   if (rc) return rc;
   std::lock_guard<std::mutex> g(v->mu);
   std::vector<uint8_t> proofs, accepted;
   decompress_device(v, (long)K, proofs_z, proofs, accepted);
   return verify_batch_core(v, (long)K, proofs.data(), challenges, seed, all_accepted, each, &accepted);
-  VB_END
+  API_CATCH
 }
 int sonic_verifier_verify_fs_batch_z(sonic_verifier_t* v, int64_t K, const uint8_t* proofs_z, const uint8_t seed[32], int* all_accepted, uint8_t* each) {
   if (!v || !proofs_z || !all_accepted) { set_error("sonic_verifier_verify_fs_batch_z: bad argument"); return SONIC_ERR_INVALID_ARG; }
   *all_accepted = 0;
-  VB_BEGIN(v->device)
+  API_BEGIN_ON(v->device)
   int rc = batch_size_ok("sonic_verifier_verify_fs_batch_z", v, K);
   if (rc) return rc;
   std::lock_guard<std::mutex> g(v->mu);
   std::vector<uint8_t> proofs, accepted;
   decompress_device(v, (long)K, proofs_z, proofs, accepted);
   return verify_fs_batch_core(v, (long)K, proofs.data(), seed, all_accepted, each, &accepted);
-  VB_END
+  API_CATCH
 }
 
 // one statement per proof: proof k against the handle's weights and cs_k (compressed: 0 = 96-byte points, 1 = 48-byte points)
 int sonic_verifier_verify_batch_cs(sonic_verifier_t* v, int64_t K, const uint8_t* proofs, int compressed, const uint8_t* challenges, const uint8_t* cs,
                                    const uint8_t seed[32], int* all_accepted, uint8_t* each) {
   if (all_accepted) *all_accepted = 0;
-  VB_BEGIN(v ? v->device : -1)                      // (first: without a device the answer is SONIC_ERR_NO_DEVICE whatever the arguments are)
+  API_BEGIN_ON(v ? v->device : -1)                      // (first: without a device the answer is SONIC_ERR_NO_DEVICE whatever the arguments are)
   if (!v || !proofs || !challenges || !cs || !all_accepted || (compressed != 0 && compressed != 1)) { set_error("sonic_verifier_verify_batch_cs: bad argument"); return SONIC_ERR_INVALID_ARG; }
   int rc = batch_size_ok("sonic_verifier_verify_batch_cs", v, K);
   if (rc) return rc;
@@ -643,12 +639,12 @@ int sonic_verifier_verify_batch_cs(sonic_verifier_t* v, int64_t K, const uint8_t
   std::vector<uint8_t> full, accepted;
   decompress_device(v, (long)K, proofs, full, accepted);
   return verify_batch_core(v, (long)K, full.data(), challenges, seed, all_accepted, each, &accepted, cs);
-  VB_END
+  API_CATCH
 }
 int sonic_verifier_verify_fs_batch_cs(sonic_verifier_t* v, int64_t K, const uint8_t* proofs, int compressed, const uint8_t* cs, const uint8_t seed[32],
                                       int* all_accepted, uint8_t* each) {
   if (all_accepted) *all_accepted = 0;
-  VB_BEGIN(v ? v->device : -1)                      // (first: without a device the answer is SONIC_ERR_NO_DEVICE whatever the arguments are)
+  API_BEGIN_ON(v ? v->device : -1)                      // (first: without a device the answer is SONIC_ERR_NO_DEVICE whatever the arguments are)
   if (!v || !proofs || !cs || !all_accepted || (compressed != 0 && compressed != 1)) { set_error("sonic_verifier_verify_fs_batch_cs: bad argument"); return SONIC_ERR_INVALID_ARG; }
   int rc = batch_size_ok("sonic_verifier_verify_fs_batch_cs", v, K);
   if (rc) return rc;
@@ -657,12 +653,12 @@ int sonic_verifier_verify_fs_batch_cs(sonic_verifier_t* v, int64_t K, const uint
   std::vector<uint8_t> full, accepted;
   decompress_device(v, (long)K, proofs, full, accepted);
   return verify_fs_batch_core(v, (long)K, full.data(), seed, all_accepted, each, &accepted, cs);
-  VB_END
+  API_CATCH
 }
 
 int sonic_verifier_eval_s(sonic_verifier_t* v, int64_t K, const uint8_t* uv, uint8_t* out) {
   if (!v || !uv || !out) { set_error("sonic_verifier_eval_s: bad argument"); return SONIC_ERR_INVALID_ARG; }
-  VB_BEGIN(v->device)
+  API_BEGIN_ON(v->device)
   int rc = batch_size_ok("sonic_verifier_eval_s", v, K);
   if (rc) return rc;
   std::vector<Fr> us((size_t)K), vs((size_t)K), sv;
@@ -680,13 +676,13 @@ int sonic_verifier_eval_s(sonic_verifier_t* v, int64_t K, const uint8_t* uv, uin
   }
   if (refused >= 0) { set_error("sonic_verifier_eval_s: u or v is zero in pair %lld", (long long)refused); return SONIC_ERR_INEXACT_DIVISION; }
   return SONIC_OK;
-  VB_END
+  API_CATCH
 }
 
 int sonic_g1_validate(const uint8_t* points, int64_t n, uint8_t* flags) {
   if (n < 0 || (n > 0 && (!points || !flags))) { set_error("sonic_g1_validate: bad argument"); return SONIC_ERR_INVALID_ARG; }
   if (n == 0) return SONIC_OK;
-  VB_BEGIN(-1)
+  API_BEGIN
   CallLease lease;
   hipStream_t st = lease.st();
   DevBuf raw(96 * (size_t)n), pts(sizeof(G1Affine) * (size_t)n), fl((size_t)n);
@@ -695,7 +691,7 @@ int sonic_g1_validate(const uint8_t* points, int64_t n, uint8_t* flags) {
   HIP_OK(hipMemcpyAsync(flags, fl.p, (size_t)n, hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));
   return SONIC_OK;
-  VB_END
+  API_CATCH
 }
 
 int sonic_verify_batch_randomizers(const uint8_t seed[32], const uint8_t batch_digest[32], int64_t count, uint8_t* out) {

@@ -315,6 +315,40 @@ def test_window_tables(sonic, orc, srs_pair):
     assert msm_g1_srs(narrow, 1, -2500, sc) == msm_g1_srs(g, 1, -2500, sc)
 
 
+PLANS_DEFAULT = [(10, 26, 1), (10, 26, 1), (10, 26, 1)]
+PLANS_TABLE_C_9 = [(9, 29, 1), (9, 29, 1), (9, 29, 1)]
+PLANS_ENDO = [(10, 13, 1), (10, 13, 1), (10, 13, 1)]
+PLANS_NO_TABLES = [(4, 64, 64), (5, 51, 51), (7, 37, 37)]
+
+
+@pytest.mark.parametrize("knob,plans", [
+    (None, PLANS_DEFAULT),
+    (("SONIC_MSM_TABLE_C", "9"), PLANS_TABLE_C_9),
+    (("SONIC_MSM_ENDO", "1"), PLANS_ENDO),
+    (("SONIC_MSM_TABLES", "0"), PLANS_NO_TABLES),
+], ids=["default", "table_c=9", "endo", "no_tables"])
+def test_msm_plan_by_knob(sonic, knob, plans):
+    """sonic_msm_plan over an SRS of d = 1024 as (window_bits, windows, bucket_sets) for MSMs of 1, 512 and 2049 terms, under each knob that
+    sizes the handle's tables.  The literals were read from the library before the sizing rule moved into srs_policy.hpp: the rule and the
+    plan over a handle must not change when the code around them does."""
+    import os
+    import ctypes as C
+    from sonic_amd import _lib
+    if knob:
+        os.environ[knob[0]] = knob[1]
+    try:
+        srs = sonic.SRS.new(1024, 12345, 67890)
+    finally:
+        if knob:
+            del os.environ[knob[0]]
+    got = []
+    for n in (1, 512, 2049):
+        c, w, b = C.c_int(), C.c_int(), C.c_int()
+        _lib.check(_lib.lib().sonic_msm_plan(srs._h, n, C.byref(c), C.byref(w), C.byref(b)))
+        got.append((c.value, w.value, b.value))
+    assert got == plans
+
+
 @pytest.mark.parametrize("c", [4, 7, 11, 16])
 def test_msm_window_sizes(sonic, orc, srs_pair, c):
     from sonic_amd import _lib

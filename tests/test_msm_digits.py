@@ -1,7 +1,7 @@
 """The digit layer of the G1 MSM on the host: a Python mirror of DigitStream and of the even-width window layout (tests/util.py), the
 digit-edge scalar families that tests/test_gpu_msm_paths.py feeds the kernels, and the closed-form reference those tests compare against.
 Every family must produce exactly the signed digits it claims, and every layout must reconstruct its scalar with no carry out of the top
-window: tables (c = 13, 16, 17, 20 as SRS.new picks them, api.hip:306-318), the unfolded windows of sonic_msm_g1 (c = 4..16) and the
+window: tables (c = 13, 16, 17, 20 as SRS.new picks them, srs_policy.hpp), the unfolded windows of sonic_msm_g1 (c = 4..16) and the
 130-bit halves of the endomorphism split."""
 import random
 
