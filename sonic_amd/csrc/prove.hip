@@ -1,6 +1,6 @@
 // Host orchestration of the Sonic prover on one MI355X: Sonic.Protocol.prove
 // (src/Sonic/Protocol.hs:47-109) with Sonic.Signature.hscProve (src/Sonic/Signature.hs:38-72),
-// plus the C-ABI faces of Sonic.SRS.new, commitPoly and openPoly.
+// plus the jobs behind commitPoly and openPoly (their C-ABI faces: poly_api.hip).
 //
 // Everything between "inputs in HBM" and "7+4Q window-sum slots + 3+2Q field elements in HBM" is
 // device work queued with no host synchronisation: the `rnd` draws are explicit (transcript), so no
@@ -119,19 +119,20 @@ MsmJob open_job_at_zero(hipStream_t st, const sonic_srs* srs, const Fr* poly, lo
 // openPoly for several openings over one exponent range as one batched set of launches (poly.hip, open_batch_enqueue); the jobs
 // that are left to run come back in jobs_out, in the order of `ops`
 struct PendingOpen { const Fr* poly; long lo, len; const Fr* zp; Fr* fz; MsmSlot* slot; long slot_index; Scratch* sc; };
+// entry i of a batch: the opening of `poly` (len coefficients) at zp = {z, z^-1}, worked in `sc`, grown to fit; fz null: f(z) is not kept
+static void open_batch_set(OpenBatch& b, int i, Scratch& sc, const Fr* poly, long len, const Fr* zp, Fr* fz) {
+  sc.reserve(len);
+  sc.scan.ensure(sizeof(Fr) * (len / 1024 + 2));
+  b.poly[i] = poly; b.D[i] = sc.D.as<Fr>(); b.q[i] = sc.q.as<Fr>(); b.tiles[i] = sc.scan.as<Fr>();
+  b.zpair[i] = zp; b.fz[i] = fz ? fz : sc.fz_discard.as<Fr>();
+}
 static void open_jobs_batched(hipStream_t st, const sonic_srs* srs, const PendingOpen* ops, int k, int* d_flags, MsmJob* jobs_out) {
   for (int at = 0; at < k;) {
     int e = at;
     OpenBatch b;
     memset(&b, 0, sizeof b);
     while (e < k && e - at < OPEN_BATCH_MAX && ops[e].lo == ops[at].lo && ops[e].len == ops[at].len) {
-      Scratch& sc = *ops[e].sc;
-      const long len = ops[e].len;
-      sc.reserve(len);
-      sc.scan.ensure(sizeof(Fr) * (len / 1024 + 2));
-      const int i = e - at;
-      b.poly[i] = ops[e].poly; b.D[i] = sc.D.as<Fr>(); b.q[i] = sc.q.as<Fr>(); b.tiles[i] = sc.scan.as<Fr>();
-      b.zpair[i] = ops[e].zp; b.fz[i] = ops[e].fz ? ops[e].fz : sc.fz_discard.as<Fr>();
+      open_batch_set(b, e - at, *ops[e].sc, ops[e].poly, ops[e].len, ops[e].zp, ops[e].fz);
       e++;
     }
     b.k = e - at;
@@ -226,22 +227,6 @@ static void s_of_u_of(sonic_prover* p, hipStream_t st, const Fr* upow, Fr* out) 
 
 extern "C" {
 
-int sonic_srs_new(int64_t d, const uint8_t x[32], const uint8_t alpha[32], sonic_srs_t** out) { return sonic_srs_new_on(-1, d, x, alpha, out); }
-int sonic_srs_new_on(int device, int64_t d, const uint8_t x[32], const uint8_t alpha[32], sonic_srs_t** out) {
-  API_BEGIN_ON(device)
-  if (d < 1 || !x || !alpha || !out) { set_error("sonic_srs_new: bad argument"); return SONIC_ERR_INVALID_ARG; }
-  Fr xs, as;
-  memcpy(xs.l, x, 32); memcpy(as.l, alpha, 32);
-  if (!fp_is_canonical(xs) || !fp_is_canonical(as)) { set_error("sonic_srs_new: x or alpha not < r"); return SONIC_ERR_BAD_ENCODING; }
-  if (xs.is_zero()) { set_error("sonic_srs_new: x = 0 has no inverse (recip x, SRS.hs:29)"); return SONIC_ERR_INEXACT_DIVISION; }
-  std::lock_guard<std::mutex> g(call_mutex());
-  sonic_srs* s = srs_alloc(d);
-  try { srs_generate(default_stream(), s, xs, as); } catch (...) { sonic_srs_free(s); throw; }
-  s->have_trapdoor = true; s->x_std = xs; s->alpha_std = as;
-  *out = s;
-  API_END
-}
-
 size_t sonic_proof_size(int64_t Q) { return ProofLayout{Q}.proof_bytes(); }
 
 static int prover_new_entry(const char* who, const sonic_srs_t* srs, const CircuitView& c, sonic_prover_t** out) {
@@ -287,16 +272,9 @@ int prover_new_impl(const sonic_srs_t* srs, const CircuitView& c, sonic_prover_t
     const MsmPlan probe = srs_msm_plan(srs, 3 * n);
     p->small_plan = msm_can_batch(probe) && probe.NB <= (1 << 17);
   }
-  int prio_low = 0, prio_high = 0;
-  (void)hipDeviceGetStreamPriorityRange(&prio_low, &prio_high);        // (numerically lowest = highest priority)
-  const char* pe = getenv("SONIC_PROVE_PRIORITIES");
-  const bool use_prio = p->small_plan && pe && atoi(pe) == 1 && prio_low != prio_high;
-  auto mkstream = [&](hipStream_t* s, int prio) {
-    if (use_prio) HIP_OK(hipStreamCreateWithPriority(s, hipStreamNonBlocking, prio));
-    else HIP_OK(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
-  };
-  mkstream(&p->st, prio_high);
-  mkstream(&p->ts, prio_high);
+  auto mkstream = [](hipStream_t* s) { HIP_OK(hipStreamCreateWithFlags(s, hipStreamNonBlocking)); };
+  mkstream(&p->st);
+  mkstream(&p->ts);
   hipStream_t st = p->st;
   p->flags.alloc(8);
   int rc_c = prover_load_circuit(p.get(), c);
@@ -337,25 +315,18 @@ int prover_new_impl(const sonic_srs_t* srs, const CircuitView& c, sonic_prover_t
   // MSM workspaces and opening scratch grow on first use: every proof maps the same group of MSMs to the same lane
   if (p->small_plan) {
     const char* le = getenv("SONIC_FUSED_LANES");
-    const int v = le ? atoi(le) : N_LANES;                 // 0: no lane of its own (few_streams); k: k lanes
-    p->few_streams = v <= 0;
-    p->n_lanes = v < 1 ? 0 : (v > N_LANES ? N_LANES : v);
-    if (p->few_streams) {
-      p->main_lane.st = p->st; p->ts_lane.st = p->ts;
-      mkev(&p->main_lane.done); mkev(&p->main_lane.prep);
-      mkev(&p->ts_lane.done); mkev(&p->ts_lane.prep);
-    }
+    p->n_lanes = std::min(std::max(le ? atoi(le) : N_LANES, 1), N_LANES);      // (lane_at and pick divide by it)
   }
   for (int i = 0; i < p->n_lanes; i++) {
     Lane& l = p->lanes[i];
-    mkstream(&l.st, prio_high);
+    mkstream(&l.st);
     mkev(&l.done);
     mkev(&l.prep);
   }
   if (p->small_plan) {
     // (the second chain stream is only used by proofs of more than MSM_MAX_JOBS MSMs: Q > 2)
     for (int c = 0; c < (L.K() > MSM_MAX_JOBS ? 2 : 1); c++) {
-      mkstream(&p->chain[c].st, prio_low);
+      mkstream(&p->chain[c].st);
       mkev(&p->chain[c].done);
     }
   }
@@ -450,16 +421,14 @@ struct GroupQueue {
     else for (auto& f : after_flush) f();
     after_flush.clear();
   }
-  // (few_streams: on_ts = the group rides on the transform's stream -- r(X,1)'s, queued there ahead of the product --, else on the main stream)
-  void begin_group(hipEvent_t e, bool on_ts = false) {
+  void begin_group(hipEvent_t e) {
     flush();
-    if (p->few_streams && on_ts) { cur = &p->ts_lane; HIP_OK(hipStreamWaitEvent(p->ts, e, 0)); }
-    else cur = &p->pick(e);
+    cur = &p->pick(e);
     cur->njobs = 0;
   }
-  // the t group's lane (prover.hpp, t_lane) takes over without a flush; it waits for the product unless it IS the product's stream
+  // the t group's lane (prover.hpp, t_lane) takes over without a flush; it waits for the product
   void begin_t_group(Lane& lane_t) {
-    if (on(PH_T) && lane_t.st != p->ts) HIP_OK(hipStreamWaitEvent(lane_t.st, p->ev_t, 0));
+    if (on(PH_T)) HIP_OK(hipStreamWaitEvent(lane_t.st, p->ev_t, 0));
     cur = &lane_t; cur->njobs = 0;
   }
   void make_room() { if (cur->njobs + (int)pend.size() == MSM_MAX_JOBS) flush(); }
@@ -525,37 +494,24 @@ struct GroupQueue {
     if (when == BEHIND_CHAIN ? !p->fused : cur->njobs == 0) fn();
     else (when == BEHIND_CHAIN ? deferred_small : after_flush).push_back(std::move(fn));
   }
-  MsmPlan chain_plan(const MsmJob* jobs, int k) const {
-    long nmax = 0;
-    for (int j = 0; j < k; j++) nmax = std::max(nmax, jobs[j].n);
-    MsmPlan pl = srs_msm_plan(srs, nmax);
-    pl.tree = true;
-    return pl;
-  }
-  // fused: the current group as a chain of its own on its lane (SONIC_FUSED_SPLIT_T)
-  void flush_as_chain() {
-    issue_opens();
-    if (cur->njobs > 0) msm_enqueue_batch(cur->st, cur->ws, chain_plan(cur->jobs, cur->njobs), cur->jobs, cur->njobs, true);
-    cur->njobs = 0;
-  }
   // the proof's chain(s): every lane has queued the openings of its groups by now; chunks of at most MSM_MAX_JOBS jobs (one chunk up to
-  // Q = 2) on the two chain streams in turn so that two chunks overlap like two groups did.  ts_used: the transform's stream carries work
-  void run_chains(bool ts_used) {
+  // Q = 2) on the two chain streams in turn so that two chunks overlap like two groups did
+  void run_chains() {
     if (!p->fused || p->fused_jobs.empty()) return;
     for (int i = 0; i < p->n_lanes; i++) HIP_OK(hipEventRecord(p->lanes[i].prep, p->lanes[i].st));
-    if (p->few_streams) { HIP_OK(hipEventRecord(p->main_lane.prep, p->st)); if (ts_used) HIP_OK(hipEventRecord(p->ts_lane.prep, p->ts)); }
     const int total = (int)p->fused_jobs.size();
     const int nchunks = (total + MSM_MAX_JOBS - 1) / MSM_MAX_JOBS, per = (total + nchunks - 1) / nchunks;
     for (int c = 0, at = 0; c < nchunks; c++, at += per) {
       Lane& cl = p->chain[c & 1];
-      if (c < 2) {
-        for (int i = 0; i < p->n_lanes; i++) HIP_OK(hipStreamWaitEvent(cl.st, p->lanes[i].prep, 0));
-        if (p->few_streams) { HIP_OK(hipStreamWaitEvent(cl.st, p->main_lane.prep, 0)); if (ts_used) HIP_OK(hipStreamWaitEvent(cl.st, p->ts_lane.prep, 0)); }
-      }
+      if (c < 2) for (int i = 0; i < p->n_lanes; i++) HIP_OK(hipStreamWaitEvent(cl.st, p->lanes[i].prep, 0));
       const int k = std::min(per, total - at);
-      MsmPlan pl = chain_plan(&p->fused_jobs[(size_t)at], k);
+      const MsmJob* jobs = &p->fused_jobs[(size_t)at];
+      long nmax = 0;
+      for (int j = 0; j < k; j++) nmax = std::max(nmax, jobs[j].n);
+      MsmPlan pl = srs_msm_plan(srs, nmax);
+      pl.tree = true;
       pl.accum_block = 128;      // (measured for this chain, n = 2^16 streamed: 128 lanes 9.19-9.27 ms, 256 9.46-9.49, 512 9.42-9.46)
-      msm_enqueue_batch(cl.st, cl.ws, pl, &p->fused_jobs[(size_t)at], k, true);
+      msm_enqueue_batch(cl.st, cl.ws, pl, jobs, k, true);
     }
     p->fused_jobs.clear();
   }
@@ -564,11 +520,10 @@ struct GroupQueue {
     deferred_small.clear();
   }
   // the main stream waits for every stream that carried a part of the proof
-  void join(bool ts_used) {
+  void join() {
     hipStream_t ms = p->st;
     for (int i = 0; i < p->n_lanes; i++) { Lane& l = p->lanes[i]; HIP_OK(hipEventRecord(l.done, l.st)); HIP_OK(hipStreamWaitEvent(ms, l.done, 0)); }
     if (p->fused) for (auto& l : p->chain) if (l.st) { HIP_OK(hipEventRecord(l.done, l.st)); HIP_OK(hipStreamWaitEvent(ms, l.done, 0)); }
-    if (p->few_streams && ts_used) { HIP_OK(hipEventRecord(p->ts_lane.done, p->ts_lane.st)); HIP_OK(hipStreamWaitEvent(ms, p->ts_lane.done, 0)); }
   }
 };
 
@@ -584,7 +539,6 @@ struct ProofPass {
   int last_group;                 // the group whose reduction nothing is left to hide under (the t group when this rank has a piece of it)
   bool g0_queued = false;
   const Fr* pair(long i) const { return PR + 2 * i; }
-  bool ts_used() const { return need_T || g0_queued; }
   ProofPass(sonic_prover_t* p, const GroupQueue& q)
       : n(p->n), Q(p->Q), d(p->srs->d), r_lo(-2 * n - 4), r_len(3 * n + 5), s_lo(-n), s_len(3 * n + 1), t_lo(-4 * n - 8), t_len(7 * n + 9),
         u_lo(-n), u_len(2 * n + Q + 1), PR(p->PAIRS.as<Fr>()), need_j((size_t)Q, 0) {
@@ -608,7 +562,7 @@ static void enqueue_group0(sonic_prover_t* p, GroupQueue& q, ProofPass& w) {
   w.g0_queued = true;
   const ProofLayout& L = q.L;
   const Fr* r1 = p->r1.as<Fr>();
-  q.begin_group(p->ev_r1, /*on_ts=*/true);
+  q.begin_group(p->ev_r1);
   q.commit(PH_R, r1, w.r_lo, w.r_len, w.n, L.R);                                       // R            Protocol.hs:63
   q.open(PH_OPEN, r1, w.r_lo, w.r_len, w.pair(L.pZ), L.a, L.Wa);                       // (a, W_a)     :79
   q.open(PH_OPEN, r1, w.r_lo, w.r_len, w.pair(L.pYZ), L.b, L.Wb);                      // (b, W_b)     :80
@@ -641,7 +595,6 @@ static void enqueue_polynomials(sonic_prover_t* p, GroupQueue& q, ProofPass& w) 
   if ((w.need_g0 || w.need_T) && q.on(PH_R)) build_r1_enqueue(ms, p->aL.as<Fr>(), p->aR.as<Fr>(), p->aO.as<Fr>(), p->S.as<Fr>(), n, r1);
   ready(p->ev_r1);
   // the group that needs nothing but r(X,1): queued here, ahead of the other polynomials, when this call's circuit is still on the host
-  if (p->few_streams && p->fused) enqueue_group0(p, q, w);          // (its openings go on the transform's stream, ahead of the product's kernels)
   if (p->pend.set) {
     enqueue_group0(p, q, w);
     prover_upload_circuit(p, ms, flags + 1);
@@ -682,15 +635,14 @@ static void enqueue_polynomials(sonic_prover_t* p, GroupQueue& q, ProofPass& w) 
   ready(p->ev_su);
 }
 
-// T and W_t, as a chain of their own when the rest of a fused proof runs without them (SONIC_FUSED_SPLIT_T)
-static void enqueue_t_group(sonic_prover_t* p, GroupQueue& q, const ProofPass& w, Lane& lane_t, bool own_chain) {
+// T and W_t: the group whose polynomial is ready last
+static void enqueue_t_group(sonic_prover_t* p, GroupQueue& q, const ProofPass& w, Lane& lane_t) {
   const ProofLayout& L = q.L;
   const Fr* t = p->fa.as<Fr>();                                                        // exponents [t_lo, t_lo + t_len)
   q.begin_t_group(lane_t);
   q.commit(PH_T, t, w.t_lo, w.t_len, w.d, L.T);                                        // T            Protocol.hs:73
   q.open(PH_OPEN, t, w.t_lo, w.t_len, w.pair(L.pZ), -1, L.Wt);                         // W_t          :81
-  if (p->fused && own_chain) q.flush_as_chain();
-  else q.flush(true);
+  q.flush(true);
 }
 
 // ---- the MSM groups, largest first where its input allows: what the protocol commits to and opens ----
@@ -701,16 +653,11 @@ static void enqueue_groups(sonic_prover_t* p, GroupQueue& q, ProofPass& w) {
   Fr* su = p->su.as<Fr>();
   Lane& lane_t = p->t_lane(p->ev_sy0);
   if (q.on(PH_OPEN) && q.first_piece(L.Wt)) {                                          // s(z,y)       :83  (reported by the rank that starts W_t)
-    // (few_streams: on the main stream, not behind the transform on its stream -- the evaluation needs s(X,y) only, and everything queued
-    // behind the transform is on the longest dependent chain of a proof)
-    Lane& le = p->few_streams ? p->main_lane : lane_t;
-    Scratch& es = le.sc[MSM_MAX_JOBS - 1];
-    es.reserve(w.s_len);
-    es.scan.ensure(sizeof(Fr) * (w.s_len / 1024 + 2));
     OpenBatch eb;
     memset(&eb, 0, sizeof eb);
-    eb.k = 1; eb.poly[0] = p->sy0.as<Fr>(); eb.D[0] = es.D.as<Fr>(); eb.q[0] = es.q.as<Fr>(); eb.tiles[0] = es.scan.as<Fr>(); eb.zpair[0] = w.pair(L.pZ); eb.fz[0] = &q.frout[L.s];
-    open_batch_enqueue(le.st, eb, w.s_lo, w.s_len, /*quotient=*/false);
+    eb.k = 1;
+    open_batch_set(eb, 0, lane_t.sc[MSM_MAX_JOBS - 1], p->sy0.as<Fr>(), w.s_len, w.pair(L.pZ), &q.frout[L.s]);
+    open_batch_enqueue(lane_t.st, eb, w.s_lo, w.s_len, /*quotient=*/false);
     p->fr_valid[(size_t)L.s] = 1;
   }
   enqueue_group0(p, q, w);
@@ -741,14 +688,8 @@ static void enqueue_groups(sonic_prover_t* p, GroupQueue& q, ProofPass& w) {
     q.open(PH_QV, su, w.u_lo, w.u_len, w.pair(L.pV), -1, L.Qv());                      // Q_v           :63
   }
   q.flush(w.last_group == 2 && q.sh != nullptr);
-  // (SONIC_FUSED_SPLIT_T=1, measured and not the default: T and W_t -- 14n of a proof's 45n terms, and the group whose polynomial is ready
-  // last -- as a SECOND chain on the stream that made the polynomial, so that the chain of the other thirteen MSMs need not wait for the
-  // product.  One at a time it gains 1-3 %; streamed it loses 3-10 % at n = 2^14 .. 2^16: two sorts, two accumulation tails and two
-  // butterflies per proof; profiles/r06_ab_small_final.txt)
-  static const bool split_t = getenv("SONIC_FUSED_SPLIT_T") && atoi(getenv("SONIC_FUSED_SPLIT_T")) != 0;
-  if (w.need_T && !(p->fused && split_t)) enqueue_t_group(p, q, w, lane_t, false);
-  q.run_chains(w.ts_used());
-  if (w.need_T && p->fused && split_t) enqueue_t_group(p, q, w, lane_t, true);
+  if (w.need_T) enqueue_t_group(p, q, w, lane_t);
+  q.run_chains();
   q.drain_deferred();
 }
 
@@ -767,7 +708,7 @@ static void enqueue_proof(sonic_prover_t* p) {
   ProofPass w(p, q);
   enqueue_polynomials(p, q, w);
   enqueue_groups(p, q, w);
-  q.join(w.ts_used());
+  q.join();
   Fr* frstd = p->frstd.as<Fr>();
   HIP_OK(hipMemcpyAsync(frstd, q.frout, sizeof(Fr) * L.F(), hipMemcpyDeviceToDevice, st));
   fr_from_mont_enqueue(st, frstd, L.F());
@@ -907,17 +848,25 @@ extern "C" size_t sonic_proof_share_size(int64_t Q) {
   return sizeof(ShareHeader) + K * 8 + K * 192 + F * 32 + F * 4;
 }
 
+// what both finishes open with: wait for the device, count the proof, say where the time went (SONIC_DEBUG_TIMING: returns whether it is set)
+static bool await_proof(sonic_prover_t* p, bool share) {
+  HIP_OK(hipStreamSynchronize(p->st));
+  p->proofs_done++;
+  if (!getenv("SONIC_DEBUG_TIMING")) return false;
+  char who[32] = "prove";
+  if (share) snprintf(who, sizeof who, "share %d/%d", p->share_rank, p->share_world);
+  fprintf(stderr, "[sonic] %s: enqueue %.3f ms, then waited %.3f ms for the device\n", who,
+          std::chrono::duration<double, std::milli>(p->t_enq - p->t_begin).count(),
+          std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - p->t_enq).count());
+  return true;
+}
+
 static int prove_finish_share(sonic_prover_t* p, uint8_t* out_share) {
   API_BEGIN_ON(p->device)
   const long Q = p->Q;
   const ProofLayout L{Q};
   const int K = (int)L.K(), F = (int)L.F();
-  HIP_OK(hipStreamSynchronize(p->st));
-  p->proofs_done++;
-  if (getenv("SONIC_DEBUG_TIMING"))
-    fprintf(stderr, "[sonic] share %d/%d: enqueue %.3f ms, then waited %.3f ms for the device\n", p->share_rank, p->share_world,
-            std::chrono::duration<double, std::milli>(p->t_enq - p->t_begin).count(),
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - p->t_enq).count());
+  await_proof(p, /*share=*/true);
   const MsmSlot* hs = p->h_slots;
   memset(out_share, 0, sonic_proof_share_size(Q));
   ShareHeader h{SHARE_MAGIC, SHARE_VERSION, p->share_rank, p->share_world > 1 ? p->share_world : 1, Q, *p->h_flags, p->share_world > 1 ? p->share_plan_tag : 0};
@@ -1016,18 +965,11 @@ static int prove_finish(sonic_prover_t* p, uint8_t* out_proof) {
   const long Q = p->Q;
   const ProofLayout L{Q};
   const int K = (int)L.K();
-  hipStream_t st = p->st;
   const uint8_t* transcript = p->h_tr;
-  const auto t_begin = p->t_begin, t_enq = p->t_enq;
-  const bool timing = getenv("SONIC_DEBUG_TIMING") != nullptr;
-  HIP_OK(hipStreamSynchronize(st));
-  p->proofs_done++;
+  const bool timing = await_proof(p, /*share=*/false);
   const MsmSlot* hs = p->h_slots;
   const uint8_t* hfr_p = p->h_fr;
   const int hflags = *p->h_flags;
-  if (timing) fprintf(stderr, "[sonic] prove: enqueue %.3f ms, then waited %.3f ms for the device\n",
-                      std::chrono::duration<double, std::milli>(t_enq - t_begin).count(),
-                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enq).count());
   if (p->h_flags[1]) { p->have_assignment = false; return flags_to_status(p->h_flags[1], "prove (circuit / assignment handed over with the call)"); }
   if (hflags) return flags_to_status(hflags, "prove");
   std::vector<uint8_t> pts(96 * (size_t)K);
@@ -1069,22 +1011,24 @@ static int prove_args_ok(sonic_prover_t* p, const char* who) {
   return SONIC_OK;
 }
 
+// the tail of every prove call: queue the proof, then `finish` it into `out` (null: leave it in flight, sonic_prover_submit)
+static int prove_run(sonic_prover_t* p, const uint8_t* transcript, int (*finish)(sonic_prover_t*, uint8_t*), uint8_t* out) {
+  int rc = prove_enqueue(p, transcript);
+  if (rc) { if (p->st) (void)hipStreamSynchronize(p->st); return rc; }      // an enqueue that failed half way: let what was queued drain
+  return finish ? finish(p, out) : SONIC_OK;
+}
+
 int sonic_prover_prove(sonic_prover_t* p, const uint8_t* transcript, uint8_t* out_proof) {
   if (!p || !transcript || !out_proof) return SONIC_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> g(p->mu);
   int rc = prove_args_ok(p, "sonic_prover_prove");
   if (!rc) rc = whole_proof_only(p, "sonic_prover_prove");
-  if (!rc) rc = prove_enqueue(p, transcript);
-  if (!rc) rc = prove_finish(p, out_proof);
-  else if (p->st) (void)hipStreamSynchronize(p->st);      // an enqueue that failed half way: let what was queued drain
+  if (!rc) rc = prove_run(p, transcript, prove_finish, out_proof);
   return rc;
 }
 
-// prove with the assignment of THIS call still in the caller's host buffers (uploaded inside the proof's queue: pend_asg)
-int prove_with_assignment(sonic_prover_t* p, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO, const uint8_t* transcript, uint8_t* out_proof) {
-  return prove_with_statement(p, aL, aR, aO, nullptr, transcript, out_proof);
-}
-// ... and its constants (pend_cs), either or both
+// prove with the assignment of THIS call still in the caller's host buffers (uploaded inside the proof's queue: pend_asg) and its
+// constants (pend_cs), either or both
 int prove_with_statement(sonic_prover_t* p, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO, const uint8_t* cs, const uint8_t* transcript,
                          uint8_t* out_proof) {
   std::lock_guard<std::mutex> g(p->mu);
@@ -1094,9 +1038,7 @@ int prove_with_statement(sonic_prover_t* p, const uint8_t* aL, const uint8_t* aR
   if (!aL && !p->have_assignment) { set_error("prove: no assignment set"); return SONIC_ERR_INVALID_ARG; }
   if (aL) { p->pend_asg[1] = aR; p->pend_asg[2] = aO; p->pend_asg[0] = aL; }
   p->pend_cs = cs;
-  rc = prove_enqueue(p, transcript);
-  if (!rc) rc = prove_finish(p, out_proof);
-  else if (p->st) (void)hipStreamSynchronize(p->st);
+  rc = prove_run(p, transcript, prove_finish, out_proof);
   p->pend_asg[0] = nullptr;
   p->pend_cs = nullptr;
   if (aL) p->have_assignment = rc == SONIC_OK;          // (a failed call may have left a partly converted assignment behind)
@@ -1107,9 +1049,8 @@ int sonic_prover_submit(sonic_prover_t* p, const uint8_t* transcript) {
   if (!p || !transcript) return SONIC_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> g(p->mu);
   int rc = prove_args_ok(p, "sonic_prover_submit");
-  if (!rc) rc = prove_enqueue(p, transcript);
+  if (!rc) rc = prove_run(p, transcript, nullptr, nullptr);
   if (!rc) p->in_flight = true;
-  else if (p->st) (void)hipStreamSynchronize(p->st);
   return rc;
 }
 
@@ -1155,9 +1096,7 @@ int sonic_prover_prove_share(sonic_prover_t* p, const uint8_t* transcript, uint8
   if (!p || !transcript || !out_share) return SONIC_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> g(p->mu);
   int rc = prove_args_ok(p, "sonic_prover_prove_share");
-  if (!rc) rc = prove_enqueue(p, transcript);
-  if (!rc) rc = prove_finish_share(p, out_share);
-  else if (p->st) (void)hipStreamSynchronize(p->st);
+  if (!rc) rc = prove_run(p, transcript, prove_finish_share, out_share);
   return rc;
 }
 
@@ -1232,9 +1171,7 @@ int sonic_prover_prove_fs(sonic_prover_t* p, const uint8_t circuit_digest[32], c
   t.init(n, Q, d, circuit_digest, srs_id);
   auto pass = [&](int ph) {
     p->phases = 1u << ph;
-    int r = prove_enqueue(p, tr.data());
-    if (!r) r = prove_finish(p, pf.data());
-    else if (p->st) (void)hipStreamSynchronize(p->st);
+    int r = prove_run(p, tr.data(), prove_finish, pf.data());
     p->phases = PH_ALL;
     return r;
   };
@@ -1316,7 +1253,6 @@ int sonic_prover_prepare(sonic_prover_t* p) {
     run_jobs(l.st, p->srs, l.ws, &job, 1);
   }
   for (int i = 0; i < p->n_lanes; i++) HIP_OK(hipStreamSynchronize(p->lanes[i].st));
-  if (p->few_streams) { HIP_OK(hipStreamSynchronize(p->st)); HIP_OK(hipStreamSynchronize(p->ts)); }
   std::vector<MsmSlot> hs(Q);
   HIP_OK(hipMemcpy(hs.data(), slots.p, sizeof(MsmSlot) * Q, hipMemcpyDeviceToHost));
   int hflags = 0;

@@ -88,7 +88,7 @@ static int one_shot_prove(const char* who, const sonic_srs_t* srs, const Circuit
     if (rc) return rc;
     sh = new OneShotShell{srs, p};
   }
-  rc = prove_with_assignment(sh->p, aL, aR, aO, transcript, out_proof);
+  rc = prove_with_statement(sh->p, aL, aR, aO, /*cs=*/nullptr, transcript, out_proof);
   sh->p->pend = sonic_prover::PendingCircuit();       // (a call that failed before its upload: the caller's buffers end with the call)
   park_shell(ctx, sh);        // (also after a failed call: the next one loads its own circuit and assignment)
   return rc;
@@ -223,7 +223,7 @@ static int prove_batch_impl(const char* who, sonic_prover_t* const* provers, int
           }
           if (!rc) rc = prove_with_statement(provers[h], per_proof ? aL + asz * (size_t)i : nullptr, per_proof ? aR + asz * (size_t)i : nullptr,
                                              per_proof ? aO + asz * (size_t)i : nullptr, cs + ksz * (size_t)i, transcripts + tsz * (size_t)i, out_proofs + psz * (size_t)i);
-        } else if (per_proof) rc = prove_with_assignment(provers[h], aL + asz * (size_t)i, aR + asz * (size_t)i, aO + asz * (size_t)i, transcripts + tsz * (size_t)i, out_proofs + psz * (size_t)i);
+        } else if (per_proof) rc = prove_with_statement(provers[h], aL + asz * (size_t)i, aR + asz * (size_t)i, aO + asz * (size_t)i, /*cs=*/nullptr, transcripts + tsz * (size_t)i, out_proofs + psz * (size_t)i);
         else rc = sonic_prover_prove(provers[h], transcripts + tsz * (size_t)i, out_proofs + psz * (size_t)i);
         if (rc && first_bad[(size_t)h] < 0) { first_bad[(size_t)h] = i; char b[512]; sonic_last_error(b, sizeof b); errs[(size_t)h] = b; }
       } catch (...) { rc = SONIC_ERR_HIP; }                          // (nothing may leave a thread's body: std::terminate)

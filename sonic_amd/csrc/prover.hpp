@@ -90,23 +90,11 @@ struct sonic_prover {
     std::vector<int32_t> h_row_ptr;           // (prepare: the entry ranges of the rows of each P_q)
   } sp;
   Lane lanes[N_LANES];
-  // lanes in use: all six by default.  SONIC_FUSED_LANES=k (small-proof handles): k lanes of their own; =0: NO lane of its own
-  // (few_streams) -- three streams per handle: main, transform, chain; the groups' openings ride on the streams that are waiting anyway
-  // (r(X,1)'s on the transform's stream ahead of the product, the s(X,y_j) groups' and s(u,Y)'s on the main stream behind the polynomials,
-  // t(X,y)'s behind the product) through two lanes that only borrow those streams.  Why the knob exists: the runtime multiplexes a process's
-  // streams onto 8 hardware queues, a new stream getting the least-used one, so WHICH of two streamed handles' twenty streams share a queue
-  // is luck -- one handle's openings behind the other handle's accumulation cost 10 % -- and more hardware queues are worse
-  // (GPU_MAX_HW_QUEUES = 12 .. 32: +1 ms on a sequential small proof, profiles/r06_ab_queues.txt).  Measured, 64 proofs at n = 2^16 on one
-  // box, four fresh pairs of handles each (profiles/r06_batch_mode.txt): six lanes 104-107 proofs/s; three streams 99.2-100.5, every time;
-  // one lane + the borrowed streams (four streams) 98-111 depending on the order the handles were made in.  Three streams lose the
-  // side-by-side openings (n = 2^14 streamed 3.8 against 3.45 ms, n = 2^10 1.5 against 1.2), so six lanes stay the default.
+  // lanes in use (always >= 1): all six by default; SONIC_FUSED_LANES=k (small-proof handles): k of them.  Six, although a fused proof's
+  // lanes only prepare openings: side by side those finish sooner than queued behind each other on fewer streams
   int n_lanes = N_LANES;
-  bool few_streams = false;
-  Lane main_lane, ts_lane;                   // st = the handle's main / transform stream (not owned)
-  // fused proofs (below): the proof's ONE chain runs on a stream of its own.  (Stream priorities -- the chain lowest, everything that builds
-  // polynomials and openings highest, so that the next streamed proof's preparation would get wave slots beside a running accumulation --
-  // were measured and made things WORSE on this runtime: n = 2^16 streamed 10.6 against 9.75 ms, n = 2^14 4.1 against 3.55,
-  // profiles/r06_ab_small.txt; SONIC_PROVE_PRIORITIES=1 still asks for them.)
+  // fused proofs (below): the proof's ONE chain runs on a stream of its own, so that the lanes can queue the next proof's openings
+  // beside it instead of behind its accumulation
   Lane chain[2];
   bool small_plan = false;                   // decided when the handle is made: the SRS plans 2^17 buckets or fewer for this n
   int next_lane = 0;
@@ -212,19 +200,14 @@ struct sonic_prover {
   // Lane N_LANES-1 carries the t(X,y) group (the largest, ready last); the other groups alternate over the rest, which
   // balances the point additions per lane (Q = 2: 55M / 51M / 48M) while one lane's sort and reduction phases run under
   // another lane's accumulation.  Streams beyond the 4 hardware queues would serialise behind each other.
-  Lane& lane_at(int i) { return few_streams ? ((i & 1) ? ts_lane : main_lane) : lanes[i % n_lanes]; }      // (prepare, hscProve: any lane)
+  Lane& lane_at(int i) { return lanes[i % n_lanes]; }      // (prepare, hscProve: any lane)
   Lane& pick(hipEvent_t ready) {
-    if (few_streams) return main_lane;
     Lane& l = lanes[next_lane];
     next_lane = (next_lane + 1) % (n_lanes > 1 ? n_lanes - 1 : 1);
     (void)hipStreamWaitEvent(l.st, ready, 0);
     return l;
   }
   Lane& t_lane(hipEvent_t ready) {
-    // (few_streams: the transform's own stream, which has waited for `ready` when it took the polynomials in -- a second wait for the same
-    // event, or one for an event of the stream itself, becomes a duplicate edge when the enqueue is captured as a hipGraph, and the
-    // runtime's capture code crashed on it)
-    if (few_streams) return ts_lane;
     Lane& l = lanes[n_lanes - 1];
     (void)hipStreamWaitEvent(l.st, ready, 0);
     return l;
@@ -232,7 +215,6 @@ struct sonic_prover {
   ~sonic_prover() {
     for (auto& l : lanes) { if (l.st) (void)hipStreamDestroy(l.st); if (l.done) (void)hipEventDestroy(l.done); if (l.prep) (void)hipEventDestroy(l.prep); }
     for (auto& l : chain) { if (l.st) (void)hipStreamDestroy(l.st); if (l.done) (void)hipEventDestroy(l.done); if (l.prep) (void)hipEventDestroy(l.prep); }
-    for (Lane* l : {&main_lane, &ts_lane}) { if (l->done) (void)hipEventDestroy(l->done); if (l->prep) (void)hipEventDestroy(l->prep); }
     for (auto& r : runs) if (r.masked_ev) (void)hipEventDestroy(r.masked_ev);
     for (hipEvent_t e : {ev_r1, ev_sy0, ev_t, ev_su}) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ev_syj) if (e) (void)hipEventDestroy(e);
@@ -246,10 +228,8 @@ struct sonic_prover {
 // (prove.hip)
 int upload_fr_mont(hipStream_t st, DevBuf& dst, const uint8_t* src, long count, int* d_flags);
 int flags_to_status(int f, const char* who);
-// (defined inside prove.hip's extern "C" block, not exported)
-extern "C" int prove_with_assignment(sonic_prover_t* p, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO, const uint8_t* transcript, uint8_t* out_proof);
-// the same with the constants of this call as well (cs: Q canonical field elements, or null: the handle's; aL, aR, aO all null: the
-// resident assignment)
+// (defined inside prove.hip's extern "C" block, not exported) prove with the assignment and the constants of THIS call still in the
+// caller's host buffers (cs: Q canonical field elements, or null: the handle's; aL, aR, aO all null: the resident assignment)
 extern "C" int prove_with_statement(sonic_prover_t* p, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO, const uint8_t* cs, const uint8_t* transcript,
                                     uint8_t* out_proof);
 // (prove.hip) what sonic_prover_new[_csr] and the one-shot calls share: the checks of a circuit against an SRS, a handle for an admitted

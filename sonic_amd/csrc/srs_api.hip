@@ -1,6 +1,6 @@
 // The SRS handle behind the C ABI (include/sonic_hip.h): sizing and allocation (the rule itself: srs_policy.hpp), the plan of an MSM over a
-// handle, construction from points, the lazy G2 half, point read-back, both on-disk containers and the device-to-device replica.  The
-// handle as a type: srs_handle.hpp; SRS.new lives with the prover's entry points (prove.hip), generation in srs.hip and srs_g2.hip.
+// handle, SRS.new, construction from points, the lazy G2 half, point read-back, both on-disk containers and the device-to-device replica.  The
+// handle as a type: srs_handle.hpp; generation in srs.hip and srs_g2.hip.
 #include <string.h>
 #include <functional>
 #include <memory>
@@ -69,6 +69,22 @@ MsmPlan srs_msm_plan(const sonic_srs* s, long n) {
 using namespace sonic;
 
 extern "C" {
+
+int sonic_srs_new(int64_t d, const uint8_t x[32], const uint8_t alpha[32], sonic_srs_t** out) { return sonic_srs_new_on(-1, d, x, alpha, out); }
+int sonic_srs_new_on(int device, int64_t d, const uint8_t x[32], const uint8_t alpha[32], sonic_srs_t** out) {
+  API_BEGIN_ON(device)
+  if (d < 1 || !x || !alpha || !out) { set_error("sonic_srs_new: bad argument"); return SONIC_ERR_INVALID_ARG; }
+  Fr xs, as;
+  memcpy(xs.l, x, 32); memcpy(as.l, alpha, 32);
+  if (!fp_is_canonical(xs) || !fp_is_canonical(as)) { set_error("sonic_srs_new: x or alpha not < r"); return SONIC_ERR_BAD_ENCODING; }
+  if (xs.is_zero()) { set_error("sonic_srs_new: x = 0 has no inverse (recip x, SRS.hs:29)"); return SONIC_ERR_INEXACT_DIVISION; }
+  std::lock_guard<std::mutex> g(call_mutex());
+  sonic_srs* s = srs_alloc(d);
+  try { srs_generate(default_stream(), s, xs, as); } catch (...) { sonic_srs_free(s); throw; }
+  s->have_trapdoor = true; s->x_std = xs; s->alpha_std = as;
+  *out = s;
+  API_END
+}
 
 int sonic_srs_from_points(int64_t d, const uint8_t* basis0, const uint8_t* basis1, sonic_srs_t** out) {
   return sonic_srs_from_points_on(-1, d, basis0, basis1, out);

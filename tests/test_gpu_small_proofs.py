@@ -1,4 +1,4 @@
-"""Round 6: small proofs as ONE kernel chain (prove.hip `fused`), the batched openings, the four-stream handle, the in-proof assignment
+"""Round 6: small proofs as ONE kernel chain (prove.hip `fused`), the batched openings, a handle's one to six lanes, the in-proof assignment
 upload of sonic_prove_batch / sonic_prove, sonic_one_shot_trim and the sampled "does the circuit have runs" hint -- every variant
 must give the bytes of the CPU oracle (and therefore of each other).
 
@@ -43,8 +43,8 @@ def _circuit(sonic, circ):
 @pytest.mark.parametrize("n,Q", [(1, 1), (2, 5), (40, 2), (300, 3), (1000, 4), (5000, 2), (3 * 4096 + 5, 6)])
 def test_one_chain_per_proof_matches_the_oracle_and_the_lanes(sonic, orc, ref, n, Q):
     """7 + 4Q = 11 .. 31 MSMs: one chunk, two chunks on two chain streams, prepared and not; against the C oracle and against the same
-    handle configuration with the chain switched off (SONIC_PROVE_FUSED=0: round 5's one-chain-per-group lanes) and with six lanes of
-    its own (SONIC_FUSED_LANES=6)"""
+    handle configuration with the chain switched off (SONIC_PROVE_FUSED=0: round 5's one-chain-per-group lanes), with six and two lanes
+    of its own (SONIC_FUSED_LANES=6, =2) and with a value below 1, which is read as 1: the handle must prove at all, and on its single lane"""
     pyr = random.Random(1000 * n + Q)
     d = max(7 * n, 12) + pyr.randrange(40)
     x, alpha = pyr.randrange(2, R), pyr.randrange(2, R)
@@ -54,7 +54,7 @@ def test_one_chain_per_proof_matches_the_oracle_and_the_lanes(sonic, orc, ref, n
     tr = fr_bytes([pyr.randrange(1, R) for _ in range(8 + 2 * Q)])
     orc.set_mode(1, NCPU)
     want = orc.prove(o, n, Q, enc["wL"], enc["wR"], enc["wO"], enc["cs"], enc["aL"], enc["aR"], enc["aO"], tr, n >= 256)
-    for env in ({}, {"SONIC_PROVE_FUSED": 0}, {"SONIC_FUSED_LANES": 6}, {"SONIC_FUSED_LANES": 2}):
+    for env in ({}, {"SONIC_PROVE_FUSED": 0}, {"SONIC_FUSED_LANES": 6}, {"SONIC_FUSED_LANES": 2}, {"SONIC_FUSED_LANES": 0}):
         with _env(**env):
             for prepare in (True, False):
                 p = sonic.Prover(g, _circuit(sonic, circ), prepare=prepare)

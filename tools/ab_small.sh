@@ -11,9 +11,6 @@ for rep in 1 2; do
 for lg in $LGS; do
   run "default" $lg A=1
   run "not fused (round 5 lanes)" $lg SONIC_PROVE_FUSED=0
-  run "three streams per handle" $lg SONIC_FUSED_LANES=0
-  run "stream priorities" $lg SONIC_PROVE_PRIORITIES=1
-  run "t group as a chain of its own" $lg SONIC_FUSED_SPLIT_T=1
   if [ $lg -le 15 ]; then
     run "table c = 17" $lg SONIC_MSM_TABLE_C=17
     run "table c = 15" $lg SONIC_MSM_TABLE_C=15

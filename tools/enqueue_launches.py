@@ -11,7 +11,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-ENVS = ["", "SONIC_PROVE_FUSED=0", "SONIC_FUSED_LANES=0", "SONIC_FUSED_LANES=2", "SONIC_PROVE_SYM=1", "SONIC_FUSED_SPLIT_T=1", "SONIC_PROVE_RUNS=1"]
+ENVS = ["", "SONIC_PROVE_FUSED=0", "SONIC_FUSED_LANES=2", "SONIC_PROVE_SYM=1", "SONIC_PROVE_RUNS=1"]
 SHAPES = [(40, 2), (300, 3), (5000, 2)]         # (300, 3): 19 MSMs, two chunks of the proof's chain
 
 
