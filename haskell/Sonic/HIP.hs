@@ -58,6 +58,8 @@ module Sonic.HIP
     -- * one circuit, many statements
   , setConstants, evalConstraints, proveBatchStatements, fsCircuitMidstate, fsCircuitDigestResume
   , Verifier, newVerifier, verifyBatchStatements, verifyFsBatchStatements
+    -- * Fiat-Shamir proofs in flight
+  , witnessDigest, submitFs, collectFs, proveBatchFs
   ) where
 
 import Protolude hiding (check)
@@ -144,6 +146,10 @@ foreign import ccall safe   "sonic_prover_set_constants"  c_set_constants  :: Pt
 foreign import ccall safe   "sonic_prove_batch_statements" c_prove_batch_st :: Ptr (Ptr ProverHandle) -> CInt -> Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> IO CInt
 foreign import ccall safe   "sonic_fs_circuit_midstate_csr" c_fs_midstate_csr :: Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_fs_circuit_digest_resume" c_fs_resume   :: Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_prover_witness_digest_v2" c_witness_digest :: Ptr ProverHandle -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_prover_submit_fs"      c_prover_submit_fs :: Ptr ProverHandle -> Ptr Word8 -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_prover_collect_fs"     c_prover_collect_fs :: Ptr ProverHandle -> Ptr Word8 -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_prove_batch_fs"        c_prove_batch_fs :: Ptr (Ptr ProverHandle) -> CInt -> Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> IO CInt
 foreign import ccall safe   "sonic_verifier_new_csr"      c_verifier_new_csr :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr (Ptr VerifierHandle) -> IO CInt
 foreign import ccall safe   "&sonic_verifier_free"        p_verifier_free  :: FunPtr (Ptr VerifierHandle -> IO ())
 foreign import ccall safe   "sonic_verifier_verify_batch_cs" c_verify_batch_cs :: Ptr VerifierHandle -> Int64 -> Ptr Word8 -> CInt -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> Ptr Word8 -> IO CInt
@@ -702,6 +708,53 @@ fsCircuitDigestResume :: ByteString -> [Fr] -> ByteString
 fsCircuitDigestResume mid cs = unsafePerformIO $
   withBytes mid $ \pm -> withFrs cs $ \pcs -> BSI.create 32 $ \out ->
     check =<< c_fs_resume pm pcs out
+
+-- ---------------------------------------------------------------------------------------------------------------------
+-- Fiat-Shamir proofs in flight: the six passes of a Fiat-Shamir proof walked by a host thread the handle owns, so that one Haskell thread
+-- keeps several handles busy; the blinders come from witness digest v2, which the GPU computes over the resident assignment
+-- ---------------------------------------------------------------------------------------------------------------------
+-- the handle for the duration of a call, and with it the SRS it proves over
+withProverAlive :: Prover -> (Ptr ProverHandle -> IO a) -> IO a
+withProverAlive Prover{..} f = case proverSrs of SRS h -> withForeignPtr h $ \_ -> withForeignPtr proverHandle f
+
+-- | witness digest v2 of the resident assignment (sonic_prover_witness_digest_v2): 32 bytes
+witnessDigest :: Prover -> IO ByteString
+witnessDigest pr = withProverAlive pr $ \p -> BSI.create 32 (check <=< c_witness_digest p)
+
+-- | hand one Fiat-Shamir proof to the handle and return (sonic_prover_submit_fs): circuit digest (fsCircuitDigest, or
+--   fsCircuitDigestResume after setConstants) and the prover's secret 32-byte blinder seed
+submitFs :: Prover -> ByteString -> ByteString -> IO ()
+submitFs pr digest seed
+  | BS.length digest /= 32 || BS.length seed /= 32 = panic "submitFs: the circuit digest and the seed are 32 bytes each"
+  | otherwise = withProverAlive pr $ \p -> withBytes digest $ \pd -> withBytes seed $ \ps -> check =<< c_prover_submit_fs p pd ps
+
+-- | wait for the proof `submitFs` started (sonic_prover_collect_fs): the proof and the 8 + 2Q transcript values it was made with
+collectFs :: Prover -> IO (Proof, [Fr])
+collectFs pr@Prover{..} = withProverAlive pr $ \p -> do
+  let tsz = 32 * (8 + 2 * proverQ)
+  allocaBytes tsz $ \ptr -> do
+    bytes <- proofBytes proverQ (\out -> c_prover_collect_fs p out ptr)
+    tr <- BS.packCStringLen (castPtr ptr, tsz)
+    pure (decodeProof proverQ bytes, map frFromBytes (chunks 32 tr))
+
+-- | K Fiat-Shamir proofs over the handles' GPUs (sonic_prove_batch_fs; proof i on handle i mod length handles): per proof its
+--   assignment, its constants, its circuit digest (fsCircuitDigestResume midstate constants) and its blinder seed
+proveBatchFs :: [Prover] -> [(Assignment Fr, [Fr], ByteString, ByteString)] -> IO [Proof]
+proveBatchFs [] _ = panic "proveBatchFs: no handles"
+proveBatchFs ps@(p0 : _) sts = do
+  let q = proverQ p0
+      k = length sts
+      asgs = [ a | (a, _, _, _) <- sts ]
+  when (any (\(_, cs, dg, sd) -> length cs /= q || BS.length dg /= 32 || BS.length sd /= 32) sts) $
+    panic "proveBatchFs: need Q constants, a 32-byte digest and a 32-byte seed per statement"
+  psz <- fromIntegral <$> c_proof_size (fromIntegral q)
+  bytes <- withProverAlive p0 $ \_ -> withProvers ps $ \arr np ->
+    withFrs (concatMap aL asgs) $ \pal -> withFrs (concatMap aR asgs) $ \par -> withFrs (concatMap aO asgs) $ \pao ->
+      withFrs (concat [ cs | (_, cs, _, _) <- sts ]) $ \pcs ->
+        withBytes (BS.concat [ dg | (_, _, dg, _) <- sts ]) $ \pdg -> withBytes (BS.concat [ sd | (_, _, _, sd) <- sts ]) $ \psd ->
+          BSI.create (psz * k) $ \out ->
+            check =<< c_prove_batch_fs arr np (fromIntegral k) pal par pao pcs pdg psd out nullPtr nullPtr
+  pure (map (decodeProof q) (chunks psz bytes))
 
 -- | the batched verifier's handle (sonic_verifier_new_csr): the circuit resident on the GPU; keeps the SRS alive as long as the handle
 data Verifier = Verifier { verifierHandle :: ForeignPtr VerifierHandle, verifierSrs :: SRS, verifierQ :: Int }

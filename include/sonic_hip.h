@@ -98,7 +98,9 @@ typedef struct sonic_verifier sonic_verifier_t;
  * sonic_g2_compress, sonic_g2_decompress, sonic_proof_size_compressed, sonic_proof_compress, sonic_proof_decompress,
  * sonic_verifier_verify_batch_z, sonic_verifier_verify_fs_batch_z, sonic_srs_save_compressed; still 7, additions only: one circuit, many
  * statements -- sonic_prover_eval_constraints, sonic_prover_set_constants, sonic_prove_batch_statements, sonic_fs_circuit_midstate[_csr],
- * sonic_fs_circuit_digest_resume, sonic_verifier_verify_batch_cs, sonic_verifier_verify_fs_batch_cs, sonic_verify_batch_digest_v2 */
+ * sonic_fs_circuit_digest_resume, sonic_verifier_verify_batch_cs, sonic_verifier_verify_fs_batch_cs, sonic_verify_batch_digest_v2;
+ * still 7, additions only: Fiat-Shamir proofs in flight -- sonic_prover_witness_digest_v2, sonic_prover_submit_fs,
+ * sonic_prover_collect_fs, sonic_prove_batch_fs */
 int sonic_abi_version(void);
 int sonic_init(int device_ordinal);                 /* choose the DEFAULT GPU (first call wins) and make it the thread's HIP device; idempotent */
 int sonic_device_count(int* out);                   /* GPUs this process can see; SONIC_ERR_NO_DEVICE (and 0) without one */
@@ -367,7 +369,9 @@ int sonic_prover_device(const sonic_prover_t* p);   /* the GPU a prover handle l
  *                   circuit digest, the srs id and a digest of the assignment (RFC 6979 style, round 4), so one seed may serve
  *                   several statements; a seed must still never be disclosed;
  *                   out_transcript (may be NULL): the 8 + 2Q values the proof was made with, in sonic_prove's transcript order --
- *                   sonic_prover_prove on them reproduces the proof byte for byte
+ *                   sonic_prover_prove on them reproduces the proof byte for byte.  This call blocks through all six passes; one proof in
+ *                   flight per handle, batches over several handles and the assignment's digest on the GPU: "Fiat-Shamir proofs in flight"
+ *                   below (sonic_prover_submit_fs / collect_fs, sonic_prove_batch_fs)
  *   fs_challenges   what a proof determines: y, z, y_1..y_Q, z_1..z_Q, u, v (32 bytes each)
  *   verify_fs       recomputes them, requires the proof's own u, v to match, then verify (Protocol.hs:111-130) */
 int sonic_fs_circuit_digest(int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO, const uint8_t* cs, uint8_t out[32]);
@@ -551,6 +555,38 @@ int sonic_verifier_verify_fs_batch_cs(sonic_verifier_t* v, int64_t K, const uint
                                       const uint8_t seed[32], int* all_accepted, uint8_t* each);
 int sonic_verify_batch_digest_v2(int64_t n, int64_t Q, int64_t d, const uint8_t circuit_digest[32], const uint8_t srs_id[32], int64_t K,
                                  const uint8_t* proofs, const uint8_t* challenges, const uint8_t* cs, uint8_t out[32]);
+
+/* ---- Fiat-Shamir proofs in flight ----
+ * The Fiat-Shamir prover beside sonic_prover_prove_fs, which stays as it is: one proof in flight per handle, batches over several handles,
+ * and the digest of the assignment computed by the GPU.  A proof made here verifies like any other (sonic_verify_fs and the batched
+ * verifier see no difference); its BLINDERS differ from sonic_prover_prove_fs's for the same seed, because they are derived from
+ *   witness digest v2 = SHA-256("sonic-hip/witness/v2" || le64 n || root), root = a SHA-256 tree over the canonical bytes of aL || aR || aO
+ *                   with 1024-byte leaves and 32 digests per node, every message opened by a 64-byte header that names the leaf or the level
+ *                   and node (exact definition: sonic_amd/csrc/fs.hpp).  The GPU hashes the handle's resident assignment where it lies; 32
+ *                   bytes come back.  Cached per assignment: set_assignment, an assignment handed over with a proof (batches, the
+ *                   one-shot calls) and a failed upload invalidate it.
+ *   witness_digest_v2  that digest of the resident assignment (SONIC_ERR_INVALID_ARG: none set, or a proof in flight)
+ *   submit_fs       checks what sonic_prover_prove_fs checks (an assignment is set, nothing in flight, not one rank's share), marks the
+ *                   handle in flight and hands the six passes to a host thread the handle owns (made on first use, joined by
+ *                   sonic_prover_free, which therefore returns only after a proof in flight has ended).  Returns without waiting for the
+ *                   device: one host thread keeps several handles busy, each handle's waits and hashes under the others' kernels.
+ *   collect_fs      waits for that proof; out_transcript (may be NULL) as for prove_fs.  Its status is the proof's, and its message
+ *                   becomes the calling thread's last error.  SONIC_ERR_INVALID_ARG with nothing in flight, or when the flight was
+ *                   submitted with a transcript (sonic_prover_submit); sonic_prover_collect / collect_share refuse a Fiat-Shamir flight
+ *                   the same way, and either leaves the flight as it is.  While a Fiat-Shamir proof is in flight every call that a
+ *                   transcript flight refuses is refused (set_assignment, set_constants, prepare, set_share, eval_constraints, any prove
+ *                   or submit).
+ *   prove_batch_fs  sonic_prove_batch_statements' shape and rules (proof i on handle i % n_provers, one host thread per handle, all K
+ *                   attempted, the first non-zero status in list order returned, out_status per proof) with a circuit digest and a
+ *                   blinder seed per proof in place of a transcript: circuit_digests[i] = sonic_fs_circuit_digest_resume(midstate, cs_i).
+ *                   aL, aR, aO: K x n x 32 each, or all NULL (the resident assignments); cs: K x Q x 32, or NULL (the handles'
+ *                   constants); out_transcripts: K x (8 + 2Q) x 32, may be NULL. */
+int sonic_prover_witness_digest_v2(sonic_prover_t* p, uint8_t out[32]);
+int sonic_prover_submit_fs(sonic_prover_t* p, const uint8_t circuit_digest[32], const uint8_t blinder_seed[32]);
+int sonic_prover_collect_fs(sonic_prover_t* p, uint8_t* out_proof, uint8_t* out_transcript);
+int sonic_prove_batch_fs(sonic_prover_t* const* provers, int n_provers, int64_t K, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO,
+                         const uint8_t* cs, const uint8_t* circuit_digests, const uint8_t* blinder_seeds, uint8_t* out_proofs,
+                         uint8_t* out_transcripts, int* out_status);
 
 /* ---- device memory for callers without a HIP binding ---- */
 int sonic_dev_alloc(size_t bytes, void** out);                       /* on the default device */

@@ -163,6 +163,10 @@ def lib() -> C.CDLL:
         "sonic_verifier_verify_batch_cs": [vp, i64, vp, i32, vp, vp, cp, C.POINTER(i32), vp],
         "sonic_verifier_verify_fs_batch_cs": [vp, i64, vp, i32, vp, cp, C.POINTER(i32), vp],
         "sonic_verify_batch_digest_v2": [i64, i64, i64, cp, cp, i64, vp, vp, vp, vp],
+        "sonic_prover_witness_digest_v2": [vp, vp],
+        "sonic_prover_submit_fs": [vp, cp, cp],
+        "sonic_prover_collect_fs": [vp, vp, vp],
+        "sonic_prove_batch_fs": [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "sonic_dev_alloc": [C.c_size_t, C.POINTER(vp)],
         "sonic_dev_free": [vp],
         "sonic_dev_upload": [vp, vp, C.c_size_t],
@@ -253,6 +257,7 @@ EXPORTED = [
     "sonic_verifier_verify_batch_z", "sonic_verifier_verify_fs_batch_z", "sonic_srs_save_compressed",
     "sonic_prover_eval_constraints", "sonic_prover_set_constants", "sonic_prove_batch_statements", "sonic_fs_circuit_midstate", "sonic_fs_circuit_midstate_csr",
     "sonic_fs_circuit_digest_resume", "sonic_verifier_verify_batch_cs", "sonic_verifier_verify_fs_batch_cs", "sonic_verify_batch_digest_v2",
+    "sonic_prover_witness_digest_v2", "sonic_prover_submit_fs", "sonic_prover_collect_fs", "sonic_prove_batch_fs",
 ]
 
 

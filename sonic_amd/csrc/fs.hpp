@@ -24,6 +24,21 @@
 // the manner of RFC 6979: with the seed alone, two proofs of different assignments under one seed would share their blinders and
 // R_1 - R_2 would be an unblinded commitment to the difference of the witnesses.  (v1, round 3, had neither this nor the srs id.)
 // The parity tests compare against an independent restatement of this definition with python's hashlib (test infrastructure).
+//
+// Witness digest v2 (sonic_prover_submit_fs / collect_fs, sonic_prove_batch_fs, sonic_prover_witness_digest_v2): the same blinder
+// formula over a digest that the GPU computes from the resident assignment, a SHA-256 tree (witness_tree.hpp, witness.hip).  The blocking
+// sonic_prover_prove_fs keeps v1.  Blinders are the prover's private randomness: no verifier sees which digest went into them.
+//   B      = the canonical little-endian bytes of aL || aR || aO: 96 n bytes, 3n elements of 32 bytes
+//   leaves   L = ceil(96 n / 1024);  leaf_i = SHA256(H_leaf(i) || B[1024 i : min(1024 (i+1), 96 n)])
+//            H_leaf(i) = 64 bytes: "sonic-hip/witness-leaf/v2" zero-padded to 56 bytes, then le64 i
+//   nodes    level 0 is the leaves; while a level has c > 1 digests the next one has ceil(c / 32) nodes,
+//            node_j = SHA256(H_node(level, j) || the digests 32 j .. min(32 (j+1), c) - 1 of the level below)
+//            H_node(level, j) = 64 bytes: "sonic-hip/witness-node/v2" zero-padded to 48 bytes, then le64 level (1 for the first level of
+//            nodes), then le64 j
+//   root   = the single digest left (leaf_0 when L = 1)
+//   witness digest v2 = SHA256("sonic-hip/witness/v2" || le64 n || root)
+// The 64-byte headers keep every message block aligned to whole field elements: one block is two elements, sixteen 32-bit limbs
+// byte-swapped.
 #pragma once
 #include <string>
 #include "field.hpp"
@@ -101,6 +116,15 @@ inline void fs_blinder(const uint8_t seed[32], const uint8_t digest[32], const u
   }
   Fr c = fs_wide_reduce(w);
   memcpy(out32, c.l, 32);
+}
+
+// witness digest v2 from the root of the tree (above)
+inline void fs_witness_digest_v2(int64_t n, const uint8_t root[32], uint8_t out32[32]) {
+  Sha256 h;
+  h.update("sonic-hip/witness/v2", 20);
+  FsTranscript::le64(h, n);
+  h.update(root, 32);
+  h.finish(out32);
 }
 
 // The challenges a proof determines, in transcript order y, z, y_1..y_Q, z_1..z_Q, u, v (each 32 bytes), from the canonical proof

@@ -12,6 +12,7 @@
 // (Protocol.hs:63,79,80), evalY y tXY twice (:72,81) and evalY y_j sXY twice per j
 // (Signature.hs:41,54).
 #include "prover.hpp"
+#include "witness_tree.hpp"
 
 namespace sonic {
 
@@ -302,6 +303,7 @@ int prover_new_impl(const sonic_srs_t* srs, const CircuitView& c, sonic_prover_t
   HIP_OK(hipHostMalloc((void**)&p->h_slots, sizeof(MsmSlot) * L.slots_total(), hipHostMallocDefault));
   HIP_OK(hipHostMalloc((void**)&p->h_fr, 32 * L.F(), hipHostMallocDefault));
   HIP_OK(hipHostMalloc((void**)&p->h_flags, 8, hipHostMallocDefault));
+  HIP_OK(hipHostMalloc((void**)&p->h_root, 32, hipHostMallocDefault));
   p->h_flags[0] = p->h_flags[1] = 0;
   p->frout.alloc(sizeof(Fr) * L.F());
   p->frstd.alloc(sizeof(Fr) * L.F());
@@ -355,7 +357,7 @@ int sonic_prover_set_assignment(sonic_prover_t* p, const uint8_t* aL, const uint
     return flags_to_status(f, "sonic_prover_set_assignment");
   }
   p->have_assignment = true;
-  p->have_witness_digest = false;
+  p->assignment_changed();
   API_END
 }
 
@@ -586,7 +588,7 @@ static void enqueue_polynomials(sonic_prover_t* p, GroupQueue& q, ProofPass& w) 
     upload_fr_mont(ms, p->aR, p->pend_asg[1], n, flags + 1);
     upload_fr_mont(ms, p->aO, p->pend_asg[2], n, flags + 1);
     p->pend_asg[0] = nullptr;
-    p->have_witness_digest = false;
+    p->assignment_changed();
   }
   if (p->pend_cs) {
     upload_fr_mont(ms, p->cs, p->pend_cs, Q, flags + 1);
@@ -1005,6 +1007,12 @@ static int whole_proof_only(sonic_prover_t* p, const char* who) {
   return SONIC_OK;
 }
 
+// a Fiat-Shamir proof in flight (sonic_prover_submit_fs) is collected by sonic_prover_collect_fs only
+static int fs_flight_refused(sonic_prover_t* p, const char* who) {
+  if (p->fs_flight) { set_error("%s: the proof in flight was submitted with sonic_prover_submit_fs: collect it with sonic_prover_collect_fs", who); return SONIC_ERR_INVALID_ARG; }
+  return SONIC_OK;
+}
+
 static int prove_args_ok(sonic_prover_t* p, const char* who) {
   if (!p->have_assignment) { set_error("%s: no assignment set", who); return SONIC_ERR_INVALID_ARG; }
   if (p->in_flight) { set_error("%s: a submitted proof has not been collected yet", who); return SONIC_ERR_INVALID_ARG; }
@@ -1058,6 +1066,7 @@ int sonic_prover_collect(sonic_prover_t* p, uint8_t* out_proof) {
   if (!p || !out_proof) return SONIC_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> g(p->mu);
   if (!p->in_flight) { set_error("sonic_prover_collect: nothing was submitted"); return SONIC_ERR_INVALID_ARG; }
+  if (fs_flight_refused(p, "sonic_prover_collect")) return SONIC_ERR_INVALID_ARG;
   if (whole_proof_only(p, "sonic_prover_collect")) return SONIC_ERR_INVALID_ARG;
   p->in_flight = false;
   return prove_finish(p, out_proof);
@@ -1088,6 +1097,7 @@ int sonic_prover_collect_share(sonic_prover_t* p, uint8_t* out_share) {
   if (!p || !out_share) return SONIC_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> g(p->mu);
   if (!p->in_flight) { set_error("sonic_prover_collect_share: nothing was submitted"); return SONIC_ERR_INVALID_ARG; }
+  if (fs_flight_refused(p, "sonic_prover_collect_share")) return SONIC_ERR_INVALID_ARG;
   p->in_flight = false;
   return prove_finish_share(p, out_share);
 }
@@ -1134,38 +1144,60 @@ int sonic_fs_challenges(int64_t, int64_t, int64_t, const uint8_t*, const uint8_t
   return SONIC_ERR_INVALID_ARG;
 }
 
-int sonic_prover_prove_fs(sonic_prover_t* p, const uint8_t circuit_digest[32], const uint8_t blinder_seed[32], uint8_t* out_proof,
-                          uint8_t* out_transcript) {
-  if (!p || !circuit_digest || !blinder_seed || !out_proof) return SONIC_ERR_INVALID_ARG;
-  API_BEGIN_ON(p->device)
-  std::lock_guard<std::mutex> g(p->mu);
-  int rc = prove_args_ok(p, "sonic_prover_prove_fs");
-  if (!rc) rc = whole_proof_only(p, "sonic_prover_prove_fs");
-  if (rc) return rc;
+// witness digest v1: SHA-256 of the assignment's canonical bytes, once per set_assignment: the device copy is Montgomery, so a scratch
+// copy is converted back and brought to the host
+static void witness_digest_v1_ensure(sonic_prover_t* p) {
+  if (p->have_witness_digest) return;
+  const long n = p->n;
+  DevBuf tmp(sizeof(Fr) * 3 * n);
+  Fr* t3 = tmp.as<Fr>();
+  HIP_OK(hipMemcpyAsync(t3, p->aL.p, sizeof(Fr) * n, hipMemcpyDeviceToDevice, p->st));
+  HIP_OK(hipMemcpyAsync(t3 + n, p->aR.p, sizeof(Fr) * n, hipMemcpyDeviceToDevice, p->st));
+  HIP_OK(hipMemcpyAsync(t3 + 2 * n, p->aO.p, sizeof(Fr) * n, hipMemcpyDeviceToDevice, p->st));
+  fr_from_mont_enqueue(p->st, t3, 3 * n);
+  std::vector<uint8_t> host(96 * (size_t)n);
+  HIP_OK(hipMemcpyAsync(host.data(), t3, host.size(), hipMemcpyDeviceToHost, p->st));
+  HIP_OK(hipStreamSynchronize(p->st));
+  Sha256 h;
+  h.update("sonic-hip/witness/v1", 20);
+  h.update(host.data(), host.size());
+  h.finish(p->witness_digest);
+  p->have_witness_digest = true;
+}
+
+// witness digest v2 (fs.hpp): the tree runs on the GPU over the resident assignment (witness.hip), 32 bytes come back.  The two halves:
+// queue (behind whatever uploads the assignment on the main stream) and, once the stream has drained, the 60-byte hash over the root.
+static void witness_digest_v2_enqueue(sonic_prover_t* p) {
+  if (p->have_witness_digest_v2) return;
+  const uint32_t* root = witness_tree_enqueue(p->st, p->aL.as<Fr>(), p->aR.as<Fr>(), p->aO.as<Fr>(), p->n, p->wtree);
+  HIP_OK(hipMemcpyAsync(p->h_root, root, 32, hipMemcpyDeviceToHost, p->st));
+}
+static void witness_digest_v2_finish(sonic_prover_t* p) {
+  if (p->have_witness_digest_v2) return;
+  uint8_t root[32];
+  wt_digest_bytes(p->h_root, root);
+  fs_witness_digest_v2(p->n, root, p->witness_digest_v2);
+  p->have_witness_digest_v2 = true;
+}
+static void witness_digest_v2_ensure(sonic_prover_t* p) {
+  if (p->have_witness_digest_v2) return;
+  witness_digest_v2_enqueue(p);
+  HIP_OK(hipStreamSynchronize(p->st));
+  witness_digest_v2_finish(p);
+}
+
+// The six passes of a Fiat-Shamir proof: the blinders from `witness_digest` (v1 for the blocking call, v2 for the proofs in flight and the
+// batches: the only difference between them), then PH_R .. PH_QV with the host's hashes in between.  The caller has checked the handle
+// and holds it: p->mu, or the flight (in_flight, which refuses every other call).  out_transcript may be null.
+static int prove_fs_walk(sonic_prover_t* p, const uint8_t circuit_digest[32], const uint8_t blinder_seed[32], const uint8_t witness_digest[32], uint8_t* out_proof,
+                         uint8_t* out_transcript) {
+  int rc;
   const long n = p->n, Q = p->Q, d = p->srs->d;
   const ProofLayout L{Q};
   std::vector<uint8_t> tr(32 * (size_t)L.transcript_len(), 0), pf(sonic_proof_size(Q));
   uint8_t srs_id[32];
   if ((rc = sonic_fs_srs_id(p->srs, srs_id))) return rc;
-  if (!p->have_witness_digest) {
-    // SHA-256 of the assignment's canonical bytes, once per set_assignment: the device copy is Montgomery, so a scratch copy is
-    // converted back and brought to the host
-    DevBuf tmp(sizeof(Fr) * 3 * n);
-    Fr* t3 = tmp.as<Fr>();
-    HIP_OK(hipMemcpyAsync(t3, p->aL.p, sizeof(Fr) * n, hipMemcpyDeviceToDevice, p->st));
-    HIP_OK(hipMemcpyAsync(t3 + n, p->aR.p, sizeof(Fr) * n, hipMemcpyDeviceToDevice, p->st));
-    HIP_OK(hipMemcpyAsync(t3 + 2 * n, p->aO.p, sizeof(Fr) * n, hipMemcpyDeviceToDevice, p->st));
-    fr_from_mont_enqueue(p->st, t3, 3 * n);
-    std::vector<uint8_t> host(96 * (size_t)n);
-    HIP_OK(hipMemcpyAsync(host.data(), t3, host.size(), hipMemcpyDeviceToHost, p->st));
-    HIP_OK(hipStreamSynchronize(p->st));
-    Sha256 h;
-    h.update("sonic-hip/witness/v1", 20);
-    h.update(host.data(), host.size());
-    h.finish(p->witness_digest);
-    p->have_witness_digest = true;
-  }
-  for (long k = 0; k < L.n_blinders; k++) fs_blinder(blinder_seed, circuit_digest, srs_id, p->witness_digest, (uint32_t)k, &tr[32 * k]);
+  for (long k = 0; k < L.n_blinders; k++) fs_blinder(blinder_seed, circuit_digest, srs_id, witness_digest, (uint32_t)k, &tr[32 * k]);
   for (long k = L.n_blinders; k < L.transcript_len(); k++) tr[32 * k] = 1;               // not drawn yet: any invertible value (results that use it are not read)
   FsTranscript t;
   t.init(n, Q, d, circuit_digest, srs_id);
@@ -1198,6 +1230,131 @@ int sonic_prover_prove_fs(sonic_prover_t* p, const uint8_t circuit_digest[32], c
   if ((rc = pass(PH_QV))) return rc;
   memcpy(out_proof, pf.data(), pf.size());
   if (out_transcript) memcpy(out_transcript, tr.data(), tr.size());
+  return SONIC_OK;
+}
+
+int sonic_prover_prove_fs(sonic_prover_t* p, const uint8_t circuit_digest[32], const uint8_t blinder_seed[32], uint8_t* out_proof,
+                          uint8_t* out_transcript) {
+  if (!p || !circuit_digest || !blinder_seed || !out_proof) return SONIC_ERR_INVALID_ARG;
+  API_BEGIN_ON(p->device)
+  std::lock_guard<std::mutex> g(p->mu);
+  int rc = prove_args_ok(p, "sonic_prover_prove_fs");
+  if (!rc) rc = whole_proof_only(p, "sonic_prover_prove_fs");
+  if (rc) return rc;
+  witness_digest_v1_ensure(p);
+  return prove_fs_walk(p, circuit_digest, blinder_seed, p->witness_digest, out_proof, out_transcript);
+  API_END
+}
+
+int sonic_prover_witness_digest_v2(sonic_prover_t* p, uint8_t out[32]) {
+  API_BEGIN_ON(p ? p->device : -1)
+  if (!p || !out) { set_error("sonic_prover_witness_digest_v2: bad argument"); return SONIC_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> g(p->mu);
+  int rc = prove_args_ok(p, "sonic_prover_witness_digest_v2");
+  if (rc) return rc;
+  witness_digest_v2_ensure(p);
+  memcpy(out, p->witness_digest_v2, 32);
+  API_END
+}
+
+// ---- one Fiat-Shamir proof in flight per handle --------------------------------------------------------------------------------
+// submit_fs marks the handle in flight and hands the six passes to the handle's worker thread (prover.hpp, FsWorker); collect_fs waits
+// for it.  Between the two, every call that an explicit-transcript flight refuses is refused (they all look at in_flight under p->mu),
+// so the worker has the handle to itself without holding the mutex.
+static int fs_job(sonic_prover_t* p, FsWorker& w) {
+  API_BEGIN_ON(p->device)
+  witness_digest_v2_ensure(p);
+  return prove_fs_walk(p, w.circuit_digest, w.seed, p->witness_digest_v2, w.proof.data(), w.transcript.data());
+  API_END
+}
+static void fs_worker_main(sonic_prover_t* p) {
+  FsWorker& w = *p->fsw;
+  std::unique_lock<std::mutex> lk(w.m);
+  for (;;) {
+    w.cv.wait(lk, [&] { return w.quit || (w.has_job && !w.done); });
+    if (!(w.has_job && !w.done)) return;        // (quit: a job that was submitted is still walked to its end first)
+    lk.unlock();
+    int rc = SONIC_ERR_HIP;
+    std::string err;
+    try {
+      rc = fs_job(p, w);
+      if (rc) { char b[512]; sonic_last_error(b, sizeof b); err = b; }
+    } catch (...) { rc = SONIC_ERR_HIP; err = "sonic_prover_submit_fs: the worker failed"; }      // (nothing may leave a thread's body: std::terminate)
+    lk.lock();
+    w.rc = rc; w.err = err; w.done = true;
+    w.cv.notify_all();
+  }
+}
+
+int sonic_prover_submit_fs(sonic_prover_t* p, const uint8_t circuit_digest[32], const uint8_t blinder_seed[32]) {
+  API_BEGIN_ON(p ? p->device : -1)
+  if (!p || !circuit_digest || !blinder_seed) { set_error("sonic_prover_submit_fs: bad argument"); return SONIC_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> g(p->mu);
+  int rc = prove_args_ok(p, "sonic_prover_submit_fs");
+  if (!rc) rc = whole_proof_only(p, "sonic_prover_submit_fs");
+  if (rc) return rc;
+  if (!p->fsw) {
+    p->fsw.reset(new FsWorker());
+    p->fsw->th = std::thread(fs_worker_main, p);
+  }
+  FsWorker& w = *p->fsw;
+  {
+    std::lock_guard<std::mutex> gw(w.m);
+    memcpy(w.circuit_digest, circuit_digest, 32); memcpy(w.seed, blinder_seed, 32);
+    w.proof.assign(sonic_proof_size(p->Q), 0);
+    w.transcript.assign(32 * (size_t)ProofLayout{p->Q}.transcript_len(), 0);
+    w.has_job = true; w.done = false; w.rc = SONIC_OK; w.err.clear();
+  }
+  p->in_flight = true; p->fs_flight = true;
+  w.cv.notify_all();
+  API_END
+}
+
+int sonic_prover_collect_fs(sonic_prover_t* p, uint8_t* out_proof, uint8_t* out_transcript) {
+  API_BEGIN_ON(p ? p->device : -1)
+  if (!p || !out_proof) { set_error("sonic_prover_collect_fs: bad argument"); return SONIC_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> g(p->mu);
+  if (!p->in_flight) { set_error("sonic_prover_collect_fs: nothing was submitted"); return SONIC_ERR_INVALID_ARG; }
+  if (!p->fs_flight) { set_error("sonic_prover_collect_fs: the proof in flight was submitted with a transcript (sonic_prover_submit): collect it with sonic_prover_collect"); return SONIC_ERR_INVALID_ARG; }
+  FsWorker& w = *p->fsw;
+  std::unique_lock<std::mutex> lk(w.m);
+  w.cv.wait(lk, [&] { return w.done; });
+  w.has_job = false;
+  p->in_flight = false; p->fs_flight = false;
+  if (w.rc) { set_error("%s", w.err.c_str()); return w.rc; }
+  memcpy(out_proof, w.proof.data(), w.proof.size());
+  if (out_transcript) memcpy(out_transcript, w.transcript.data(), w.transcript.size());
+  API_END
+}
+
+// a Fiat-Shamir proof with the assignment and the constants of THIS call (sonic_prove_batch_fs).  The assignment goes up at once, not at
+// the head of the first pass: its digest decides the blinders, so the tree is queued right behind the upload and one wait serves both.
+int prove_fs_with_statement(sonic_prover_t* p, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO, const uint8_t* cs, const uint8_t circuit_digest[32],
+                            const uint8_t blinder_seed[32], uint8_t* out_proof, uint8_t* out_transcript) {
+  API_BEGIN_ON(p->device)
+  std::lock_guard<std::mutex> g(p->mu);
+  if (p->in_flight) { set_error("prove: a submitted proof has not been collected yet"); return SONIC_ERR_INVALID_ARG; }
+  int rc = whole_proof_only(p, "prove");
+  if (rc) return rc;
+  if (!aL && !p->have_assignment) { set_error("prove: no assignment set"); return SONIC_ERR_INVALID_ARG; }
+  hipStream_t st = p->st;
+  if (aL) {
+    p->have_assignment = false;             // (until the upload is known to be good: a failed one leaves a partly converted assignment)
+    p->assignment_changed();
+    HIP_OK(hipMemsetAsync(p->flags.p, 0, 4, st));
+    upload_fr_mont(st, p->aL, aL, p->n, p->flags.as<int>());
+    upload_fr_mont(st, p->aR, aR, p->n, p->flags.as<int>());
+    upload_fr_mont(st, p->aO, aO, p->n, p->flags.as<int>());
+    witness_digest_v2_enqueue(p);
+    const int f = read_flags(st, p->flags);
+    if (f) return flags_to_status(f, "prove (assignment handed over with the call)");
+    witness_digest_v2_finish(p);
+    p->have_assignment = true;
+  } else witness_digest_v2_ensure(p);
+  p->pend_cs = cs;
+  rc = prove_fs_walk(p, circuit_digest, blinder_seed, p->witness_digest_v2, out_proof, out_transcript);
+  p->pend_cs = nullptr;
+  return rc;
   API_END
 }
 

@@ -193,10 +193,12 @@ int sonic_prove_shared(sonic_prover_t* const* provers, int world, const uint8_t*
   return sonic_proof_from_shares(Q, world, shares.data(), transcript, out_proof);
 }
 
-// sonic_prove_batch (cs == null) and sonic_prove_batch_statements (cs: K x Q constants, proof i's uploaded at the head of its own queue)
+// sonic_prove_batch (cs == null), sonic_prove_batch_statements (cs: K x Q constants, proof i's uploaded at the head of its own queue) and
+// sonic_prove_batch_fs (fs: the circuit digests and blinder seeds in place of transcripts; the transcripts come back)
+struct BatchFs { const uint8_t *circuit_digests, *blinder_seeds; uint8_t* out_transcripts; };
 static int prove_batch_impl(const char* who, sonic_prover_t* const* provers, int n_provers, int64_t K, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO,
-                            const uint8_t* cs, const uint8_t* transcripts, uint8_t* out_proofs, int* out_status) {
-  if (!provers || n_provers < 1 || n_provers > 1024 || K < 0 || (K > 0 && (!transcripts || !out_proofs))) return SONIC_ERR_INVALID_ARG;
+                            const uint8_t* cs, const uint8_t* transcripts, uint8_t* out_proofs, int* out_status, const BatchFs* fs = nullptr) {
+  if (!provers || n_provers < 1 || n_provers > 1024 || K < 0 || (K > 0 && (!(fs ? fs->circuit_digests && fs->blinder_seeds : transcripts != nullptr) || !out_proofs))) return SONIC_ERR_INVALID_ARG;
   const bool per_proof = aL || aR || aO;
   if (per_proof && !(aL && aR && aO)) { set_error("%s: aL, aR, aO must be given together (or all NULL: the handles' resident assignments)", who); return SONIC_ERR_INVALID_ARG; }
   for (int i = 0; i < n_provers; i++) {
@@ -214,17 +216,20 @@ static int prove_batch_impl(const char* who, sonic_prover_t* const* provers, int
     for (int64_t i = h; i < K; i += n_provers) {
       int rc = SONIC_OK;
       try {
-        if (cs) {
-          // (checked here, before anything of proof i is queued: its status, and the handle keeps the constants it has)
-          for (long q = 0; q < Q && !rc; q++) {
-            Fr k;
-            memcpy(k.l, cs + ksz * (size_t)i + 32 * (size_t)q, 32);
-            if (!fp_is_canonical(k)) { set_error("%s: cs[%ld] of proof %ld is not a canonical field element", who, q, (long)i); rc = SONIC_ERR_BAD_ENCODING; }
-          }
-          if (!rc) rc = prove_with_statement(provers[h], per_proof ? aL + asz * (size_t)i : nullptr, per_proof ? aR + asz * (size_t)i : nullptr,
-                                             per_proof ? aO + asz * (size_t)i : nullptr, cs + ksz * (size_t)i, transcripts + tsz * (size_t)i, out_proofs + psz * (size_t)i);
-        } else if (per_proof) rc = prove_with_statement(provers[h], aL + asz * (size_t)i, aR + asz * (size_t)i, aO + asz * (size_t)i, /*cs=*/nullptr, transcripts + tsz * (size_t)i, out_proofs + psz * (size_t)i);
-        else rc = sonic_prover_prove(provers[h], transcripts + tsz * (size_t)i, out_proofs + psz * (size_t)i);
+        // (the constants are checked here, before anything of proof i is queued: its status, and the handle keeps the constants it has)
+        for (long q = 0; cs && q < Q && !rc; q++) {
+          Fr k;
+          memcpy(k.l, cs + ksz * (size_t)i + 32 * (size_t)q, 32);
+          if (!fp_is_canonical(k)) { set_error("%s: cs[%ld] of proof %ld is not a canonical field element", who, q, (long)i); rc = SONIC_ERR_BAD_ENCODING; }
+        }
+        const uint8_t *aLi = per_proof ? aL + asz * (size_t)i : nullptr, *aRi = per_proof ? aR + asz * (size_t)i : nullptr, *aOi = per_proof ? aO + asz * (size_t)i : nullptr;
+        const uint8_t* csi = cs ? cs + ksz * (size_t)i : nullptr;
+        uint8_t* out = out_proofs + psz * (size_t)i;
+        if (rc) {}      // (refused above)
+        else if (fs) rc = prove_fs_with_statement(provers[h], aLi, aRi, aOi, csi, fs->circuit_digests + 32 * (size_t)i, fs->blinder_seeds + 32 * (size_t)i, out,
+                                                  fs->out_transcripts ? fs->out_transcripts + tsz * (size_t)i : nullptr);
+        else if (cs || per_proof) rc = prove_with_statement(provers[h], aLi, aRi, aOi, csi, transcripts + tsz * (size_t)i, out);
+        else rc = sonic_prover_prove(provers[h], transcripts + tsz * (size_t)i, out);
         if (rc && first_bad[(size_t)h] < 0) { first_bad[(size_t)h] = i; char b[512]; sonic_last_error(b, sizeof b); errs[(size_t)h] = b; }
       } catch (...) { rc = SONIC_ERR_HIP; }                          // (nothing may leave a thread's body: std::terminate)
       status[(size_t)i] = rc;
@@ -257,6 +262,13 @@ int sonic_prove_batch_statements(sonic_prover_t* const* provers, int n_provers, 
   try { DeviceScope probe(-1); } catch (const HipFail& f) { return f.code; }      // (no device: SONIC_ERR_NO_DEVICE whatever the arguments are)
   if (K > 0 && !cs) { set_error("sonic_prove_batch_statements: cs is NULL (sonic_prove_batch proves with the handles' constants)"); return SONIC_ERR_INVALID_ARG; }
   return prove_batch_impl("sonic_prove_batch_statements", provers, n_provers, K, aL, aR, aO, cs, transcripts, out_proofs, out_status);
+}
+
+int sonic_prove_batch_fs(sonic_prover_t* const* provers, int n_provers, int64_t K, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO, const uint8_t* cs,
+                         const uint8_t* circuit_digests, const uint8_t* blinder_seeds, uint8_t* out_proofs, uint8_t* out_transcripts, int* out_status) {
+  try { DeviceScope probe(-1); } catch (const HipFail& f) { return f.code; }      // (no device: SONIC_ERR_NO_DEVICE whatever the arguments are)
+  const BatchFs fs{circuit_digests, blinder_seeds, out_transcripts};
+  return prove_batch_impl("sonic_prove_batch_fs", provers, n_provers, K, aL, aR, aO, cs, nullptr, out_proofs, out_status, &fs);
 }
 
 }  // extern "C"

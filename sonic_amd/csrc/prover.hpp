@@ -6,6 +6,7 @@
 #include <string.h>
 #include <algorithm>
 #include <chrono>
+#include <condition_variable>
 #include <functional>
 #include <memory>
 #include <thread>
@@ -71,6 +72,20 @@ struct Lane {
   int njobs = 0;
 };
 constexpr int N_LANES = 6;
+
+// One Fiat-Shamir proof in flight (sonic_prover_submit_fs / collect_fs): the host thread that walks the six passes for the handle while the
+// submitting thread goes on -- it waits for the device between passes, runs the host tails and hashes, so another handle's kernels fill
+// the GPU meanwhile.  Made on the first submit_fs, joined when the handle is freed.  `m` guards everything below it.
+struct FsWorker {
+  std::thread th;
+  std::mutex m;
+  std::condition_variable cv;
+  bool has_job = false, done = false, quit = false;
+  uint8_t circuit_digest[32], seed[32];
+  int rc = 0;
+  std::string err;                             // the job's error text: set_error is per thread, collect_fs hands it to its caller
+  std::vector<uint8_t> proof, transcript;
+};
 
 struct sonic_prover {
   const sonic_srs* srs = nullptr;
@@ -171,7 +186,9 @@ struct sonic_prover {
   hipGraphExec_t graph = nullptr;
   bool graph_tried = false;
   long proofs_done = 0;
-  bool in_flight = false;                    // between sonic_prover_submit and sonic_prover_collect
+  bool in_flight = false;                    // between sonic_prover_submit and sonic_prover_collect, or submit_fs and collect_fs
+  bool fs_flight = false;                    // the proof in flight is a Fiat-Shamir one: fsw walks it, and only collect_fs ends it
+  std::unique_ptr<FsWorker> fsw;
   // Which steps of the proof an enqueue runs (bit = phase; PH_ALL normally).  The Fiat-Shamir mode (sonic_prover_prove_fs) proves in
   // six passes, each running exactly the MSMs whose challenges have become known: results of earlier passes stay in `slots` / `frout`.
   uint32_t phases = 0x7e;
@@ -197,6 +214,13 @@ struct sonic_prover {
   std::vector<uint8_t> fr_valid;             // per evaluation: the last enqueue computed it
   uint8_t witness_digest[32] = {0};          // SHA-256 of the assignment (Fiat-Shamir blinders, fs.hpp), made on first use
   bool have_witness_digest = false;
+  // witness digest v2 (fs.hpp): the SHA-256 tree over the resident assignment, computed by the GPU (witness.hip) into `wtree` (all levels,
+  // grown on first use; the root comes back through the pinned h_root), cached until the assignment changes
+  uint8_t witness_digest_v2[32] = {0};
+  bool have_witness_digest_v2 = false;
+  DevBuf wtree;
+  uint32_t* h_root = nullptr;
+  void assignment_changed() { have_witness_digest = false; have_witness_digest_v2 = false; }
   // Lane N_LANES-1 carries the t(X,y) group (the largest, ready last); the other groups alternate over the rest, which
   // balances the point additions per lane (Q = 2: 55M / 51M / 48M) while one lane's sort and reduction phases run under
   // another lane's accumulation.  Streams beyond the 4 hardware queues would serialise behind each other.
@@ -213,6 +237,11 @@ struct sonic_prover {
     return l;
   }
   ~sonic_prover() {
+    if (fsw) {      // a proof in flight is walked to its end first: it uses everything below
+      { std::lock_guard<std::mutex> g(fsw->m); fsw->quit = true; }
+      fsw->cv.notify_all();
+      if (fsw->th.joinable()) fsw->th.join();
+    }
     for (auto& l : lanes) { if (l.st) (void)hipStreamDestroy(l.st); if (l.done) (void)hipEventDestroy(l.done); if (l.prep) (void)hipEventDestroy(l.prep); }
     for (auto& l : chain) { if (l.st) (void)hipStreamDestroy(l.st); if (l.done) (void)hipEventDestroy(l.done); if (l.prep) (void)hipEventDestroy(l.prep); }
     for (auto& r : runs) if (r.masked_ev) (void)hipEventDestroy(r.masked_ev);
@@ -221,7 +250,7 @@ struct sonic_prover {
     if (st) (void)hipStreamDestroy(st);
     if (ts) (void)hipStreamDestroy(ts);
     if (graph) (void)hipGraphExecDestroy(graph);
-    for (void* h : {(void*)h_tr, (void*)h_pairs, (void*)h_slots, (void*)h_fr, (void*)h_flags}) if (h) (void)hipHostFree(h);
+    for (void* h : {(void*)h_tr, (void*)h_pairs, (void*)h_slots, (void*)h_fr, (void*)h_flags, (void*)h_root}) if (h) (void)hipHostFree(h);
   }
 };
 
@@ -232,6 +261,12 @@ int flags_to_status(int f, const char* who);
 // caller's host buffers (cs: Q canonical field elements, or null: the handle's; aL, aR, aO all null: the resident assignment)
 extern "C" int prove_with_statement(sonic_prover_t* p, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO, const uint8_t* cs, const uint8_t* transcript,
                                     uint8_t* out_proof);
+// the same for a Fiat-Shamir proof (sonic_prove_batch_fs): the six passes over witness digest v2; out_transcript may be null
+extern "C" int prove_fs_with_statement(sonic_prover_t* p, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO, const uint8_t* cs, const uint8_t circuit_digest[32],
+                                       const uint8_t blinder_seed[32], uint8_t* out_proof, uint8_t* out_transcript);
+// (witness.hip) queues the SHA-256 tree of witness digest v2 over the Montgomery arrays into `tree` (grown to fit); returns where the
+// root's eight state words will be
+namespace sonic { const uint32_t* witness_tree_enqueue(hipStream_t st, const Fr* aL, const Fr* aR, const Fr* aO, long n, DevBuf& tree); }
 // (prove.hip) what sonic_prover_new[_csr] and the one-shot calls share: the checks of a circuit against an SRS, a handle for an admitted
 // circuit, and the hand-over of the next call's circuit to a handle that exists (uploaded inside its next proof)
 int prover_admits(const char* who, const sonic_srs* srs, const CircuitView& c);

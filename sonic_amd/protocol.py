@@ -298,6 +298,28 @@ class Prover:
         _lib.check(_lib.lib().sonic_prover_prove_fs(self._h, bytes(circuit_digest), bytes(blinder_seed), out, tr))
         return out.raw, [int.from_bytes(tr.raw[32 * i:32 * i + 32], "little") for i in range(transcript_len(self.Q))]
 
+    def witness_digest(self) -> bytes:
+        """witness digest v2 of the resident assignment (sonic_prover_witness_digest_v2): the SHA-256 tree the GPU computes over aL, aR, aO
+        where they lie; cached until the assignment changes"""
+        out = C.create_string_buffer(32)
+        _lib.check(_lib.lib().sonic_prover_witness_digest_v2(self._h, out))
+        return out.raw
+
+    def submit_fs(self, circuit_digest: bytes, blinder_seed: bytes) -> None:
+        """hand one Fiat-Shamir proof to the handle's host worker and return without waiting (sonic_prover_submit_fs); one proof in flight
+        per handle.  The blinders come from witness digest v2, so the bytes differ from prove_fs's for the same seed."""
+        circuit_digest, blinder_seed = bytes(circuit_digest), bytes(blinder_seed)
+        if len(circuit_digest) != 32 or len(blinder_seed) != 32:      # the C side reads 32 bytes of each
+            raise ValueError("submit_fs: circuit_digest and blinder_seed must be 32 bytes each")
+        _lib.check(_lib.lib().sonic_prover_submit_fs(self._h, circuit_digest, blinder_seed))
+
+    def collect_fs(self):
+        """wait for the proof submit_fs started (sonic_prover_collect_fs): (proof bytes, the 8 + 2Q transcript values it was made with)"""
+        out = C.create_string_buffer(_lib.lib().sonic_proof_size(self.Q))
+        tr = C.create_string_buffer(32 * transcript_len(self.Q))
+        _lib.check(_lib.lib().sonic_prover_collect_fs(self._h, out, tr))
+        return out.raw, [int.from_bytes(tr.raw[32 * i:32 * i + 32], "little") for i in range(transcript_len(self.Q))]
+
     def hsc_prove(self, yzs, u: int, v: int) -> HscProof:
         """hscProve srs sXY yzs (Signature.hs:32-72) for the s(X,Y) of this handle's circuit; u, v: its two `rnd` draws"""
         yzs = list(yzs)
@@ -407,6 +429,41 @@ def prove_batch(provers, transcripts, assignments=None, constants=None) -> List[
         return [out[i].tobytes() for i in range(K)]
     _lib.check(_lib.lib().sonic_prove_batch(_handle_array(provers), len(provers), K, ptr(aL), ptr(aR), ptr(aO), tr.ctypes.data, out.ctypes.data, status))
     return [out[i].tobytes() for i in range(K)]
+
+
+def prove_batch_fs(provers, digests, seeds, assignments=None, constants=None):
+    """K Fiat-Shamir proofs of one circuit spread over several prover handles (sonic_prove_batch_fs: proof i on handle i % len(provers), one
+    host thread per handle walking the six passes): [(proof bytes, transcript values), ...].  digests, seeds: one circuit digest and one
+    blinder seed (32 bytes each) per proof -- with per-proof constants, digests[i] = fs_circuit_digest_resume(midstate, constants[i]).
+    assignments: K Assignment objects, or None (the handles' resident assignments); constants: one cs per proof, or None."""
+    provers = list(provers)
+    Q, n = provers[0].Q, provers[0].n
+    digests, seeds = [bytes(d) for d in digests], [bytes(s) for s in seeds]
+    K = len(digests)
+    if len(seeds) != K or any(len(b) != 32 for b in digests + seeds):
+        raise ValueError("prove_batch_fs: one 32-byte circuit digest and one 32-byte seed per proof")
+    psz, tl = _lib.lib().sonic_proof_size(Q), transcript_len(Q)
+    out = np.zeros((max(K, 1), psz), np.uint8)
+    tr = np.zeros((max(K, 1), tl, 32), np.uint8)
+    status = (C.c_int * max(K, 1))()
+    aL = aR = aO = None
+    if assignments is not None:
+        if len(assignments) != K:
+            raise ValueError("prove_batch_fs: one assignment per proof")
+        aL, aR, aO = (np.ascontiguousarray(np.stack([fr_array(getattr(a, k)) for a in assignments])) for k in ("aL", "aR", "aO"))
+        if any(a.shape != (K, n, 32) for a in (aL, aR, aO)):
+            raise ValueError(f"prove_batch_fs: every assignment needs n = {n} values in aL, aR, aO")
+    cs = None
+    if constants is not None:
+        constants = list(constants)
+        if len(constants) != K:
+            raise ValueError("prove_batch_fs: one set of constants per proof")
+        cs = b"".join(_constants_bytes(c, Q, "prove_batch_fs") for c in constants) or bytes(32)
+    ptr = lambda a: None if a is None else a.ctypes.data       # noqa: E731
+    _lib.check(_lib.lib().sonic_prove_batch_fs(_handle_array(provers), len(provers), K, ptr(aL), ptr(aR), ptr(aO), cs, b"".join(digests) or bytes(32),
+                                               b"".join(seeds) or bytes(32), out.ctypes.data, tr.ctypes.data, status))
+    raw_tr = tr.tobytes()
+    return [(out[i].tobytes(), [int.from_bytes(raw_tr[32 * (i * tl + k):32 * (i * tl + k) + 32], "little") for k in range(tl)]) for i in range(K)]
 
 
 class _Statement(C.Structure):          # sonic_statement_t
