@@ -60,6 +60,8 @@ module Sonic.HIP
   , Verifier, newVerifier, verifyBatchStatements, verifyFsBatchStatements
     -- * Fiat-Shamir proofs in flight
   , witnessDigest, submitFs, collectFs, proveBatchFs
+    -- * witness sources
+  , WitnessSrc(..), setWitnessI64, proveBatchI64
   ) where
 
 import Protolude hiding (check)
@@ -73,8 +75,8 @@ import Data.Field.Galois (fromE, fromP, rnd, toE, toU')
 import Data.Pairing.BLS12381 (BLS12381, Fq, Fq12, Fr, G1, G2, GT)
 import Data.Poly.Sparse.Laurent (VLaurent)
 import Bulletproofs.ArithmeticCircuit (ArithCircuit(..), Assignment(..), GateWeights(..))
-import Foreign (FunPtr, ForeignPtr, Ptr, alloca, allocaArray, allocaBytes, castPtr, newForeignPtr, nullPtr,
-                peek, peekElemOff, pokeArray, withArrayLen, withForeignPtr)
+import Foreign (FunPtr, ForeignPtr, Ptr, Storable(..), alloca, allocaArray, allocaBytes, castPtr, newForeignPtr, nullPtr,
+                peekElemOff, pokeArray, with, withArray, withArrayLen, withForeignPtr)
 import Foreign.C.String (CString, peekCString, withCString)
 import Foreign.C.Types (CChar, CInt(..), CSize(..))
 import System.IO.Unsafe (unsafePerformIO)
@@ -150,6 +152,9 @@ foreign import ccall safe   "sonic_prover_witness_digest_v2" c_witness_digest ::
 foreign import ccall safe   "sonic_prover_submit_fs"      c_prover_submit_fs :: Ptr ProverHandle -> Ptr Word8 -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_prover_collect_fs"     c_prover_collect_fs :: Ptr ProverHandle -> Ptr Word8 -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_prove_batch_fs"        c_prove_batch_fs :: Ptr (Ptr ProverHandle) -> CInt -> Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> IO CInt
+-- witness sources (ABI 7, additions): where an assignment comes from, as one description (sonic_witness_src_t)
+foreign import ccall safe   "sonic_prover_set_witness"    c_prover_set_witness :: Ptr ProverHandle -> Ptr WitnessSrc -> IO CInt
+foreign import ccall safe   "sonic_prove_batch_src"       c_prove_batch_src :: Ptr (Ptr ProverHandle) -> CInt -> Int64 -> Ptr WitnessSrc -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> IO CInt
 foreign import ccall safe   "sonic_verifier_new_csr"      c_verifier_new_csr :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr (Ptr VerifierHandle) -> IO CInt
 foreign import ccall safe   "&sonic_verifier_free"        p_verifier_free  :: FunPtr (Ptr VerifierHandle -> IO ())
 foreign import ccall safe   "sonic_verifier_verify_batch_cs" c_verify_batch_cs :: Ptr VerifierHandle -> Int64 -> Ptr Word8 -> CInt -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> Ptr Word8 -> IO CInt
@@ -755,6 +760,60 @@ proveBatchFs ps@(p0 : _) sts = do
           BSI.create (psz * k) $ \out ->
             check =<< c_prove_batch_fs arr np (fromIntegral k) pal par pao pcs pdg psd out nullPtr nullPtr
   pure (map (decodeProof q) (chunks psz bytes))
+
+-- ---------------------------------------------------------------------------------------------------------------------
+-- witness sources (include/sonic_hip.h, "Witness sources"): host or device memory, 32-byte canonical Fr or int64, aO given or derived.
+-- The source is only read and must stay unchanged until the call returns; every call is blocking.  A non-NULL stream of a device
+-- source is the stream whose work produces the data: the library records an event on it at entry and the handle's stream waits on
+-- that event; NULL states that the data is complete.
+-- ---------------------------------------------------------------------------------------------------------------------
+-- | sonic_witness_src_t: 48 bytes -- aL, aR, aO at 0, 8, 16; kind, on_device (int32) at 24, 28; stride (int64) at 32; hip_stream at 40
+data WitnessSrc = WitnessSrc
+  { wsAL, wsAR, wsAO :: Ptr ()       -- ^ wsAO = nullPtr: the library sets aO = aL * aR in Fr
+  , wsKind     :: Int32              -- ^ 0 = SONIC_WIT_FR32 (32-byte canonical Fr), 1 = SONIC_WIT_I64 (v < 0 is r - |v|)
+  , wsOnDevice :: Int32              -- ^ 0: host memory; 1: memory of the GPU the handle lives on
+  , wsStride   :: Int64              -- ^ bytes from assignment b to b + 1 in batched calls; 0 = packed
+  , wsStream   :: Ptr ()             -- ^ device sources only: the producing stream, or nullPtr
+  }
+
+instance Storable WitnessSrc where
+  sizeOf _    = 48
+  alignment _ = 8
+  peek p = WitnessSrc <$> peekByteOff p 0 <*> peekByteOff p 8 <*> peekByteOff p 16 <*> peekByteOff p 24 <*> peekByteOff p 28
+                      <*> peekByteOff p 32 <*> peekByteOff p 40
+  poke p WitnessSrc{..} = do
+    pokeByteOff p 0 wsAL; pokeByteOff p 8 wsAR; pokeByteOff p 16 wsAO
+    pokeByteOff p 24 wsKind; pokeByteOff p 28 wsOnDevice; pokeByteOff p 32 wsStride; pokeByteOff p 40 wsStream
+
+-- a host source of int64 with aO derived
+hostI64 :: Ptr Int64 -> Ptr Int64 -> WitnessSrc
+hostI64 pl pr = WitnessSrc { wsAL = castPtr pl, wsAR = castPtr pr, wsAO = nullPtr, wsKind = 1, wsOnDevice = 0, wsStride = 0, wsStream = nullPtr }
+
+-- | the handle's assignment from machine integers (sonic_prover_set_witness): aL, aR as int64, aO = aL * aR formed on the GPU; 8 n bytes
+--   per vector cross the bus instead of 32 n, and nothing is widened on the host
+setWitnessI64 :: Prover -> [Int64] -> [Int64] -> IO ()
+setWitnessI64 pr ls rs
+  | length ls /= length rs = panic "setWitnessI64: aL and aR differ in length"
+  | otherwise = withProverAlive pr $ \p -> withArray ls $ \pl -> withArray rs $ \prr ->
+      with (hostI64 pl prr) $ \src -> check =<< c_prover_set_witness p src
+
+-- | proveBatch over assignments given as (aL, aR) in machine integers (sonic_prove_batch_src; the handles' constants): proof i reads
+--   block i of the two packed arrays, converted at the head of its own queue
+proveBatchI64 :: [Prover] -> [([Int64], [Int64])] -> IO [(Proof, RndOracle)]
+proveBatchI64 [] _ = panic "proveBatchI64: no handles"
+proveBatchI64 ps@(p0 : _) asgs = do
+  let q = proverQ p0
+      k = length asgs
+      n = case asgs of { ((l, _) : _) -> length l; [] -> 0 }
+  when (any (\(l, r) -> length l /= n || length r /= n) asgs) $ panic "proveBatchI64: every assignment needs n values in aL and in aR"
+  drawn <- replicateM k (drawTranscript q)
+  psz <- fromIntegral <$> c_proof_size (fromIntegral q)
+  bytes <- withProverAlive p0 $ \_ -> withProvers ps $ \arr np ->
+    withArray (concatMap fst asgs) $ \pl -> withArray (concatMap snd asgs) $ \prr ->
+      with (hostI64 pl prr) $ \src -> withFrs (concatMap fst drawn) $ \ptr ->
+        BSI.create (psz * k) $ \out ->
+          check =<< c_prove_batch_src arr np (fromIntegral k) src nullPtr ptr out nullPtr
+  pure (zip (map (decodeProof q) (chunks psz bytes)) (map snd drawn))
 
 -- | the batched verifier's handle (sonic_verifier_new_csr): the circuit resident on the GPU; keeps the SRS alive as long as the handle
 data Verifier = Verifier { verifierHandle :: ForeignPtr VerifierHandle, verifierSrs :: SRS, verifierQ :: Int }

@@ -100,7 +100,8 @@ typedef struct sonic_verifier sonic_verifier_t;
  * statements -- sonic_prover_eval_constraints, sonic_prover_set_constants, sonic_prove_batch_statements, sonic_fs_circuit_midstate[_csr],
  * sonic_fs_circuit_digest_resume, sonic_verifier_verify_batch_cs, sonic_verifier_verify_fs_batch_cs, sonic_verify_batch_digest_v2;
  * still 7, additions only: Fiat-Shamir proofs in flight -- sonic_prover_witness_digest_v2, sonic_prover_submit_fs,
- * sonic_prover_collect_fs, sonic_prove_batch_fs */
+ * sonic_prover_collect_fs, sonic_prove_batch_fs; still 7, additions only: witness sources -- sonic_witness_src_t, sonic_prover_set_witness,
+ * sonic_prover_eval_constraints_src, sonic_prove_batch_src, sonic_prove_batch_fs_src */
 int sonic_abi_version(void);
 int sonic_init(int device_ordinal);                 /* choose the DEFAULT GPU (first call wins) and make it the thread's HIP device; idempotent */
 int sonic_device_count(int* out);                   /* GPUs this process can see; SONIC_ERR_NO_DEVICE (and 0) without one */
@@ -587,6 +588,52 @@ int sonic_prover_collect_fs(sonic_prover_t* p, uint8_t* out_proof, uint8_t* out_
 int sonic_prove_batch_fs(sonic_prover_t* const* provers, int n_provers, int64_t K, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO,
                          const uint8_t* cs, const uint8_t* circuit_digests, const uint8_t* blinder_seeds, uint8_t* out_proofs,
                          uint8_t* out_transcripts, int* out_status);
+
+/* ---- Witness sources ----
+ * Where an assignment comes from, as ONE description that every prover entry point below accepts: host or device memory, 32-byte
+ * canonical Fr or signed 64-bit integers, aO given or derived on the GPU.  The calls above that take three host buffers of n x 32
+ * canonical bytes stay as they are; for the same values these give the same bytes (proofs, constants, witness digests).
+ *
+ * Memory and alignment.  A device source with kind SONIC_WIT_FR32: the three pointers are 32-byte aligned and stride is a multiple of
+ * 32; with kind SONIC_WIT_I64: 8-byte aligned, stride a multiple of 8.  A host source: any alignment.  stride, where it is not 0, is at
+ * least n * element size.  The source is only read, and it must stay unchanged until the call returns; every call here is blocking.
+ *
+ * Ordering.  With a non-NULL hip_stream the library records an event on that stream at entry, and the handle's stream (each handle's,
+ * in a batch) waits on that event before it reads the source.  With NULL the caller states that the data is complete.  The library
+ * never makes the caller's stream wait.
+ *
+ * Devices.  A device source must lie on the GPU of every handle that reads it (checked with hipPointerGetAttributes): a mismatch is
+ * SONIC_ERR_INVALID_ARG with a message that names both devices, and so is a host pointer passed with on_device = 1.  No peer copy is made.
+ *
+ * A device source is read where it lies, by one launch that checks, converts to Montgomery form and, with aO == NULL, multiplies; a host
+ * source is copied into a staging buffer of the handle first (8 n bytes per vector for SONIC_WIT_I64) and read by the same launch.
+ *
+ *   set_witness     sonic_prover_set_assignment from a source.  A proof in flight, or a description that breaks a rule above:
+ *                   SONIC_ERR_INVALID_ARG, before anything is launched and with the resident assignment left as it is.  A non-canonical
+ *                   SONIC_WIT_FR32 element: SONIC_ERR_BAD_ENCODING, and the handle then has no assignment.  The witness digests are
+ *                   recomputed on their next use, as after set_assignment.
+ *   eval_constraints_src   sonic_prover_eval_constraints over B assignments of a source (B n <= 2^26; assignment b is block b of each
+ *                   vector).  With aO == NULL no gate can break: out_gates is {0, -1} for every assignment.
+ *   prove_batch_src   sonic_prove_batch_statements' shape and rules with proof i's assignment read from block i of the source, converted
+ *                   at the head of proof i's own queue: no device wait of its own.  cs: K x Q x 32, or NULL (the handles' constants).
+ *                   A proof with a non-canonical element gets SONIC_ERR_BAD_ENCODING in out_status; the others are unaffected.
+ *   prove_batch_fs_src   the same for sonic_prove_batch_fs. */
+#define SONIC_WIT_FR32 0   /* 32-byte little-endian canonical Fr per element (what set_assignment takes) */
+#define SONIC_WIT_I64  1   /* int64_t per element; v >= 0 is v, v < 0 is r - |v| (INT64_MIN is r - 2^63) */
+typedef struct sonic_witness_src {
+  const void *aL, *aR, *aO;  /* aO == NULL: the library sets aO[i] = aL[i] * aR[i] in Fr */
+  int32_t kind;              /* SONIC_WIT_*; one kind for all three vectors */
+  int32_t on_device;         /* 0: host memory; 1: memory of the GPU the handle lives on */
+  int64_t stride;            /* bytes from assignment b to b + 1 within each vector, in batched calls; 0 = packed (n * element size) */
+  void*   hip_stream;        /* on_device only: the stream whose work produces the data, or NULL */
+} sonic_witness_src_t;
+int sonic_prover_set_witness(sonic_prover_t* p, const sonic_witness_src_t* src);
+int sonic_prover_eval_constraints_src(sonic_prover_t* p, int64_t B, const sonic_witness_src_t* src, uint8_t* out_cs, int64_t* out_gates);
+int sonic_prove_batch_src(sonic_prover_t* const* provers, int n_provers, int64_t K, const sonic_witness_src_t* src, const uint8_t* cs,
+                          const uint8_t* transcripts, uint8_t* out_proofs, int* out_status);
+int sonic_prove_batch_fs_src(sonic_prover_t* const* provers, int n_provers, int64_t K, const sonic_witness_src_t* src, const uint8_t* cs,
+                             const uint8_t* circuit_digests, const uint8_t* blinder_seeds, uint8_t* out_proofs, uint8_t* out_transcripts,
+                             int* out_status);
 
 /* ---- device memory for callers without a HIP binding ---- */
 int sonic_dev_alloc(size_t bytes, void** out);                       /* on the default device */

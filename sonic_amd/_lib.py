@@ -167,6 +167,10 @@ def lib() -> C.CDLL:
         "sonic_prover_submit_fs": [vp, cp, cp],
         "sonic_prover_collect_fs": [vp, vp, vp],
         "sonic_prove_batch_fs": [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "sonic_prover_set_witness": [vp, vp],
+        "sonic_prover_eval_constraints_src": [vp, i64, vp, vp, vp],
+        "sonic_prove_batch_src": [vp, i32, i64, vp, vp, vp, vp, vp],
+        "sonic_prove_batch_fs_src": [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp],
         "sonic_dev_alloc": [C.c_size_t, C.POINTER(vp)],
         "sonic_dev_free": [vp],
         "sonic_dev_upload": [vp, vp, C.c_size_t],
@@ -230,6 +234,12 @@ def lib() -> C.CDLL:
 HIP_RUNTIME_NOTE = None
 ABI_VERSION = 7          # SONIC_ABI_VERSION of include/sonic_hip.h
 FS_MIDSTATE_SIZE = 112   # SONIC_FS_MIDSTATE_SIZE
+WIT_FR32, WIT_I64 = 0, 1  # SONIC_WIT_*
+
+
+class WitnessSrc(C.Structure):          # sonic_witness_src_t
+    _fields_ = [("aL", C.c_void_p), ("aR", C.c_void_p), ("aO", C.c_void_p), ("kind", C.c_int32), ("on_device", C.c_int32),
+                ("stride", C.c_int64), ("hip_stream", C.c_void_p)]
 
 
 def _hipver(v: int) -> str:
@@ -258,6 +268,7 @@ EXPORTED = [
     "sonic_prover_eval_constraints", "sonic_prover_set_constants", "sonic_prove_batch_statements", "sonic_fs_circuit_midstate", "sonic_fs_circuit_midstate_csr",
     "sonic_fs_circuit_digest_resume", "sonic_verifier_verify_batch_cs", "sonic_verifier_verify_fs_batch_cs", "sonic_verify_batch_digest_v2",
     "sonic_prover_witness_digest_v2", "sonic_prover_submit_fs", "sonic_prover_collect_fs", "sonic_prove_batch_fs",
+    "sonic_prover_set_witness", "sonic_prover_eval_constraints_src", "sonic_prove_batch_src", "sonic_prove_batch_fs_src",
 ]
 
 

@@ -590,6 +590,14 @@ static void enqueue_polynomials(sonic_prover_t* p, GroupQueue& q, ProofPass& w) 
     p->pend_asg[0] = nullptr;
     p->assignment_changed();
   }
+  if (p->pend_wit.set) {
+    // (a witness source: the handle's stream waits for the source's, then ONE launch checks, converts and writes the three arrays)
+    for (DevBuf* a : {&p->aL, &p->aR, &p->aO}) a->ensure(sizeof(Fr) * (size_t)n);
+    if (p->pend_wit.ready) HIP_OK(hipStreamWaitEvent(ms, p->pend_wit.ready, 0));
+    witness_load_enqueue(p, ms, p->pend_wit.v, 1, p->aL.as<Fr>(), p->aR.as<Fr>(), p->aO.as<Fr>(), n, flags + 1);
+    p->pend_wit.set = false;
+    p->assignment_changed();
+  }
   if (p->pend_cs) {
     upload_fr_mont(ms, p->cs, p->pend_cs, Q, flags + 1);
     p->pend_cs = nullptr;
@@ -813,7 +821,7 @@ static int prove_enqueue(sonic_prover_t* p, const uint8_t* transcript) {
   challenge_pairs_host(p, transcript);
   // Launch-bound sizes replay the whole multi-stream enqueue as one hipGraph: captured on the second proof of a handle (the
   // first one grows the workspaces), every address in it is owned by the handle.
-  const bool pending = p->pend.set || p->pend_asg[0] != nullptr || p->pend_cs != nullptr;
+  const bool pending = p->pend.set || p->pend_asg[0] != nullptr || p->pend_wit.set || p->pend_cs != nullptr;
   const bool want_graph = p->use_graph && p->proofs_done >= 1 && !profiler().on && p->phases == PH_ALL && !pending;
   const bool replay = want_graph && p->graph != nullptr;
   const bool capturing = want_graph && !replay && !p->graph_tried;
@@ -1050,6 +1058,22 @@ int prove_with_statement(sonic_prover_t* p, const uint8_t* aL, const uint8_t* aR
   p->pend_asg[0] = nullptr;
   p->pend_cs = nullptr;
   if (aL) p->have_assignment = rc == SONIC_OK;          // (a failed call may have left a partly converted assignment behind)
+  return rc;
+}
+
+// the same with the assignment of THIS call in a witness source (witness_src.hpp): block 0 of `w`, checked by the caller, read at the
+// head of the proof's queue (pend_wit)
+int prove_with_witness(sonic_prover_t* p, const WitnessView& w, hipEvent_t ready, const uint8_t* cs, const uint8_t* transcript, uint8_t* out_proof) {
+  std::lock_guard<std::mutex> g(p->mu);
+  if (p->in_flight) { set_error("prove: a submitted proof has not been collected yet"); return SONIC_ERR_INVALID_ARG; }
+  int rc = whole_proof_only(p, "prove");
+  if (rc) return rc;
+  p->pend_wit.v = w; p->pend_wit.ready = ready; p->pend_wit.set = true;
+  p->pend_cs = cs;
+  rc = prove_run(p, transcript, prove_finish, out_proof);
+  p->pend_wit.set = false;
+  p->pend_cs = nullptr;
+  p->have_assignment = rc == SONIC_OK;          // (a failed call may have left a refused assignment behind)
   return rc;
 }
 
@@ -1351,6 +1375,33 @@ int prove_fs_with_statement(sonic_prover_t* p, const uint8_t* aL, const uint8_t*
     witness_digest_v2_finish(p);
     p->have_assignment = true;
   } else witness_digest_v2_ensure(p);
+  p->pend_cs = cs;
+  rc = prove_fs_walk(p, circuit_digest, blinder_seed, p->witness_digest_v2, out_proof, out_transcript);
+  p->pend_cs = nullptr;
+  return rc;
+  API_END
+}
+
+// the same with the assignment in a witness source: block 0 of `w`, checked by the caller
+int prove_fs_with_witness(sonic_prover_t* p, const WitnessView& w, hipEvent_t ready, const uint8_t* cs, const uint8_t circuit_digest[32],
+                          const uint8_t blinder_seed[32], uint8_t* out_proof, uint8_t* out_transcript) {
+  API_BEGIN_ON(p->device)
+  std::lock_guard<std::mutex> g(p->mu);
+  if (p->in_flight) { set_error("prove: a submitted proof has not been collected yet"); return SONIC_ERR_INVALID_ARG; }
+  int rc = whole_proof_only(p, "prove");
+  if (rc) return rc;
+  hipStream_t st = p->st;
+  p->have_assignment = false;               // (until the source is known to be good)
+  p->assignment_changed();
+  for (DevBuf* a : {&p->aL, &p->aR, &p->aO}) a->ensure(sizeof(Fr) * (size_t)p->n);
+  if (ready) HIP_OK(hipStreamWaitEvent(st, ready, 0));
+  HIP_OK(hipMemsetAsync(p->flags.p, 0, 4, st));
+  witness_load_enqueue(p, st, w, 1, p->aL.as<Fr>(), p->aR.as<Fr>(), p->aO.as<Fr>(), p->n, p->flags.as<int>());
+  witness_digest_v2_enqueue(p);
+  const int f = read_flags(st, p->flags);
+  if (f) return flags_to_status(f, "prove (assignment handed over with the call)");
+  witness_digest_v2_finish(p);
+  p->have_assignment = true;
   p->pend_cs = cs;
   rc = prove_fs_walk(p, circuit_digest, blinder_seed, p->witness_digest_v2, out_proof, out_transcript);
   p->pend_cs = nullptr;

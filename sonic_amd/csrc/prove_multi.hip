@@ -197,7 +197,8 @@ int sonic_prove_shared(sonic_prover_t* const* provers, int world, const uint8_t*
 // sonic_prove_batch_fs (fs: the circuit digests and blinder seeds in place of transcripts; the transcripts come back)
 struct BatchFs { const uint8_t *circuit_digests, *blinder_seeds; uint8_t* out_transcripts; };
 static int prove_batch_impl(const char* who, sonic_prover_t* const* provers, int n_provers, int64_t K, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO,
-                            const uint8_t* cs, const uint8_t* transcripts, uint8_t* out_proofs, int* out_status, const BatchFs* fs = nullptr) {
+                            const uint8_t* cs, const uint8_t* transcripts, uint8_t* out_proofs, int* out_status, const BatchFs* fs = nullptr,
+                            const sonic_witness_src_t* src = nullptr, bool from_src = false) {
   if (!provers || n_provers < 1 || n_provers > 1024 || K < 0 || (K > 0 && (!(fs ? fs->circuit_digests && fs->blinder_seeds : transcripts != nullptr) || !out_proofs))) return SONIC_ERR_INVALID_ARG;
   const bool per_proof = aL || aR || aO;
   if (per_proof && !(aL && aR && aO)) { set_error("%s: aL, aR, aO must be given together (or all NULL: the handles' resident assignments)", who); return SONIC_ERR_INVALID_ARG; }
@@ -208,6 +209,20 @@ static int prove_batch_impl(const char* who, sonic_prover_t* const* provers, int
     for (int q = 0; q < i; q++) if (provers[q] == provers[i]) { set_error("%s: handle %d appears twice", who, i); return SONIC_ERR_INVALID_ARG; }
   }
   const long n = provers[0]->n, Q = provers[0]->Q;
+  // a witness source (sonic_prove_batch_src, sonic_prove_batch_fs_src): checked once, against every handle's GPU, before anything is
+  // queued; the event that orders a device source is recorded here, at entry, and every handle's stream waits for it
+  WitnessView wv;
+  WitnessReady ready;
+  if (from_src && K > 0) {
+    int rc = witness_view_of(who, src, n, K, &wv);
+    if (rc) return rc;
+    try {
+      DeviceScope scope(provers[0]->device);
+      for (int i = 0; i < n_provers && !rc; i++) rc = witness_on_device_of(who, wv, n, K, provers[i]->device);
+      if (!rc) ready.record(wv);
+    } catch (const HipFail& f) { return f.code; }
+    if (rc) return rc;
+  }
   const size_t psz = sonic_proof_size(Q), tsz = 32 * (size_t)(8 + 2 * Q), asz = 32 * (size_t)n, ksz = 32 * (size_t)Q;
   std::vector<int> status((size_t)K, SONIC_OK);
   std::vector<std::string> errs((size_t)n_provers);
@@ -226,6 +241,9 @@ static int prove_batch_impl(const char* who, sonic_prover_t* const* provers, int
         const uint8_t* csi = cs ? cs + ksz * (size_t)i : nullptr;
         uint8_t* out = out_proofs + psz * (size_t)i;
         if (rc) {}      // (refused above)
+        else if (from_src && fs) rc = prove_fs_with_witness(provers[h], wv.block(i), ready.ev, csi, fs->circuit_digests + 32 * (size_t)i, fs->blinder_seeds + 32 * (size_t)i, out,
+                                                            fs->out_transcripts ? fs->out_transcripts + tsz * (size_t)i : nullptr);
+        else if (from_src) rc = prove_with_witness(provers[h], wv.block(i), ready.ev, csi, transcripts + tsz * (size_t)i, out);
         else if (fs) rc = prove_fs_with_statement(provers[h], aLi, aRi, aOi, csi, fs->circuit_digests + 32 * (size_t)i, fs->blinder_seeds + 32 * (size_t)i, out,
                                                   fs->out_transcripts ? fs->out_transcripts + tsz * (size_t)i : nullptr);
         else if (cs || per_proof) rc = prove_with_statement(provers[h], aLi, aRi, aOi, csi, transcripts + tsz * (size_t)i, out);
@@ -269,6 +287,20 @@ int sonic_prove_batch_fs(sonic_prover_t* const* provers, int n_provers, int64_t 
   try { DeviceScope probe(-1); } catch (const HipFail& f) { return f.code; }      // (no device: SONIC_ERR_NO_DEVICE whatever the arguments are)
   const BatchFs fs{circuit_digests, blinder_seeds, out_transcripts};
   return prove_batch_impl("sonic_prove_batch_fs", provers, n_provers, K, aL, aR, aO, cs, nullptr, out_proofs, out_status, &fs);
+}
+
+// the two batch calls over a witness source (include/sonic_hip.h, "Witness sources"): proof i reads block i of each vector
+int sonic_prove_batch_src(sonic_prover_t* const* provers, int n_provers, int64_t K, const sonic_witness_src_t* src, const uint8_t* cs, const uint8_t* transcripts,
+                          uint8_t* out_proofs, int* out_status) {
+  try { DeviceScope probe(-1); } catch (const HipFail& f) { return f.code; }      // (no device: SONIC_ERR_NO_DEVICE whatever the arguments are)
+  return prove_batch_impl("sonic_prove_batch_src", provers, n_provers, K, nullptr, nullptr, nullptr, cs, transcripts, out_proofs, out_status, nullptr, src, true);
+}
+
+int sonic_prove_batch_fs_src(sonic_prover_t* const* provers, int n_provers, int64_t K, const sonic_witness_src_t* src, const uint8_t* cs, const uint8_t* circuit_digests,
+                             const uint8_t* blinder_seeds, uint8_t* out_proofs, uint8_t* out_transcripts, int* out_status) {
+  try { DeviceScope probe(-1); } catch (const HipFail& f) { return f.code; }      // (no device: SONIC_ERR_NO_DEVICE whatever the arguments are)
+  const BatchFs fs{circuit_digests, blinder_seeds, out_transcripts};
+  return prove_batch_impl("sonic_prove_batch_fs_src", provers, n_provers, K, nullptr, nullptr, nullptr, cs, nullptr, out_proofs, out_status, &fs, src, true);
 }
 
 }  // extern "C"

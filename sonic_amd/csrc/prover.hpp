@@ -18,6 +18,7 @@
 #include "fs.hpp"
 #include "share_plan.hpp"
 #include "csr.hpp"
+#include "witness_src.hpp"
 
 
 namespace sonic {
@@ -136,6 +137,11 @@ struct sonic_prover {
   // caller, uploaded into `cs` in place at the same point of the queue -- k(y) reads them on the transform's stream, which waits for the
   // main stream's polynomials anyway
   const uint8_t* pend_cs = nullptr;
+  // and for an assignment that comes from a witness source (witness_src.hpp; sonic_prove_batch_src): the block of this proof, read at the
+  // same point of the queue by the one launch of k_witness_ingest -- a device source where it lies, a host source through wit_raw.  `ready`
+  // (may be null) is the event recorded on the source's stream when the call was entered: the handle's stream waits for it first
+  struct PendingWitness { bool set = false; WitnessView v; hipEvent_t ready = nullptr; } pend_wit;
+  DevBuf wit_raw;                            // a host source's bytes as they are: 3 x n elements (statement.hip: 3 x a chunk of assignments)
   // sonic_prover_eval_constraints (statement.hip): the staging buffer of the assignments of one chunk, the partial sums, the results
   struct StatementBufs { DevBuf stage, partial, out, gates; } stm;
   // runs of equal coefficients in the S_j of a handle that is not prepared (poly.hip, k_run_tiles): per j the masked copy of s(X, y_j),
@@ -264,6 +270,27 @@ extern "C" int prove_with_statement(sonic_prover_t* p, const uint8_t* aL, const 
 // the same for a Fiat-Shamir proof (sonic_prove_batch_fs): the six passes over witness digest v2; out_transcript may be null
 extern "C" int prove_fs_with_statement(sonic_prover_t* p, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO, const uint8_t* cs, const uint8_t circuit_digest[32],
                                        const uint8_t blinder_seed[32], uint8_t* out_proof, uint8_t* out_transcript);
+// the same two with the assignment read from block 0 of a witness source (sonic_prove_batch_src, sonic_prove_batch_fs_src); `ready` as in
+// sonic_prover::PendingWitness
+extern "C" int prove_with_witness(sonic_prover_t* p, const WitnessView& w, hipEvent_t ready, const uint8_t* cs, const uint8_t* transcript, uint8_t* out_proof);
+extern "C" int prove_fs_with_witness(sonic_prover_t* p, const WitnessView& w, hipEvent_t ready, const uint8_t* cs, const uint8_t circuit_digest[32],
+                                     const uint8_t blinder_seed[32], uint8_t* out_proof, uint8_t* out_transcript);
+// (witness_src.hip) a source checked against the rules of include/sonic_hip.h ("Witness sources"), the host's half and the device's;
+// nb blocks of a checked source brought into three planes of Montgomery elements (block b at plane + b * out_stride), by ONE launch --
+// a host source goes through p->wit_raw first; and the event that orders a device source
+namespace sonic {
+int witness_view_of(const char* who, const sonic_witness_src_t* src, long n, long B, WitnessView* out);
+int witness_on_device_of(const char* who, const WitnessView& v, long n, long B, int device);
+void witness_load_enqueue(sonic_prover* p, hipStream_t st, const WitnessView& v, long nb, Fr* oL, Fr* oR, Fr* oO, long out_stride, int* d_err);
+struct WitnessReady {
+  hipEvent_t ev = nullptr;
+  WitnessReady() {}
+  WitnessReady(const WitnessReady&) = delete;
+  WitnessReady& operator=(const WitnessReady&) = delete;
+  void record(const WitnessView& v);      // on v.hip_stream, if it names one (the current device must be the stream's)
+  ~WitnessReady() { if (ev) (void)hipEventDestroy(ev); }
+};
+}
 // (witness.hip) queues the SHA-256 tree of witness digest v2 over the Montgomery arrays into `tree` (grown to fit); returns where the
 // root's eight state words will be
 namespace sonic { const uint32_t* witness_tree_enqueue(hipStream_t st, const Fr* aL, const Fr* aR, const Fr* aO, long n, DevBuf& tree); }

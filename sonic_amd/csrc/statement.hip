@@ -132,20 +132,14 @@ __global__ __launch_bounds__(CS_BLOCK) void k_gates(const Fr* __restrict__ aL, c
 }  // namespace
 }  // namespace sonic
 
-extern "C" {
-
-int sonic_prover_eval_constraints(sonic_prover_t* p, int64_t B, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO, uint8_t* out_cs, int64_t* out_gates) {
-  API_BEGIN_ON(p ? p->device : -1)
-  const char* who = "sonic_prover_eval_constraints";
-  if (!p || !out_cs) { set_error("%s: bad argument", who); return SONIC_ERR_INVALID_ARG; }
-  const bool resident = !aL && !aR && !aO;
-  if (!resident && !(aL && aR && aO)) { set_error("%s: aL, aR, aO must be given together (or all NULL: the handle's resident assignment)", who); return SONIC_ERR_INVALID_ARG; }
+// What sonic_prover_eval_constraints and sonic_prover_eval_constraints_src share, under p->mu and inside the caller's device scope: B
+// assignments in chunks through the staging planes -- three host buffers of canonical bytes (copied, then converted in place), or a
+// witness source `w` (witness_src.hpp: read by the one launch of k_witness_ingest; a device source where it lies) -- or, with neither, the
+// handle's resident assignment.
+static int eval_constraints_run(const char* who, sonic_prover_t* p, int64_t B, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO, const WitnessView* w,
+                                uint8_t* out_cs, int64_t* out_gates) {
+  const bool resident = !aL && !w;
   const long n = p->n, Q = p->Q;
-  if (B < 1 || B > MSM_TABLE_MAX_TERMS / n) { set_error("%s: B = %lld outside [1, 2^26 / n]", who, (long long)B); return SONIC_ERR_INVALID_ARG; }
-  if (resident && B != 1) { set_error("%s: the resident assignment is one assignment (B = 1)", who); return SONIC_ERR_INVALID_ARG; }
-  std::lock_guard<std::mutex> g(p->mu);
-  if (resident && !p->have_assignment) { set_error("%s: no assignment set", who); return SONIC_ERR_INVALID_ARG; }
-  if (p->in_flight) { set_error("%s: a submitted proof is still reading the handle's buffers (collect it first)", who); return SONIC_ERR_INVALID_ARG; }
   hipStream_t st = p->st;
   sonic_prover::CsrBufs& sp = p->sp;
   sonic_prover::StatementBufs& sb = p->stm;
@@ -164,7 +158,11 @@ int sonic_prover_eval_constraints(sonic_prover_t* p, int64_t B, const uint8_t* a
   for (long b0 = 0; b0 < B; b0 += Bc) {
     const long nb = std::min<long>(Bc, B - b0);
     const Fr *dL = p->aL.as<Fr>(), *dR = p->aR.as<Fr>(), *dO = p->aO.as<Fr>();
-    if (!resident) {
+    if (w) {
+      Fr* s = sb.stage.as<Fr>();
+      witness_load_enqueue(p, st, w->block(b0), nb, s, s + nb * n, s + 2 * nb * n, n, p->flags.as<int>());
+      dL = s; dR = s + nb * n; dO = s + 2 * nb * n;
+    } else if (!resident) {
       Fr* s = sb.stage.as<Fr>();
       const size_t bytes = 32 * (size_t)nb * (size_t)n, off = 32 * (size_t)b0 * (size_t)n;
       HIP_OK(hipMemcpyAsync(s, aL + off, bytes, hipMemcpyHostToDevice, st));
@@ -185,20 +183,61 @@ int sonic_prover_eval_constraints(sonic_prover_t* p, int64_t B, const uint8_t* a
       LAUNCH(k_cs_finish, dim3((unsigned)Q, (unsigned)nb), CS_BLOCK, 0, st, (const int32_t*)nullptr, nblk, (int)Q, (const Fr*)partial, sb.out.as<Fr>());
     }
     HIP_OK(hipMemcpyAsync(out_cs + 32 * (size_t)b0 * (size_t)Q, sb.out.p, 32 * (size_t)nb * (size_t)Q, hipMemcpyDeviceToHost, st));
-    if (out_gates) {
+    const bool gates_derived = w && !w->aO;      // aO = aL aR by construction: no gate can break, and none is looked at
+    if (out_gates && !gates_derived) {
       HIP_OK(hipMemcpyAsync(sb.gates.p, gates_init.data(), 16 * (size_t)nb, hipMemcpyHostToDevice, st));
       LAUNCH(k_gates, dim3((unsigned)nblk, (unsigned)nb), CS_BLOCK, 0, st, dL, dR, dO, n, n, sb.gates.as<unsigned long long>());
       HIP_OK(hipMemcpyAsync(gates_host.data(), sb.gates.p, 16 * (size_t)nb, hipMemcpyDeviceToHost, st));
     }
     HIP_OK(hipStreamSynchronize(st));       // the staging buffer and gates_host are reused by the next chunk
-    for (long b = 0; out_gates && b < nb; b++) {
+    for (long b = 0; out_gates && gates_derived && b < nb; b++) { out_gates[2 * (b0 + b)] = 0; out_gates[2 * (b0 + b) + 1] = -1; }
+    for (long b = 0; out_gates && !gates_derived && b < nb; b++) {
       out_gates[2 * (b0 + b)] = (int64_t)gates_host[2 * (size_t)b];
       out_gates[2 * (b0 + b) + 1] = gates_host[2 * (size_t)b] ? (int64_t)gates_host[2 * (size_t)b + 1] : -1;
     }
   }
   const int f = read_flags(st, p->flags);
   if (f) return flags_to_status(f, who);
-  API_END
+  return SONIC_OK;
+}
+
+extern "C" {
+
+int sonic_prover_eval_constraints(sonic_prover_t* p, int64_t B, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO, uint8_t* out_cs, int64_t* out_gates) {
+  API_BEGIN_ON(p ? p->device : -1)
+  const char* who = "sonic_prover_eval_constraints";
+  if (!p || !out_cs) { set_error("%s: bad argument", who); return SONIC_ERR_INVALID_ARG; }
+  const bool resident = !aL && !aR && !aO;
+  if (!resident && !(aL && aR && aO)) { set_error("%s: aL, aR, aO must be given together (or all NULL: the handle's resident assignment)", who); return SONIC_ERR_INVALID_ARG; }
+  const long n = p->n;
+  if (B < 1 || B > MSM_TABLE_MAX_TERMS / n) { set_error("%s: B = %lld outside [1, 2^26 / n]", who, (long long)B); return SONIC_ERR_INVALID_ARG; }
+  if (resident && B != 1) { set_error("%s: the resident assignment is one assignment (B = 1)", who); return SONIC_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> g(p->mu);
+  if (resident && !p->have_assignment) { set_error("%s: no assignment set", who); return SONIC_ERR_INVALID_ARG; }
+  if (p->in_flight) { set_error("%s: a submitted proof is still reading the handle's buffers (collect it first)", who); return SONIC_ERR_INVALID_ARG; }
+  return eval_constraints_run(who, p, B, aL, aR, aO, nullptr, out_cs, out_gates);
+  API_CATCH
+}
+
+// the same over a witness source (include/sonic_hip.h, "Witness sources"): assignment b is block b of each vector
+int sonic_prover_eval_constraints_src(sonic_prover_t* p, int64_t B, const sonic_witness_src_t* src, uint8_t* out_cs, int64_t* out_gates) {
+  API_BEGIN_ON(p ? p->device : -1)
+  const char* who = "sonic_prover_eval_constraints_src";
+  if (!p || !out_cs) { set_error("%s: bad argument", who); return SONIC_ERR_INVALID_ARG; }
+  const long n = p->n;
+  if (B < 1 || B > MSM_TABLE_MAX_TERMS / n) { set_error("%s: B = %lld outside [1, 2^26 / n]", who, (long long)B); return SONIC_ERR_INVALID_ARG; }
+  WitnessView v;
+  int rc = witness_view_of(who, src, n, B, &v);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> g(p->mu);
+  if (p->in_flight) { set_error("%s: a submitted proof is still reading the handle's buffers (collect it first)", who); return SONIC_ERR_INVALID_ARG; }
+  rc = witness_on_device_of(who, v, n, B, p->device);
+  if (rc) return rc;
+  WitnessReady ready;
+  ready.record(v);
+  if (ready.ev) HIP_OK(hipStreamWaitEvent(p->st, ready.ev, 0));
+  return eval_constraints_run(who, p, B, nullptr, nullptr, nullptr, &v, out_cs, out_gates);
+  API_CATCH
 }
 
 int sonic_prover_set_constants(sonic_prover_t* p, const uint8_t* cs) {

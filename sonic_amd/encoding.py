@@ -51,6 +51,54 @@ def fr_matrix(rows) -> np.ndarray:
     return fr_array([v for row in rows for v in row])
 
 
+# ---- witness sources (include/sonic_hip.h, "Witness sources") ----
+WIT_FR32, WIT_I64 = 0, 1
+
+
+def _is_torch(x) -> bool:
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+def witness_vector(x, n: int, batch, who: str):
+    """One vector of a witness source -> (kind, pointer, stride in bytes, device index or None for host memory, what to keep alive).
+    x: a torch tensor or a numpy array, uint8 [n, 32] (canonical Fr) or int64 [n] -- with batch = K: [K, n, 32] or [K, n], inner
+    dimensions contiguous, any leading stride that is a whole number of elements -- or, unbatched, a list of ints (fr_array).
+    Everything that does not fit raises ValueError; nothing is copied except a list."""
+    if not _is_torch(x) and not isinstance(x, np.ndarray):
+        if batch is not None:
+            raise ValueError(f"{who}: a batch is a torch tensor or a numpy array [K, n, 32] uint8 or [K, n] int64")
+        x = fr_array(x)
+    torch_like = _is_torch(x)
+    dtype = str(x.dtype).replace("torch.", "")
+    if dtype == "uint8":
+        kind, elem, inner = WIT_FR32, 32, (n, 32)
+    elif dtype == "int64":
+        kind, elem, inner = WIT_I64, 8, (n,)
+    else:
+        raise ValueError(f"{who}: dtype {dtype} is neither uint8 ([n, 32] canonical Fr) nor int64 ([n])")
+    want = inner if batch is None else (batch,) + inner
+    if tuple(x.shape) != want:
+        raise ValueError(f"{who}: shape {tuple(x.shape)}, need {want}")
+    # strides in elements of the dtype (torch) or bytes (numpy) -> bytes
+    item = 1 if kind == WIT_FR32 else 8
+    strides = [s * item for s in x.stride()] if torch_like else list(x.strides)
+    dense = [8] if kind == WIT_I64 else [32, 1]
+    lead = strides[:len(strides) - len(dense)]
+    if any(size > 1 and got != need for size, got, need in zip(inner, strides[len(lead):], dense)):
+        raise ValueError(f"{who}: the inner dimensions must be contiguous")
+    stride = n * elem
+    if batch is not None:
+        stride = lead[0] if batch > 1 else n * elem
+        if stride < n * elem:
+            raise ValueError(f"{who}: the leading stride ({stride} bytes) is below one assignment ({n * elem} bytes)")
+    if torch_like:
+        if x.device.type not in ("cuda", "cpu"):
+            raise ValueError(f"{who}: a tensor on {x.device} is neither on a GPU nor on the CPU")
+        device = x.device.index if x.device.type == "cuda" else None
+        return kind, x.data_ptr(), stride, device, x
+    return kind, x.ctypes.data, stride, None, x
+
+
 # ---- compressed encodings: the host mirror (Python integers) ----
 Z_MALFORMED, Z_OFF_CURVE, Z_OUTSIDE_SUBGROUP = 1, 2, 4          # verdicts: the error bits of the SRS loaders
 

@@ -10,7 +10,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from .encoding import R_MODULUS, fr_array, fr_matrix, fr_to_bytes, g1_from_bytes, g1_to_bytes
+from .encoding import R_MODULUS, fr_array, fr_matrix, fr_to_bytes, g1_from_bytes, g1_to_bytes, witness_vector
 from .srs import SRS
 from .workload import csr_from_dense
 
@@ -96,6 +96,50 @@ class Assignment:            # Bulletproofs.ArithmeticCircuit.Assignment
     aL: list
     aR: list
     aO: list
+
+
+class WitnessBatch:
+    """K assignments as a witness source (include/sonic_hip.h, "Witness sources"), accepted by Prover.eval_constraints, prove_batch and
+    prove_batch_fs in place of a list of Assignment objects: aL, aR and optionally aO as torch tensors or numpy arrays, uint8 [K, n, 32]
+    (canonical Fr) or int64 [K, n] (v < 0 stands for r - |v|), on the handles' GPU or on the CPU, inner dimensions contiguous, any
+    leading stride.  aO = None: the GPU sets aO = aL * aR.  stream: for CUDA tensors, the stream whose work produces them (an int handle,
+    or a torch stream); default: the current stream of their device.  Nothing is copied or converted on the host."""
+
+    def __init__(self, aL, aR, aO=None, stream=None):
+        self.aL, self.aR, self.aO, self.stream = aL, aR, aO, stream
+        self.K = int(aL.shape[0]) if hasattr(aL, "shape") and len(aL.shape) else 0
+
+    def __len__(self) -> int:
+        return self.K
+
+
+def _witness_src(aL, aR, aO, stream, n: int, batch, devices, who: str):
+    """the sonic_witness_src_t of one source, and what keeps its memory alive; every mismatch is a ValueError, before any C call.
+    devices: the GPUs of the handles that will read it"""
+    vecs = [witness_vector(v, n, batch, f"{who}: {name}") for name, v in (("aL", aL), ("aR", aR), ("aO", aO)) if v is not None]
+    if len({v[0] for v in vecs}) != 1:
+        raise ValueError(f"{who}: aL, aR, aO must be of one kind (all uint8 [.., 32] or all int64)")
+    if len({v[3] for v in vecs}) != 1:
+        raise ValueError(f"{who}: aL, aR, aO must lie in one memory (one GPU, or the CPU)")
+    if len({v[2] for v in vecs}) != 1:
+        raise ValueError(f"{who}: aL, aR, aO must have the same leading stride")
+    kind, _, stride, device, _ = vecs[0]
+    if device is not None and any(d != device for d in devices):
+        raise ValueError(f"{who}: the tensors lie on GPU {device}, the handle(s) on {sorted(set(devices))}")
+    handle = None
+    if device is not None:
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(device)
+        if hasattr(stream, "cuda_stream"):
+            if stream.cuda_stream == 0:
+                stream.synchronize()        # (the library takes NULL as "the data is complete": the default stream is waited for here)
+            stream = stream.cuda_stream
+        handle = int(stream) or None
+    elif stream is not None:
+        raise ValueError(f"{who}: stream is for tensors on a GPU")
+    ptrs = [v[1] for v in vecs] + ([None] if aO is None else [])
+    return _lib.WitnessSrc(ptrs[0], ptrs[1], ptrs[2], kind, int(device is not None), stride, handle), [v[4] for v in vecs]
 
 
 @dataclass
@@ -222,6 +266,18 @@ class Prover:
         assert aL.shape[0] == self.n and aR.shape[0] == self.n and aO.shape[0] == self.n
         _lib.check(_lib.lib().sonic_prover_set_assignment(self._h, aL.ctypes.data, aR.ctypes.data, aO.ctypes.data))
 
+    def set_witness(self, aL, aR, aO=None, stream=None) -> None:
+        """the assignment from a witness source (sonic_prover_set_witness): each vector a torch tensor or numpy array, uint8 [n, 32]
+        (canonical Fr) or int64 [n] (v < 0 stands for r - |v|), on this handle's GPU or on the CPU, contiguous -- or a list of ints.
+        aO = None: the GPU sets aO = aL * aR.  A tensor on the GPU is read where it lies, after the work queued on `stream` (default: the
+        current stream of its device).  Same proofs and digests as set_assignment of the same values."""
+        src, _keep = _witness_src(aL, aR, aO, stream, self.n, None, [self.device], "set_witness")
+        _lib.check(_lib.lib().sonic_prover_set_witness(self._h, C.byref(src)))
+
+    @property
+    def device(self) -> int:
+        return _lib.lib().sonic_prover_device(self._h)
+
     def set_constants(self, cs) -> None:
         """the constants of the next statement (sonic_prover_set_constants): the handle's cs overwritten in place -- the assignment, the
         prepared rows, the share mode and a captured proof graph stay.  cs: Q ints, or Q x 32 canonical bytes (passed as they are)"""
@@ -231,8 +287,19 @@ class Prover:
     def eval_constraints(self, assignments=None):
         """the constants the assignments satisfy under this handle's weights, and the multiplication gates they break, on the GPU
         (sonic_prover_eval_constraints): ([cs of assignment b as Q ints], [(bad_count, first_bad or -1)]).  assignments: Assignment
-        objects, or None for the handle's resident assignment (one entry)."""
+        objects, a WitnessBatch (sonic_prover_eval_constraints_src), or None for the handle's resident assignment (one entry)."""
         n, Q = self.n, self.Q
+        if isinstance(assignments, WitnessBatch):
+            w, B = assignments, len(assignments)
+            if B < 1:
+                raise ValueError("eval_constraints: need at least one assignment")
+            src, _keep = _witness_src(w.aL, w.aR, w.aO, w.stream, n, B, [self.device], "eval_constraints")
+            out = np.zeros((B, Q, 32), np.uint8)
+            gates = np.zeros((B, 2), np.int64)
+            _lib.check(_lib.lib().sonic_prover_eval_constraints_src(self._h, B, C.byref(src), out.ctypes.data, gates.ctypes.data))
+            raw = out.tobytes()
+            cs = [[int.from_bytes(raw[32 * (b * Q + q):32 * (b * Q + q) + 32], "little") for q in range(Q)] for b in range(B)]
+            return cs, [(int(c), int(f)) for c, f in gates]
         if assignments is None:
             B, ptrs = 1, (None, None, None)
         else:
@@ -401,8 +468,9 @@ def _constants_bytes(cs, Q: int, who: str) -> bytes:
 def prove_batch(provers, transcripts, assignments=None, constants=None) -> List[bytes]:
     """`mapM prove` over K statements of one circuit, spread over several prover handles (sonic_prove_batch: proof i on handle
     i % len(provers), one host thread per handle, no collective): the throughput mode of BASELINE's "batch of 64 independent proofs
-    streamed over 8 GPUs".  assignments: K Assignment objects, or None to prove every statement with the handles' resident
-    assignment (then only the transcripts differ).  constants: None, or one cs (Q ints or Q x 32 bytes) per proof -- one statement
+    streamed over 8 GPUs".  assignments: K Assignment objects, a WitnessBatch of K assignments (sonic_prove_batch_src: tensors or
+    arrays read where they lie), or None to prove every statement with the handles' resident assignment (then only the transcripts
+    differ).  constants: None, or one cs (Q ints or Q x 32 bytes) per proof -- one statement
     per proof (sonic_prove_batch_statements); afterwards each handle holds the constants of the last proof it ran."""
     provers = list(provers)
     Q, n = provers[0].Q, provers[0].n
@@ -413,6 +481,19 @@ def prove_batch(provers, transcripts, assignments=None, constants=None) -> List[
     out = np.zeros((max(K, 1), psz), np.uint8)
     status = (C.c_int * max(K, 1))()
     aL = aR = aO = None
+    if isinstance(assignments, WitnessBatch):
+        if len(assignments) != K:
+            raise ValueError("prove_batch: one assignment per proof")
+        cs = None
+        if constants is not None:
+            constants = list(constants)
+            if len(constants) != K:
+                raise ValueError("prove_batch: one set of constants per proof")
+            cs = b"".join(_constants_bytes(c, Q, "prove_batch") for c in constants) or bytes(32)
+        w = assignments
+        src, _keep = _witness_src(w.aL, w.aR, w.aO, w.stream, n, K, [p.device for p in provers], "prove_batch") if K else (_lib.WitnessSrc(), None)
+        _lib.check(_lib.lib().sonic_prove_batch_src(_handle_array(provers), len(provers), K, C.byref(src), cs, tr.ctypes.data, out.ctypes.data, status))
+        return [out[i].tobytes() for i in range(K)]
     if assignments is not None:
         assert len(assignments) == K
         aL = np.ascontiguousarray(np.stack([fr_array(a.aL) for a in assignments]))
@@ -435,7 +516,8 @@ def prove_batch_fs(provers, digests, seeds, assignments=None, constants=None):
     """K Fiat-Shamir proofs of one circuit spread over several prover handles (sonic_prove_batch_fs: proof i on handle i % len(provers), one
     host thread per handle walking the six passes): [(proof bytes, transcript values), ...].  digests, seeds: one circuit digest and one
     blinder seed (32 bytes each) per proof -- with per-proof constants, digests[i] = fs_circuit_digest_resume(midstate, constants[i]).
-    assignments: K Assignment objects, or None (the handles' resident assignments); constants: one cs per proof, or None."""
+    assignments: K Assignment objects, a WitnessBatch (sonic_prove_batch_fs_src), or None (the handles' resident assignments);
+    constants: one cs per proof, or None."""
     provers = list(provers)
     Q, n = provers[0].Q, provers[0].n
     digests, seeds = [bytes(d) for d in digests], [bytes(s) for s in seeds]
@@ -447,7 +529,13 @@ def prove_batch_fs(provers, digests, seeds, assignments=None, constants=None):
     tr = np.zeros((max(K, 1), tl, 32), np.uint8)
     status = (C.c_int * max(K, 1))()
     aL = aR = aO = None
-    if assignments is not None:
+    wsrc = None
+    if isinstance(assignments, WitnessBatch):
+        if len(assignments) != K:
+            raise ValueError("prove_batch_fs: one assignment per proof")
+        w = assignments
+        wsrc, _keep = _witness_src(w.aL, w.aR, w.aO, w.stream, n, K, [p.device for p in provers], "prove_batch_fs") if K else (_lib.WitnessSrc(), None)
+    elif assignments is not None:
         if len(assignments) != K:
             raise ValueError("prove_batch_fs: one assignment per proof")
         aL, aR, aO = (np.ascontiguousarray(np.stack([fr_array(getattr(a, k)) for a in assignments])) for k in ("aL", "aR", "aO"))
@@ -460,8 +548,12 @@ def prove_batch_fs(provers, digests, seeds, assignments=None, constants=None):
             raise ValueError("prove_batch_fs: one set of constants per proof")
         cs = b"".join(_constants_bytes(c, Q, "prove_batch_fs") for c in constants) or bytes(32)
     ptr = lambda a: None if a is None else a.ctypes.data       # noqa: E731
-    _lib.check(_lib.lib().sonic_prove_batch_fs(_handle_array(provers), len(provers), K, ptr(aL), ptr(aR), ptr(aO), cs, b"".join(digests) or bytes(32),
-                                               b"".join(seeds) or bytes(32), out.ctypes.data, tr.ctypes.data, status))
+    if wsrc is not None:
+        _lib.check(_lib.lib().sonic_prove_batch_fs_src(_handle_array(provers), len(provers), K, C.byref(wsrc), cs, b"".join(digests) or bytes(32),
+                                                       b"".join(seeds) or bytes(32), out.ctypes.data, tr.ctypes.data, status))
+    else:
+        _lib.check(_lib.lib().sonic_prove_batch_fs(_handle_array(provers), len(provers), K, ptr(aL), ptr(aR), ptr(aO), cs, b"".join(digests) or bytes(32),
+                                                   b"".join(seeds) or bytes(32), out.ctypes.data, tr.ctypes.data, status))
     raw_tr = tr.tobytes()
     return [(out[i].tobytes(), [int.from_bytes(raw_tr[32 * (i * tl + k):32 * (i * tl + k) + 32], "little") for k in range(tl)]) for i in range(K)]
 
