@@ -176,6 +176,7 @@ HD G1XYZZ g1_add_affine_walk(const G1Affine& first, const G1Affine& q, bool firs
 }
 
 // p + q, both XYZZ (add-2008-s): 12M + 2S
+// (msm.hip's LdsPoint::add is this formula once more, with p's coordinates fetched from LDS where they are used: change both together)
 HD G1XYZZ g1_add(const G1XYZZ& p, const G1XYZZ& q) {
   if (q.is_inf()) return p;
   if (p.is_inf()) return q;

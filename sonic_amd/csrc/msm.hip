@@ -16,9 +16,10 @@
 //                      is all ones, test/Test/Reference.hs:143-145) are only recorded here; their entries,
 //                      end to end, are cut into equal stretches, one per workgroup (k_heavy_accum, k_heavy_finish)
 //   5. k_bucket_segments / k_group_sum / k_window_sum   sum_b b*B_b per bucket set by running sums over K-bucket
-//                      segments, then LDS trees
+//                      segments, then LDS trees; over shared bucket sets the segments' runs go to the
+//                      butterfly (k_bucket_tree_*) instead of being multiplied by their weights
 //   6. host tail       Horner over the W window sums + normalisation to the canonical affine
-//                      bytes (msm_finish_host): O(W) sequential work, deferred by the caller
+//                      bytes (msm_finish_host, msm_slot.hpp): O(W) sequential work, deferred by the caller
 //
 // msm_enqueue_batch runs k MSMs that share a plan as ONE such chain (job j = bucket set j): see msm.hpp.
 //
@@ -141,6 +142,8 @@ MsmPlan msm_plan_tables(long n, int c, int W, long table_stride, bool endo) {
   return p;
 }
 
+static size_t segres_runs_offset(size_t sets, int nseg) { return sets * nseg + sets * (nseg / 256 + 1) + 2; }
+
 void MsmWorkspace::reserve(long n, const MsmPlan& pl, int k) {
   const size_t sets = (size_t)k * pl.Wb;
   size_t M = sets * pl.NB;
@@ -151,7 +154,8 @@ void MsmWorkspace::reserve(long n, const MsmPlan& pl, int k) {
   digits.ensure(NW * 8);
   entries.ensure(NW * 4);
   buckets.ensure(M * sizeof(G1XYZZ));
-  segres.ensure((sets * pl.nseg + sets * (pl.nseg / 256 + 1) + 2) * sizeof(G1XYZZ));
+  // the segments' totals, their 256-way group sums and (two-level form) their runs
+  segres.ensure((segres_runs_offset(sets, pl.nseg) + (pl.two_level && pl.Wb == 1 ? sets * pl.nseg : 0)) * sizeof(G1XYZZ));
   scan_tmp.ensure((part_hn / 2048 + 4) * 4);
   order.ensure((M + 1) * 4);
   size_t max_heavy = NW / pl.heavy_threshold + 1;
@@ -795,12 +799,18 @@ __global__ __launch_bounds__(64, 2) void k_heavy_finish(const HeavyMeta* hm, con
 }
 
 // ---- bucket reduction: sum_b (b+1) * B_b per window -----------------------------------------
-// sg_base: the set's first segment is segment sg_base of a longer bucket sequence (one rank's bucket range of an MSM whose buckets are
-// sharded across ranks, msm_reduce_slices_enqueue): bucket j of segment sg weighs (sg_base + sg) K + j + 1
+// One thread per segment of K buckets: run = sum_j B[j] and tot = sum_j (j + 1) B[j] by running sums, 2 K additions.  Segment sg of a
+// set still owes sg K run_sg, and there are two forms of paying it:
+//   RUNS (shared bucket sets, Wb == 1): the thread writes both points.  sum_sg sg run_sg over the nseg runs of a set is a bucket
+//     reduction of its own, with weights that start at 0: the bit-sum butterfly takes it (msm_enqueue_batch), 2 additions per segment,
+//     and the factor K is left to the host (slot form 3).  2 + 2 / K additions per bucket in all.
+//   otherwise (a bucket set per window: the W window sums fill the slot): the thread multiplies, tot += (sg K) run_sg by a
+//     double-and-add -- ~19 doublings and ~10 additions per segment at K = 64, nseg = 8192, 15 % of the kernel there.
 //
 // Registers: two XYZZ operands, the result and the temporaries of a full addition around the product routine's own 75 registers
 // are ~320 VGPRs when both running sums live in registers: one wave per SIMD.  `tot` is touched once per bucket, so it lives in
 // LDS (48 words per thread, word-major: conflict-free) while `run` takes the bucket in; the kernel then fits two waves per SIMD.
+// (LdsPoint::add below is g1_add, g1.hpp, written out with the left operand in LDS: the two must change together.)
 #ifndef SONIC_SEGMENTS_LDS_TOT
 #define SONIC_SEGMENTS_LDS_TOT 1
 #endif
@@ -818,25 +828,60 @@ struct LdsPoint {
     for (int k = 0; k < 48; k++) w[k] = base[k * 256];
     return p;
   }
+  // coordinate i (x, y, zz, zzz) alone
+  __device__ __forceinline__ Fq coord(int i) const {
+    Fq f;
+#pragma unroll
+    for (int k = 0; k < 12; k++) f.l[k] = base[(12 * i + k) * 256];
+    return f;
+  }
+  __device__ __forceinline__ void set_coord(int i, const Fq& f) const {
+#pragma unroll
+    for (int k = 0; k < 12; k++) base[(12 * i + k) * 256] = f.l[k];
+  }
+  // *this += q, g1_add with the left operand's coordinates fetched where the formula uses them and the sum's stored as they come out:
+  // beside q and the temporaries only one coordinate of the LDS operand is live at a time (whole, the addition spilled)
+  __device__ __forceinline__ void add(const G1XYZZ& q) const {
+    if (q.is_inf()) return;
+    const Fq pzz = coord(2);
+    if (pzz.is_zero_strict()) { store(q); return; }
+    const Fq U1 = fp_mul(coord(0), q.zz);
+    const Fq U2 = fp_mul(q.x, pzz);
+    const Fq S1 = fp_mul(coord(1), q.zzz);
+    const Fq S2 = fp_mul(q.y, coord(3));
+    const Fq Pp = fp_sub(U2, U1);
+    const Fq R = fp_sub(S2, S1);
+    if (Pp.is_zero()) {
+      store(R.is_zero() ? g1_dbl(load()) : G1XYZZ::inf());
+      return;
+    }
+    const Fq PP = fp_sqr(Pp);
+    const Fq PPP = fp_mul(Pp, PP);
+    const Fq Qv = fp_mul(U1, PP);
+    const Fq x = fp_sub(fp_sub(fp_sqr(R), PPP), fp_dbl(Qv));
+    set_coord(0, x);
+    set_coord(1, fp_sub(fp_mul(R, fp_sub(Qv, x)), fp_mul(S1, PPP)));
+    set_coord(2, fp_mul(fp_mul(coord(2), q.zz), PP));
+    set_coord(3, fp_mul(fp_mul(coord(3), q.zzz), PPP));
+  }
 };
-__global__ __launch_bounds__(256, SONIC_SEGMENTS_LDS_TOT ? 2 : 1) void k_bucket_segments(const G1XYZZ* __restrict__ buckets, int W, int NB, int K, int nseg, int sg_base,
-                                                        G1XYZZ* __restrict__ segres) {
+template <bool RUNS>
+__global__ __launch_bounds__(256, SONIC_SEGMENTS_LDS_TOT ? 2 : 1) void k_bucket_segments(const G1XYZZ* __restrict__ buckets, int W, int NB, int K, int nseg,
+                                                        G1XYZZ* __restrict__ segres, G1XYZZ* __restrict__ runs) {
 #if SONIC_SEGMENTS_LDS_TOT
   __shared__ uint32_t tot_sh[48 * 256];
   const LdsPoint tl{tot_sh + threadIdx.x};
 #endif
   int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= W * nseg) return;
-  const int w = t / nseg, sl = t % nseg;
-  const G1XYZZ* B = buckets + (size_t)w * NB + (size_t)sl * K;
-  const int sg = sg_base + sl;
-  const int k0 = sg * K;
+  const int w = t / nseg, sg = t % nseg;
+  const G1XYZZ* B = buckets + (size_t)w * NB + (size_t)sg * K;
   G1XYZZ run = G1XYZZ::inf();
 #if SONIC_SEGMENTS_LDS_TOT
   tl.store(G1XYZZ::inf());
   for (int j = K - 1; j >= 0; j--) {
     run = g1_add(run, B[j]);
-    tl.store(g1_add(tl.load(), run));          // ends as sum_j (j+1) B[j]
+    tl.add(run);                               // ends as sum_j (j+1) B[j]
   }
 #else
   G1XYZZ tot = G1XYZZ::inf();
@@ -845,9 +890,19 @@ __global__ __launch_bounds__(256, SONIC_SEGMENTS_LDS_TOT ? 2 : 1) void k_bucket_
     tot = g1_add(tot, run);          // ends as sum_j (j+1) B[j]
   }
 #endif
+  if (RUNS) {
+    runs[t] = run;
+#if SONIC_SEGMENTS_LDS_TOT
+    segres[t] = tl.load();
+#else
+    segres[t] = tot;
+#endif
+    return;
+  }
+  const int k0 = sg * K;
   G1XYZZ acc = G1XYZZ::inf();
   bool have_multiple = false;
-  if (nseg % 64 == 0 && sg_base % 64 == 0) {
+  if (nseg % 64 == 0) {
     // k0 * run with k0 = sg * K: the 64 lanes of a wave hold consecutive sg, so the bits of sg above the lane bits are
     // wave-uniform and their conditional additions are uniform branches; only the six lane bits pay for both paths
     // (a per-lane double-and-add executes an addition at every bit as soon as any lane needs one).
@@ -873,8 +928,10 @@ __global__ __launch_bounds__(256, SONIC_SEGMENTS_LDS_TOT ? 2 : 1) void k_bucket_
   segres[t] = tot;
 }
 
-// block = bucket set (job * Wb + window); the sum lands in that job's slot
-__global__ __launch_bounds__(256, 2) void k_window_sum(const G1XYZZ* __restrict__ segres, int W, int c, int nseg, const MsmBatchDev batch) {
+// block = bucket set (job * Wb + window); the sum lands in that job's slot.  runs_L > 0 (W == 1, after k_bucket_segments<true>): the sum
+// is the last point of slot form 3, win[runs_L], beside the runs_L bit sums of the set's runs that the butterfly has written; this
+// kernel is the later of the two in stream order and writes the slot's header (pad0 = K: the host multiplies the bit sums by it)
+__global__ __launch_bounds__(256, 2) void k_window_sum(const G1XYZZ* __restrict__ segres, int W, int c, int nseg, int runs_L, int K, const MsmBatchDev batch) {
   __shared__ G1XYZZ sh[256];
   const int w = blockIdx.x % W;
   MsmSlot* slot = batch.slot[blockIdx.x / W];
@@ -890,6 +947,7 @@ __global__ __launch_bounds__(256, 2) void k_window_sum(const G1XYZZ* __restrict_
   if (threadIdx.x == 0) {
     G1XYZZ r = sh[0];                 // leaves the device for the host tail: representatives below q (field.hpp, lazy range)
     r.x = fp_canonical(r.x); r.y = fp_canonical(r.y); r.zz = fp_canonical(r.zz); r.zzz = fp_canonical(r.zzz);
+    if (runs_L > 0) { slot->win[runs_L] = r; slot->W = runs_L; slot->c = 1; slot->pad0 = K; slot->pad1 = 3; return; }
     slot->win[w] = r;
     if (w == 0) { slot->W = W; slot->c = c; slot->pad0 = 0; slot->pad1 = 0; }
   }
@@ -991,7 +1049,9 @@ __global__ __launch_bounds__(256, 2) void k_bucket_tree_block(G1XYZZ* __restrict
 
 // later launches: levels m_lo .. m_hi over spans of 2^span_log buckets, one workgroup per span.  final_L > 0 (then span_log == final_L:
 // one workgroup per bucket set): the set's sums go to its job's slot -- win[j] = bs_j (j < L), win[L] = total, W = L, c = 1,
-// pad0 = the total's weight (1, or base + 1 for a bucket range that starts at `base`), pad1 = 1 marks the form (msm_finish_host)
+// pad0 = the total's weight (1, or base + 1 for a bucket range that starts at `base`), pad1 = 1 marks the form (msm_finish_host).
+// tot_mul == 0 (the runs of k_bucket_segments<true>, whose weights start at 0): only the L bit sums are written -- win[L] and the
+// header of that slot belong to k_window_sum
 template <int THREADS>
 __global__ __launch_bounds__(THREADS, THREADS == 256 ? 2 : 1) void k_bucket_tree_levels(G1XYZZ* __restrict__ Z, int span_log, int m_lo, int m_hi, int final_L,
                                                                uint32_t tot_mul, int quads, const MsmBatchDev batch) {
@@ -1004,12 +1064,12 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 2 : 1) void k_bucket_tree
     __syncthreads();
     MsmSlot* slot = batch.slot[blockIdx.x];
     const int off = batch.slot_off[blockIdx.x];
-    if ((int)threadIdx.x <= final_L) {
+    if ((int)threadIdx.x < final_L + (tot_mul != 0u ? 1 : 0)) {
       G1XYZZ r = Z[s0 + ((int)threadIdx.x == final_L ? 0 : (size_t)1 << threadIdx.x)];
       r.x = fp_canonical(r.x); r.y = fp_canonical(r.y); r.zz = fp_canonical(r.zz); r.zzz = fp_canonical(r.zzz);   // leaves the device (lazy range)
       slot->win[off + threadIdx.x] = r;
     }
-    if (threadIdx.x == 0 && off == 0) { slot->W = final_L; slot->c = 1; slot->pad0 = (int)tot_mul; slot->pad1 = batch.slot_form; }
+    if (threadIdx.x == 0 && off == 0 && tot_mul != 0u) { slot->W = final_L; slot->c = 1; slot->pad0 = (int)tot_mul; slot->pad1 = batch.slot_form; }
   }
 }
 
@@ -1058,42 +1118,7 @@ static void bucket_tree_enqueue(hipStream_t st, G1XYZZ* Z, int sets, int L, uint
   LAUNCH(k_bucket_tree_levels<256>, (uint32_t)sets, 256, 0, st, Z, L, done + 1, L, L, tot_mul, quads, batch);
 }
 
-// ---- tail (host) -----------------------------------------------------------------------------
-// What is left of an MSM after the bulk kernels is W <= 64 window sums: Horner over the windows
-// (255 dependent doublings) and one Fq inversion for the canonical affine form.  That is ~2600
-// strictly sequential Fq products -- ~10 ms on one GPU lane (measured), ~0.5 ms on a host core --
-// so the host layer finishes it, with the same limb code (g1.hpp compiles for both sides).
-G1XYZZ msm_finish_host(const MsmSlot& s) {
-  // slots usually sit in pinned host memory, which the CPU reads uncached: limb-by-limb arithmetic straight out of it cost
-  // ~20 us per window sum (0.3 ms per proof), so every window sum is copied out once before it is used
-  const int W = s.W, c = s.c;
-  G1XYZZ acc = G1XYZZ::inf();
-  if (s.pad1 == 1 || s.pad1 == 2) {
-    // bit-sum form (k_bucket_tree_levels): sum_j 2^j win[off + j] + pad0 * win[off + W]
-    auto bitsum = [&](int off) {
-      G1XYZZ a = G1XYZZ::inf();
-      for (int w = W - 1; w >= 0; w--) {
-        G1XYZZ win;
-        memcpy(&win, &s.win[off + w], sizeof win);
-        a = g1_add(g1_dbl(a), win);
-      }
-      G1XYZZ tot;
-      memcpy(&tot, &s.win[off + W], sizeof tot);
-      const uint32_t mul = (uint32_t)s.pad0;
-      return g1_add(a, mul == 1 ? tot : g1_mul_small(tot, mul));
-    };
-    if (s.pad1 == 1) return bitsum(0);
-    return g1_add(bitsum(0), g1_endo(bitsum(MSM_ENDO_SLOT_OFFSET)));         // endomorphism pair: sum(s1 P) + phi(sum(s2 P))
-  }
-  for (int w = W - 1; w >= 0; w--) {
-    G1XYZZ win;
-    memcpy(&win, &s.win[w], sizeof win);
-    if (w == W - 1) { acc = win; continue; }
-    for (int j = 0; j < c; j++) acc = g1_dbl(acc);
-    acc = g1_add(acc, win);
-  }
-  return acc;
-}
+// (the host tail -- Horner over what the kernels above leave in a slot -- is msm_finish_host, msm_slot.hpp)
 // ---------------------------------------------------------------------------------------------
 bool msm_can_batch(const MsmPlan& pl) { return pl.Wb == 1 && pl.NB >= (1 << PART_LOW_BITS); }
 
@@ -1247,16 +1272,29 @@ void msm_enqueue_batch(hipStream_t st, MsmWorkspace& ws, const MsmPlan& pl, cons
     bucket_tree_enqueue(st, ws.buckets.as<G1XYZZ>(), sets, L, 1u, batch);
     return;
   }
-  LAUNCH(k_bucket_segments, ceil_div((long)sets * pl.nseg, 256), 256, 0, st, (const G1XYZZ*)ws.buckets.as<G1XYZZ>(), sets,
-         pl.NB, pl.K, pl.nseg, 0, ws.segres.as<G1XYZZ>());
+  // Shared bucket sets of a plan that asks for it (MsmPlan::two_level): the segments leave their runs beside their local totals and sum_sg sg run_sg is the butterfly's (weights from
+  // 0: no total), on the runs of all sets of the batch at once -- sets x nseg points: a group of prove() has at most four jobs of
+  // 16384 segments, so its latency form.  The totals go through the sums below as before.  (nseg < 4: nothing for a tree; the segments multiply as they do for
+  // per-window sets.)
+  int runs_L = 0;
+  if (pl.two_level && pl.Wb == 1 && pl.nseg >= 4) while ((1 << runs_L) < pl.nseg) runs_L++;
+  if (runs_L > 0) {
+    G1XYZZ* runs = ws.segres.as<G1XYZZ>() + segres_runs_offset(sets, pl.nseg);
+    LAUNCH(k_bucket_segments<true>, ceil_div((long)sets * pl.nseg, 256), 256, 0, st, (const G1XYZZ*)ws.buckets.as<G1XYZZ>(), sets,
+           pl.NB, pl.K, pl.nseg, ws.segres.as<G1XYZZ>(), runs);
+    bucket_tree_enqueue(st, runs, sets, runs_L, 0u, batch);
+  } else {
+    LAUNCH(k_bucket_segments<false>, ceil_div((long)sets * pl.nseg, 256), 256, 0, st, (const G1XYZZ*)ws.buckets.as<G1XYZZ>(), sets,
+           pl.NB, pl.K, pl.nseg, ws.segres.as<G1XYZZ>(), (G1XYZZ*)nullptr);
+  }
   if (pl.nseg > 4096) {
     // sets with tens of thousands of segments: 256-way groups first (nseg is a power of two), then one tree per set
     const int group = 256, ngroups = pl.nseg / group;
     G1XYZZ* part = ws.segres.as<G1XYZZ>() + (size_t)sets * pl.nseg;
     LAUNCH(k_group_sum, sets * ngroups, 256, 0, st, (const G1XYZZ*)ws.segres.as<G1XYZZ>(), (long)sets * pl.nseg, group, part);
-    LAUNCH(k_window_sum, sets, 256, 0, st, (const G1XYZZ*)part, pl.Wb, pl.c, ngroups, batch);
+    LAUNCH(k_window_sum, sets, 256, 0, st, (const G1XYZZ*)part, pl.Wb, pl.c, ngroups, runs_L, pl.K, batch);
   } else {
-    LAUNCH(k_window_sum, sets, 256, 0, st, (const G1XYZZ*)ws.segres.as<G1XYZZ>(), pl.Wb, pl.c, pl.nseg, batch);
+    LAUNCH(k_window_sum, sets, 256, 0, st, (const G1XYZZ*)ws.segres.as<G1XYZZ>(), pl.Wb, pl.c, pl.nseg, runs_L, pl.K, batch);
   }
 }
 

@@ -3,6 +3,7 @@
 #include "common.hpp"
 #include "g1.hpp"
 #include "g1_host.hpp"
+#include "msm_slot.hpp"     // MsmSlot, MSM_MAX_WINDOWS, MSM_ENDO_SLOT_OFFSET, msm_finish_host
 
 namespace sonic {
 
@@ -34,6 +35,10 @@ struct MsmPlan {
   // exposed -- a stand-alone MSM, the last group of a proof, a rank's few pieces of a shared proof -- the segments where it hides under
   // other groups' accumulation (profiles/r04_bucket_tree.txt).
   bool tree = true;
+  // (tree == false, shared bucket sets) the running sums in their two-level form: a segment writes its run beside its local total and
+  // the runs go to the butterfly, instead of every segment multiplying its run by its weight (msm.hip, k_bucket_segments<true>; slot
+  // form 3).  Set by prove() for the batched groups it was measured on (prove.hip, prove_two_level); off everywhere else.
+  bool two_level = false;
   // endomorphism plan (endo.hpp): the tables hold W windows over 130 bits; every job runs as TWO device jobs over the same points,
   // with the halves s1, s2 of its scalars, and the host adds phi(second sum) to the first.  Tree reduction only.
   bool endo = false;
@@ -47,25 +52,15 @@ MsmPlan msm_plan(long n, bool fold = true);
 MsmPlan msm_plan_tables(long n, int c, int W, long table_stride, bool endo = false);
 // Trade latency for work in the bucket running sums: K buckets per segment.  A standalone MSM wants the shortest
 // dependent chain (K = 8); inside prove() the reduction of one MSM hides under the accumulation of others, so fewer,
-// longer segments (fewer small scalar multiplications) cost less MAD issue overall.
+// longer segments cost less MAD issue overall: 2 + 2 / K additions per bucket over shared bucket sets, whose segments hand their runs
+// to the butterfly (MsmPlan::two_level; prove.hip picks K = 32 there), 2 + a ~30-step multiple per segment over per-window sets.
 void msm_plan_set_segment(MsmPlan& p, int K);
 
-constexpr int MSM_MAX_WINDOWS = 64;
 // sorted entry = term index | window << 26 | sign << 31 over window tables (index < 2^26, window < 32), term index | sign << 31
 // otherwise: msm_enqueue_batch refuses anything else with SONIC_ERR_INVALID_ARG (srs_msm_plan never plans it)
 constexpr long MSM_TABLE_MAX_TERMS = 1L << 26;
 constexpr int MSM_TABLE_MAX_WINDOWS = 32;
 constexpr long MSM_MAX_TERMS = 1L << 31;
-
-// Per-MSM hand-off between the bulk kernels and the (deferred, batched) tail: the per-window sums.
-// Two forms: W window sums of a c-bit Horner walk (per-window bucket sets; pad1 == 0), or -- shared bucket sets reduced by the
-// bit-sum butterfly, pad1 == 1 -- win[j] = sum of the buckets whose index has bit j set (j < W), win[W] = the sum of all buckets
-// and pad0 = its weight: the MSM is sum_j 2^j win[j] + pad0 win[W].  pad1 == 2: an endomorphism pair -- the same form twice, the
-// second at win[32 ..], result = first + phi(second).  msm_finish_host folds all of them.
-struct MsmSlot {
-  int W, c, pad0, pad1;
-  G1XYZZ win[MSM_MAX_WINDOWS];
-};
 
 struct MsmWorkspace {
   DevBuf count, off, digits, entries, buckets, segres, scan_tmp, order, heavy_meta, heavy_partial, endo_scalars;
@@ -83,7 +78,6 @@ void msm_enqueue(hipStream_t st, MsmWorkspace& ws, const MsmPlan& pl, PointArray
 // latency-bound phases (running sums, trees, sort passes) run k times wider instead of k times in a row.  The jobs may
 // differ in size, points and scalars; they share the plan (c, W, table stride).  k <= MSM_MAX_JOBS.
 constexpr int MSM_MAX_JOBS = 16;     // (16 since round 6: the 7 + 4Q MSMs of a Q = 2 proof as ONE chain, prove.hip `fused`)
-constexpr int MSM_ENDO_SLOT_OFFSET = 32;      // where the second half of an endomorphism pair sits in MsmSlot::win
 // (the jobs of a batch share the byte stride between points; table_stride != 0: this job's window tables are that many points apart instead
 // of the plan's -- the SRS's symmetric-sum tables hold d + 1 points per window where the bases hold 2d + 1)
 struct MsmJob { PointArray points; const Fr* scalars; long n; MsmSlot* slot; long table_stride = 0; };
@@ -97,8 +91,6 @@ void msm_enqueue_batch(hipStream_t st, MsmWorkspace& ws, const MsmPlan& pl, cons
 constexpr long MSM_SLICE_QUANTUM = 16384;     // = 2048 segments: whole 256-segment groups and wave-uniform segment bits
 void msm_reduce_slices_enqueue(hipStream_t st, MsmWorkspace& ws, const G1XYZZ* d_slices, int k, long len, long base, int c, MsmSlot* d_slot);
 
-// Host tail: Horner over the slot's window sums -> un-normalised XYZZ sum.
-G1XYZZ msm_finish_host(const MsmSlot& s);
 // canonical 96-byte encodings on the host: g1_host.hpp
 int msm_window_override();
 void msm_set_window_override(int c);

@@ -16,10 +16,33 @@
 
 namespace sonic {
 
-static int prove_segment(const MsmPlan& pl, int k, bool last) {
+// How a batched group over large bucket sets (>= 2^18 buckets) that is not the proof's last reduces them by running sums.
+// Until round 7 every K-bucket segment multiplied its run by its weight, a ~30-step double-and-add, and K = 64 was the shortest segment
+// whose multiple was bearable (15 % of the kernel).  In the two-level form (msm.hip, k_bucket_segments<true>) a segment costs 2 K
+// additions and its run 2 more in a small butterfly -- 2 + 2 / K per bucket -- so a short segment is cheap, and it halves the chain a
+// wave walks before its slot is free for the accumulation beside it.  ms per streamed proof at n = 2^18, one box, alternating
+// (profiles/r07_two_level_reduce.txt, block C): before 34.87; the multiple at K = 32 33.86; two-level at K = 64 / 32  34.84 / 33.46
+// (block A / B, two-level: K = 128 38.1, K = 16 34.4).  So: two-level with K = 32 -- for jobs of up to 2^21 terms.  A single n = 2^20
+// proof (jobs of up to 7n terms, four times the entries per bucket) measured 1 % SLOWER with either half of that change, so larger
+// groups keep the multiple and K = 64, the path they had.  Only two sizes are measured: the bound sits between them.
+// SONIC_PROVE_SEGMENT=K (8..1024) and SONIC_PROVE_TWO_LEVEL=0/1 override the two choices: the A/B knobs behind those tables, and how the
+// tests reach both forms and the sums over few segments at a small size.  They are read per group and not once per process, because
+// the tests switch them inside one process; that is two getenv calls per group, five groups per proof.
+constexpr long PROVE_TWO_LEVEL_MAX_TERMS = 1L << 21;
+static bool prove_two_level(const MsmPlan& pl, int k, bool last, long nmax) {
+  if (last || k <= 1 || pl.NB < (1 << 18)) return false;
+  const char* e = getenv("SONIC_PROVE_TWO_LEVEL");
+  if (e && (e[0] == '0' || e[0] == '1') && !e[1]) return e[0] == '1';
+  return nmax <= PROVE_TWO_LEVEL_MAX_TERMS;
+}
+static int prove_segment(const MsmPlan& pl, int k, bool last, bool two_level) {
   const bool big = pl.NB >= (1 << 18);
   if (last) return big ? 16 : 4;
-  return k > 1 ? (big ? 64 : 16) : (big ? 8 : 4);
+  if (k <= 1) return big ? 8 : 4;
+  if (!big) return 16;
+  const char* e = getenv("SONIC_PROVE_SEGMENT");
+  const int v = e ? atoi(e) : 0;
+  return v >= 8 && v <= 1024 ? v : (two_level ? 32 : 64);
 }
 
 // commitPoly (CommitmentScheme.hs:20-33): F = sum_e c_e * A[e + d - max], A = alpha basis.
@@ -49,8 +72,10 @@ void run_jobs(hipStream_t st, const sonic_srs* srs, MsmWorkspace& ws, const MsmJ
   MsmPlan pl = srs_msm_plan(srs, nmax);
   // Which groups reduce their buckets by the bit-sum butterfly: the group that finishes last, and every group when the caller knows
   // that little else runs beside it (`exposed`: a rank's share of a proof split over many GPUs); the others keep the running sums
-  // over K-bucket segments.  Both forms cost the same instructions per bucket set (1.8e8 wave-instructions at 2^19 buckets:
-  // profiles/r04_valu_budget.txt); the butterfly is one addition deep instead of ~2K + 30, the segments touch every bucket once.
+  // over K-bucket segments.  The butterfly costs 2 additions per bucket and is one addition deep per level; the segments touch every
+  // bucket once, are 2K additions deep and cost 2 + 2 / K in the two-level form (a run and a local total per segment, the runs reduced
+  // by a small butterfly of their own: prove_two_level above) or 2 + a ~30-step multiple per segment, 2.35 at K = 64, where every
+  // segment multiplies its run (larger groups, and the MSMs that run alone); profiles/r07_two_level_reduce.txt.
   // Butterfly in EVERY group, measured again in round 5 (same box, alternating, ms per proof): streamed 33.76 / 33.91 against
   // 33.67 / 33.76, one at a time 34.75 / 34.98 against 34.21 / 34.50, n = 2^20 127.6 / 127.5 against 126.6 / 127.2 -- not adopted.
   // Small bucket sets (<= 2^17, round 6): always the butterfly.  Their running sums are pure latency -- K = 16 segments and the 256-lane
@@ -59,14 +84,15 @@ void run_jobs(hipStream_t st, const sonic_srs* srs, MsmWorkspace& ws, const MsmJ
   const bool tree = last || exposed || pl.NB <= (1 << 17);
   if (k > 1 && msm_can_batch(pl)) {
     // the group that finishes last reduces with nothing left to hide under: shortest chain instead of least work
-    msm_plan_set_segment(pl, prove_segment(pl, k, last));
+    pl.two_level = prove_two_level(pl, k, last, nmax);
+    msm_plan_set_segment(pl, prove_segment(pl, k, last, pl.two_level));
     pl.tree = tree;
     msm_enqueue_batch(st, ws, pl, jobs, k, true);
     return;
   }
   for (int j = 0; j < k; j++) {
     MsmPlan p1 = srs_msm_plan(srs, jobs[j].n);
-    msm_plan_set_segment(p1, prove_segment(p1, 1, false));
+    msm_plan_set_segment(p1, prove_segment(p1, 1, false, false));
     p1.tree = tree;
     msm_enqueue_batch(st, ws, p1, &jobs[j], 1, true);
   }
@@ -963,8 +989,13 @@ static bool slots_folded(const MsmSlot* hs, long K) {
   for (long i = 0; i < K; i++) if (hs[i].W > 1 && hs[i].pad1 == 0) return false;
   return true;
 }
+// (round 7) a slot of the two-level running sums (pad1 == 3) is a ~14-step walk over bit sums, 35 us: the 13 of a large proof were
+// 0.45 ms on one thread, which only a stream of proofs hides.  From eight such slots on they are folded on up to four threads (a
+// thread costs about as much to start as one slot to fold).  Fewer, and the butterfly's own slots, stay on the caller's thread as before.
 static void finish_slots_host(const MsmSlot* hs, long K, G1XYZZ* out, int max_threads) {
-  const int nt = slots_folded(hs, K) ? 1 : (int)std::min<long>(K, max_threads);
+  long two_level = 0;
+  for (long i = 0; i < K; i++) two_level += hs[i].pad1 == 3;
+  const int nt = !slots_folded(hs, K) ? (int)std::min<long>(K, max_threads) : (two_level >= 8 ? std::min(4, max_threads) : 1);
   ThreadGroup th;
   for (int w = 1; w < nt; w++) th.emplace_back([=] { for (long i = w; i < K; i += nt) out[i] = msm_finish_host(hs[i]); });
   for (long i = 0; i < K; i += nt) out[i] = msm_finish_host(hs[i]);
