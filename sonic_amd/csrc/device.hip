@@ -44,9 +44,6 @@ static thread_local DeviceCtx* t_ctx = nullptr;
 
 static int device_count_locked() {
   if (g_device_count >= 0) return g_device_count;
-  // one hardware queue per prover stream (the runtime's default of 4 makes streams queue behind each other); only effective when
-  // this is the process's first HIP call, harmless otherwise
-  setenv("GPU_MAX_HW_QUEUES", "8", 0);
   int n = 0;
   hipError_t e = hipGetDeviceCount(&n);
   if (e != hipSuccess || n <= 0) {
@@ -117,6 +114,18 @@ const NttTables& device_ntt_tables(int log2n) {
     t = nt.release();
   }
   return *t;
+}
+int device_prover_streams() {
+  DeviceCtx& c = current_ctx();
+  std::lock_guard<std::mutex> g(c.pool_mu);
+  if (c.prover_streams < 0) {
+    // (the number of queues is READ: the variable counts only when it is set before the process's first HIP call -- stream_pool.hpp)
+    const int n = pool_size_of_env(getenv("GPU_MAX_HW_QUEUES"), getenv("SONIC_STREAM_POOL"));
+    if (n > 0) c.prover_stream[0] = c.stream;
+    for (int i = 1; i < n; i++) HIP_OK(hipStreamCreateWithFlags(&c.prover_stream[i], hipStreamNonBlocking));
+    c.prover_streams = n;
+  }
+  return c.prover_streams;
 }
 DeviceCtx& current_ctx() {
   if (!t_ctx) { set_error("internal: no device scope on this thread"); throw HipFail{SONIC_ERR_HIP}; }

@@ -5,6 +5,7 @@
 #include "common.hpp"
 #include "g1.hpp"
 #include "msm.hpp"
+#include "stream_pool.hpp"
 
 struct sonic_srs;
 struct sonic_prover;
@@ -22,7 +23,20 @@ struct NttTables;
 struct CallCtx;
 struct DeviceCtx {
   int dev = -1;
-  hipStream_t stream = nullptr;          // the device's default stream for the serialised (state-changing) calls
+  hipStream_t stream = nullptr;          // the device's default stream for the serialised (state-changing) calls; pool stream 0
+  // the prover's stream pool (stream_pool.hpp): made on first use under pool_mu, non-blocking streams that live as long as the process.
+  // prover_streams < 0: not asked yet; 0: no pool (SONIC_STREAM_POOL=0, or the default), handles make private streams
+  int prover_streams = -1;
+  hipStream_t prover_stream[POOL_MAX] = {};
+  // The enqueue lock.  Every call that queues work for a pooled handle holds it while it queues (prover.hpp, EnqueueLock), so all pool
+  // streams see the proofs of all handles in ONE order.  Why two handles can never wait for each other: a stream runs in order, and
+  // hipStreamWaitEvent waits for a record that was queued BEFORE the wait, so every wait points backwards in that one order -- to work
+  // of the same proof (its roles are queued HEAD, NTT, GROUPs, T_GROUP, CHAINs, TAIL, each waiting only for earlier ones) or of a proof
+  // queued earlier.  The first unfinished item of the order therefore never waits for anything unfinished, whatever shares its stream:
+  // by induction everything drains.  That holds for sonic_prove_batch's thread per handle too: the lock makes their enqueues one order.
+  // Without the lock two threads could interleave their proofs differently on different streams; still no cycle (a wait always points at
+  // something already queued), but proof B's head could sit behind proof A's groups on one stream and in front of them on another.
+  std::mutex enqueue_mu;
   std::mutex call_mu;                    // SRS construction, the lazy G2 half, the shared NTT tables of the stand-alone entry points
   std::mutex pool_mu;
   std::vector<CallCtx*> pool;            // leased call contexts (CallLease)
@@ -60,6 +74,12 @@ class DeviceScope {
 DeviceCtx& current_ctx();                 // the innermost DeviceScope of the calling thread
 int default_device_ordinal();             // -1 before the first call that needed a device
 inline hipStream_t default_stream() { return current_ctx().stream; }
+// the current device's prover stream pool: its size (0: none), made on first use; stream i < size
+int device_prover_streams();
+inline hipStream_t device_prover_stream(PoolRole role, int k = 0) {
+  DeviceCtx& c = current_ctx();
+  return c.prover_stream[pool_stream_of(role, k, c.prover_streams)];
+}
 // serialises the calls that CHANGE shared state on the current device; the read-only entry points over an SRS (commitPoly, openPoly,
 // hscProve, the blocking MSMs, srs_get_points) run on a leased context instead
 inline std::mutex& call_mutex() { return current_ctx().call_mu; }

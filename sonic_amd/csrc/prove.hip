@@ -29,6 +29,7 @@ namespace sonic {
 // tests reach both forms and the sums over few segments at a small size.  They are read per group and not once per process, because
 // the tests switch them inside one process; that is two getenv calls per group, five groups per proof.
 constexpr long PROVE_TWO_LEVEL_MAX_TERMS = 1L << 21;
+constexpr long POOL_MAX_TERMS = 1L << 21;      // the largest job (T: 7n + 9 terms) of a handle that borrows the device's pooled streams (prover_new_impl)
 static bool prove_two_level(const MsmPlan& pl, int k, bool last, long nmax) {
   if (last || k <= 1 || pl.NB < (1 << 18)) return false;
   const char* e = getenv("SONIC_PROVE_TWO_LEVEL");
@@ -285,7 +286,7 @@ int prover_admits(const char* who, const sonic_srs* srs, const CircuitView& c) {
 }
 
 // (an admitted circuit)
-int prover_new_impl(const sonic_srs_t* srs, const CircuitView& c, sonic_prover_t** out) {
+int prover_new_impl(const sonic_srs_t* srs, const CircuitView& c, sonic_prover_t** out, bool own_streams) {
   const long n = c.n, Q = c.Q;
   const ProofLayout L{Q};
   for (long q = 0; c.csr && q < Q; q++) {
@@ -299,10 +300,24 @@ int prover_new_impl(const sonic_srs_t* srs, const CircuitView& c, sonic_prover_t
     const MsmPlan probe = srs_msm_plan(srs, 3 * n);
     p->small_plan = msm_can_batch(probe) && probe.NB <= (1 << 17);
   }
-  auto mkstream = [](hipStream_t* s) { HIP_OK(hipStreamCreateWithFlags(s, hipStreamNonBlocking)); };
-  mkstream(&p->st);
-  mkstream(&p->ts);
+  p->use_graph = getenv("SONIC_PROVE_GRAPH") && atoi(getenv("SONIC_PROVE_GRAPH")) != 0;
+  // the handle's streams: borrowed from the device's pool by role, or its own (prover.hpp, `pooled`)
+  // Not the largest proofs.  At n = 2^20 (jobs of 7n terms) every group fills the chip for ~20 ms and the head and tail that the pool
+  // orders are 3 % of a proof; what counts there is that one group's sort and reduction run under another's accumulation, a lane per
+  // group, and a pool of 4 has two group streams: one proof at a time measured 122.2 ms pooled against 120.0 (n = 2^18: 34.0 against
+  // 35.3).  As with PROVE_TWO_LEVEL_MAX_TERMS only these two sizes are measured, and the bound sits between them.  SONIC_STREAM_POOL=k,
+  // k > 0, pools every size (the tests force the pool at small sizes either way: they are below the bound).
+  const bool pool_size_ok = 7 * n + 9 <= POOL_MAX_TERMS || (getenv("SONIC_STREAM_POOL") && atoi(getenv("SONIC_STREAM_POOL")) > 0);
+  p->pooled = !p->use_graph && !own_streams && pool_size_ok && device_prover_streams() > 0;
+  auto mkstream = [&p](hipStream_t* s, PoolRole role, int k = 0) {
+    if (p->pooled) *s = device_prover_stream(role, k);
+    else HIP_OK(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
+  };
+  mkstream(&p->st, PoolRole::HEAD);
+  mkstream(&p->ts, PoolRole::NTT);
+  p->tail = p->pooled ? device_prover_stream(PoolRole::TAIL) : p->st;
   hipStream_t st = p->st;
+  EnqueueLock enq(p.get());      // (held to the end: the circuit's upload and the first memsets are queued and waited for here)
   p->flags.alloc(8);
   int rc_c = prover_load_circuit(p.get(), c);
   if (rc_c) return rc_c;
@@ -323,7 +338,6 @@ int prover_new_impl(const sonic_srs_t* srs, const CircuitView& c, sonic_prover_t
   p->kpow.alloc(sizeof(Fr) * Q);
   p->S.alloc(sizeof(Fr) * L.transcript_len()); p->PAIRS.alloc(sizeof(Fr) * 2 * L.n_pairs());
   p->slots.alloc(sizeof(MsmSlot) * L.slots_total());
-  p->use_graph = getenv("SONIC_PROVE_GRAPH") && atoi(getenv("SONIC_PROVE_GRAPH")) != 0;
   HIP_OK(hipHostMalloc((void**)&p->h_tr, 32 * L.transcript_len(), hipHostMallocDefault));
   HIP_OK(hipHostMalloc((void**)&p->h_pairs, sizeof(Fr) * 2 * L.n_pairs(), hipHostMallocDefault));
   HIP_OK(hipHostMalloc((void**)&p->h_slots, sizeof(MsmSlot) * L.slots_total(), hipHostMallocDefault));
@@ -340,6 +354,7 @@ int prover_new_impl(const sonic_srs_t* srs, const CircuitView& c, sonic_prover_t
   mkev(&p->ev_r1); mkev(&p->ev_sy0); mkev(&p->ev_t); mkev(&p->ev_su);
   p->ev_syj.resize(Q, nullptr);
   for (auto& e : p->ev_syj) mkev(&e);
+  mkev(&p->done); mkev(&p->ev_head); mkev(&p->ev_ts);
   // MSM workspaces and opening scratch grow on first use: every proof maps the same group of MSMs to the same lane
   if (p->small_plan) {
     const char* le = getenv("SONIC_FUSED_LANES");
@@ -347,14 +362,20 @@ int prover_new_impl(const sonic_srs_t* srs, const CircuitView& c, sonic_prover_t
   }
   for (int i = 0; i < p->n_lanes; i++) {
     Lane& l = p->lanes[i];
-    mkstream(&l.st);
+    // (the last lane in use carries the t group: prover.hpp, t_lane.  On a small-proof handle it only prepares the group's openings for
+    // the chain, like the other lanes, and must not sit behind another handle's tail: a GROUP -- stream_pool.hpp -- and the one after
+    // the last lane's, which at P = 4 is the group stream that the product does NOT share: there the lanes queued in front of it do not
+    // wait for the product, so its openings start the moment the product ends.  On the product's stream, behind two other lanes, one
+    // n = 2^14 proof at a time took 3.94 ms against 3.71)
+    const bool t_lane = i == p->n_lanes - 1;
+    if (t_lane && !p->small_plan) mkstream(&l.st, PoolRole::T_GROUP); else mkstream(&l.st, PoolRole::GROUP, t_lane ? i + 1 : i);
     mkev(&l.done);
     mkev(&l.prep);
   }
   if (p->small_plan) {
     // (the second chain stream is only used by proofs of more than MSM_MAX_JOBS MSMs: Q > 2)
     for (int c = 0; c < (L.K() > MSM_MAX_JOBS ? 2 : 1); c++) {
-      mkstream(&p->chain[c].st);
+      mkstream(&p->chain[c].st, PoolRole::CHAIN, c);
       mkev(&p->chain[c].done);
     }
   }
@@ -371,6 +392,7 @@ int sonic_prover_set_assignment(sonic_prover_t* p, const uint8_t* aL, const uint
   std::lock_guard<std::mutex> g(p->mu);
   if (p->in_flight) { set_error("sonic_prover_set_assignment: a submitted proof is still reading the current assignment (collect it first)"); return SONIC_ERR_INVALID_ARG; }
   hipStream_t st = p->st;
+  EnqueueLock enq(p);
   HIP_OK(hipMemsetAsync(p->flags.p, 0, 4, st));
   upload_fr_mont(st, p->aL, aL, p->n, p->flags.as<int>());
   upload_fr_mont(st, p->aR, aR, p->n, p->flags.as<int>());
@@ -547,9 +569,13 @@ struct GroupQueue {
     for (auto& f : deferred_small) f();
     deferred_small.clear();
   }
-  // the main stream waits for every stream that carried a part of the proof
+  // the tail stream (a handle with private streams: its main stream) waits for every stream that carried a part of the proof
   void join() {
-    hipStream_t ms = p->st;
+    hipStream_t ms = p->tail;
+    if (p->pooled) {
+      HIP_OK(hipEventRecord(p->ev_head, p->st)); HIP_OK(hipStreamWaitEvent(ms, p->ev_head, 0));
+      HIP_OK(hipEventRecord(p->ev_ts, p->ts)); HIP_OK(hipStreamWaitEvent(ms, p->ev_ts, 0));
+    }
     for (int i = 0; i < p->n_lanes; i++) { Lane& l = p->lanes[i]; HIP_OK(hipEventRecord(l.done, l.st)); HIP_OK(hipStreamWaitEvent(ms, l.done, 0)); }
     if (p->fused) for (auto& l : p->chain) if (l.st) { HIP_OK(hipEventRecord(l.done, l.st)); HIP_OK(hipStreamWaitEvent(ms, l.done, 0)); }
   }
@@ -731,11 +757,33 @@ static void enqueue_groups(sonic_prover_t* p, GroupQueue& q, ProofPass& w) {
 
 // Everything between "inputs in HBM" and "window-sum slots + evaluations on the host", queued with no host synchronisation: what a
 // captured hipGraph replays
+// a pooled handle: the assignment of this call goes up on the handle's own upload stream, before the enqueue lock is taken (prover.hpp,
+// `up`); it collects its flags in flags[1], which enqueue_proof then leaves alone
+static void stage_assignment(sonic_prover_t* p) {
+  if (!p->up) {
+    HIP_OK(hipStreamCreateWithFlags(&p->up, hipStreamNonBlocking));
+    HIP_OK(hipEventCreateWithFlags(&p->ev_up, hipEventDisableTiming));
+  }
+  int* flags = p->flags.as<int>();
+  HIP_OK(hipMemsetAsync(flags + 1, 0, 4, p->up));
+  upload_fr_mont(p->up, p->aL, p->pend_asg[0], p->n, flags + 1);
+  upload_fr_mont(p->up, p->aR, p->pend_asg[1], p->n, flags + 1);
+  upload_fr_mont(p->up, p->aO, p->pend_asg[2], p->n, flags + 1);
+  HIP_OK(hipEventRecord(p->ev_up, p->up));
+  p->pend_asg[0] = nullptr;
+  p->assignment_changed();
+  p->asg_staged = true;
+}
+
 static void enqueue_proof(sonic_prover_t* p) {
   const ProofLayout L{p->Q};
   hipStream_t st = p->st;
   int* flags = p->flags.as<int>();
-  HIP_OK(hipMemsetAsync(flags, 0, 8, st));
+  if (p->asg_staged) {
+    HIP_OK(hipMemsetAsync(flags, 0, 4, st));
+    HIP_OK(hipStreamWaitEvent(st, p->ev_up, 0));
+    p->asg_staged = false;
+  } else HIP_OK(hipMemsetAsync(flags, 0, 8, st));
   Fr* S = p->S.as<Fr>();
   HIP_OK(hipMemcpyAsync(S, p->h_tr, 32 * L.transcript_len(), hipMemcpyHostToDevice, st));
   fr_to_mont_enqueue(st, S, L.transcript_len(), flags);
@@ -745,14 +793,17 @@ static void enqueue_proof(sonic_prover_t* p) {
   enqueue_polynomials(p, q, w);
   enqueue_groups(p, q, w);
   q.join();
+  // the copy-out, behind the join on the tail stream (a pooled handle: not the stream the next proof's head is queued on)
+  hipStream_t tl = p->tail;
   Fr* frstd = p->frstd.as<Fr>();
-  HIP_OK(hipMemcpyAsync(frstd, q.frout, sizeof(Fr) * L.F(), hipMemcpyDeviceToDevice, st));
-  fr_from_mont_enqueue(st, frstd, L.F());
+  HIP_OK(hipMemcpyAsync(frstd, q.frout, sizeof(Fr) * L.F(), hipMemcpyDeviceToDevice, tl));
+  fr_from_mont_enqueue(tl, frstd, L.F());
   // (the side slots that this proof's modes fill: the second halves of the S_j, and of C)
   const long KS = p->sym_on ? L.slots_total() : (p->prepared || p->runs_on) ? L.C_extra() : L.K();
-  HIP_OK(hipMemcpyAsync(p->h_slots, q.slots, sizeof(MsmSlot) * KS, hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(p->h_fr, frstd, 32 * L.F(), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(p->h_flags, flags, 8, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(p->h_slots, q.slots, sizeof(MsmSlot) * KS, hipMemcpyDeviceToHost, tl));
+  HIP_OK(hipMemcpyAsync(p->h_fr, frstd, 32 * L.F(), hipMemcpyDeviceToHost, tl));
+  HIP_OK(hipMemcpyAsync(p->h_flags, flags, 8, hipMemcpyDeviceToHost, tl));
+  if (p->pooled) HIP_OK(hipEventRecord(p->done, tl));
 }
 
 // ---- the per-proof mode decisions ------------------------------------------------------------------------------------------------
@@ -856,7 +907,8 @@ static int prove_enqueue(sonic_prover_t* p, const uint8_t* transcript) {
     ~CaptureGuard() { if (active) { hipGraph_t g = nullptr; (void)hipStreamEndCapture(st, &g); if (g) (void)hipGraphDestroy(g); } }
   } capture{st};
   if (capturing) { p->graph_tried = true; HIP_OK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed)); capture.active = true; }
-  if (!replay) enqueue_proof(p);
+  if (p->pooled && p->pend_asg[0]) stage_assignment(p);
+  if (!replay) { EnqueueLock enq(p); enqueue_proof(p); }
   if (capturing) {
     hipGraph_t g = nullptr;
     capture.active = false;
@@ -886,7 +938,7 @@ extern "C" size_t sonic_proof_share_size(int64_t Q) {
 
 // what both finishes open with: wait for the device, count the proof, say where the time went (SONIC_DEBUG_TIMING: returns whether it is set)
 static bool await_proof(sonic_prover_t* p, bool share) {
-  HIP_OK(hipStreamSynchronize(p->st));
+  p->await_done();
   p->proofs_done++;
   if (!getenv("SONIC_DEBUG_TIMING")) return false;
   char who[32] = "prove";
@@ -1061,7 +1113,17 @@ static int prove_args_ok(sonic_prover_t* p, const char* who) {
 // the tail of every prove call: queue the proof, then `finish` it into `out` (null: leave it in flight, sonic_prover_submit)
 static int prove_run(sonic_prover_t* p, const uint8_t* transcript, int (*finish)(sonic_prover_t*, uint8_t*), uint8_t* out) {
   int rc = prove_enqueue(p, transcript);
-  if (rc) { if (p->st) (void)hipStreamSynchronize(p->st); return rc; }      // an enqueue that failed half way: let what was queued drain
+  if (rc) {      // an enqueue that failed half way: let what was queued drain (a pooled handle: on every stream it may have queued on)
+    if (p->st) (void)hipStreamSynchronize(p->st);
+    if (p->pooled) {
+      (void)hipStreamSynchronize(p->ts); (void)hipStreamSynchronize(p->tail);
+      if (p->up) (void)hipStreamSynchronize(p->up);
+      p->asg_staged = false;
+      for (auto& l : p->lanes) if (l.st) (void)hipStreamSynchronize(l.st);
+      for (auto& l : p->chain) if (l.st) (void)hipStreamSynchronize(l.st);
+    }
+    return rc;
+  }
   return finish ? finish(p, out) : SONIC_OK;
 }
 
@@ -1142,6 +1204,7 @@ int sonic_prover_set_share(sonic_prover_t* p, int rank, int world) {
   p->share_world = world > 1 ? world : 0;
   p->share_planned = false;
   // slots and evaluations of pieces this rank no longer runs must not survive from an earlier proof
+  EnqueueLock enq(p);
   HIP_OK(hipMemsetAsync(p->slots.p, 0, sizeof(MsmSlot) * ProofLayout{p->Q}.C_extra(), p->st));      // (all but C's side slot, which a share never fills)
   HIP_OK(hipMemsetAsync(p->frout.p, 0, sizeof(Fr) * ProofLayout{p->Q}.F(), p->st));
   HIP_OK(hipStreamSynchronize(p->st));
@@ -1204,6 +1267,7 @@ int sonic_fs_challenges(int64_t, int64_t, int64_t, const uint8_t*, const uint8_t
 static void witness_digest_v1_ensure(sonic_prover_t* p) {
   if (p->have_witness_digest) return;
   const long n = p->n;
+  EnqueueLock enq(p);
   DevBuf tmp(sizeof(Fr) * 3 * n);
   Fr* t3 = tmp.as<Fr>();
   HIP_OK(hipMemcpyAsync(t3, p->aL.p, sizeof(Fr) * n, hipMemcpyDeviceToDevice, p->st));
@@ -1236,6 +1300,7 @@ static void witness_digest_v2_finish(sonic_prover_t* p) {
 }
 static void witness_digest_v2_ensure(sonic_prover_t* p) {
   if (p->have_witness_digest_v2) return;
+  EnqueueLock enq(p);
   witness_digest_v2_enqueue(p);
   HIP_OK(hipStreamSynchronize(p->st));
   witness_digest_v2_finish(p);
@@ -1394,6 +1459,7 @@ int prove_fs_with_statement(sonic_prover_t* p, const uint8_t* aL, const uint8_t*
   if (!aL && !p->have_assignment) { set_error("prove: no assignment set"); return SONIC_ERR_INVALID_ARG; }
   hipStream_t st = p->st;
   if (aL) {
+    EnqueueLock enq(p);
     p->have_assignment = false;             // (until the upload is known to be good: a failed one leaves a partly converted assignment)
     p->assignment_changed();
     HIP_OK(hipMemsetAsync(p->flags.p, 0, 4, st));
@@ -1425,12 +1491,15 @@ int prove_fs_with_witness(sonic_prover_t* p, const WitnessView& w, hipEvent_t re
   p->have_assignment = false;               // (until the source is known to be good)
   p->assignment_changed();
   for (DevBuf* a : {&p->aL, &p->aR, &p->aO}) a->ensure(sizeof(Fr) * (size_t)p->n);
-  if (ready) HIP_OK(hipStreamWaitEvent(st, ready, 0));
-  HIP_OK(hipMemsetAsync(p->flags.p, 0, 4, st));
-  witness_load_enqueue(p, st, w, 1, p->aL.as<Fr>(), p->aR.as<Fr>(), p->aO.as<Fr>(), p->n, p->flags.as<int>());
-  witness_digest_v2_enqueue(p);
-  const int f = read_flags(st, p->flags);
-  if (f) return flags_to_status(f, "prove (assignment handed over with the call)");
+  {
+    EnqueueLock enq(p);
+    if (ready) HIP_OK(hipStreamWaitEvent(st, ready, 0));
+    HIP_OK(hipMemsetAsync(p->flags.p, 0, 4, st));
+    witness_load_enqueue(p, st, w, 1, p->aL.as<Fr>(), p->aR.as<Fr>(), p->aO.as<Fr>(), p->n, p->flags.as<int>());
+    witness_digest_v2_enqueue(p);
+    const int f = read_flags(st, p->flags);
+    if (f) return flags_to_status(f, "prove (assignment handed over with the call)");
+  }
   witness_digest_v2_finish(p);
   p->have_assignment = true;
   p->pend_cs = cs;
@@ -1453,6 +1522,7 @@ int sonic_prover_prepare(sonic_prover_t* p) {
   p->graph_tried = false;
   const long n = p->n, Q = p->Q, d = p->srs->d;
   int* flags = p->flags.as<int>();
+  EnqueueLock enq(p);      // (to the end: the rows' MSMs are queued on the lanes and waited for here)
   HIP_OK(hipMemsetAsync(flags, 0, 4, p->st));
   HIP_OK(hipStreamSynchronize(p->st));
   DevBuf slots(sizeof(MsmSlot) * Q);
@@ -1557,6 +1627,7 @@ int sonic_prover_hsc_prove(sonic_prover_t* p, int64_t m, const uint8_t* yzs, con
     if (bytes_are_zero(yzs + 32 * k, 32)) { set_error("hscProve: y_j / z_j number %ld is zero: Laurent evaluation at 0 divides by zero", k); return SONIC_ERR_INEXACT_DIVISION; }
   if (bytes_are_zero(u, 32) || bytes_are_zero(v, 32)) { set_error("hscProve: u or v is zero"); return SONIC_ERR_INEXACT_DIVISION; }
   hipStream_t st = p->st;
+  EnqueueLock enq(p);      // (to the end: everything is queued on the main stream and waited for here)
   const sonic_srs* srs = p->srs;
   const long NS = 2 * m + 2;                                   // scalars: y_1..y_m, z_1..z_m, u, v
   const long K = 4 * m + 2;                                    // MSMs

@@ -83,8 +83,12 @@ static int one_shot_prove(const char* who, const sonic_srs_t* srs, const Circuit
   OneShotShell* sh = take_shell(ctx, srs, c.n, c.Q);
   if (sh) prover_hand_over(sh->p, c);
   else {
+    // A shell keeps streams of its own, pool or not: a one-shot proof's head carries the call's circuit and assignment (50 MB at n = 2^18),
+    // and on the pool's shared head stream that upload sits in front of every other handle's next proof -- and of the other thread's
+    // call in sonic_prove_many.  Measured with pooled shells, n = 2^18 on 4 queues: 36.5 ms per call against 34.8
+    // (profiles/r13_stream_pool.txt).
     sonic_prover_t* p = nullptr;
-    rc = prover_new_impl(srs, c, &p);
+    rc = prover_new_impl(srs, c, &p, /*own_streams=*/true);
     if (rc) return rc;
     sh = new OneShotShell{srs, p};
   }

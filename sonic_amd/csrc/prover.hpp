@@ -94,6 +94,26 @@ struct sonic_prover {
   long n = 0, Q = 0;
   hipStream_t st = nullptr;
   hipStream_t ts = nullptr;                  // the t(X,y) product (NTT) runs beside the hscProve polynomials
+  // Where the streams come from (stream_pool.hpp).  pooled: st, ts, tail, every Lane::st and chain[].st are BORROWED from the device's
+  // pool, picked by role (HEAD, NTT, TAIL, GROUP(i) / T_GROUP, CHAIN(c)) -- shared with every other pooled handle on the device and
+  // never destroyed here.  Not pooled (SONIC_STREAM_POOL=0, the default when the pool is off, and SONIC_PROVE_GRAPH=1 handles: a
+  // capture on a shared stream would take the other handle's work with it): private streams, and tail == st.
+  // Workspaces, scratch and events are the handle's own either way.
+  bool pooled = false;
+  hipStream_t tail = nullptr;                // the join over the lanes and the copy-out of a proof's results
+  // pooled: recorded on `tail` behind a proof's last copy.  The caller waits for THIS (await_done): synchronising a shared stream
+  // would also wait for whatever another handle has queued on it since.
+  hipEvent_t done = nullptr;
+  hipEvent_t ev_head = nullptr, ev_ts = nullptr;      // pooled: the ends of this proof's work on st and ts, which tail waits for
+  // pooled: the assignment of THIS call (pend_asg, 6.3 MB at n = 2^16) goes up on a stream of the handle's own, queued BEFORE the enqueue
+  // lock is taken, and the head waits for ev_up: a pageable upload blocks its host thread, and on the shared head stream under the lock
+  // it held up the other handle's thread and head as well (sonic_prove_batch with per-proof assignments: 11.5 against 10.9 ms per proof)
+  hipStream_t up = nullptr;
+  hipEvent_t ev_up = nullptr;
+  bool asg_staged = false;
+  // blocks until the proof queued last has left the device.  (The calls off the hot path -- set_assignment, prepare, hscProve, ... --
+  // still synchronise the stream they queued on: they hold the enqueue lock meanwhile, so nothing newer can be on it.)
+  void await_done() { if (pooled) HIP_OK(hipEventSynchronize(done)); else HIP_OK(hipStreamSynchronize(st)); }
   bool have_assignment = false;
   DevBuf wL, wR, wO, cs, aL, aR, aO;        // Montgomery, resident across proofs
   // the circuit in sparse form (sonic_prover_new_csr, sonic_prove_csr; csr.hpp): the 3Q stacked rows and their column-major copy, int32
@@ -248,16 +268,36 @@ struct sonic_prover {
       fsw->cv.notify_all();
       if (fsw->th.joinable()) fsw->th.join();
     }
-    for (auto& l : lanes) { if (l.st) (void)hipStreamDestroy(l.st); if (l.done) (void)hipEventDestroy(l.done); if (l.prep) (void)hipEventDestroy(l.prep); }
-    for (auto& l : chain) { if (l.st) (void)hipStreamDestroy(l.st); if (l.done) (void)hipEventDestroy(l.done); if (l.prep) (void)hipEventDestroy(l.prep); }
+    if (pooled) {
+      // the streams are the pool's and go on serving other handles: wait for this handle's OWN events -- the end of its last proof and
+      // of its lanes (an event that was never recorded counts as complete) -- and only then let the members below release the buffers
+      if (done) (void)hipEventSynchronize(done);
+      for (auto& l : lanes) if (l.done) (void)hipEventSynchronize(l.done);
+      for (auto& l : chain) if (l.done) (void)hipEventSynchronize(l.done);
+      for (hipEvent_t e : {ev_head, ev_ts, ev_up}) if (e) (void)hipEventSynchronize(e);
+    }
+    if (up) (void)hipStreamDestroy(up);
+    if (ev_up) (void)hipEventDestroy(ev_up);
+    for (auto& l : lanes) { if (l.st && !pooled) (void)hipStreamDestroy(l.st); if (l.done) (void)hipEventDestroy(l.done); if (l.prep) (void)hipEventDestroy(l.prep); }
+    for (auto& l : chain) { if (l.st && !pooled) (void)hipStreamDestroy(l.st); if (l.done) (void)hipEventDestroy(l.done); if (l.prep) (void)hipEventDestroy(l.prep); }
     for (auto& r : runs) if (r.masked_ev) (void)hipEventDestroy(r.masked_ev);
-    for (hipEvent_t e : {ev_r1, ev_sy0, ev_t, ev_su}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {ev_r1, ev_sy0, ev_t, ev_su, done, ev_head, ev_ts}) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ev_syj) if (e) (void)hipEventDestroy(e);
-    if (st) (void)hipStreamDestroy(st);
-    if (ts) (void)hipStreamDestroy(ts);
+    if (st && !pooled) (void)hipStreamDestroy(st);
+    if (ts && !pooled) (void)hipStreamDestroy(ts);
     if (graph) (void)hipGraphExecDestroy(graph);
     for (void* h : {(void*)h_tr, (void*)h_pairs, (void*)h_slots, (void*)h_fr, (void*)h_flags, (void*)h_root}) if (h) (void)hipHostFree(h);
   }
+};
+
+// Held by every call that queues work for a pooled handle, for as long as it queues (a proof or a share, each Fiat-Shamir pass, prepare,
+// set_assignment / set_witness, hscProve, a new handle's circuit upload): the device's enqueue lock, so that all pool streams see the
+// handles' work in one order (the argument: internal.hpp, DeviceCtx::enqueue_mu).  Nothing for a handle with private streams -- the
+// one-shot shells among them (prove_multi.hip).  Taken inside the call's device scope, never while another EnqueueLock is held by the
+// same thread.
+struct EnqueueLock {
+  std::unique_lock<std::mutex> l;
+  explicit EnqueueLock(const sonic_prover* p) { if (p->pooled) l = std::unique_lock<std::mutex>(current_ctx().enqueue_mu); }
 };
 
 // (prove.hip)
@@ -297,6 +337,7 @@ namespace sonic { const uint32_t* witness_tree_enqueue(hipStream_t st, const Fr*
 // (prove.hip) what sonic_prover_new[_csr] and the one-shot calls share: the checks of a circuit against an SRS, a handle for an admitted
 // circuit, and the hand-over of the next call's circuit to a handle that exists (uploaded inside its next proof)
 int prover_admits(const char* who, const sonic_srs* srs, const CircuitView& c);
-int prover_new_impl(const sonic_srs_t* srs, const CircuitView& c, sonic_prover_t** out);
+// (own_streams: the handle makes private streams whatever the device's pool says -- the shells of the one-shot calls, below)
+int prover_new_impl(const sonic_srs_t* srs, const CircuitView& c, sonic_prover_t** out, bool own_streams = false);
 void prover_hand_over(sonic_prover_t* p, const CircuitView& c);
 

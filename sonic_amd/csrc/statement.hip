@@ -215,6 +215,7 @@ int sonic_prover_eval_constraints(sonic_prover_t* p, int64_t B, const uint8_t* a
   std::lock_guard<std::mutex> g(p->mu);
   if (resident && !p->have_assignment) { set_error("%s: no assignment set", who); return SONIC_ERR_INVALID_ARG; }
   if (p->in_flight) { set_error("%s: a submitted proof is still reading the handle's buffers (collect it first)", who); return SONIC_ERR_INVALID_ARG; }
+  EnqueueLock enq(p);
   return eval_constraints_run(who, p, B, aL, aR, aO, nullptr, out_cs, out_gates);
   API_CATCH
 }
@@ -235,6 +236,7 @@ int sonic_prover_eval_constraints_src(sonic_prover_t* p, int64_t B, const sonic_
   if (rc) return rc;
   WitnessReady ready;
   ready.record(v);
+  EnqueueLock enq(p);
   if (ready.ev) HIP_OK(hipStreamWaitEvent(p->st, ready.ev, 0));
   return eval_constraints_run(who, p, B, nullptr, nullptr, nullptr, &v, out_cs, out_gates);
   API_CATCH
@@ -252,6 +254,7 @@ int sonic_prover_set_constants(sonic_prover_t* p, const uint8_t* cs) {
     if (!fp_is_canonical(k)) { set_error("sonic_prover_set_constants: cs[%ld] is not a canonical field element", q); return SONIC_ERR_BAD_ENCODING; }
   }
   // in place: p->cs keeps its address (DevBuf::ensure of the size it has), so a captured proof graph stays valid and is kept
+  EnqueueLock enq(p);
   HIP_OK(hipMemsetAsync(p->flags.p, 0, 4, p->st));
   upload_fr_mont(p->st, p->cs, cs, p->Q, p->flags.as<int>());
   HIP_OK(hipStreamSynchronize(p->st));

@@ -157,6 +157,7 @@ int sonic_prover_set_witness(sonic_prover_t* p, const sonic_witness_src_t* src) 
   ready.record(v);
   hipStream_t st = p->st;
   for (DevBuf* b : {&p->aL, &p->aR, &p->aO}) b->ensure(sizeof(Fr) * (size_t)p->n);
+  EnqueueLock enq(p);
   if (ready.ev) HIP_OK(hipStreamWaitEvent(st, ready.ev, 0));
   HIP_OK(hipMemsetAsync(p->flags.p, 0, 4, st));
   p->have_assignment = false;      // (until the source is known to be good)
