@@ -44,7 +44,7 @@ module Sonic.HIP
     SRS, new, newOn, replicate', srsD, srsDevice
   , gNegativeX, gPositiveX, gNegativeAlphaX, gPositiveAlphaX
   , hNegativeX, hPositiveX, hNegativeAlphaX, hPositiveAlphaX, srsPairing
-  , saveSRS, loadSRS
+  , saveSRS, loadSRS, srsForCircuit, loadSrsForCircuit
     -- * Sonic.CommitmentScheme
   , commitPoly, openPoly, pcV
     -- * Sonic.Protocol
@@ -107,6 +107,8 @@ foreign import ccall safe   "sonic_srs_get_g2_points" c_srs_get_g2       :: Ptr 
 foreign import ccall safe   "sonic_srs_pairing"       c_srs_pairing      :: Ptr SrsHandle -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_srs_save"          c_srs_save         :: Ptr SrsHandle -> CString -> CInt -> IO CInt
 foreign import ccall safe   "sonic_srs_load"          c_srs_load         :: CString -> Ptr (Ptr SrsHandle) -> IO CInt
+foreign import ccall safe   "sonic_srs_for_circuit"   c_srs_for_circuit  :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr (Ptr SrsHandle) -> IO CInt
+foreign import ccall safe   "sonic_srs_load_for_circuit" c_srs_load_for_circuit :: CString -> Int64 -> Int64 -> Ptr (Ptr SrsHandle) -> IO CInt
 
 foreign import ccall safe   "sonic_commit_poly"       c_commit_poly      :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_open_poly"         c_open_poly        :: Ptr SrsHandle -> Ptr Word8 -> Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> IO CInt
@@ -342,6 +344,19 @@ saveSRS (SRS h) path withG2 = withForeignPtr h $ \p -> withCString path $ \cp ->
 loadSRS :: FilePath -> IO SRS
 loadSRS path = libraryReady `seq` withCString path (\cp -> alloca $ \out -> do
   check =<< c_srs_load cp out
+  wrapSRS out)
+
+-- | a circuit-sized view of a universal string (include/sonic_hip.h, "circuit-sized views"): the same d, the same proofs, over copies
+-- of only the exponents a circuit of n gates and q constraints touches; the string itself may be dropped afterwards
+srsForCircuit :: SRS -> Int -> Int -> IO SRS
+srsForCircuit (SRS h) n q = withForeignPtr h $ \p -> alloca $ \out -> do
+  check =<< c_srs_for_circuit p (fromIntegral n) (fromIntegral q) out
+  wrapSRS out
+
+-- | the same view read from a file of either container: only the byte ranges of its windows are read
+loadSrsForCircuit :: FilePath -> Int -> Int -> IO SRS
+loadSrsForCircuit path n q = libraryReady `seq` withCString path (\cp -> alloca $ \out -> do
+  check =<< c_srs_load_for_circuit cp (fromIntegral n) (fromIntegral q) out
   wrapSRS out)
 
 -- ---------------------------------------------------------------------------------------------------------------------

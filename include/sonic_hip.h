@@ -175,6 +175,33 @@ int sonic_srs_load_on(int device, const char* path, sonic_srs_t** out);
  * version 3 of SONICSRS, so that every reader of that format keeps refusing what it does not know. */
 int sonic_srs_save_compressed(const sonic_srs_t* srs, const char* path, int with_g2);
 
+/* ---- circuit-sized views of a universal string (additions under ABI 7) ----
+ * A VIEW is a second kind of sonic_srs_t: the same d, the same Fiat-Shamir id, the same commitments and proofs as the string it was made
+ * from, but it holds only the exponent windows a circuit of (n, Q) touches,
+ *     low   [-4n - 8, max(3n, n + Q)]     both G1 bases
+ *     high  [d - 3n - 4, d]               (R is committed with max = n; only the alpha basis is read there)
+ * merged into one window where they touch, with window tables, running sums and symmetric sums sized for those windows and a window
+ * width chosen as for a string of d = 8n.  It owns copies of all it holds: the source may be freed.  Its G2 half is exactly what the
+ * verifiers fetch -- basis 0 at exponents n - d and 0, basis 1 at 0 and 1 -- asked of the source the way a verifier asks (generated on
+ * first use where the source still has its trapdoor); a source that cannot supply them gives a view without a G2 half.
+ * n < 1, Q < 1, d < 7n or d < 4n + 8: SONIC_ERR_INVALID_ARG.  The source may itself be a view whose windows contain the new ones.
+ * Every entry point that takes an SRS takes a view.  Asking a view for an exponent inside [-d, d] that it does not hold -- an MSM or
+ * polynomial whose (dense) exponent range leaves a window or crosses the gap, sonic_srs_get_points, a G2 element other than its four, a
+ * prover or verifier for a circuit whose windows the view's do not contain (refused when the handle is made; a smaller circuit, n' <= n
+ * and n' + Q' <= max(3n, n + Q), passes for the prover; a verifier needs h^{x^{n' - d}} and so n' = n) -- is SONIC_ERR_INVALID_ARG with
+ * the range and the windows in sonic_last_error, decided on the host before anything is launched; never a wrong point.  Exponents outside
+ * [-d, d] keep SONIC_ERR_SRS_INDEX.  sonic_srs_save*, sonic_srs_set_g2_points refuse a view: it is not a reference string.
+ * sonic_srs_for_circuit makes the view on the source's GPU, device to device.  sonic_srs_load_for_circuit[_on] reads only the windows'
+ * byte ranges (and the four G2 points where the file has a G2 half) of either container, after the header has been checked against the
+ * file's real size, and validates what it read as sonic_srs_load does. */
+int sonic_srs_for_circuit(const sonic_srs_t* srs, int64_t n, int64_t Q, sonic_srs_t** out);
+int sonic_srs_load_for_circuit(const char* path, int64_t n, int64_t Q, sonic_srs_t** out);
+int sonic_srs_load_for_circuit_on(int device, const char* path, int64_t n, int64_t Q, sonic_srs_t** out);
+/* lo0, hi0, lo1, hi1: the exponent windows a handle holds; one window (every whole string: [-d, d]): lo1 = 1, hi1 = 0 */
+int sonic_srs_windows(const sonic_srs_t* srs, int64_t out[4]);
+/* device memory of the G1 side: both bases with their window tables, the running sums, the symmetric sums */
+int sonic_srs_device_bytes(const sonic_srs_t* srs, size_t* out);
+
 /* ---- Sonic.CommitmentScheme ---- */
 /* commitPoly :: SRS -> Int -> VLaurent Fr -> G1  (CommitmentScheme.hs:20-33) */
 int sonic_commit_poly(const sonic_srs_t* srs, int64_t max, int64_t n_terms, const int64_t* exps,

@@ -71,6 +71,11 @@ def lib() -> C.CDLL:
         "sonic_srs_device": [vp],
         "sonic_srs_pairing": [vp, vp],
         "sonic_srs_load_on": [i32, cp, C.POINTER(vp)],
+        "sonic_srs_for_circuit": [vp, i64, i64, C.POINTER(vp)],
+        "sonic_srs_load_for_circuit": [cp, i64, i64, C.POINTER(vp)],
+        "sonic_srs_load_for_circuit_on": [i32, cp, i64, i64, C.POINTER(vp)],
+        "sonic_srs_windows": [vp, C.POINTER(i64)],
+        "sonic_srs_device_bytes": [vp, C.POINTER(C.c_size_t)],
         "sonic_msm_lane_new_on": [i32, C.POINTER(vp)],
         "sonic_prove_shared": [vp, i32, vp, vp],
         "sonic_prove_batch": [vp, i32, i64, vp, vp, vp, vp, vp, vp],
@@ -269,6 +274,7 @@ EXPORTED = [
     "sonic_fs_circuit_digest_resume", "sonic_verifier_verify_batch_cs", "sonic_verifier_verify_fs_batch_cs", "sonic_verify_batch_digest_v2",
     "sonic_prover_witness_digest_v2", "sonic_prover_submit_fs", "sonic_prover_collect_fs", "sonic_prove_batch_fs",
     "sonic_prover_set_witness", "sonic_prover_eval_constraints_src", "sonic_prove_batch_src", "sonic_prove_batch_fs_src",
+    "sonic_srs_for_circuit", "sonic_srs_load_for_circuit", "sonic_srs_load_for_circuit_on", "sonic_srs_windows", "sonic_srs_device_bytes",
 ]
 
 

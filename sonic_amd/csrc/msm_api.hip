@@ -136,6 +136,7 @@ static int msm_submit_common(sonic_msm_lane_t* l, const sonic_srs_t* srs, int ba
   if (!l || !srs || n < 0 || (n > 0 && !d_scalars) || (basis != 0 && basis != 1)) return SONIC_ERR_INVALID_ARG;
   if (!same_device(l, srs, "sonic_msm_submit")) return SONIC_ERR_INVALID_ARG;
   if (n > 0 && !srs_range_ok("msm over SRS", srs, e0, n)) return SONIC_ERR_SRS_INDEX;
+  if (n > 0 && !srs_held_ok("msm over SRS", srs, e0, n)) return SONIC_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> g(l->mu);
   if (l->in_flight) { set_error("sonic_msm_submit: the lane's previous MSM has not been collected"); return SONIC_ERR_INVALID_ARG; }
   hipStream_t st = l->st;
@@ -144,7 +145,7 @@ static int msm_submit_common(sonic_msm_lane_t* l, const sonic_srs_t* srs, int ba
   fr_check_enqueue(st, dsc, n, l->err.as<int>());
   MsmPlan pl = srs_msm_plan(srs, n);
   pl.accum_block = 64;           // a lane's MSM runs alone or beside other lanes' MSMs, not inside a proof (msm.hpp)
-  msm_enqueue(st, l->ws, pl, srs->basis(basis) + (e0 + srs->d), dsc, n, false, l->slot.as<MsmSlot>());
+  msm_enqueue(st, l->ws, pl, srs->basis(basis) + srs->geo.slot(e0), dsc, n, false, l->slot.as<MsmSlot>());
   l->Wb = pl.Wb;
   if (d_partial_out) HIP_OK(hipMemcpyAsync(d_partial_out, l->slot.p, sizeof(MsmSlot), hipMemcpyDeviceToDevice, st));
   HIP_OK(hipMemcpyAsync(l->h_slot, l->slot.p, sizeof(MsmSlot), hipMemcpyDeviceToHost, st));
@@ -240,6 +241,7 @@ int sonic_msm_accumulate_dev(sonic_msm_lane_t* l, const sonic_srs_t* srs, int ba
   if (!l || !srs || n < 0 || (n > 0 && !d_scalars) || (basis != 0 && basis != 1) || !d_buckets) return SONIC_ERR_INVALID_ARG;
   if (!same_device(l, srs, "sonic_msm_accumulate_dev")) return SONIC_ERR_INVALID_ARG;
   if (n > 0 && !srs_range_ok("msm over SRS", srs, e0, n)) return SONIC_ERR_SRS_INDEX;
+  if (n > 0 && !srs_held_ok("msm over SRS", srs, e0, n)) return SONIC_ERR_INVALID_ARG;
   if (srs->tab_W <= 1 || srs->tab_endo) { set_error("sonic_msm_accumulate_dev needs the full window tables of the SRS"); return SONIC_ERR_INVALID_ARG; }
   const int64_t NB = 1LL << (srs->tab_c - 1);
   if (capacity < NB) { set_error("sonic_msm_accumulate_dev: room for %ld buckets, the plan has %ld", (long)capacity, (long)NB); return SONIC_ERR_INVALID_ARG; }
@@ -249,9 +251,9 @@ int sonic_msm_accumulate_dev(sonic_msm_lane_t* l, const sonic_srs_t* srs, int ba
   HIP_OK(hipMemsetAsync(l->err.p, 0, 4, st));
   fr_check_enqueue(st, dsc, n, l->err.as<int>());
   // always over the tables (a term-range share may be small against the bucket set; every rank must fill the SAME buckets)
-  MsmPlan pl = msm_plan_tables(n > 0 ? n : 1, srs->tab_c, srs->tab_W, 2 * srs->d + 1);
+  MsmPlan pl = msm_plan_tables(n > 0 ? n : 1, srs->tab_c, srs->tab_W, srs->geo.npts());
   pl.accum_block = 64;
-  MsmJob job{srs->basis(basis) + (e0 + srs->d), dsc, (long)n, nullptr};
+  MsmJob job{srs->basis(basis) + srs->geo.slot(e0), dsc, (long)n, nullptr};
   msm_enqueue_batch(st, l->ws, pl, &job, 1, false, static_cast<G1XYZZ*>(d_buckets));
   if (capacity > NB) HIP_OK(hipMemsetAsync(static_cast<G1XYZZ*>(d_buckets) + NB, 0, sizeof(G1XYZZ) * (size_t)(capacity - NB), st));   // padding = infinity
   HIP_OK(hipMemcpyAsync(l->h_err, l->err.p, 4, hipMemcpyDeviceToHost, st));

@@ -45,6 +45,16 @@ struct ProofLayout {
   static constexpr long pY = 0, pZ = 1, pYZ = 2, pU = 3, pV = 4;
   constexpr long pYj(long j) const { return 5 + j; }
   constexpr long pZj(long j) const { return 5 + Q + j; }
+  // exponent ranges of a proof's dense polynomials over n multiplication gates: r(X, 1) with its four blinders, s(X, y_j), t(X, y) and
+  // s(u, Y) with its Q constraint terms; R is committed with max = n, the others with max = d (prove.hip; srs_view.hpp sizes a view by them)
+  static constexpr long r_lo(long n) { return -2 * n - 4; }
+  static constexpr long r_len(long n) { return 3 * n + 5; }
+  static constexpr long s_lo(long n) { return -n; }
+  static constexpr long s_len(long n) { return 3 * n + 1; }
+  static constexpr long t_lo(long n) { return -4 * n - 8; }
+  static constexpr long t_len(long n) { return 7 * n + 9; }
+  static constexpr long u_lo(long n) { return -n; }
+  constexpr long u_len(long n) const { return 2 * n + Q + 1; }
 };
 
 // canonical proof bytes from the 7 + 4Q points (slot order) and the 3 + 2Q evaluations: record order of `Proof` (Protocol.hs:28-38)

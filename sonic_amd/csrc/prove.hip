@@ -57,11 +57,12 @@ MsmJob commit_job(hipStream_t st, const sonic_srs* srs, const Fr* poly, long lo,
   if (i0 < 0) i0 = 0;
   if (i1 > len) i1 = len;
   if (i1 < i0) i1 = i0;
+  const PointArray points = srs_job_points("commitPoly", srs, 1, lo + i0 + shift, i1 - i0);      // (a view refuses here, before any launch)
   flag_nonzero_enqueue(st, poly, i0, d_flags, FLAG_SRS_INDEX);
   flag_nonzero_enqueue(st, poly + i1, len - i1, d_flags, FLAG_SRS_INDEX);
   const long ih = -shift - lo;
   if (ih >= i0 && ih < i1) flag_nonzero_enqueue(st, poly + ih, 1, d_flags, FLAG_SRS_INDEX);
-  return MsmJob{srs->basis(1) + (lo + i0 + shift + d), poly + i0, i1 - i0, slot};
+  return MsmJob{points, poly + i0, i1 - i0, slot};
 }
 
 // The MSMs that become ready together run as one batched kernel chain when the SRS has window tables (msm.hpp);
@@ -115,9 +116,10 @@ static MsmJob quotient_job(hipStream_t st, const sonic_srs* srs, const Fr* q, lo
   if (i0 < 0) i0 = 0;
   if (i1 > qn) i1 = qn;
   if (i1 < i0) i1 = i0;
+  const PointArray points = srs_job_points("openPoly", srs, 0, lo + i0, i1 - i0);
   flag_nonzero_enqueue(st, q, i0, d_flags, FLAG_SRS_INDEX);
   flag_nonzero_enqueue(st, q + i1, qn - i1, d_flags, FLAG_SRS_INDEX);
-  return MsmJob{srs->basis(0) + (lo + i0 + d), q + i0, i1 - i0, slot};
+  return MsmJob{points, q + i0, i1 - i0, slot};
 }
 
 // openPoly (CommitmentScheme.hs:36-48).  Requires lo <= 0 <= lo+len-1 (callers extend the range to
@@ -141,7 +143,7 @@ MsmJob open_job_at_zero(hipStream_t st, const sonic_srs* srs, const Fr* poly, lo
   long i1 = d + 1;
   if (i1 > qn) i1 = qn;
   flag_nonzero_enqueue(st, poly + 1 + i1, qn - i1, d_flags, FLAG_SRS_INDEX);
-  return MsmJob{srs->basis(0) + d, poly + 1, i1, slot};
+  return MsmJob{srs_job_points("openPoly", srs, 0, 0, i1), poly + 1, i1, slot};
 }
 
 // openPoly for several openings over one exponent range as one batched set of launches (poly.hip, open_batch_enqueue); the jobs
@@ -282,6 +284,8 @@ int prover_admits(const char* who, const sonic_srs* srs, const CircuitView& c) {
     set_error("Parameter d is not large enough: %ld should be greater than %ld", (long)srs->d, (long)(7 * c.n));
     return SONIC_ERR_D_TOO_SMALL;
   }
+  // a view must hold the windows of this circuit (srs_view.hpp): refused here, not in the middle of a proof
+  if (circuit_args_ok(c) && srs->is_view() && !srs_view_admits(who, srs, c.n, c.Q)) return SONIC_ERR_INVALID_ARG;
   return circuit_validate(who, c);
 }
 
@@ -524,10 +528,10 @@ struct GroupQueue {
     const long d = srs->d;
     make_room();
     MsmJob job = commit_job(cur->st, srs, su, lo, len, d, &slots[L.C()], flags);      // (the index checks of the whole range)
-    job.points = srs->sym() + 1; job.scalars = su + (n + 1); job.n = n; job.table_stride = d + 1;
+    job.points = srs->sym() + 1; job.scalars = su + (n + 1); job.n = n; job.table_stride = srs->geo.sym_n();
     push(job, L.C());
     p->slot_ran[(size_t)L.C_extra()] = 1;
-    side([this, su, d, n] { msm_enqueue(p->st, p->runs_ws, msm_plan(L.Q), srs->basis(1) + (d + n + 1), su + (2 * n + 1), L.Q, true, &slots[L.C_extra()]); }, BEHIND_CHAIN);
+    side([this, su, n] { msm_enqueue(p->st, p->runs_ws, msm_plan(L.Q), srs->basis(1) + srs->geo.slot(n + 1), su + (2 * n + 1), L.Q, true, &slots[L.C_extra()]); }, BEHIND_CHAIN);
   }
   // fr: index of the evaluation in frout (-1: not reported); every rank with a piece of the opening computes it (the quotient
   // needs the prefix sums anyway), the rank whose piece starts at term 0 reports it
@@ -594,8 +598,8 @@ struct ProofPass {
   bool g0_queued = false;
   const Fr* pair(long i) const { return PR + 2 * i; }
   ProofPass(sonic_prover_t* p, const GroupQueue& q)
-      : n(p->n), Q(p->Q), d(p->srs->d), r_lo(-2 * n - 4), r_len(3 * n + 5), s_lo(-n), s_len(3 * n + 1), t_lo(-4 * n - 8), t_len(7 * n + 9),
-        u_lo(-n), u_len(2 * n + Q + 1), PR(p->PAIRS.as<Fr>()), need_j((size_t)Q, 0) {
+      : n(p->n), Q(p->Q), d(p->srs->d), r_lo(ProofLayout::r_lo(n)), r_len(ProofLayout::r_len(n)), s_lo(ProofLayout::s_lo(n)), s_len(ProofLayout::s_len(n)),
+        t_lo(ProofLayout::t_lo(n)), t_len(ProofLayout::t_len(n)), u_lo(ProofLayout::u_lo(n)), u_len(q.L.u_len(n)), PR(p->PAIRS.as<Fr>()), need_j((size_t)Q, 0) {
     const ProofLayout& L = q.L;
     need_su = q.own(L.C()) || q.own(L.Qv());
     for (long j = 0; j < Q; j++) {
@@ -826,7 +830,7 @@ static void decide_modes(sonic_prover_t* p) {
     const int mode = se ? atoi(se) : -1;
     // (round 6, n = 2^16 again, where a proof is one chain now: with / without 9.20-9.25 / 9.08-9.15 ms streamed, 10.44-10.51 / 10.49-10.80
     // one at a time -- still no gain below 2^17; profiles/r06_ab_small_final.txt)
-    p->sym_on = mode != 0 && (mode == 1 || p->n >= (1L << 17)) && p->share_world <= 1 && p->srs->sym().p != nullptr;
+    p->sym_on = mode != 0 && (mode == 1 || p->n >= (1L << 17)) && p->share_world <= 1 && p->srs->sym().p != nullptr && p->n < p->srs->geo.sym_n();
   }
   {
     const MsmPlan probe = srs_msm_plan(p->srs, 3 * p->n);
@@ -1540,7 +1544,7 @@ int sonic_prover_prepare(sonic_prover_t* p) {
     terms_scal.alloc(sizeof(Fr) * (nnz > 0 ? nnz : 1));
     HIP_OK(hipMemsetAsync(slots.p, 0, sizeof(MsmSlot) * Q, p->st));
     HIP_OK(hipStreamSynchronize(p->st));
-    const PointArray A = p->srs->basis(1) + d;                   // the alpha basis at exponent 0
+    const PointArray A = p->srs->basis(1) + p->srs->geo.centre();                   // the alpha basis at exponent 0
     long at = 0;
     for (long q = 0; q < Q; q++) {
       const int32_t seg[6] = {rp[q], rp[q + 1] - rp[q], rp[Q + q], rp[Q + q + 1] - rp[Q + q], rp[2 * Q + q], rp[2 * Q + q + 1] - rp[2 * Q + q]};

@@ -90,6 +90,8 @@ __global__ __launch_bounds__(256) void k_table_step(PointArray src, G1XYZZ* __re
 }
 
 // ---- running sums of the alpha basis (round 5): ps[i] = A[0] + ... + A[i] in storage order (exponents -d .. i - d) ---------------
+// (over SLOTS: in a view -- srs_view.hpp -- the high window follows the low one.  Only differences inside one job's run are ever used,
+// and a job never straddles two windows.)
 // commitPoly of a polynomial with a RUN of equal coefficients c over exponents [a, b] contributes c (A[a] + ... + A[b]) =
 // c ps[b] - c ps[a - 1]: two terms instead of b - a + 1 (prove.hip, the unprepared S_j: rndCircuit's all-ones weight rows make 2n of
 // the 3n + 1 coefficients of s(X, y_j) two values, test/Test/Reference.hs:141-155).  One more table of 2d + 1 affine points.
@@ -122,7 +124,7 @@ __global__ __launch_bounds__(256) void k_ps_apply(G1XYZZ* __restrict__ x, const 
 void srs_build_prefix(hipStream_t st, sonic_srs* s) {
   PointArrayMut ps = s->prefix_mut();
   if (!ps.p) return;
-  const long n = 2 * s->d + 1;
+  const long n = s->geo.npts();
   const long SLAB = 1L << 20;
   const long cap = n < SLAB ? n : SLAB, ccap = ceil_div(cap, PS_CHUNK);
   DevBuf x(sizeof(G1XYZZ) * cap), pref(sizeof(Fq) * cap), t0(sizeof(G1XYZZ) * ccap), t1(sizeof(G1XYZZ) * ccap), carry(sizeof(G1XYZZ));
@@ -150,17 +152,18 @@ void srs_build_prefix(hipStream_t st, sonic_srs* s) {
 // points apart -- the job over them shares a batched chain with the openings of the same polynomial and tells the kernels its own table
 // stride (MsmJob::table_stride).  Up to round 5 the tables were laid out like a basis, 2d + 1 slots each, half of them never touched:
 // 3.5 GB at d = 2^21 that were allocated, cleared and copied to every replica.
-__global__ __launch_bounds__(256) void k_sym_sum(PointArray A, long d, long e0, long m, G1XYZZ* __restrict__ out) {
+// (centre: the slot of exponent 0; the caller keeps e0 + m - 1 inside the window around it)
+__global__ __launch_bounds__(256) void k_sym_sum(PointArray A, long centre, long e0, long m, G1XYZZ* __restrict__ out) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= m) return;
   const long e = e0 + i;
-  out[i] = g1_add_mixed(G1XYZZ::from_affine(A[(size_t)(d + e)]), A[(size_t)(d - e)]);
+  out[i] = g1_add_mixed(G1XYZZ::from_affine(A[(size_t)(centre + e)]), A[(size_t)(centre - e)]);
 }
 void srs_build_sym(hipStream_t st, sonic_srs* s) {
   PointArrayMut sym = s->sym_mut();
   if (!sym.p) return;
   const int W = s->tab_W;
-  const long d = s->d, n = d + 1;                          // points per table: exponents 0 .. d
+  const long n = s->geo.sym_n(), d = n - 1;                // points per table: exponents 0 .. d of a whole string, 0 .. min(hi, -lo) of a view's low window
   for (int w = 0; w < W; w++) HIP_OK(hipMemsetAsync((sym + (long)((size_t)w * n)).p, 0, sym.stride, st));      // slot 0 of every table: infinity
   const long SLAB = 1L << 20;
   const long cap = d < SLAB ? d : SLAB;
@@ -168,7 +171,7 @@ void srs_build_sym(hipStream_t st, sonic_srs* s) {
   const PointArray A = s->basis(1);
   for (long base = 0; base < d; base += SLAB) {              // exponents e = 1 + base ...
     const long m = d - base < SLAB ? d - base : SLAB;
-    LAUNCH(k_sym_sum, ceil_div(m, 256), 256, 0, st, A, d, 1 + base, m, x.as<G1XYZZ>());
+    LAUNCH(k_sym_sum, ceil_div(m, 256), 256, 0, st, A, (long)s->geo.centre(), 1 + base, m, x.as<G1XYZZ>());
     LAUNCH(k_batch_affine, ceil_div(ceil_div(m, 64), 64), 64, 0, st, (const G1XYZZ*)x.as<G1XYZZ>(), sym + (1 + base), pref.as<Fq>(), m);
   }
   for (int w = 1; w < W; w++)
@@ -187,7 +190,7 @@ void srs_build_tables(hipStream_t st, sonic_srs* s) {
   const int W = s->tab_W, c = s->tab_c;
   if (getenv("SONIC_DEBUG_TIMING")) fprintf(stderr, "[sonic] window tables: c=%d W=%d d=%ld\n", c, W, (long)s->d);
   if (W <= 1) return;
-  const long n = 2 * s->d + 1;
+  const long n = s->geo.npts();
   const long SLAB = 1L << 20;
   const long cap = n < SLAB ? n : SLAB;
   DevBuf x(sizeof(G1XYZZ) * cap), pref(sizeof(Fq) * cap);

@@ -31,24 +31,28 @@ int srs_cached_id(const sonic_srs* s, int (*make)(const sonic_srs*, uint8_t*), u
 }
 
 // read the knobs, then ask, allocate, ask, allocate, ask, allocate: the free memory is read again before every question (srs_policy.hpp)
-sonic_srs* srs_alloc(int64_t d) {
-  sonic_srs* s = new sonic_srs();
-  s->d = d;
+// (a whole string: view_n = 0, the width by d; a view: the width by its n, srs_view_window_policy; the memory questions by the point
+// counts of the geometry either way)
+static sonic_srs* srs_alloc_geo(const SrsGeometry& geo, int64_t view_n) {
+  std::unique_ptr<sonic_srs> s(new sonic_srs());
+  s->d = geo.d; s->geo = geo; s->view_n = view_n;
   s->device = current_ctx().dev;
   const SrsKnobs knobs = srs_knobs_from_env();
-  const size_t n = (size_t)(2 * d + 1);
+  const size_t n = (size_t)geo.npts(), sym_n = (size_t)geo.sym_n();
   size_t free_b = 0, total_b = 0;
   (void)hipMemGetInfo(&free_b, &total_b);
-  const SrsWindows win = srs_window_policy(d, free_b, knobs);
+  const SrsWindows win = view_n ? srs_view_window_policy(view_n, geo.npts(), free_b, knobs) : srs_window_policy(geo.d, n, free_b, knobs);
   s->tab_c = win.c; s->tab_W = win.W; s->tab_endo = win.endo;
   s->g.alloc((size_t)SONIC_SRS_POINT_BYTES * n * win.W);
   s->ga.alloc((size_t)SONIC_SRS_POINT_BYTES * n * win.W);
   (void)hipMemGetInfo(&free_b, &total_b);
-  if (srs_holds_prefix(d, free_b, knobs)) s->ps.alloc(srs_prefix_bytes(d));
+  if (srs_holds_prefix_of(n, free_b, knobs)) s->ps.alloc(srs_prefix_bytes_of(n));
   (void)hipMemGetInfo(&free_b, &total_b);
-  if (srs_holds_sym(d, win.W, win.endo, free_b, knobs)) s->gs.alloc(srs_sym_bytes(d, win.W));
-  return s;
+  if (srs_holds_sym_of(sym_n, win.W, win.endo, free_b, knobs)) s->gs.alloc(srs_sym_bytes_of(sym_n, win.W));
+  return s.release();
 }
+sonic_srs* srs_alloc(int64_t d) { return srs_alloc_geo(srs_full_geometry(d), 0); }
+sonic_srs* srs_alloc_view(int64_t d, int64_t n, int64_t Q) { return srs_alloc_geo(srs_view_geometry(d, n, Q), n); }
 
 // plan for an MSM over n consecutive SRS points: shared-bucket plan over the window tables unless the MSM is
 // tiny compared with the bucket set, the tables are off, or a test forces a window size
@@ -61,7 +65,7 @@ MsmPlan srs_msm_plan(const sonic_srs* s, long n) {
   // own criterion shape, n = 1 / d = 25, paid fifteen times per proof: profiles/r05_criterion_shape.txt.  Over the tables the same MSM
   // is a batchable job whose cost is the butterfly over the shared bucket set: 0.12 ms at 2^16 buckets, 0.55 ms at 2^19.)
   if (s->tab_W > 1 && s->tab_W <= MSM_TABLE_MAX_WINDOWS && n < MSM_TABLE_MAX_TERMS && msm_window_override() == 0)
-    return msm_plan_tables(n > 0 ? n : 1, s->tab_c, s->tab_W, 2 * s->d + 1, s->tab_endo);
+    return msm_plan_tables(n > 0 ? n : 1, s->tab_c, s->tab_W, s->geo.npts(), s->tab_endo);
   return msm_plan(n > 0 ? n : 1);
 }
 }  // namespace sonic
@@ -93,7 +97,7 @@ int sonic_srs_from_points(int64_t d, const uint8_t* basis0, const uint8_t* basis
 // both bases, the error bits the head and the walk have collected in `err` (1 non-canonical or malformed, 2 off the curve, 4 outside the
 // subgroup, 8 infinity where none may be), then the window tables.  Takes the handle: it is deleted when the points are refused.
 static int srs_finish_g1(const char* who, hipStream_t st, sonic_srs* s, DevBuf& err, sonic_srs_t** out) {
-  const long n = 2 * s->d + 1;
+  const long n = s->geo.npts();
   for (int b = 0; b < 2; b++) points_subgroup_check_enqueue(st, s->basis(b), n, err.as<int>());
   const int herr = read_flags(st, err);
   if (herr) {
@@ -136,6 +140,12 @@ int sonic_srs_get_points(const sonic_srs_t* srs, int basis, int64_t e0, int64_t 
   if (!srs || !out || n < 0) return SONIC_ERR_INVALID_ARG;
   if (!srs_range_ok("sonic_srs_get_points", srs, e0, n)) return SONIC_ERR_SRS_INDEX;
   if (n == 0) return SONIC_OK;
+  const bool sym_read = basis == SONIC_BASIS_ALPHA_SYM;            // (reads exponents max(e0, 0) .. of its own table)
+  if (!sym_read && !srs_held_ok("sonic_srs_get_points", srs, e0, n)) return SONIC_ERR_INVALID_ARG;
+  if (sym_read && e0 + n > srs->geo.sym_n()) {
+    set_error("sonic_srs_get_points: this view of the SRS holds the symmetric sums of exponents 0 .. %ld, asked for [%ld, %ld]", (long)srs->geo.sym_n() - 1, (long)e0, (long)(e0 + n - 1));
+    return SONIC_ERR_INVALID_ARG;
+  }
   CallLease lease;
   hipStream_t st = lease.st();
   DevBuf raw(96 * n);
@@ -149,11 +159,11 @@ int sonic_srs_get_points(const sonic_srs_t* srs, int basis, int64_t e0, int64_t 
     src = srs->sym() + lo;
   } else if (basis == SONIC_BASIS_ALPHA_PREFIX) {     // diagnostic: the running sums of the alpha basis (srs_build_prefix)
     if (!srs->ps.p) { set_error("sonic_srs_get_points: this SRS holds no running sums"); return SONIC_ERR_INVALID_ARG; }
-    src = srs->prefix() + (e0 + srs->d);
+    src = srs->prefix() + srs->geo.slot(e0);
   } else {                                     // diagnostic: basis = b + 2 w reads window table w (2^(c w) multiples) of basis b
     const int w = basis >> 1;
     if (w >= srs->tab_W) { set_error("sonic_srs_get_points: no window table %d", w); return SONIC_ERR_INVALID_ARG; }
-    src = srs->basis(basis & 1) + (size_t)w * (2 * srs->d + 1) + (e0 + srs->d);
+    src = srs->basis(basis & 1) + (size_t)w * srs->geo.npts() + srs->geo.slot(e0);
   }
   points_to_bytes_enqueue(st, src, raw.as<uint8_t>() + 96 * (lo - e0), (long)(e0 + n - lo));
   HIP_OK(hipMemcpyAsync(out, raw.p, 96 * n, hipMemcpyDeviceToHost, st));
@@ -165,6 +175,7 @@ int sonic_srs_get_points(const sonic_srs_t* srs, int basis, int64_t e0, int64_t 
 static int srs_ensure_g2(const sonic_srs_t* srs, hipStream_t st, const char* who) {
   std::lock_guard<std::mutex> g2(srs->g2_mu);
   if (srs->h.p) return SONIC_OK;
+  if (srs->is_view()) { set_error("%s: this view of the SRS has no G2 half (the string it was made from could not supply one)", who); return SONIC_ERR_INVALID_ARG; }
   if (!srs->have_trapdoor) { set_error("%s: this SRS has no G2 half (built from G1 points only)", who); return SONIC_ERR_INVALID_ARG; }
   const size_t cnt = (size_t)(2 * srs->d + 1);
   // generated into local buffers and attached only when the generation has finished: a failure half way (e.g. no memory for
@@ -189,7 +200,17 @@ int sonic_srs_get_g2_points(const sonic_srs_t* srs, int basis, int64_t e0, int64
   if (rc) return rc;
   if (n == 0) return SONIC_OK;
   DevBuf raw(192 * n);
-  g2_points_to_bytes_enqueue(st, (basis ? srs->ha : srs->h).as<G2Affine>() + (e0 + srs->d), raw.as<uint8_t>(), n);
+  int64_t at = e0 + srs->d;
+  if (srs->is_view()) {                 // two elements per basis, and nothing else
+    const SrsViewG2 q = srs_view_g2(srs->d, srs->view_n);
+    at = n == 1 && e0 == q.e[basis][0] ? 0 : n == 1 && e0 == q.e[basis][1] ? 1 : -1;
+    if (at < 0) {
+      set_error("sonic_srs_get_g2_points: exponent range [%ld, %ld] of basis %d is not held by this view of the SRS: it holds %ld and %ld", (long)e0,
+                (long)(e0 + n - 1), basis, (long)q.e[basis][0], (long)q.e[basis][1]);
+      return SONIC_ERR_INVALID_ARG;
+    }
+  }
+  g2_points_to_bytes_enqueue(st, (basis ? srs->ha : srs->h).as<G2Affine>() + at, raw.as<uint8_t>(), n);
   HIP_OK(hipMemcpyAsync(out, raw.p, 192 * n, hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));
   API_END
@@ -213,6 +234,7 @@ static int srs_attach_g2(const char* who, hipStream_t st, sonic_srs_t* srs, DevB
 int sonic_srs_set_g2_points(sonic_srs_t* srs, const uint8_t* basis0, const uint8_t* basis1) {
   API_BEGIN_ON(srs_device(srs))
   if (!srs || !basis0 || !basis1) return SONIC_ERR_INVALID_ARG;
+  if (srs->is_view()) { set_error("sonic_srs_set_g2_points: a circuit-sized view is not a reference string (attach the G2 half to the string and make the view from it)"); return SONIC_ERR_INVALID_ARG; }
   std::lock_guard<std::mutex> g(call_mutex());
   hipStream_t st = default_stream();
   const long n = 2 * srs->d + 1;
@@ -238,6 +260,7 @@ int sonic_srs_has_g2(const sonic_srs_t* srs) {
 int sonic_srs_save(const sonic_srs_t* srs, const char* path, int with_g2) {
   API_BEGIN_ON(srs_device(srs))
   if (!srs || !path || with_g2 < 0 || with_g2 > 2) return SONIC_ERR_INVALID_ARG;
+  if (srs->is_view()) { set_error("sonic_srs_save: a circuit-sized view is not a reference string and has no container"); return SONIC_ERR_INVALID_ARG; }
   if (with_g2 == 2) with_g2 = sonic_srs_has_g2(srs) ? 1 : 0;          // "if the handle has (or can generate) it"
   if (with_g2) {
     std::lock_guard<std::mutex> g(call_mutex());
@@ -268,6 +291,7 @@ int sonic_srs_save(const sonic_srs_t* srs, const char* path, int with_g2) {
 int sonic_srs_save_compressed(const sonic_srs_t* srs, const char* path, int with_g2) {
   API_BEGIN_ON(srs_device(srs))
   if (!srs || !path || with_g2 < 0 || with_g2 > 2) return SONIC_ERR_INVALID_ARG;
+  if (srs->is_view()) { set_error("sonic_srs_save_compressed: a circuit-sized view is not a reference string and has no container"); return SONIC_ERR_INVALID_ARG; }
   if (with_g2 == 2) with_g2 = sonic_srs_has_g2(srs) ? 1 : 0;
   std::lock_guard<std::mutex> g(call_mutex());
   hipStream_t st = default_stream();
@@ -389,7 +413,7 @@ int sonic_srs_replicate(const sonic_srs_t* srs, int device, sonic_srs_t** out) {
   DeviceCtx& ctx = current_ctx();
   std::lock_guard<std::mutex> g(ctx.call_mu);
   std::unique_ptr<sonic_srs> r(new sonic_srs());
-  r->d = srs->d; r->device = ctx.dev;
+  r->d = srs->d; r->geo = srs->geo; r->view_n = srs->view_n; r->device = ctx.dev;
   r->tab_c = srs->tab_c; r->tab_W = srs->tab_W; r->tab_endo = srs->tab_endo;
   r->g.alloc(srs->g.bytes); r->ga.alloc(srs->ga.bytes);
   HIP_OK(hipMemcpyPeer(r->g.p, ctx.dev, srs->g.p, srs->device, srs->g.bytes));
@@ -409,6 +433,131 @@ int sonic_srs_replicate(const sonic_srs_t* srs, int device, sonic_srs_t** out) {
   HIP_OK(hipDeviceSynchronize());
   *out = r.release();
   API_END
+}
+
+// ---- circuit-sized views (srs_view.hpp): the same d, the same Fiat-Shamir id, the same commitments and proofs, over copies of only the
+// exponent windows a circuit of (n, Q) touches, with window tables, running sums and symmetric sums sized for those windows ------------
+static int view_args_ok(const char* who, int64_t d, int64_t n, int64_t Q) {
+  if (n < 1 || Q < 1) { set_error("%s: a circuit has n >= 1 and Q >= 1, got n = %ld, Q = %ld", who, (long)n, (long)Q); return SONIC_ERR_INVALID_ARG; }
+  if (n > SRS_FILE_MAX_D || Q > SRS_FILE_MAX_D) { set_error("%s: n = %ld, Q = %ld is no circuit size", who, (long)n, (long)Q); return SONIC_ERR_INVALID_ARG; }
+  const int64_t need = srs_view_d_needed(d, n);
+  if (need) {
+    set_error("%s: d = %ld is too small for a circuit of n = %ld: it needs d >= %ld (7n for the prover, 4n + 8 for the blinders of t)", who, (long)d, (long)n, (long)need);
+    return SONIC_ERR_INVALID_ARG;
+  }
+  return SONIC_OK;
+}
+// the four G2 points of a view from their 192-byte encodings (basis-major), validated like every G2 half that is attached
+static int view_attach_g2(const char* who, hipStream_t st, sonic_srs* v, const uint8_t* bytes) {
+  DevBuf raw(192 * 4), err(4), h0(sizeof(G2Affine) * 2), h1(sizeof(G2Affine) * 2);
+  HIP_OK(hipMemsetAsync(err.p, 0, 4, st));
+  HIP_OK(hipMemcpyAsync(raw.p, bytes, 192 * 4, hipMemcpyHostToDevice, st));
+  g2_points_from_bytes_enqueue(st, raw.as<uint8_t>(), h0.as<G2Affine>(), 2, err.as<int>());
+  g2_points_from_bytes_enqueue(st, raw.as<uint8_t>() + 192 * 2, h1.as<G2Affine>(), 2, err.as<int>());
+  return srs_attach_g2(who, st, v, err, h0, h1);
+}
+
+int sonic_srs_for_circuit(const sonic_srs_t* srs, int64_t n, int64_t Q, sonic_srs_t** out) {
+  API_BEGIN_ON(srs_device(srs))
+  if (!srs || !out) { set_error("sonic_srs_for_circuit: bad argument"); return SONIC_ERR_INVALID_ARG; }
+  int rc = view_args_ok("sonic_srs_for_circuit", srs->d, n, Q);
+  if (rc) return rc;
+  const SrsGeometry geo = srs_view_geometry(srs->d, n, Q);
+  if (!srs_held_ok("sonic_srs_for_circuit", srs, geo.lo0, geo.len0()) || !srs_held_ok("sonic_srs_for_circuit", srs, geo.lo1, geo.len1())) return SONIC_ERR_INVALID_ARG;
+  // the G2 half the way a verifier asks for it (generated on first use where the source still has its trapdoor); a source that cannot
+  // supply all four gives a view without one
+  uint8_t g2[192 * 4];
+  bool with_g2 = sonic_srs_has_g2(srs) != 0;
+  const SrsViewG2 q = srs_view_g2(srs->d, n);
+  for (int b = 0; b < 2 && with_g2; b++)
+    for (int i = 0; i < 2 && with_g2; i++) with_g2 = sonic_srs_get_g2_points(srs, b, q.e[b][i], 1, g2 + 192 * (2 * b + i)) == SONIC_OK;
+  std::lock_guard<std::mutex> g(call_mutex());
+  hipStream_t st = default_stream();
+  std::unique_ptr<sonic_srs> v(srs_alloc_view(srs->d, n, Q));
+  const size_t pb = SONIC_SRS_POINT_BYTES;
+  for (int b = 0; b < 2; b++) {            // table 0 of both bases, window by window (windows are contiguous in both handles)
+    const char* from = srs->basis(b).p;
+    char* to = v->basis_mut(b).p;
+    HIP_OK(hipMemcpyAsync(to, from + pb * (size_t)srs->geo.slot(geo.lo0), pb * (size_t)geo.len0(), hipMemcpyDeviceToDevice, st));
+    if (geo.two()) HIP_OK(hipMemcpyAsync(to + pb * (size_t)geo.len0(), from + pb * (size_t)srs->geo.slot(geo.lo1), pb * (size_t)geo.len1(), hipMemcpyDeviceToDevice, st));
+  }
+  srs_build_tables(st, v.get());          // (synchronises: the source may be freed from here on)
+  if (with_g2) {
+    rc = view_attach_g2("sonic_srs_for_circuit", st, v.get(), g2);
+    if (rc) return rc;
+  }
+  *out = v.release();
+  API_END
+}
+
+int sonic_srs_load_for_circuit(const char* path, int64_t n, int64_t Q, sonic_srs_t** out) { return sonic_srs_load_for_circuit_on(-1, path, n, Q, out); }
+int sonic_srs_load_for_circuit_on(int device, const char* path, int64_t n, int64_t Q, sonic_srs_t** out) {
+  API_BEGIN_ON(device)
+  if (!path || !out) { set_error("sonic_srs_load_for_circuit: bad argument"); return SONIC_ERR_INVALID_ARG; }
+  int rc = view_args_ok("sonic_srs_load_for_circuit", SRS_FILE_MAX_D, n, Q);          // (d is the file's to say: srs_view_file_read)
+  if (rc) return rc;
+  SrsViewFile file;
+  std::string why;
+  const int frc = srs_view_file_read(path, n, Q, file, why);       // header against the real file size, then only the windows' byte ranges
+  if (frc) { set_error("sonic_srs_load_for_circuit: %s", why.c_str()); return frc == 1 || frc == 4 ? SONIC_ERR_INVALID_ARG : SONIC_ERR_BAD_ENCODING; }
+  std::lock_guard<std::mutex> g(call_mutex());
+  hipStream_t st = default_stream();
+  const int64_t d = file.head.d;
+  sonic_srs* s = srs_alloc_view(d, n, Q);
+  const long npts = s->geo.npts(), hole = s->geo.centre();          // basis 1 has the empty slot e = 0 (SRS.hs:38); basis 0 has none
+  DevBuf err(4);
+  try {
+    if (file.head.compressed) {
+      int herr = 0;
+      for (int b = 0; b < 2; b++)
+        srs_zload_vector(st, file.g[b], 48, npts, b ? hole : -2L, &herr, [&](const uint8_t* in, uint8_t* fl, long i, long m) {
+          g1_decompress_enqueue(st, in, s->basis_mut(b) + i, nullptr, fl, m, false);
+        });
+      HIP_OK(hipMemcpyAsync(err.p, &herr, 4, hipMemcpyHostToDevice, st));
+      HIP_OK(hipStreamSynchronize(st));
+    } else {
+      DevBuf raw(96 * (size_t)npts);
+      HIP_OK(hipMemsetAsync(err.p, 0, 4, st));
+      for (int b = 0; b < 2; b++) {
+        HIP_OK(hipMemcpyAsync(raw.p, file.g[b].data(), 96 * (size_t)npts, hipMemcpyHostToDevice, st));
+        points_from_bytes_enqueue(st, raw.as<uint8_t>(), s->basis_mut(b), npts, err.as<int>(), b ? hole : -2L);
+      }
+      HIP_OK(hipStreamSynchronize(st));
+    }
+  } catch (...) { delete s; throw; }
+  rc = srs_finish_g1("sonic_srs_load_for_circuit", st, s, err, &s);          // r P = O for every point read, then the tables
+  if (rc) return rc;
+  std::unique_ptr<sonic_srs> v(s);
+  if (file.head.has_g2()) {
+    if (file.head.compressed) {
+      DevBuf h0(sizeof(G2Affine) * 2), h1(sizeof(G2Affine) * 2);
+      int herr = 0;
+      const std::vector<uint8_t> half[2] = {std::vector<uint8_t>(file.g2.begin(), file.g2.begin() + 192), std::vector<uint8_t>(file.g2.begin() + 192, file.g2.end())};
+      for (int b = 0; b < 2; b++)
+        srs_zload_vector(st, half[b], 96, 2, -2L, &herr, [&](const uint8_t* in, uint8_t* fl, long i, long m) {
+          g2_decompress_enqueue(st, in, (b ? h1 : h0).as<G2Affine>() + i, nullptr, fl, m, true);
+        });
+      HIP_OK(hipMemcpyAsync(err.p, &herr, 4, hipMemcpyHostToDevice, st));
+      HIP_OK(hipStreamSynchronize(st));
+      rc = srs_attach_g2("sonic_srs_load_for_circuit", st, v.get(), err, h0, h1);
+    } else {
+      rc = view_attach_g2("sonic_srs_load_for_circuit", st, v.get(), file.g2.data());
+    }
+    if (rc) return rc;
+  }
+  *out = v.release();
+  API_END
+}
+
+int sonic_srs_windows(const sonic_srs_t* srs, int64_t out[4]) {
+  if (!srs || !out) return SONIC_ERR_INVALID_ARG;
+  out[0] = srs->geo.lo0; out[1] = srs->geo.hi0; out[2] = srs->geo.lo1; out[3] = srs->geo.hi1;
+  return SONIC_OK;
+}
+int sonic_srs_device_bytes(const sonic_srs_t* srs, size_t* out) {
+  if (!srs || !out) return SONIC_ERR_INVALID_ARG;
+  *out = srs->g.bytes + srs->ga.bytes + srs->ps.bytes + srs->gs.bytes;
+  return SONIC_OK;
 }
 
 int sonic_srs_point_bytes(void) { return SONIC_SRS_POINT_BYTES; }

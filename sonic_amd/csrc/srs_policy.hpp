@@ -28,8 +28,10 @@ struct SrsWindows { int c, W; bool endo; };
 
 // Window tables trade HBM capacity (288 GB) for work: W x the SRS size buys one shared bucket set per MSM.
 // c grows with d (MSM sizes are a fraction of d); off with SONIC_MSM_TABLES=0 or when memory is short.
-inline SrsWindows srs_window_policy(int64_t d, size_t free_bytes, const SrsKnobs& k) {
-  const size_t n = (size_t)(2 * d + 1);
+// (d decides the width; npts, the points a table holds, is what the memory questions are asked with: 2d + 1 for a whole string, fewer
+// for a circuit-sized view of one, srs_view.hpp)
+inline SrsWindows srs_window_policy(int64_t d, size_t npts, size_t free_bytes, const SrsKnobs& k) {
+  const size_t n = npts;
   int lg = 0;
   while ((2L << lg) <= d) lg++;                 // floor(log2 d)
   // measured (prove at n = d/8, profiles/r05_table_c_ab.txt): up to d = 2^19 the MSMs (0.4 d .. 0.9 d terms) run best with ~2^16
@@ -61,17 +63,23 @@ inline SrsWindows srs_window_policy(int64_t d, size_t free_bytes, const SrsKnobs
   else { c = 0; W = 1; }
   return SrsWindows{c, W, endo};
 }
+inline SrsWindows srs_window_policy(int64_t d, size_t free_bytes, const SrsKnobs& k) { return srs_window_policy(d, (size_t)(2 * d + 1), free_bytes, k); }
 
 // the running sums of the alpha basis: one more table, where 1/13 of what the window tables took is still to be had
-inline size_t srs_prefix_bytes(int64_t d) { return (size_t)SONIC_SRS_POINT_BYTES * (size_t)(2 * d + 1); }
-inline bool srs_holds_prefix(int64_t d, size_t free_bytes, const SrsKnobs& k) { return k.prefix != 0 && srs_prefix_bytes(d) <= free_bytes / 4; }
+inline size_t srs_prefix_bytes_of(size_t npts) { return (size_t)SONIC_SRS_POINT_BYTES * npts; }
+inline size_t srs_prefix_bytes(int64_t d) { return srs_prefix_bytes_of((size_t)(2 * d + 1)); }
+inline bool srs_holds_prefix_of(size_t npts, size_t free_bytes, const SrsKnobs& k) { return k.prefix != 0 && srs_prefix_bytes_of(npts) <= free_bytes / 4; }
+inline bool srs_holds_prefix(int64_t d, size_t free_bytes, const SrsKnobs& k) { return srs_holds_prefix_of((size_t)(2 * d + 1), free_bytes, k); }
 
 // the symmetric sums of the alpha basis with window tables of their own: half of what the two bases took, where a quarter of the rest holds it
 // (only with the full tables: the job over them shares a batched chain with jobs over the bases)
 // (round 6: d + 1 slots per window -- exponents 0 .. d -- instead of a whole basis of 2d + 1)
-inline size_t srs_sym_bytes(int64_t d, int W) { return (size_t)SONIC_SRS_POINT_BYTES * (size_t)(d + 1) * (size_t)W; }
-inline bool srs_holds_sym(int64_t d, int W, bool endo, size_t free_bytes, const SrsKnobs& k) {
-  return k.sym != 0 && W > 1 && !endo && srs_sym_bytes(d, W) <= free_bytes / 4;
+// (sym_n: the slots of one table, exponents 0 .. sym_n - 1; d + 1 for a whole string)
+inline size_t srs_sym_bytes_of(size_t sym_n, int W) { return (size_t)SONIC_SRS_POINT_BYTES * sym_n * (size_t)W; }
+inline size_t srs_sym_bytes(int64_t d, int W) { return srs_sym_bytes_of((size_t)(d + 1), W); }
+inline bool srs_holds_sym_of(size_t sym_n, int W, bool endo, size_t free_bytes, const SrsKnobs& k) {
+  return k.sym != 0 && W > 1 && !endo && srs_sym_bytes_of(sym_n, W) <= free_bytes / 4;
 }
+inline bool srs_holds_sym(int64_t d, int W, bool endo, size_t free_bytes, const SrsKnobs& k) { return srs_holds_sym_of((size_t)(d + 1), W, endo, free_bytes, k); }
 
 }  // namespace sonic

@@ -77,10 +77,41 @@ class SRS:
         _lib.check(save(self._h, str(path).encode(), 2 if g2 is None else (1 if g2 else 0)))
 
     @classmethod
-    def load(cls, path: str, device: int = -1) -> "SRS":
+    def load(cls, path: str, device: int = -1, circuit=None) -> "SRS":
+        """read either container.  circuit=(n, Q): a circuit-sized view (see for_circuit) made by reading only the byte ranges of its
+        windows, and the four G2 points where the file has a G2 half (sonic_srs_load_for_circuit_on)"""
         h = C.c_void_p()
-        _lib.check(_lib.lib().sonic_srs_load_on(device, str(path).encode(), C.byref(h)))
+        if circuit is None:
+            _lib.check(_lib.lib().sonic_srs_load_on(device, str(path).encode(), C.byref(h)))
+        else:
+            n, Q = circuit
+            _lib.check(_lib.lib().sonic_srs_load_for_circuit_on(device, str(path).encode(), n, Q, C.byref(h)))
         return cls(h, int(_lib.lib().sonic_srs_d(h)))
+
+    def for_circuit(self, n: int, Q: int) -> "SRS":
+        """a circuit-sized VIEW of this string on the same GPU (sonic_srs_for_circuit): the same d, Fiat-Shamir id, commitments and
+        proofs, over copies of only the exponents a circuit of (n, Q) touches -- [-4n-8, max(3n, n+Q)] and [d-3n-4, d] -- with tables
+        sized for those windows and the window width of a string of d = 8n.  The view owns what it holds: this handle may be closed.
+        It needs d >= max(7n, 4n + 8); it refuses (SONIC_ERR_INVALID_ARG) exponents it does not hold, provers for circuits whose
+        windows it does not contain, verifiers for another n, save() and set_g2_points().  Measured against the whole string in
+        profiles/r14_srs_view.txt (README, "Circuit-sized SRS views")."""
+        h = C.c_void_p()
+        _lib.check(_lib.lib().sonic_srs_for_circuit(self._h, n, Q, C.byref(h)))
+        return SRS(h, self.srsD)
+
+    @property
+    def windows(self):
+        """(lo0, hi0, lo1, hi1): the exponent windows the handle holds; one window -- every whole string: (-d, d) -- has lo1 = 1, hi1 = 0"""
+        w = (C.c_int64 * 4)()
+        _lib.check(_lib.lib().sonic_srs_windows(self._h, w))
+        return tuple(int(v) for v in w)
+
+    @property
+    def device_bytes(self) -> int:
+        """device memory of the G1 side: both bases with their window tables, the running sums, the symmetric sums"""
+        out = C.c_size_t()
+        _lib.check(_lib.lib().sonic_srs_device_bytes(self._h, C.byref(out)))
+        return int(out.value)
 
     def points(self, basis: int, e0: int, n: int) -> np.ndarray:
         out = np.zeros((n, 96), np.uint8)
