@@ -62,6 +62,8 @@ module Sonic.HIP
   , witnessDigest, submitFs, collectFs, proveBatchFs
     -- * witness sources
   , WitnessSrc(..), setWitnessI64, proveBatchI64
+    -- * core proofs
+  , CoreProof(..), coreOf, decodeCoreProof, encodeCoreProof, proveCore, submitCore, collectCore, proveCoreFs, verifyCore, verifyCoreBatch
   ) where
 
 import Protolude hiding (check)
@@ -160,6 +162,12 @@ foreign import ccall safe   "sonic_prove_batch_src"       c_prove_batch_src :: P
 foreign import ccall safe   "sonic_verifier_new_csr"      c_verifier_new_csr :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr (Ptr VerifierHandle) -> IO CInt
 foreign import ccall safe   "&sonic_verifier_free"        p_verifier_free  :: FunPtr (Ptr VerifierHandle -> IO ())
 foreign import ccall safe   "sonic_verifier_verify_batch_cs" c_verify_batch_cs :: Ptr VerifierHandle -> Int64 -> Ptr Word8 -> CInt -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_prover_prove_core"     c_prover_prove_core :: Ptr ProverHandle -> Ptr Word8 -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_prover_submit_core"    c_prover_submit_core :: Ptr ProverHandle -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_prover_collect_core"   c_prover_collect_core :: Ptr ProverHandle -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_prover_prove_core_fs"  c_prover_prove_core_fs :: Ptr ProverHandle -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_verify_core_csr"       c_verify_core_csr :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> IO CInt
+foreign import ccall safe   "sonic_verifier_verify_core_batch" c_verify_core_batch :: Ptr VerifierHandle -> Int64 -> Ptr Word8 -> CInt -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_verifier_verify_fs_batch_cs" c_verify_fs_batch_cs :: Ptr VerifierHandle -> Int64 -> Ptr Word8 -> CInt -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> Ptr Word8 -> IO CInt
 
 -- ---------------------------------------------------------------------------------------------------------------------
@@ -864,6 +872,96 @@ verifyFsBatchStatements Verifier{..} sts = do
       alloca $ \acc -> do
         each <- BSI.create k $ \out -> check =<< c_verify_fs_batch_cs v (fromIntegral k) ppf 0 pcs nullPtr acc out
         pure (map (/= 0) (BS.unpack each))
+
+-- ---------------------------------------------------------------------------------------------------------------------
+-- core proofs (include/sonic_hip.h, "Core proofs"): the head of a `Proof` -- R, T, a, W_a, b, W_b, W_t, s -- and no signature.  Nothing
+-- that `verify` checks ties a proof's s to s(z, y); `verifyCore` evaluates s(z, y) itself, rejects a proof whose s differs and checks
+-- the three pcV equations of the head.  `verifyCore srs circuit (coreOf proof) y z` is the sound check of an existing full proof.
+-- ---------------------------------------------------------------------------------------------------------------------
+data CoreProof = CoreProof
+  { cpR :: G1 BLS12381, cpT :: G1 BLS12381, cpA :: Fr, cpWa :: G1 BLS12381, cpB :: Fr, cpWb :: G1 BLS12381, cpWt :: G1 BLS12381, cpS :: Fr }
+
+-- | the head of a full proof
+coreOf :: Proof -> CoreProof
+coreOf Proof{..} = CoreProof { cpR = prR, cpT = prT, cpA = prA, cpWa = prWa, cpB = prB, cpWb = prWb, cpWt = prWt, cpS = prS }
+
+-- | 5 G1 + 3 Fr = 576 bytes, whatever Q is
+decodeCoreProof :: ByteString -> CoreProof
+decodeCoreProof b0 =
+  let (r, b1)  = takeG b0
+      (t, b2)  = takeG b1
+      (a, b3)  = takeF b2
+      (wa, b4) = takeG b3
+      (b, b5)  = takeF b4
+      (wb, b6) = takeG b5
+      (wt, b7) = takeG b6
+      (s, _)   = takeF b7
+  in CoreProof { cpR = r, cpT = t, cpA = a, cpWa = wa, cpB = b, cpWb = wb, cpWt = wt, cpS = s }
+
+encodeCoreProof :: CoreProof -> ByteString
+encodeCoreProof CoreProof{..} = BS.concat
+  [ g1ToBytes cpR, g1ToBytes cpT, frToBytes cpA, g1ToBytes cpWa, frToBytes cpB, g1ToBytes cpWb, g1ToBytes cpWt, frToBytes cpS ]
+
+coreProofSize :: Int
+coreProofSize = 576
+
+-- the four blinders and y, z, drawn in the order `prove` draws them (Protocol.hs:58,66,76)
+drawCoreTranscript :: MonadRandom m => m ([Fr], (Fr, Fr))
+drawCoreTranscript = do
+  cns <- replicateM 4 rnd
+  y   <- rnd
+  z   <- rnd
+  pure (cns ++ [y, z], (y, z))
+
+-- | a core proof on a resident handle (sonic_prover_prove_core) and the (y, z) it was made at: the head of what `proveWith` would give
+--   for the same draws, from 5 MSMs instead of 7 + 4Q
+proveCore :: Prover -> IO (CoreProof, (Fr, Fr))
+proveCore pr = do
+  (transcript, yz) <- drawCoreTranscript
+  bytes <- withProverAlive pr $ \p -> withFrs transcript $ \ptr ->
+    BSI.create coreProofSize (check <=< c_prover_prove_core p ptr)
+  pure (decodeCoreProof bytes, yz)
+
+-- | the two halves of `proveCore`, as `submit` / `collect`
+submitCore :: Prover -> IO (Fr, Fr)
+submitCore pr = do
+  (transcript, yz) <- drawCoreTranscript
+  withProverAlive pr $ \p -> withFrs transcript $ \ptr -> check =<< c_prover_submit_core p ptr
+  pure yz
+
+collectCore :: Prover -> IO CoreProof
+collectCore pr = decodeCoreProof <$> withProverAlive pr (\p -> BSI.create coreProofSize (check <=< c_prover_collect_core p))
+
+-- | a core proof under its own Fiat-Shamir transcript (sonic_prover_prove_core_fs; label "sonic-hip/fs-core/v1"): circuit digest and
+--   the prover's secret 32-byte blinder seed in, the proof and its (y, z) out
+proveCoreFs :: Prover -> ByteString -> ByteString -> IO (CoreProof, (Fr, Fr))
+proveCoreFs pr digest seed
+  | BS.length digest /= 32 || BS.length seed /= 32 = panic "proveCoreFs: the circuit digest and the seed are 32 bytes each"
+  | otherwise = withProverAlive pr $ \p -> withBytes digest $ \pd -> withBytes seed $ \ps -> allocaBytes 64 $ \pyz -> do
+      bytes <- BSI.create coreProofSize (\out -> check =<< c_prover_prove_core_fs p pd ps out pyz)
+      yz <- BS.packCStringLen (castPtr pyz, 64)
+      pure (decodeCoreProof bytes, (frFromBytes (BS.take 32 yz), frFromBytes (BS.drop 32 yz)))
+
+-- | the sound check of a proof's head (sonic_verify_core_csr): False when the proof's s is not s(z, y) or one of the three equations fails
+verifyCore :: SRS -> ArithCircuit Fr -> CoreProof -> Fr -> Fr -> Bool
+verifyCore (SRS h) circuit proof y z = unsafePerformIO $
+  withForeignPtr h $ \p -> withCircuitCsr circuit $ \n q prp pcol pval pcs ->
+    withBytes (encodeCoreProof proof) $ \ppf -> withFr y $ \py -> withFr z $ \pz -> alloca $ \acc -> do
+      check =<< c_verify_core_csr p n q prp pcol pval pcs ppf py pz acc
+      (/= 0) <$> peek acc
+
+-- | K core proofs of K statements of the handle's circuit in one pairing product (sonic_verifier_verify_core_batch): proof k at its
+--   (y, z) against cs_k; the per-proof verdicts.  A proof whose s is not s(z_k, y_k) is a rejected proof.
+verifyCoreBatch :: Verifier -> [(CoreProof, (Fr, Fr), [Fr])] -> IO [Bool]
+verifyCoreBatch _ [] = pure []
+verifyCoreBatch Verifier{..} sts = do
+  let k = length sts
+  withForeignPtr verifierHandle $ \v ->
+    withBytes (BS.concat [ encodeCoreProof pf | (pf, _, _) <- sts ]) $ \ppf ->
+      withFrs (concat [ [y, z] | (_, (y, z), _) <- sts ]) $ \pyz -> withFrs (concat [ cs | (_, _, cs) <- sts ]) $ \pcs ->
+        alloca $ \acc -> do
+          each <- BSI.create k $ \out -> check =<< c_verify_core_batch v (fromIntegral k) ppf 0 pyz pcs nullPtr acc out
+          pure (map (/= 0) (BS.unpack each))
 
 deviceCount :: IO Int
 deviceCount = alloca $ \out -> do

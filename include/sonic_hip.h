@@ -101,7 +101,11 @@ typedef struct sonic_verifier sonic_verifier_t;
  * sonic_fs_circuit_digest_resume, sonic_verifier_verify_batch_cs, sonic_verifier_verify_fs_batch_cs, sonic_verify_batch_digest_v2;
  * still 7, additions only: Fiat-Shamir proofs in flight -- sonic_prover_witness_digest_v2, sonic_prover_submit_fs,
  * sonic_prover_collect_fs, sonic_prove_batch_fs; still 7, additions only: witness sources -- sonic_witness_src_t, sonic_prover_set_witness,
- * sonic_prover_eval_constraints_src, sonic_prove_batch_src, sonic_prove_batch_fs_src */
+ * sonic_prover_eval_constraints_src, sonic_prove_batch_src, sonic_prove_batch_fs_src; still 7, additions only: core proofs --
+ * sonic_prover_prove_core, sonic_prover_submit_core, sonic_prover_collect_core, sonic_prover_prove_core_fs, sonic_fs_core_challenges,
+ * sonic_prove_batch_core_src, sonic_prove_batch_core_fs_src, sonic_verify_core[_csr], sonic_verify_core_fs[_csr],
+ * sonic_verifier_verify_core_batch, sonic_verifier_verify_core_fs_batch, sonic_verify_core_batch_digest, sonic_core_proof_compress,
+ * sonic_core_proof_decompress */
 int sonic_abi_version(void);
 int sonic_init(int device_ordinal);                 /* choose the DEFAULT GPU (first call wins) and make it the thread's HIP device; idempotent */
 int sonic_device_count(int* out);                   /* GPUs this process can see; SONIC_ERR_NO_DEVICE (and 0) without one */
@@ -661,6 +665,78 @@ int sonic_prove_batch_src(sonic_prover_t* const* provers, int n_provers, int64_t
 int sonic_prove_batch_fs_src(sonic_prover_t* const* provers, int n_provers, int64_t K, const sonic_witness_src_t* src, const uint8_t* cs,
                              const uint8_t* circuit_digests, const uint8_t* blinder_seeds, uint8_t* out_proofs, uint8_t* out_transcripts,
                              int* out_status);
+
+/* ---- Core proofs ----
+ * A second proof form beside the reference-shaped one, which stays byte for byte what it is.
+ *
+ * Why.  `verify` (Protocol.hs:119-126) reads the proof's s in one place, t = a (b + s) - k(y), and the embedded HscProof is made at pairs
+ * (y_j, z_j) drawn independently of (y, z): nothing that sonic_verify* or the batched verifier checks ties s to s(z, y).  Whoever picks
+ * r(X) and t'(X) freely, opens them honestly and SOLVES the head equation for s satisfies every check for any statement, with any honest
+ * signature of the same circuit appended.  That is the reference's behaviour; a deployed verifier must close it.
+ *
+ * A CORE proof is the head and nothing else -- R, T, a, W_a, b, W_b, W_t, s: 5 points and 3 field elements, SONIC_CORE_PROOF_SIZE bytes
+ * whatever Q is -- and its verifier is Sonic's unhelped one: it evaluates s(z, y) itself (O(nnz + n); the batched verifier on the GPU),
+ * REJECTS a proof whose s differs, and checks the three pcV equations of the head.  The head of a full proof is a core proof, so an
+ * existing proof is checked soundly by sonic_verify_core over its first 576 bytes with its own y, z (a Fiat-Shamir proof's:
+ * sonic_fs_challenges_v2).
+ *
+ * Prover.  The same kernel chain with the signature's jobs left out: 5 MSMs instead of 7 + 4Q.
+ *   prove_core      transcript: 6 x 32 bytes (the blinders c_{n+1..n+4}, y, z).  For every transcript t of a full proof,
+ *                   prove_core(t[0:6]) is the first 576 bytes of sonic_prover_prove(t): prepared or not, dense or CSR, over an SRS view.
+ *                   A handle may alternate core and full proofs.  A handle in share mode: SONIC_ERR_INVALID_ARG.
+ *   submit_core / collect_core   one proof in flight per handle, as sonic_prover_submit / collect.  sonic_prover_collect, collect_share and
+ *                   collect_fs on a core flight are SONIC_ERR_INVALID_ARG and leave the flight as it is; so is collect_core on a
+ *                   transcript or Fiat-Shamir flight, or on nothing.
+ *   prove_core_fs   the Fiat-Shamir form, three passes; blinders from witness digest v2 as sonic_prover_submit_fs's.  The transcript has a
+ *                   label of its own, so that a core proof can never be replayed as the head of a full one:
+ *                     st0 = SHA256("sonic-hip/fs-core/v1" || le64 n || le64 Q || le64 d || circuit digest || srs id)
+ *                     absorb("R", R) -> y = challenge("y", 0);   absorb("T", T) -> z = challenge("z", 0)
+ *                   (absorb / challenge: sonic_amd/csrc/fs.hpp).  out_yz: y || z, 64 bytes, may be NULL.
+ *   fs_core_challenges   y || z of a core proof, recomputed on the host; no device needed.
+ *   prove_batch_core_src / prove_batch_core_fs_src   sonic_prove_batch_src's / _fs_src's shape and rules (proof i on handle i % n_provers, all
+ *                   attempted, the first non-zero status returned).  src NULL: the handles' resident assignments.  cs: K x Q x 32 or
+ *                   NULL; transcripts: K x 192; out_proofs: K x 576; out_yz: K x 64, may be NULL.
+ *
+ * Verifiers.
+ *   verify_core[_csr]   one proof on the host, like sonic_verify: *accepted = 0 when the proof's s is not s(z, y) or an equation fails.
+ *                   y = 0 or z = 0: SONIC_ERR_INEXACT_DIVISION.  verify_core_fs[_csr] recomputes y, z first.
+ *   verifier_verify_core_batch / _core_fs_batch   K core proofs on a sonic_verifier_t handle: the 5K points validated (compressed = 1:
+ *                   decompressed) on the GPU, s(z_k, y_k) by the kernel that evaluates s(u_k, v_k) for full proofs, the 3K checks folded
+ *                   into the same four Miller loops.  yz: K x 64; cs: K x Q x 32, or NULL (the handle's constants for every proof).
+ *                   A proof whose s is not s(z_k, y_k), a malformed proof (a non-canonical cs_k included) and one with y_k or z_k zero
+ *                   are REJECTED proofs, not failed calls: each[k] = 0, the others' verdicts stand, sonic_last_error names the first.
+ *                   Randomizers as sonic_verify_batch_randomizers' over
+ *                     D = SHA-256("sonic-hip/batch-digest/core/v1" || le64 n || le64 Q || le64 d || circuit digest || srs id || le64 K ||
+ *                                 K x (576 proof bytes || y_k || z_k || cs_k))
+ *                   with check index 3k + i; compressed proofs are hashed as their rebuilt uncompressed bytes.
+ *   verify_core_batch_digest   that D on its own; no device needed. */
+#define SONIC_CORE_PROOF_SIZE 576
+#define SONIC_CORE_PROOF_SIZE_COMPRESSED 336
+int sonic_prover_prove_core(sonic_prover_t* p, const uint8_t* transcript, uint8_t* out_proof);
+int sonic_prover_submit_core(sonic_prover_t* p, const uint8_t* transcript);
+int sonic_prover_collect_core(sonic_prover_t* p, uint8_t* out_proof);
+int sonic_prover_prove_core_fs(sonic_prover_t* p, const uint8_t circuit_digest[32], const uint8_t blinder_seed[32], uint8_t* out_proof, uint8_t* out_yz);
+int sonic_fs_core_challenges(int64_t n, int64_t Q, int64_t d, const uint8_t circuit_digest[32], const uint8_t srs_id[32], const uint8_t* proof, uint8_t* out_yz);
+int sonic_prove_batch_core_src(sonic_prover_t* const* provers, int n_provers, int64_t K, const sonic_witness_src_t* src, const uint8_t* cs,
+                               const uint8_t* transcripts, uint8_t* out_proofs, int* out_status);
+int sonic_prove_batch_core_fs_src(sonic_prover_t* const* provers, int n_provers, int64_t K, const sonic_witness_src_t* src, const uint8_t* cs,
+                                  const uint8_t* circuit_digests, const uint8_t* blinder_seeds, uint8_t* out_proofs, uint8_t* out_yz, int* out_status);
+int sonic_verify_core(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO, const uint8_t* cs,
+                      const uint8_t* proof, const uint8_t y[32], const uint8_t z[32], int* accepted);
+int sonic_verify_core_csr(const sonic_srs_t* srs, int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val,
+                          const uint8_t* cs, const uint8_t* proof, const uint8_t y[32], const uint8_t z[32], int* accepted);
+int sonic_verify_core_fs(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO, const uint8_t* cs,
+                         const uint8_t* proof, int* accepted);
+int sonic_verify_core_fs_csr(const sonic_srs_t* srs, int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val,
+                             const uint8_t* cs, const uint8_t* proof, int* accepted);
+int sonic_verifier_verify_core_batch(sonic_verifier_t* v, int64_t K, const uint8_t* proofs, int compressed, const uint8_t* yz, const uint8_t* cs,
+                                     const uint8_t seed[32], int* all_accepted, uint8_t* each);
+int sonic_verifier_verify_core_fs_batch(sonic_verifier_t* v, int64_t K, const uint8_t* proofs, int compressed, const uint8_t* cs,
+                                        const uint8_t seed[32], int* all_accepted, uint8_t* each);
+int sonic_verify_core_batch_digest(int64_t n, int64_t Q, int64_t d, const uint8_t circuit_digest[32], const uint8_t srs_id[32], int64_t K,
+                                   const uint8_t* proofs, const uint8_t* yz, const uint8_t* cs, uint8_t out[32]);
+int sonic_core_proof_compress(const uint8_t* proof, uint8_t* out);
+int sonic_core_proof_decompress(const uint8_t* proof_z, uint8_t* out_proof);
 
 /* ---- device memory for callers without a HIP binding ---- */
 int sonic_dev_alloc(size_t bytes, void** out);                       /* on the default device */

@@ -176,6 +176,22 @@ def lib() -> C.CDLL:
         "sonic_prover_eval_constraints_src": [vp, i64, vp, vp, vp],
         "sonic_prove_batch_src": [vp, i32, i64, vp, vp, vp, vp, vp],
         "sonic_prove_batch_fs_src": [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp],
+        "sonic_prover_prove_core": [vp, vp, vp],
+        "sonic_prover_submit_core": [vp, vp],
+        "sonic_prover_collect_core": [vp, vp],
+        "sonic_prover_prove_core_fs": [vp, cp, cp, vp, vp],
+        "sonic_fs_core_challenges": [i64, i64, i64, cp, cp, vp, vp],
+        "sonic_prove_batch_core_src": [vp, i32, i64, vp, vp, vp, vp, vp],
+        "sonic_prove_batch_core_fs_src": [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp],
+        "sonic_verify_core": [vp, i64, i64, vp, vp, vp, vp, vp, cp, cp, C.POINTER(i32)],
+        "sonic_verify_core_csr": [vp, i64, i64, vp, vp, vp, vp, vp, cp, cp, C.POINTER(i32)],
+        "sonic_verify_core_fs": [vp, i64, i64, vp, vp, vp, vp, vp, C.POINTER(i32)],
+        "sonic_verify_core_fs_csr": [vp, i64, i64, vp, vp, vp, vp, vp, C.POINTER(i32)],
+        "sonic_verifier_verify_core_batch": [vp, i64, vp, i32, vp, vp, cp, C.POINTER(i32), vp],
+        "sonic_verifier_verify_core_fs_batch": [vp, i64, vp, i32, vp, cp, C.POINTER(i32), vp],
+        "sonic_verify_core_batch_digest": [i64, i64, i64, cp, cp, i64, vp, vp, vp, vp],
+        "sonic_core_proof_compress": [cp, cp],
+        "sonic_core_proof_decompress": [cp, cp],
         "sonic_dev_alloc": [C.c_size_t, C.POINTER(vp)],
         "sonic_dev_free": [vp],
         "sonic_dev_upload": [vp, vp, C.c_size_t],
@@ -240,6 +256,7 @@ HIP_RUNTIME_NOTE = None
 ABI_VERSION = 7          # SONIC_ABI_VERSION of include/sonic_hip.h
 FS_MIDSTATE_SIZE = 112   # SONIC_FS_MIDSTATE_SIZE
 WIT_FR32, WIT_I64 = 0, 1  # SONIC_WIT_*
+CORE_PROOF_SIZE, CORE_PROOF_SIZE_COMPRESSED = 576, 336   # SONIC_CORE_PROOF_SIZE[_COMPRESSED]
 
 
 class WitnessSrc(C.Structure):          # sonic_witness_src_t
@@ -275,6 +292,9 @@ EXPORTED = [
     "sonic_prover_witness_digest_v2", "sonic_prover_submit_fs", "sonic_prover_collect_fs", "sonic_prove_batch_fs",
     "sonic_prover_set_witness", "sonic_prover_eval_constraints_src", "sonic_prove_batch_src", "sonic_prove_batch_fs_src",
     "sonic_srs_for_circuit", "sonic_srs_load_for_circuit", "sonic_srs_load_for_circuit_on", "sonic_srs_windows", "sonic_srs_device_bytes",
+    "sonic_prover_prove_core", "sonic_prover_submit_core", "sonic_prover_collect_core", "sonic_prover_prove_core_fs", "sonic_fs_core_challenges",
+    "sonic_prove_batch_core_src", "sonic_prove_batch_core_fs_src", "sonic_verify_core", "sonic_verify_core_csr", "sonic_verify_core_fs", "sonic_verify_core_fs_csr",
+    "sonic_verifier_verify_core_batch", "sonic_verifier_verify_core_fs_batch", "sonic_verify_core_batch_digest", "sonic_core_proof_compress", "sonic_core_proof_decompress",
 ]
 
 

@@ -189,4 +189,34 @@ int sonic_proof_decompress(int64_t Q, const uint8_t* proof_z, uint8_t* out_proof
   return SONIC_OK;
 }
 
+// a core proof's 576 <-> 336 bytes: the same point encodings over the head's five points (proof_layout.hpp, core_proof_repack)
+int sonic_core_proof_compress(const uint8_t* proof, uint8_t* out) {
+  if (!proof || !out) { set_error("sonic_core_proof_compress: bad argument"); return SONIC_ERR_INVALID_ARG; }
+  const bool ok = core_proof_repack(proof, 96, out, 48, [](const uint8_t* in, uint8_t* o) {
+    G1Affine p;
+    const bool k = load_g1(in, p);
+    g1_compress_point(k ? p : G1Affine::inf(), o);
+    return k;
+  });
+  if (!ok) { set_error("sonic_core_proof_compress: the proof holds a point that is non-canonical, off the curve or outside the order-r subgroup"); return SONIC_ERR_BAD_ENCODING; }
+  return SONIC_OK;
+}
+
+int sonic_core_proof_decompress(const uint8_t* proof_z, uint8_t* out_proof) {
+  if (!proof_z || !out_proof) { set_error("sonic_core_proof_decompress: bad argument"); return SONIC_ERR_INVALID_ARG; }
+  bool ok = core_proof_repack(proof_z, 48, out_proof, 96, [](const uint8_t* in, uint8_t* o) {
+    G1Affine p;
+    bool k = g1_decompress_point(in, p) == 0;
+    if (k && !p.is_inf() && !g1_in_subgroup(p)) { k = false; p = G1Affine::inf(); }
+    uint32_t w[24];
+    g1_canonical_words(p, w);
+    memcpy(o, w, 96);
+    return k;
+  });
+  const uint8_t* p = out_proof;
+  core_proof_record_order([&](long) { p += 96; }, [&](long) { Fr f; ok = load_fr(p, f) && ok; p += 32; });
+  if (!ok) { set_error("sonic_core_proof_decompress: malformed point, point off the curve or outside the order-r subgroup, or non-canonical field element"); return SONIC_ERR_BAD_ENCODING; }
+  return SONIC_OK;
+}
+
 }  // extern "C"

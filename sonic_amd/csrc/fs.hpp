@@ -66,9 +66,9 @@ inline Fr fs_wide_reduce(const uint8_t w[64]) {
 
 struct FsTranscript {
   uint8_t st[32];
-  void init(int64_t n, int64_t Q, int64_t d, const uint8_t digest[32], const uint8_t srs_id[32]) {
+  void init(int64_t n, int64_t Q, int64_t d, const uint8_t digest[32], const uint8_t srs_id[32], const char* label = "sonic-hip/fs/v2") {
     Sha256 h;
-    h.update("sonic-hip/fs/v2", 15);
+    h.update(label, strlen(label));
     le64(h, n); le64(h, Q); le64(h, d);
     h.update(digest, 32);
     h.update(srs_id, 32);
@@ -147,6 +147,38 @@ inline void fs_challenges_of_proof(int64_t n, int64_t Q, int64_t d, const uint8_
   w.append(reinterpret_cast<const char*>(hscW), (size_t)Q * 224);
   t.absorb("hscW", reinterpret_cast<const uint8_t*>(w.data()), w.size());
   t.challenge("v", 0, out + 32 * (3 + 2 * Q));
+}
+
+// ---- core proofs (include/sonic_hip.h, "Core proofs"): R, T, a, W_a, b, W_b, W_t, s and no signature -----------------------------------
+// The transcript of a core proof, under a label of its own so that a core proof can never be replayed as the head of a full one (nor
+// the head of a full one pass for a core proof): the same state machine,
+//   st_0 = SHA256("sonic-hip/fs-core/v1" || le64 n || le64 Q || le64 d || circuit digest || srs id)
+//   absorb("R", R) -> y = challenge("y", 0);   absorb("T", T) -> z = challenge("z", 0)
+// and the same blinders (above, over witness digest v2).  The openings are not absorbed: nothing is drawn after them.
+constexpr const char* FS_CORE_LABEL = "sonic-hip/fs-core/v1";
+// y, z (64 bytes) from the 576 canonical bytes of a core proof: what the verifier recomputes
+inline void fs_core_challenges_of_proof(int64_t n, int64_t Q, int64_t d, const uint8_t digest[32], const uint8_t srs_id[32], const uint8_t* proof, uint8_t* out_yz) {
+  FsTranscript t;
+  t.init(n, Q, d, digest, srs_id, FS_CORE_LABEL);
+  t.absorb("R", proof, 96);
+  t.challenge("y", 0, out_yz);
+  t.absorb("T", proof + 96, 96);
+  t.challenge("z", 0, out_yz + 32);
+}
+// The digest of a batch of core proofs (sonic_verifier_verify_core_batch), from which the randomizers are derived as for the other batches
+// (check index 3k + i):
+//   D = SHA-256("sonic-hip/batch-digest/core/v1" || le64 n || le64 Q || le64 d || circuit digest || srs id || le64 K ||
+//               K x (576 proof bytes || y_k || z_k || cs_k))
+inline void fs_core_batch_digest(int64_t n, int64_t Q, int64_t d, const uint8_t digest[32], const uint8_t srs_id[32], int64_t K, const uint8_t* proofs,
+                                 const uint8_t* yz, const uint8_t* cs, uint8_t out[32]) {
+  const size_t ksz = 32 * (size_t)Q;
+  Sha256 h;
+  h.update("sonic-hip/batch-digest/core/v1", 30);
+  FsTranscript::le64(h, n); FsTranscript::le64(h, Q); FsTranscript::le64(h, d);
+  h.update(digest, 32); h.update(srs_id, 32);
+  FsTranscript::le64(h, K);
+  for (int64_t k = 0; k < K; k++) { h.update(proofs + 576 * (size_t)k, 576); h.update(yz + 64 * (size_t)k, 64); h.update(cs + ksz * (size_t)k, ksz); }
+  h.finish(out);
 }
 
 // ---- the circuit digest in two halves: one circuit, many statements ----------------------------------------------------------------

@@ -55,15 +55,26 @@ struct ProofLayout {
   static constexpr long t_len(long n) { return 7 * n + 9; }
   static constexpr long u_lo(long n) { return -n; }
   constexpr long u_len(long n) const { return 2 * n + Q + 1; }
+  // a CORE proof (include/sonic_hip.h, "Core proofs"): the head of the record -- R, T, a, W_a, b, W_b, W_t, s -- and nothing of the
+  // signature, whatever Q is: the slots 0 .. 4, the evaluations 0 .. 2, the transcript elements 0 .. 5 (4 blinders, y, z)
+  static constexpr long core_K = 5, core_F = 3, core_transcript_len = 6;
+  static constexpr size_t core_proof_bytes() { return (size_t)(core_K * 96 + core_F * 32); }                  // 576
+  static constexpr size_t core_proof_bytes_compressed() { return (size_t)(core_K * 48 + core_F * 32); }       // 336
 };
 
 // canonical proof bytes from the 7 + 4Q points (slot order) and the 3 + 2Q evaluations: record order of `Proof` (Protocol.hs:28-38)
 // then `HscProof` (Signature.hs:22-29)
 // the record order itself: onG(slot) for a point, onF(i) for evaluation i, then onF(-1), onF(-2) for u and v
+// (a core proof's record order: the head of a proof's, which proof_record_order opens with)
+template <class OnG, class OnF>
+inline void core_proof_record_order(OnG&& onG, OnF&& onF) {
+  using L = ProofLayout;
+  onG(L::R); onG(L::T); onF(L::a); onG(L::Wa); onF(L::b); onG(L::Wb); onG(L::Wt); onF(L::s);
+}
 template <class OnG, class OnF>
 inline void proof_record_order(long Q, OnG&& onG, OnF&& onF) {
   const ProofLayout L{Q};
-  onG(L.R); onG(L.T); onF(L.a); onG(L.Wa); onF(L.b); onG(L.Wb); onG(L.Wt); onF(L.s);
+  core_proof_record_order(onG, onF);
   for (long j = 0; j < Q; j++) { onG(L.S(j)); onF(L.s_j(j)); onG(L.W(j)); }             // hscS
   for (long j = 0; j < Q; j++) { onF(L.sp_j(j)); onG(L.Wp(j)); onG(L.Qj(j)); }          // hscW
   onG(L.Qv()); onG(L.C());
@@ -82,6 +93,18 @@ template <class Point>
 inline bool proof_repack(long Q, const uint8_t* in, size_t in_pt, uint8_t* out, size_t out_pt, Point&& point) {
   bool ok = true;
   proof_record_order(Q, [&](long) { ok = point(in, out) && ok; in += in_pt; out += out_pt; }, [&](long) { memcpy(out, in, 32); in += 32; out += 32; });
+  return ok;
+}
+
+// the two for a core proof: 576 bytes from the points of the slots 0 .. 4 and the evaluations a, b, s; and its 96 <-> 48 byte repack
+inline void core_proof_layout(const uint8_t* pts, const uint8_t* frs, uint8_t* out_proof) {
+  uint8_t* o = out_proof;
+  core_proof_record_order([&](long slot) { memcpy(o, pts + 96 * (size_t)slot, 96); o += 96; }, [&](long i) { memcpy(o, frs + 32 * (size_t)i, 32); o += 32; });
+}
+template <class Point>
+inline bool core_proof_repack(const uint8_t* in, size_t in_pt, uint8_t* out, size_t out_pt, Point&& point) {
+  bool ok = true;
+  core_proof_record_order([&](long) { ok = point(in, out) && ok; in += in_pt; out += out_pt; }, [&](long) { memcpy(out, in, 32); in += 32; out += 32; });
   return ok;
 }
 

@@ -601,8 +601,8 @@ struct ProofPass {
       : n(p->n), Q(p->Q), d(p->srs->d), r_lo(ProofLayout::r_lo(n)), r_len(ProofLayout::r_len(n)), s_lo(ProofLayout::s_lo(n)), s_len(ProofLayout::s_len(n)),
         t_lo(ProofLayout::t_lo(n)), t_len(ProofLayout::t_len(n)), u_lo(ProofLayout::u_lo(n)), u_len(q.L.u_len(n)), PR(p->PAIRS.as<Fr>()), need_j((size_t)Q, 0) {
     const ProofLayout& L = q.L;
-    need_su = q.own(L.C()) || q.own(L.Qv());
-    for (long j = 0; j < Q; j++) {
+    need_su = !p->core && (q.own(L.C()) || q.own(L.Qv()));
+    for (long j = 0; j < Q && !p->core; j++) {      // (a core proof has no signature: none of its groups)
       need_j[(size_t)j] = q.own(L.S(j)) || q.own(L.W(j)) || q.own(L.Wp(j));
       need_j_any = need_j_any || need_j[(size_t)j];
       if (need_j[(size_t)j]) last_j = j;
@@ -800,12 +800,13 @@ static void enqueue_proof(sonic_prover_t* p) {
   // the copy-out, behind the join on the tail stream (a pooled handle: not the stream the next proof's head is queued on)
   hipStream_t tl = p->tail;
   Fr* frstd = p->frstd.as<Fr>();
-  HIP_OK(hipMemcpyAsync(frstd, q.frout, sizeof(Fr) * L.F(), hipMemcpyDeviceToDevice, tl));
-  fr_from_mont_enqueue(tl, frstd, L.F());
-  // (the side slots that this proof's modes fill: the second halves of the S_j, and of C)
-  const long KS = p->sym_on ? L.slots_total() : (p->prepared || p->runs_on) ? L.C_extra() : L.K();
+  const long F = p->core ? L.core_F : L.F();
+  HIP_OK(hipMemcpyAsync(frstd, q.frout, sizeof(Fr) * F, hipMemcpyDeviceToDevice, tl));
+  fr_from_mont_enqueue(tl, frstd, F);
+  // (the side slots that this proof's modes fill: the second halves of the S_j, and of C; a core proof: the head's five slots)
+  const long KS = p->core ? L.core_K : p->sym_on ? L.slots_total() : (p->prepared || p->runs_on) ? L.C_extra() : L.K();
   HIP_OK(hipMemcpyAsync(p->h_slots, q.slots, sizeof(MsmSlot) * KS, hipMemcpyDeviceToHost, tl));
-  HIP_OK(hipMemcpyAsync(p->h_fr, frstd, 32 * L.F(), hipMemcpyDeviceToHost, tl));
+  HIP_OK(hipMemcpyAsync(p->h_fr, frstd, 32 * F, hipMemcpyDeviceToHost, tl));
   HIP_OK(hipMemcpyAsync(p->h_flags, flags, 8, hipMemcpyDeviceToHost, tl));
   if (p->pooled) HIP_OK(hipEventRecord(p->done, tl));
 }
@@ -1095,6 +1096,21 @@ static int prove_finish(sonic_prover_t* p, uint8_t* out_proof) {
   API_END
 }
 
+// the finish of a CORE proof: the five slots of the head on the caller's thread (no side slots, no thread group), one shared inversion
+static int prove_finish_core(sonic_prover_t* p, uint8_t* out_proof) {
+  API_BEGIN_ON(p->device)
+  await_proof(p, /*share=*/false);
+  const MsmSlot* hs = p->h_slots;
+  if (p->h_flags[1]) { p->have_assignment = false; return flags_to_status(p->h_flags[1], "prove (circuit / assignment handed over with the call)"); }
+  if (p->h_flags[0]) return flags_to_status(p->h_flags[0], "prove");
+  G1XYZZ sums[ProofLayout::core_K];
+  uint8_t pts[96 * ProofLayout::core_K];
+  for (long i = 0; i < ProofLayout::core_K; i++) sums[i] = msm_finish_host(hs[i]);
+  g1_canonical_bytes_host_batch(sums, (int)ProofLayout::core_K, pts);
+  core_proof_layout(pts, p->h_fr, out_proof);
+  API_END
+}
+
 extern "C" {
 
 static int whole_proof_only(sonic_prover_t* p, const char* who) {
@@ -1105,6 +1121,7 @@ static int whole_proof_only(sonic_prover_t* p, const char* who) {
 // a Fiat-Shamir proof in flight (sonic_prover_submit_fs) is collected by sonic_prover_collect_fs only
 static int fs_flight_refused(sonic_prover_t* p, const char* who) {
   if (p->fs_flight) { set_error("%s: the proof in flight was submitted with sonic_prover_submit_fs: collect it with sonic_prover_collect_fs", who); return SONIC_ERR_INVALID_ARG; }
+  if (p->core_flight) { set_error("%s: the proof in flight was submitted with sonic_prover_submit_core: collect it with sonic_prover_collect_core", who); return SONIC_ERR_INVALID_ARG; }
   return SONIC_OK;
 }
 
@@ -1191,6 +1208,66 @@ int sonic_prover_collect(sonic_prover_t* p, uint8_t* out_proof) {
   if (whole_proof_only(p, "sonic_prover_collect")) return SONIC_ERR_INVALID_ARG;
   p->in_flight = false;
   return prove_finish(p, out_proof);
+}
+
+// ---- core proofs (include/sonic_hip.h, "Core proofs") -----------------------------------------------------------------------------
+// The same enqueue with the phase mask PH_CORE: build_r1, s(X, y), the NTT product, group 0, the t group and s(z, y); no MSM of the
+// signature is queued and none of its polynomials built.  The six transcript elements of the caller are completed with 1 for the
+// challenges that are never drawn (as prove_fs_walk does), so that the head's bytes are those of sonic_prover_prove for every transcript
+// that starts with these six.
+static int prove_core_run(sonic_prover_t* p, const uint8_t* transcript6, uint32_t phases, int (*finish)(sonic_prover_t*, uint8_t*), uint8_t* out) {
+  const ProofLayout L{p->Q};
+  std::vector<uint8_t> tr(32 * (size_t)L.transcript_len(), 0);
+  memcpy(tr.data(), transcript6, 32 * (size_t)L.core_transcript_len);
+  for (long k = L.core_transcript_len; k < L.transcript_len(); k++) tr[32 * (size_t)k] = 1;
+  p->phases = phases; p->core = true;
+  const int rc = prove_run(p, tr.data(), finish, out);
+  p->phases = PH_ALL; p->core = false;
+  return rc;
+}
+
+int sonic_prover_prove_core(sonic_prover_t* p, const uint8_t* transcript, uint8_t* out_proof) {
+  if (!p || !transcript || !out_proof) return SONIC_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> g(p->mu);
+  int rc = prove_args_ok(p, "sonic_prover_prove_core");
+  if (!rc) rc = whole_proof_only(p, "sonic_prover_prove_core");
+  if (!rc) rc = prove_core_run(p, transcript, PH_CORE, prove_finish_core, out_proof);
+  return rc;
+}
+
+int sonic_prover_submit_core(sonic_prover_t* p, const uint8_t* transcript) {
+  if (!p || !transcript) return SONIC_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> g(p->mu);
+  int rc = prove_args_ok(p, "sonic_prover_submit_core");
+  if (!rc) rc = whole_proof_only(p, "sonic_prover_submit_core");
+  if (!rc) rc = prove_core_run(p, transcript, PH_CORE, nullptr, nullptr);
+  if (!rc) { p->in_flight = true; p->core_flight = true; }
+  return rc;
+}
+
+int sonic_prover_collect_core(sonic_prover_t* p, uint8_t* out_proof) {
+  if (!p || !out_proof) return SONIC_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> g(p->mu);
+  if (!p->in_flight) { set_error("sonic_prover_collect_core: nothing was submitted"); return SONIC_ERR_INVALID_ARG; }
+  if (!p->core_flight) { set_error("sonic_prover_collect_core: the proof in flight is not a core proof: collect it with the call that belongs to its submit"); return SONIC_ERR_INVALID_ARG; }
+  p->in_flight = false; p->core_flight = false;
+  return prove_finish_core(p, out_proof);
+}
+
+// a core proof with the constants of THIS call and, with w, its assignment from block 0 of a witness source (sonic_prove_batch_core_src)
+int prove_core_with_witness(sonic_prover_t* p, const WitnessView* w, hipEvent_t ready, const uint8_t* cs, const uint8_t* transcript, uint8_t* out_proof) {
+  std::lock_guard<std::mutex> g(p->mu);
+  if (p->in_flight) { set_error("prove: a submitted proof has not been collected yet"); return SONIC_ERR_INVALID_ARG; }
+  int rc = whole_proof_only(p, "prove");
+  if (rc) return rc;
+  if (!w && !p->have_assignment) { set_error("prove: no assignment set"); return SONIC_ERR_INVALID_ARG; }
+  if (w) { p->pend_wit.v = *w; p->pend_wit.ready = ready; p->pend_wit.set = true; }
+  p->pend_cs = cs;
+  rc = prove_core_run(p, transcript, PH_CORE, prove_finish_core, out_proof);
+  p->pend_wit.set = false;
+  p->pend_cs = nullptr;
+  if (w) p->have_assignment = rc == SONIC_OK;          // (a failed call may have left a refused assignment behind)
+  return rc;
 }
 
 // ONE proof over `world` GPUs (SURVEY 8e "MSM-level parallelism"; BASELINE configs[3] as one n = 2^20 instance on 8 GPUs): every rank
@@ -1313,8 +1390,10 @@ static void witness_digest_v2_ensure(sonic_prover_t* p) {
 // The six passes of a Fiat-Shamir proof: the blinders from `witness_digest` (v1 for the blocking call, v2 for the proofs in flight and the
 // batches: the only difference between them), then PH_R .. PH_QV with the host's hashes in between.  The caller has checked the handle
 // and holds it: p->mu, or the flight (in_flight, which refuses every other call).  out_transcript may be null.
+// A CORE proof (core: fs.hpp, "core proofs") walks the first three passes of the same chain under its own label and ends there: out_proof
+// gets its 576 bytes and out_transcript, where given, y and z (64 bytes).
 static int prove_fs_walk(sonic_prover_t* p, const uint8_t circuit_digest[32], const uint8_t blinder_seed[32], const uint8_t witness_digest[32], uint8_t* out_proof,
-                         uint8_t* out_transcript) {
+                         uint8_t* out_transcript, bool core = false) {
   int rc;
   const long n = p->n, Q = p->Q, d = p->srs->d;
   const ProofLayout L{Q};
@@ -1324,8 +1403,10 @@ static int prove_fs_walk(sonic_prover_t* p, const uint8_t circuit_digest[32], co
   for (long k = 0; k < L.n_blinders; k++) fs_blinder(blinder_seed, circuit_digest, srs_id, witness_digest, (uint32_t)k, &tr[32 * k]);
   for (long k = L.n_blinders; k < L.transcript_len(); k++) tr[32 * k] = 1;               // not drawn yet: any invertible value (results that use it are not read)
   FsTranscript t;
-  t.init(n, Q, d, circuit_digest, srs_id);
+  if (core) t.init(n, Q, d, circuit_digest, srs_id, FS_CORE_LABEL);
+  else t.init(n, Q, d, circuit_digest, srs_id);
   auto pass = [&](int ph) {
+    if (core) return prove_core_run(p, tr.data(), 1u << ph, prove_finish_core, pf.data());
     p->phases = 1u << ph;
     int r = prove_run(p, tr.data(), prove_finish, pf.data());
     p->phases = PH_ALL;
@@ -1339,6 +1420,11 @@ static int prove_fs_walk(sonic_prover_t* p, const uint8_t circuit_digest[32], co
   t.absorb("T", T, 96);
   t.challenge("z", 0, &tr[32 * L.z]);
   if ((rc = pass(PH_OPEN))) return rc;
+  if (core) {
+    memcpy(out_proof, pf.data(), L.core_proof_bytes());
+    if (out_transcript) memcpy(out_transcript, &tr[32 * L.y], 64);
+    return SONIC_OK;
+  }
   t.absorb("open", open, 384);
   for (long j = 0; j < Q; j++) { t.challenge("yj", (uint32_t)j, &tr[32 * L.y_j(j)]); t.challenge("zj", (uint32_t)j, &tr[32 * L.z_j(j)]); }
   if ((rc = pass(PH_HSCS))) return rc;
@@ -1367,6 +1453,65 @@ int sonic_prover_prove_fs(sonic_prover_t* p, const uint8_t circuit_digest[32], c
   if (rc) return rc;
   witness_digest_v1_ensure(p);
   return prove_fs_walk(p, circuit_digest, blinder_seed, p->witness_digest, out_proof, out_transcript);
+  API_END
+}
+
+// the assignment of a Fiat-Shamir proof from block 0 of a witness source, checked by the caller: it goes up at once, with the tree of its
+// digest queued right behind it, so that one wait serves both (the caller runs inside API_BEGIN_ON and holds p->mu)
+static int fs_take_witness(sonic_prover_t* p, const WitnessView& w, hipEvent_t ready) {
+  hipStream_t st = p->st;
+  p->have_assignment = false;               // (until the source is known to be good)
+  p->assignment_changed();
+  for (DevBuf* a : {&p->aL, &p->aR, &p->aO}) a->ensure(sizeof(Fr) * (size_t)p->n);
+  {
+    EnqueueLock enq(p);
+    if (ready) HIP_OK(hipStreamWaitEvent(st, ready, 0));
+    HIP_OK(hipMemsetAsync(p->flags.p, 0, 4, st));
+    witness_load_enqueue(p, st, w, 1, p->aL.as<Fr>(), p->aR.as<Fr>(), p->aO.as<Fr>(), p->n, p->flags.as<int>());
+    witness_digest_v2_enqueue(p);
+    const int f = read_flags(st, p->flags);
+    if (f) return flags_to_status(f, "prove (assignment handed over with the call)");
+  }
+  witness_digest_v2_finish(p);
+  p->have_assignment = true;
+  return SONIC_OK;
+}
+
+// a core proof under its own Fiat-Shamir transcript (fs.hpp): three passes, the blinders from witness digest v2 as for the proofs in flight
+int sonic_prover_prove_core_fs(sonic_prover_t* p, const uint8_t circuit_digest[32], const uint8_t blinder_seed[32], uint8_t* out_proof, uint8_t* out_yz) {
+  if (!p || !circuit_digest || !blinder_seed || !out_proof) return SONIC_ERR_INVALID_ARG;
+  API_BEGIN_ON(p->device)
+  std::lock_guard<std::mutex> g(p->mu);
+  int rc = prove_args_ok(p, "sonic_prover_prove_core_fs");
+  if (!rc) rc = whole_proof_only(p, "sonic_prover_prove_core_fs");
+  if (rc) return rc;
+  witness_digest_v2_ensure(p);
+  return prove_fs_walk(p, circuit_digest, blinder_seed, p->witness_digest_v2, out_proof, out_yz, /*core=*/true);
+  API_END
+}
+
+int sonic_fs_core_challenges(int64_t n, int64_t Q, int64_t d, const uint8_t circuit_digest[32], const uint8_t srs_id[32], const uint8_t* proof, uint8_t* out_yz) {
+  if (n < 1 || Q < 1 || d < 1 || !circuit_digest || !srs_id || !proof || !out_yz) return SONIC_ERR_INVALID_ARG;
+  fs_core_challenges_of_proof(n, Q, d, circuit_digest, srs_id, proof, out_yz);
+  return SONIC_OK;
+}
+
+// the same with the constants of THIS call and, with w, the assignment from block 0 of a witness source (sonic_prove_batch_core_fs_src)
+int prove_core_fs_with_witness(sonic_prover_t* p, const WitnessView* w, hipEvent_t ready, const uint8_t* cs, const uint8_t circuit_digest[32],
+                               const uint8_t blinder_seed[32], uint8_t* out_proof, uint8_t* out_yz) {
+  API_BEGIN_ON(p->device)
+  std::lock_guard<std::mutex> g(p->mu);
+  if (p->in_flight) { set_error("prove: a submitted proof has not been collected yet"); return SONIC_ERR_INVALID_ARG; }
+  int rc = whole_proof_only(p, "prove");
+  if (rc) return rc;
+  if (!w && !p->have_assignment) { set_error("prove: no assignment set"); return SONIC_ERR_INVALID_ARG; }
+  if (w) {
+    if ((rc = fs_take_witness(p, *w, ready))) return rc;
+  } else witness_digest_v2_ensure(p);
+  p->pend_cs = cs;
+  rc = prove_fs_walk(p, circuit_digest, blinder_seed, p->witness_digest_v2, out_proof, out_yz, /*core=*/true);
+  p->pend_cs = nullptr;
+  return rc;
   API_END
 }
 
@@ -1491,21 +1636,7 @@ int prove_fs_with_witness(sonic_prover_t* p, const WitnessView& w, hipEvent_t re
   if (p->in_flight) { set_error("prove: a submitted proof has not been collected yet"); return SONIC_ERR_INVALID_ARG; }
   int rc = whole_proof_only(p, "prove");
   if (rc) return rc;
-  hipStream_t st = p->st;
-  p->have_assignment = false;               // (until the source is known to be good)
-  p->assignment_changed();
-  for (DevBuf* a : {&p->aL, &p->aR, &p->aO}) a->ensure(sizeof(Fr) * (size_t)p->n);
-  {
-    EnqueueLock enq(p);
-    if (ready) HIP_OK(hipStreamWaitEvent(st, ready, 0));
-    HIP_OK(hipMemsetAsync(p->flags.p, 0, 4, st));
-    witness_load_enqueue(p, st, w, 1, p->aL.as<Fr>(), p->aR.as<Fr>(), p->aO.as<Fr>(), p->n, p->flags.as<int>());
-    witness_digest_v2_enqueue(p);
-    const int f = read_flags(st, p->flags);
-    if (f) return flags_to_status(f, "prove (assignment handed over with the call)");
-  }
-  witness_digest_v2_finish(p);
-  p->have_assignment = true;
+  if ((rc = fs_take_witness(p, w, ready))) return rc;
   p->pend_cs = cs;
   rc = prove_fs_walk(p, circuit_digest, blinder_seed, p->witness_digest_v2, out_proof, out_transcript);
   p->pend_cs = nullptr;

@@ -202,7 +202,7 @@ int sonic_prove_shared(sonic_prover_t* const* provers, int world, const uint8_t*
 struct BatchFs { const uint8_t *circuit_digests, *blinder_seeds; uint8_t* out_transcripts; };
 static int prove_batch_impl(const char* who, sonic_prover_t* const* provers, int n_provers, int64_t K, const uint8_t* aL, const uint8_t* aR, const uint8_t* aO,
                             const uint8_t* cs, const uint8_t* transcripts, uint8_t* out_proofs, int* out_status, const BatchFs* fs = nullptr,
-                            const sonic_witness_src_t* src = nullptr, bool from_src = false) {
+                            const sonic_witness_src_t* src = nullptr, bool from_src = false, bool core = false) {
   if (!provers || n_provers < 1 || n_provers > 1024 || K < 0 || (K > 0 && (!(fs ? fs->circuit_digests && fs->blinder_seeds : transcripts != nullptr) || !out_proofs))) return SONIC_ERR_INVALID_ARG;
   const bool per_proof = aL || aR || aO;
   if (per_proof && !(aL && aR && aO)) { set_error("%s: aL, aR, aO must be given together (or all NULL: the handles' resident assignments)", who); return SONIC_ERR_INVALID_ARG; }
@@ -227,7 +227,9 @@ static int prove_batch_impl(const char* who, sonic_prover_t* const* provers, int
     } catch (const HipFail& f) { return f.code; }
     if (rc) return rc;
   }
-  const size_t psz = sonic_proof_size(Q), tsz = 32 * (size_t)(8 + 2 * Q), asz = 32 * (size_t)n, ksz = 32 * (size_t)Q;
+  // (core proofs: 576 bytes each, 6 transcript elements in, and y, z where a Fiat-Shamir batch gives the transcripts back)
+  const size_t psz = core ? ProofLayout::core_proof_bytes() : sonic_proof_size(Q), tsz = core ? (fs ? 64 : 32 * (size_t)ProofLayout::core_transcript_len) : 32 * (size_t)(8 + 2 * Q);
+  const size_t asz = 32 * (size_t)n, ksz = 32 * (size_t)Q;
   std::vector<int> status((size_t)K, SONIC_OK);
   std::vector<std::string> errs((size_t)n_provers);
   std::vector<int64_t> first_bad((size_t)n_provers, -1);
@@ -244,7 +246,11 @@ static int prove_batch_impl(const char* who, sonic_prover_t* const* provers, int
         const uint8_t *aLi = per_proof ? aL + asz * (size_t)i : nullptr, *aRi = per_proof ? aR + asz * (size_t)i : nullptr, *aOi = per_proof ? aO + asz * (size_t)i : nullptr;
         const uint8_t* csi = cs ? cs + ksz * (size_t)i : nullptr;
         uint8_t* out = out_proofs + psz * (size_t)i;
+        WitnessView blk;
         if (rc) {}      // (refused above)
+        else if (core && fs) rc = prove_core_fs_with_witness(provers[h], from_src ? &(blk = wv.block(i)) : nullptr, ready.ev, csi, fs->circuit_digests + 32 * (size_t)i,
+                                                             fs->blinder_seeds + 32 * (size_t)i, out, fs->out_transcripts ? fs->out_transcripts + tsz * (size_t)i : nullptr);
+        else if (core) rc = prove_core_with_witness(provers[h], from_src ? &(blk = wv.block(i)) : nullptr, ready.ev, csi, transcripts + tsz * (size_t)i, out);
         else if (from_src && fs) rc = prove_fs_with_witness(provers[h], wv.block(i), ready.ev, csi, fs->circuit_digests + 32 * (size_t)i, fs->blinder_seeds + 32 * (size_t)i, out,
                                                             fs->out_transcripts ? fs->out_transcripts + tsz * (size_t)i : nullptr);
         else if (from_src) rc = prove_with_witness(provers[h], wv.block(i), ready.ev, csi, transcripts + tsz * (size_t)i, out);
@@ -305,6 +311,20 @@ int sonic_prove_batch_fs_src(sonic_prover_t* const* provers, int n_provers, int6
   try { DeviceScope probe(-1); } catch (const HipFail& f) { return f.code; }      // (no device: SONIC_ERR_NO_DEVICE whatever the arguments are)
   const BatchFs fs{circuit_digests, blinder_seeds, out_transcripts};
   return prove_batch_impl("sonic_prove_batch_fs_src", provers, n_provers, K, nullptr, nullptr, nullptr, cs, nullptr, out_proofs, out_status, &fs, src, true);
+}
+
+// the two for core proofs (include/sonic_hip.h, "Core proofs"): the same per-handle routine with the core mask; src NULL: the resident assignments
+int sonic_prove_batch_core_src(sonic_prover_t* const* provers, int n_provers, int64_t K, const sonic_witness_src_t* src, const uint8_t* cs, const uint8_t* transcripts,
+                               uint8_t* out_proofs, int* out_status) {
+  try { DeviceScope probe(-1); } catch (const HipFail& f) { return f.code; }      // (no device: SONIC_ERR_NO_DEVICE whatever the arguments are)
+  return prove_batch_impl("sonic_prove_batch_core_src", provers, n_provers, K, nullptr, nullptr, nullptr, cs, transcripts, out_proofs, out_status, nullptr, src, src != nullptr, true);
+}
+
+int sonic_prove_batch_core_fs_src(sonic_prover_t* const* provers, int n_provers, int64_t K, const sonic_witness_src_t* src, const uint8_t* cs, const uint8_t* circuit_digests,
+                                  const uint8_t* blinder_seeds, uint8_t* out_proofs, uint8_t* out_yz, int* out_status) {
+  try { DeviceScope probe(-1); } catch (const HipFail& f) { return f.code; }      // (no device: SONIC_ERR_NO_DEVICE whatever the arguments are)
+  const BatchFs fs{circuit_digests, blinder_seeds, out_yz};
+  return prove_batch_impl("sonic_prove_batch_core_fs_src", provers, n_provers, K, nullptr, nullptr, nullptr, cs, nullptr, out_proofs, out_status, &fs, src, src != nullptr, true);
 }
 
 }  // extern "C"

@@ -33,7 +33,8 @@ enum { PH_R = 1,      // R                                   (blinders)
        PH_HSCS = 4,   // S_j, s_j, W_j                       (+ y_j, z_j)
        PH_HSCW = 5,   // C, s'_j, W'_j, Q_j                  (+ u)
        PH_QV = 6,     // Q_v                                 (+ v)
-       PH_ALL = 0x7e };
+       PH_ALL = 0x7e,
+       PH_CORE = 0x0e };      // R, T and the openings: all of a core proof (include/sonic_hip.h, "Core proofs")
 // Buckets per running-sum segment inside prove().  More buckets per segment = fewer small scalar multiplications (less work),
 // fewer = shorter dependent chains.  Batched groups hide their chains under other groups' accumulation, so they take the
 // work-optimal end; the group that finishes last has nothing left to hide under and takes a short chain.  Measured
@@ -214,6 +215,11 @@ struct sonic_prover {
   long proofs_done = 0;
   bool in_flight = false;                    // between sonic_prover_submit and sonic_prover_collect, or submit_fs and collect_fs
   bool fs_flight = false;                    // the proof in flight is a Fiat-Shamir one: fsw walks it, and only collect_fs ends it
+  bool core_flight = false;                  // the proof in flight is a core proof (sonic_prover_submit_core): only collect_core ends it
+  // The enqueue in progress belongs to a CORE proof: the groups of the signature are not even visited (their commits and openings would
+  // all return at once: 4Q empty jobs and Q + 1 lane hand-overs at Q = 64), and only the slots 0 .. 4 and the evaluations a, b, s come
+  // back.  Set around prove_run by the core calls, under p->mu or the flight; a full proof never sees it.
+  bool core = false;
   std::unique_ptr<FsWorker> fsw;
   // Which steps of the proof an enqueue runs (bit = phase; PH_ALL normally).  The Fiat-Shamir mode (sonic_prover_prove_fs) proves in
   // six passes, each running exactly the MSMs whose challenges have become known: results of earlier passes stay in `slots` / `frout`.
@@ -315,6 +321,11 @@ extern "C" int prove_fs_with_statement(sonic_prover_t* p, const uint8_t* aL, con
 extern "C" int prove_with_witness(sonic_prover_t* p, const WitnessView& w, hipEvent_t ready, const uint8_t* cs, const uint8_t* transcript, uint8_t* out_proof);
 extern "C" int prove_fs_with_witness(sonic_prover_t* p, const WitnessView& w, hipEvent_t ready, const uint8_t* cs, const uint8_t circuit_digest[32],
                                      const uint8_t blinder_seed[32], uint8_t* out_proof, uint8_t* out_transcript);
+// the two for a CORE proof (sonic_prove_batch_core_src, sonic_prove_batch_core_fs_src): w null: the resident assignment; transcript: 6 x 32;
+// out_proof: 576 bytes; out_yz (64 bytes) may be null
+extern "C" int prove_core_with_witness(sonic_prover_t* p, const WitnessView* w, hipEvent_t ready, const uint8_t* cs, const uint8_t* transcript, uint8_t* out_proof);
+extern "C" int prove_core_fs_with_witness(sonic_prover_t* p, const WitnessView* w, hipEvent_t ready, const uint8_t* cs, const uint8_t circuit_digest[32],
+                                          const uint8_t blinder_seed[32], uint8_t* out_proof, uint8_t* out_yz);
 // (witness_src.hip) a source checked against the rules of include/sonic_hip.h ("Witness sources"), the host's half and the device's;
 // nb blocks of a checked source brought into three planes of Montgomery elements (block b at plane + b * out_stride), by ONE launch --
 // a host source goes through p->wit_raw first; and the event that orders a device source

@@ -284,3 +284,60 @@ int sonic_hsc_verify_poly(const sonic_srs_t* srs, int64_t n_terms, const int64_t
 }
 
 }  // extern "C"
+
+// ---- core proofs (include/sonic_hip.h, "Core proofs") ------------------------------------------------------------------------------
+// The unhelped verifier: no signature vouches for the proof's s, so the verifier evaluates s(z, y) itself -- O(nnz + n) field work
+// (s_of_uv) -- and a proof whose s differs is rejected before any pairing; then the three pcV equations of the head (core_checks).
+static int verify_core_circuit(const sonic_srs* srs, const CircuitView& c, const uint8_t* proof, const uint8_t y[32], const uint8_t z[32], int* accepted) {
+  ProofViewT<G1Affine> pv;
+  Fr ym, zm, t, sv;
+  if (!parse_core_proof(proof, y, z, pv, ym, zm, load_g1)) { set_error("verify_core: non-canonical field element, or point off the curve or outside the order-r subgroup"); return SONIC_ERR_BAD_ENCODING; }
+  if (ym.is_zero() || zm.is_zero()) { set_error("verify_core: y or z is zero"); return SONIC_ERR_INEXACT_DIVISION; }
+  if (!proof_t(c, pv, ym, t)) return SONIC_ERR_BAD_ENCODING;         // k(y), Protocol.hs:120
+  VerifierKey vk;
+  int rc = load_verifier_key(srs, vk);
+  if (!rc) rc = s_of_uv(c, zm, ym, sv);                              // s(X, Y) at X = z, Y = y
+  if (rc) return rc;
+  if (!(sv == pv.s)) return SONIC_OK;                                // the proof's s is not s(z, y): rejected
+  return checks_accept(srs, vk, core_checks(c.n, srs_d(srs), pv, ym, zm, t), accepted);
+}
+
+static int verify_core_entry(const char* who, const sonic_srs_t* srs, const CircuitView& c, const uint8_t* proof, const uint8_t* y, const uint8_t* z, bool fs, int* accepted) {
+  API_HOST_BEGIN
+    if (!srs || !c.cs || !proof || (!fs && (!y || !z)) || !accepted) { set_error("%s: bad argument", who); return SONIC_ERR_INVALID_ARG; }
+    *accepted = 0;
+    int rc = circuit_validate(who, c);
+    if (rc) return rc;
+    uint8_t yz[64];
+    if (fs) {      // y, z are the ones the proof's own transcript yields (fs.hpp, "core proofs")
+      uint8_t digest[32], srs_id[32];
+      circuit_digest(c, digest);
+      rc = sonic_fs_srs_id(srs, srs_id);
+      if (rc) return rc;
+      fs_core_challenges_of_proof(c.n, c.Q, srs_d(srs), digest, srs_id, proof, yz);
+      y = yz; z = yz + 32;
+    }
+    return verify_core_circuit(srs, c, proof, y, z, accepted);
+  API_CATCH
+}
+
+extern "C" {
+
+int sonic_verify_core(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO, const uint8_t* cs,
+                      const uint8_t* proof, const uint8_t y[32], const uint8_t z[32], int* accepted) {
+  return verify_core_entry("sonic_verify_core", srs, dense_view(n, Q, wL, wR, wO, cs), proof, y, z, false, accepted);
+}
+int sonic_verify_core_csr(const sonic_srs_t* srs, int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val, const uint8_t* cs,
+                          const uint8_t* proof, const uint8_t y[32], const uint8_t z[32], int* accepted) {
+  return verify_core_entry("sonic_verify_core_csr", srs, csr_view(n, Q, row_ptr, col, val, cs), proof, y, z, false, accepted);
+}
+int sonic_verify_core_fs(const sonic_srs_t* srs, int64_t n, int64_t Q, const uint8_t* wL, const uint8_t* wR, const uint8_t* wO, const uint8_t* cs,
+                         const uint8_t* proof, int* accepted) {
+  return verify_core_entry("sonic_verify_core_fs", srs, dense_view(n, Q, wL, wR, wO, cs), proof, nullptr, nullptr, true, accepted);
+}
+int sonic_verify_core_fs_csr(const sonic_srs_t* srs, int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val, const uint8_t* cs,
+                             const uint8_t* proof, int* accepted) {
+  return verify_core_entry("sonic_verify_core_fs_csr", srs, csr_view(n, Q, row_ptr, col, val, cs), proof, nullptr, nullptr, true, accepted);
+}
+
+}  // extern "C"

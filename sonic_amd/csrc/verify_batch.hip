@@ -310,6 +310,78 @@ void decompress_device(sonic_verifier* v, long K, const uint8_t* proofs_z, std::
     proof_repack(Q, proofs_z + zsz * (size_t)k, 48, &proofs[psz * (size_t)k], 96, [&](const uint8_t*, uint8_t* out) { memcpy(out, c, 96); c += 96; return true; });
 }
 
+// The end of every batch, whatever its proofs are: the scalars of the fold (host) -- rho on W, rho z on W, rho on F by class of max, from
+// checks_of(k), the NC checks of the well-formed proof k with points as indices into its NP points, and the randomizers rho_{k NC + i}
+// of (seed, D) -- then the fold over every well-formed proof (a malformed one contributes zero scalars) and, where `each` is asked for and
+// the fold fails, every proof folded on its own.  t0: when the host began with the digest (the profiler's host_scalars phase).
+template <class ChecksOf>
+int fold_batch(Batch& b, const uint8_t seed[32], const uint8_t D[32], bool any_bad, double t0, ChecksOf&& checks_of, int* all_accepted, uint8_t* each) {
+  sonic_verifier* v = b.v;
+  const long K = b.K, NP = b.NP, NC = b.NC;
+  const size_t N = b.N();
+  const size_t nclass = v->ms.size();
+  std::vector<Fr> sc((2 + nclass) * N, Fr::zero());          // Montgomery while they are summed
+  std::vector<uint8_t> rho((size_t)(16 * NC));
+  long good_count = 0;
+  for (long k = 0; k < K; k++) {
+    if (!b.good[(size_t)k]) continue;
+    good_count++;
+    const auto checks = checks_of(k);
+    batch_randomizers(seed, D, (int64_t)k * NC, NC, rho.data());
+    const size_t base = (size_t)(k * NP);
+    for (long i = 0; i < NC; i++) {
+      const auto& c = checks[(size_t)i];
+      Fr r = Fr::zero();
+      memcpy(r.l, &rho[(size_t)(16 * i)], 16);
+      r = fp_to_mont(r);
+      sc[base + (size_t)c.W] = fp_add(sc[base + (size_t)c.W], r);
+      sc[N + base + (size_t)c.W] = fp_add(sc[N + base + (size_t)c.W], fp_mul(r, c.z));
+      b.gv[(size_t)k] = fp_add(b.gv[(size_t)k], fp_mul(r, c.val));
+      size_t cls = 0;
+      while (v->ms[cls] != c.maxm) cls++;
+      sc[(2 + cls) * N + base + (size_t)c.F] = fp_add(sc[(2 + cls) * N + base + (size_t)c.F], r);
+    }
+  }
+  for (auto& x : sc) x = fp_from_mont(x);
+  v->scalars.ensure(sizeof(Fr) * sc.size());
+  HIP_OK(hipMemcpyAsync(v->scalars.p, sc.data(), sizeof(Fr) * sc.size(), hipMemcpyHostToDevice, v->st));
+  HIP_OK(hipStreamSynchronize(v->st));
+  host_phase("verify_batch:host_scalars", now_ms() - t0);
+
+  // 5. the fold over every well-formed proof (a malformed one contributes zero scalars)
+  bool fold_ok = false;
+  if (good_count > 0) {
+    t0 = now_ms();
+    const Sums s = fold_sums(b, 0, K);
+    host_phase("verify_batch:msm", now_ms() - t0);
+    t0 = now_ms();
+    fold_ok = fold_accepts(v, s, true);
+    host_phase("verify_batch:host_pairing", now_ms() - t0);
+  }
+  *all_accepted = (fold_ok && !any_bad) ? 1 : 0;
+  if (!each) return SONIC_OK;
+  // the fold of the well-formed proofs held: each of them is accepted (the soundness of the fold); else every one is folded on its own
+  for (long k = 0; k < K; k++) each[k] = (fold_ok && b.good[(size_t)k]) ? 1 : 0;
+  if (fold_ok || good_count == 0) return SONIC_OK;
+  t0 = now_ms();
+  std::vector<Sums> sums((size_t)K);
+  for (long k = 0; k < K; k++) if (b.good[(size_t)k]) sums[(size_t)k] = fold_sums(b, k, k + 1);
+  const int nt = (int)std::min<long>(K, 16);
+  auto work = [&](int w) { for (long k = w; k < K; k += nt) if (b.good[(size_t)k]) each[k] = fold_accepts(v, sums[(size_t)k], false) ? 1 : 0; };
+  {
+    ThreadGroup th;
+    int started = 1;
+    try {
+      for (; started < nt; started++) th.emplace_back(work, started);
+    } catch (const std::system_error&) {}
+    work(0);
+    for (int w = started; w < nt; w++) work(w);
+    th.join();
+  }
+  host_phase("verify_batch:each", now_ms() - t0);
+  return SONIC_OK;
+}
+
 // challenges: K blocks of (2 + 2Q) x 32 bytes (y, z, then the pairs).  accepted: null, or the per-point flags of a batch that decompress_device
 // has already validated into v->pts.  cs_each: null -- every proof is checked against the handle's constants, batch digest v1 -- or K x Q
 // constants, proof k's own: k(y) of proof k is summed over cs_k (Q more field products per proof, on the host beside the K (3Q + 4) of the
@@ -380,71 +452,13 @@ int verify_batch_core(sonic_verifier* v, long K, const uint8_t* proofs, const ui
     for (long k = 0; k < K; k++) { h.update(proofs + psz * (size_t)k, psz); h.update(challenges + csz * (size_t)k, csz); }
     h.finish(D);
   }
-  const size_t nclass = v->ms.size();
-  std::vector<Fr> sc((2 + nclass) * N, Fr::zero());          // Montgomery while they are summed
   CircuitView cview{v->n, Q, v->cs.data(), true, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  std::vector<uint8_t> rho((size_t)(16 * NC));
-  long good_count = 0;
-  for (long k = 0; k < K; k++) {
-    if (!b.good[(size_t)k]) continue;
-    good_count++;
+  return fold_batch(b, seed, D, any_bad, t0, [&](long k) {
     Fr t;
     if (cs_each) cview.cs = cs_each + 32 * (size_t)(k * Q);
     proof_t(cview, views[(size_t)k], yms[(size_t)k], t);      // (cs was checked when the handle was made, cs_k in step 1)
-    const auto checks = proof_checks<int32_t>(v->n, v->d, views[(size_t)k], yms[(size_t)k], zms[(size_t)k], t, svs[(size_t)k]);
-    batch_randomizers(seed, D, (int64_t)k * NC, NC, rho.data());
-    const size_t base = (size_t)(k * NP);
-    for (long i = 0; i < NC; i++) {
-      const auto& c = checks[(size_t)i];
-      Fr r = Fr::zero();
-      memcpy(r.l, &rho[(size_t)(16 * i)], 16);
-      r = fp_to_mont(r);
-      sc[base + (size_t)c.W] = fp_add(sc[base + (size_t)c.W], r);
-      sc[N + base + (size_t)c.W] = fp_add(sc[N + base + (size_t)c.W], fp_mul(r, c.z));
-      b.gv[(size_t)k] = fp_add(b.gv[(size_t)k], fp_mul(r, c.val));
-      size_t cls = 0;
-      while (v->ms[cls] != c.maxm) cls++;
-      sc[(2 + cls) * N + base + (size_t)c.F] = fp_add(sc[(2 + cls) * N + base + (size_t)c.F], r);
-    }
-  }
-  for (auto& x : sc) x = fp_from_mont(x);
-  v->scalars.ensure(sizeof(Fr) * sc.size());
-  HIP_OK(hipMemcpyAsync(v->scalars.p, sc.data(), sizeof(Fr) * sc.size(), hipMemcpyHostToDevice, v->st));
-  HIP_OK(hipStreamSynchronize(v->st));
-  host_phase("verify_batch:host_scalars", now_ms() - t0);
-
-  // 5. the fold over every well-formed proof (a malformed one contributes zero scalars)
-  bool fold_ok = false;
-  if (good_count > 0) {
-    t0 = now_ms();
-    const Sums s = fold_sums(b, 0, K);
-    host_phase("verify_batch:msm", now_ms() - t0);
-    t0 = now_ms();
-    fold_ok = fold_accepts(v, s, true);
-    host_phase("verify_batch:host_pairing", now_ms() - t0);
-  }
-  *all_accepted = (fold_ok && !any_bad) ? 1 : 0;
-  if (!each) return SONIC_OK;
-  // the fold of the well-formed proofs held: each of them is accepted (the soundness of the fold); else every one is folded on its own
-  for (long k = 0; k < K; k++) each[k] = (fold_ok && b.good[(size_t)k]) ? 1 : 0;
-  if (fold_ok || good_count == 0) return SONIC_OK;
-  t0 = now_ms();
-  std::vector<Sums> sums((size_t)K);
-  for (long k = 0; k < K; k++) if (b.good[(size_t)k]) sums[(size_t)k] = fold_sums(b, k, k + 1);
-  const int nt = (int)std::min<long>(K, 16);
-  auto work = [&](int w) { for (long k = w; k < K; k += nt) if (b.good[(size_t)k]) each[k] = fold_accepts(v, sums[(size_t)k], false) ? 1 : 0; };
-  {
-    ThreadGroup th;
-    int started = 1;
-    try {
-      for (; started < nt; started++) th.emplace_back(work, started);
-    } catch (const std::system_error&) {}
-    work(0);
-    for (int w = started; w < nt; w++) work(w);
-    th.join();
-  }
-  host_phase("verify_batch:each", now_ms() - t0);
-  return SONIC_OK;
+    return proof_checks<int32_t>(v->n, v->d, views[(size_t)k], yms[(size_t)k], zms[(size_t)k], t, svs[(size_t)k]);
+  }, all_accepted, each);
 }
 
 // the Fiat-Shamir form: the challenges each proof determines (fs.hpp), in sonic_verify's order; a proof whose own u, v are not its
@@ -476,6 +490,122 @@ int verify_fs_batch_core(sonic_verifier* v, long K, const uint8_t* proofs, const
     for (int64_t k = 0; k < K; k++) if (!mine[(size_t)k]) each[k] = 0;
   }
   return SONIC_OK;
+}
+
+// ---- core proofs (include/sonic_hip.h, "Core proofs"): K x (R, T, a, W_a, b, W_b, W_t, s) ------------------------------------------------
+// No signature vouches for a core proof's s: the verifier evaluates s(z_k, y_k) itself -- k_s_of_uv_batch at (u, v) = (z_k, y_k), what the
+// full batch spends on s(u_k, v_k) -- and a proof whose s differs is REJECTED, like a malformed one: it rides along with zero scalars and
+// the others' verdicts stand.  The 3K checks of the heads (core_checks) fold into the same four Miller loops.
+// K compressed core proofs: decompress_device's steps over the 5K points
+void decompress_core_device(sonic_verifier* v, long K, const uint8_t* proofs_z, std::vector<uint8_t>& proofs, std::vector<uint8_t>& accepted) {
+  const long NP = ProofLayout::core_K;
+  const size_t psz = ProofLayout::core_proof_bytes(), zsz = ProofLayout::core_proof_bytes_compressed(), M = (size_t)K * (size_t)NP;
+  std::vector<uint8_t> stage(48 * M), canon(96 * M);
+  proofs.resize(psz * (size_t)K);
+  uint8_t* s = stage.data();
+  for (long k = 0; k < K; k++)
+    core_proof_repack(proofs_z + zsz * (size_t)k, 48, &proofs[psz * (size_t)k], 96, [&](const uint8_t* in, uint8_t*) { memcpy(s, in, 48); s += 48; return true; });
+  v->raw.ensure(96 * M); v->zraw.ensure(48 * M); v->pts.ensure(sizeof(G1Affine) * M); v->flags.ensure(M);
+  hipStream_t st = v->st;
+  HIP_OK(hipMemcpyAsync(v->zraw.p, stage.data(), 48 * M, hipMemcpyHostToDevice, st));
+  g1_decompress_enqueue(st, v->zraw.as<uint8_t>(), PointArrayMut{v->pts.as<char>(), (uint32_t)sizeof(G1Affine)}, v->raw.as<uint8_t>(), v->flags.as<uint8_t>(), (long)M, true);
+  accepted.resize(M);
+  HIP_OK(hipMemcpyAsync(canon.data(), v->raw.p, 96 * M, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(accepted.data(), v->flags.p, M, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  for (auto& f : accepted) f = f ? 0 : 1;                       // the kernel's verdict is 0 = accepted
+  const uint8_t* c = canon.data();
+  for (long k = 0; k < K; k++)
+    core_proof_repack(proofs_z + zsz * (size_t)k, 48, &proofs[psz * (size_t)k], 96, [&](const uint8_t*, uint8_t* out) { memcpy(out, c, 96); c += 96; return true; });
+}
+
+// proofs: K x 576 bytes; yz: K x (y_k, z_k); cs_each: K x Q constants or null (the handle's, for every proof); accepted: as verify_batch_core's
+int verify_core_proofs_batch(sonic_verifier* v, long K, const uint8_t* proofs, const uint8_t* yz, const uint8_t* cs_each, const uint8_t* seed_in, int* all_accepted,
+                             uint8_t* each, const std::vector<uint8_t>* accepted = nullptr) {
+  const long Q = v->Q, NP = ProofLayout::core_K, NC = 3;
+  const size_t psz = ProofLayout::core_proof_bytes(), N = (size_t)K * (size_t)NP;
+  uint8_t seed[32];
+  if (seed_in) memcpy(seed, seed_in, 32);
+  else if (getrandom(seed, 32, 0) != 32) { set_error("sonic_verifier_verify_core_batch: the operating system gave no random bytes for the seed"); return SONIC_ERR_INVALID_ARG; }
+  double t0 = now_ms();
+
+  // 1. decode, as the full batch does
+  Batch b{v, K, NP, NC, std::vector<char>((size_t)K, 0), std::vector<Fr>((size_t)K, Fr::zero())};
+  std::vector<ProofViewT<int32_t>> views((size_t)K);
+  std::vector<Fr> yms((size_t)K), zms((size_t)K);
+  std::vector<uint8_t> stage(accepted ? 0 : 96 * N, 0);
+  long first_bad = -1;
+  for (long k = 0; k < K; k++) {
+    int32_t idx = 0;
+    uint8_t* dst = accepted ? nullptr : &stage[96 * (size_t)(k * NP)];
+    auto take = [&](const uint8_t* enc, int32_t& o) { o = idx++; if (!accepted) memcpy(dst + 96 * (size_t)o, enc, 96); return true; };
+    b.good[(size_t)k] = parse_core_proof(proofs + psz * (size_t)k, yz + 64 * (size_t)k, yz + 64 * (size_t)k + 32, views[(size_t)k], yms[(size_t)k], zms[(size_t)k], take) ? 1 : 0;
+    for (long q = 0; cs_each && q < Q && b.good[(size_t)k]; q++) { Fr c; if (!load_fr(cs_each + 32 * (size_t)(k * Q + q), c)) b.good[(size_t)k] = 0; }
+    if (!b.good[(size_t)k] && first_bad < 0) first_bad = k;
+  }
+  host_phase("verify_core_batch:host_decode", now_ms() - t0);
+
+  // 2. the 5K points (device)
+  std::vector<uint8_t> flags;
+  if (accepted) flags = *accepted;
+  else validate_device(v, stage.data(), (long)N, flags);
+  for (long k = 0; k < K; k++) {
+    bool ok = true;
+    for (long j = 0; j < NP; j++) ok = ok && flags[(size_t)(k * NP + j)];
+    if (!ok) { b.good[(size_t)k] = 0; if (first_bad < 0 || k < first_bad) first_bad = k; }
+  }
+  const bool any_malformed = first_bad >= 0;
+  if (any_malformed) set_error("verify_core_batch: proof %ld is malformed (non-canonical field element in the proof, its challenges or its constants, or point off the curve or "
+                               "outside the order-r subgroup)", first_bad);
+
+  // 3. s(z_k, y_k) (device), held against the proof's own s; a malformed proof rides along as the pair (1, 1)
+  std::vector<Fr> us((size_t)K), vs((size_t)K), svs;
+  std::vector<uint8_t> sok;
+  for (long k = 0; k < K; k++) {
+    us[(size_t)k] = b.good[(size_t)k] ? zms[(size_t)k] : Fr::one();
+    vs[(size_t)k] = b.good[(size_t)k] ? yms[(size_t)k] : Fr::one();
+  }
+  eval_s_device(v, K, us, vs, svs, sok);
+  long first_refused = -1, first_unbound = -1;
+  for (long k = 0; k < K; k++) {
+    if (!b.good[(size_t)k]) continue;
+    if (!sok[(size_t)k]) { b.good[(size_t)k] = 0; if (first_refused < 0) first_refused = k; }
+    else if (!(svs[(size_t)k] == views[(size_t)k].s)) { b.good[(size_t)k] = 0; if (first_unbound < 0) first_unbound = k; }
+  }
+  if (!any_malformed && (first_refused >= 0 || first_unbound >= 0)) {
+    if (first_unbound < 0 || (first_refused >= 0 && first_refused < first_unbound)) set_error("verify_core_batch: proof %ld has y or z zero", first_refused);
+    else set_error("verify_core_batch: the s of proof %ld is not s(z, y) of the circuit", first_unbound);
+  }
+  const bool any_bad = any_malformed || first_refused >= 0 || first_unbound >= 0;
+
+  // 4. the digest that the randomizers bind, then the fold over the checks of the heads
+  t0 = now_ms();
+  uint8_t D[32];
+  std::vector<uint8_t> cs_all;
+  if (!cs_each) { cs_all.resize(32 * (size_t)(K * Q)); for (long k = 0; k < K; k++) memcpy(&cs_all[32 * (size_t)(k * Q)], v->cs.data(), 32 * (size_t)Q); }
+  fs_core_batch_digest(v->n, Q, v->d, v->digest, v->srs_id, K, proofs, yz, cs_each ? cs_each : cs_all.data(), D);
+  CircuitView cview{v->n, Q, v->cs.data(), true, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  return fold_batch(b, seed, D, any_bad, t0, [&](long k) {
+    Fr t;
+    if (cs_each) cview.cs = cs_each + 32 * (size_t)(k * Q);
+    proof_t(cview, views[(size_t)k], yms[(size_t)k], t);
+    return core_checks<int32_t>(v->n, v->d, views[(size_t)k], yms[(size_t)k], zms[(size_t)k], t);
+  }, all_accepted, each);
+}
+
+// the Fiat-Shamir form: y_k, z_k from each proof's own transcript (fs.hpp, "core proofs"), proof k's from the digest of ITS statement
+int verify_core_proofs_fs_batch(sonic_verifier* v, long K, const uint8_t* proofs, const uint8_t* cs_each, const uint8_t* seed, int* all_accepted, uint8_t* each,
+                                const std::vector<uint8_t>* accepted) {
+  const long Q = v->Q;
+  std::vector<uint8_t> yz(64 * (size_t)K);
+  for (int64_t k = 0; k < K; k++) {
+    uint8_t dk[32];
+    memcpy(dk, v->digest, 32);
+    // (a cs_k that is not canonical has no digest: the proof rides along under the handle's and is refused as malformed)
+    if (cs_each && fs_circuit_digest_resume(v->midstate, cs_each + 32 * (size_t)(k * Q), dk) != 0) memcpy(dk, v->digest, 32);
+    fs_core_challenges_of_proof(v->n, Q, v->d, dk, v->srs_id, proofs + ProofLayout::core_proof_bytes() * (size_t)k, &yz[64 * (size_t)k]);
+  }
+  return verify_core_proofs_batch(v, K, proofs, yz.data(), cs_each, seed, all_accepted, each, accepted);
 }
 
 int verifier_new(const char* who, const sonic_srs_t* srs, const CircuitView& c, sonic_verifier_t** out) {
@@ -654,6 +784,43 @@ int sonic_verifier_verify_fs_batch_cs(sonic_verifier_t* v, int64_t K, const uint
   decompress_device(v, (long)K, proofs, full, accepted);
   return verify_fs_batch_core(v, (long)K, full.data(), seed, all_accepted, each, &accepted, cs);
   API_CATCH
+}
+
+// K core proofs against the handle's circuit: yz = K x (y_k, z_k); cs = K x Q constants or NULL (the handle's); compressed as above
+int sonic_verifier_verify_core_batch(sonic_verifier_t* v, int64_t K, const uint8_t* proofs, int compressed, const uint8_t* yz, const uint8_t* cs, const uint8_t seed[32],
+                                     int* all_accepted, uint8_t* each) {
+  if (all_accepted) *all_accepted = 0;
+  API_BEGIN_ON(v ? v->device : -1)                      // (first: without a device the answer is SONIC_ERR_NO_DEVICE whatever the arguments are)
+  if (!v || !proofs || !yz || !all_accepted || (compressed != 0 && compressed != 1)) { set_error("sonic_verifier_verify_core_batch: bad argument"); return SONIC_ERR_INVALID_ARG; }
+  int rc = batch_size_ok("sonic_verifier_verify_core_batch", v, K);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> g(v->mu);
+  if (!compressed) return verify_core_proofs_batch(v, (long)K, proofs, yz, cs, seed, all_accepted, each);
+  std::vector<uint8_t> full, accepted;
+  decompress_core_device(v, (long)K, proofs, full, accepted);
+  return verify_core_proofs_batch(v, (long)K, full.data(), yz, cs, seed, all_accepted, each, &accepted);
+  API_CATCH
+}
+int sonic_verifier_verify_core_fs_batch(sonic_verifier_t* v, int64_t K, const uint8_t* proofs, int compressed, const uint8_t* cs, const uint8_t seed[32], int* all_accepted,
+                                        uint8_t* each) {
+  if (all_accepted) *all_accepted = 0;
+  API_BEGIN_ON(v ? v->device : -1)
+  if (!v || !proofs || !all_accepted || (compressed != 0 && compressed != 1)) { set_error("sonic_verifier_verify_core_fs_batch: bad argument"); return SONIC_ERR_INVALID_ARG; }
+  int rc = batch_size_ok("sonic_verifier_verify_core_fs_batch", v, K);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> g(v->mu);
+  if (!compressed) return verify_core_proofs_fs_batch(v, (long)K, proofs, cs, seed, all_accepted, each, nullptr);
+  std::vector<uint8_t> full, accepted;
+  decompress_core_device(v, (long)K, proofs, full, accepted);
+  return verify_core_proofs_fs_batch(v, (long)K, full.data(), cs, seed, all_accepted, each, &accepted);
+  API_CATCH
+}
+// the digest of a batch of core proofs on its own (host only; fs.hpp)
+int sonic_verify_core_batch_digest(int64_t n, int64_t Q, int64_t d, const uint8_t circuit_digest[32], const uint8_t srs_id[32], int64_t K, const uint8_t* proofs,
+                                   const uint8_t* yz, const uint8_t* cs, uint8_t out[32]) {
+  if (n < 1 || Q < 1 || d < 1 || !circuit_digest || !srs_id || K < 0 || (K > 0 && (!proofs || !yz || !cs)) || !out) { set_error("sonic_verify_core_batch_digest: bad argument"); return SONIC_ERR_INVALID_ARG; }
+  fs_core_batch_digest(n, Q, d, circuit_digest, srs_id, K, proofs, yz, cs, out);
+  return SONIC_OK;
 }
 
 int sonic_verifier_eval_s(sonic_verifier_t* v, int64_t K, const uint8_t* uv, uint8_t* out) {

@@ -152,14 +152,30 @@ void hsc_checks(int64_t d, const HscProofViewT<P>& h, const Fr& sv, std::vector<
   checks.push_back(PcvCheckT<P>{d, h.C, h.v, sv, h.Qv});           // Signature.hs:89
 }
 
+// the three checks of the head (Protocol.hs:123-125): ALL the pcV checks of a core proof, whose fourth condition -- the proof's s is
+// s(z, y) -- the verifier establishes itself (s_of_uv at u = z, v = y); of a full proof the first three
+template <class P>
+std::vector<PcvCheckT<P>> core_checks(int64_t n, int64_t d, const ProofViewT<P>& v, const Fr& ym, const Fr& zm, const Fr& t) {
+  return std::vector<PcvCheckT<P>>{PcvCheckT<P>{n, v.R, zm, v.a, v.Wa},                       // Protocol.hs:123
+                                   PcvCheckT<P>{n, v.R, fp_mul(ym, zm), v.b, v.Wb},           // :124
+                                   PcvCheckT<P>{d, v.T, zm, t, v.Wt}};                        // :125
+}
+
 // THE list of a proof's 4 + 3Q checks (Protocol.hs:123-125, then hscVerify's), in the order both verifiers number them
 template <class P>
 std::vector<PcvCheckT<P>> proof_checks(int64_t n, int64_t d, const ProofViewT<P>& v, const Fr& ym, const Fr& zm, const Fr& t, const Fr& sv) {
-  std::vector<PcvCheckT<P>> checks{PcvCheckT<P>{n, v.R, zm, v.a, v.Wa},                       // Protocol.hs:123
-                                   PcvCheckT<P>{n, v.R, fp_mul(ym, zm), v.b, v.Wb},           // :124
-                                   PcvCheckT<P>{d, v.T, zm, t, v.Wt}};                        // :125
+  std::vector<PcvCheckT<P>> checks = core_checks(n, d, v, ym, zm, t);
   hsc_checks(d, v.h, sv, checks);
   return checks;
+}
+
+// 576 bytes of core proof (R, T, a, Wa, b, Wb, Wt, s) and the challenges y, z it is checked at; the signature part of the view stays empty
+template <class P, class LoadPoint>
+bool parse_core_proof(const uint8_t* proof, const uint8_t y[32], const uint8_t z[32], ProofViewT<P>& v, Fr& ym, Fr& zm, LoadPoint&& load_point) {
+  const uint8_t* p = proof;
+  auto G = [&](P& o) { bool k = load_point(p, o); p += 96; return k; };
+  auto F = [&](Fr& o) { bool k = load_fr(p, o); p += 32; return k; };
+  return G(v.R) && G(v.T) && F(v.a) && G(v.Wa) && F(v.b) && G(v.Wb) && G(v.Wt) && F(v.s) && load_fr(y, ym) && load_fr(z, zm);
 }
 
 // s(u, v) for the s(X,Y) of a circuit (Signature.hs:81; Constraints.hs:34-53): sum_i u^-i U_i(v) + u^i V_i(v) + u^{i+n} W_i(v).  Dense

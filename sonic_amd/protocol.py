@@ -194,6 +194,45 @@ def _hsc_from_bytes(b: bytes, m: int) -> "HscProof":
 
 
 @dataclass
+class CoreProof:
+    """A core proof (include/sonic_hip.h, "Core proofs"): the head of a Proof -- R, T, a, W_a, b, W_b, W_t, s -- and no signature; its
+    verifier (verify_core, Verifier.verify_core_batch) evaluates s(z, y) itself.  576 bytes, 336 compressed, whatever Q is."""
+    prR: object
+    prT: object
+    prA: int
+    prWa: object
+    prB: int
+    prWb: object
+    prWt: object
+    prS: int
+
+    def to_bytes(self, compressed: bool = False) -> bytes:
+        """record order R T a Wa b Wb Wt s, serialised from the fields; compressed=True: every point as its 48 compressed bytes
+        (sonic_core_proof_compress, which validates the points)"""
+        fr = lambda v: int(v).to_bytes(32, "little")     # noqa: E731  (as is: a non-canonical element must reach the verifier unreduced)
+        raw = b"".join([g1_to_bytes(self.prR), g1_to_bytes(self.prT), fr(self.prA), g1_to_bytes(self.prWa), fr(self.prB),
+                        g1_to_bytes(self.prWb), g1_to_bytes(self.prWt), fr(self.prS)])
+        if not compressed:
+            return raw
+        out = C.create_string_buffer(_lib.CORE_PROOF_SIZE_COMPRESSED)
+        _lib.check(_lib.lib().sonic_core_proof_compress(raw, out))
+        return out.raw
+
+    @classmethod
+    def from_bytes(cls, b: bytes) -> "CoreProof":
+        b = bytes(b)
+        if len(b) == _lib.CORE_PROOF_SIZE_COMPRESSED:
+            out = C.create_string_buffer(_lib.CORE_PROOF_SIZE)
+            _lib.check(_lib.lib().sonic_core_proof_decompress(b, out))
+            b = out.raw
+        if len(b) != _lib.CORE_PROOF_SIZE:
+            raise ValueError(f"a core proof is {_lib.CORE_PROOF_SIZE} bytes ({_lib.CORE_PROOF_SIZE_COMPRESSED} compressed), got {len(b)}")
+        g = lambda o: g1_from_bytes(b[o:o + 96])                  # noqa: E731
+        f = lambda o: int.from_bytes(b[o:o + 32], "little")       # noqa: E731
+        return cls(g(0), g(96), f(192), g(224), f(320), g(352), g(448), f(544))
+
+
+@dataclass
 class Proof:                 # Protocol.hs:28-38
     prR: object
     prT: object
@@ -217,6 +256,10 @@ class Proof:                 # Protocol.hs:28-38
         head = [g1_to_bytes(self.prR), g1_to_bytes(self.prT), fr(self.prA), g1_to_bytes(self.prWa), fr(self.prB),
                 g1_to_bytes(self.prWb), g1_to_bytes(self.prWt), fr(self.prS)]
         return b"".join(head) + _hsc_to_bytes(self.prHscProof)
+
+    def core(self) -> CoreProof:
+        """the head of this proof as a core proof: what verify_core checks soundly, with this proof's own y, z"""
+        return CoreProof(self.prR, self.prT, self.prA, self.prWa, self.prB, self.prWb, self.prWt, self.prS)
 
     @classmethod
     def from_bytes(cls, b: bytes, Q: int) -> "Proof":
@@ -336,6 +379,38 @@ class Prover:
         out = C.create_string_buffer(_lib.lib().sonic_proof_size(self.Q))
         _lib.check(_lib.lib().sonic_prover_collect(self._h, out))
         return out.raw
+
+    # ---- core proofs: R, T and the openings, no signature (include/sonic_hip.h, "Core proofs") ----
+    def prove_core_bytes(self, transcript) -> bytes:
+        """the 576 bytes of a core proof (sonic_prover_prove_core); transcript: the four blinders, y, z.  Equal to the first 576 bytes of
+        prove_bytes for every transcript that starts with these six."""
+        tr = fr_array(transcript)
+        assert tr.shape[0] == 6
+        out = C.create_string_buffer(_lib.CORE_PROOF_SIZE)
+        _lib.check(_lib.lib().sonic_prover_prove_core(self._h, tr.ctypes.data, out))
+        return out.raw
+
+    def submit_core(self, transcript) -> None:
+        """queue one core proof and return without waiting (sonic_prover_submit_core); one proof in flight per handle"""
+        tr = fr_array(transcript)
+        assert tr.shape[0] == 6
+        _lib.check(_lib.lib().sonic_prover_submit_core(self._h, tr.ctypes.data))
+
+    def collect_core(self) -> bytes:
+        """wait for the core proof submit_core queued and return its bytes (sonic_prover_collect_core)"""
+        out = C.create_string_buffer(_lib.CORE_PROOF_SIZE)
+        _lib.check(_lib.lib().sonic_prover_collect_core(self._h, out))
+        return out.raw
+
+    def prove_core_fs(self, circuit_digest: bytes, blinder_seed: bytes):
+        """a core proof under its own Fiat-Shamir transcript (sonic_prover_prove_core_fs): (proof bytes, y, z); blinders from witness digest v2"""
+        circuit_digest, blinder_seed = bytes(circuit_digest), bytes(blinder_seed)
+        if len(circuit_digest) != 32 or len(blinder_seed) != 32:      # the C side reads 32 bytes of each
+            raise ValueError("prove_core_fs: circuit_digest and blinder_seed must be 32 bytes each")
+        out = C.create_string_buffer(_lib.CORE_PROOF_SIZE)
+        yz = C.create_string_buffer(64)
+        _lib.check(_lib.lib().sonic_prover_prove_core_fs(self._h, circuit_digest, blinder_seed, out, yz))
+        return out.raw, int.from_bytes(yz.raw[:32], "little"), int.from_bytes(yz.raw[32:], "little")
 
     # ---- ONE proof over several GPUs (sonic_prover_set_share): this handle runs rank's pieces of the proof's MSMs ----
     def set_share(self, rank: int, world: int) -> None:
@@ -556,6 +631,60 @@ def prove_batch_fs(provers, digests, seeds, assignments=None, constants=None):
                                                    b"".join(seeds) or bytes(32), out.ctypes.data, tr.ctypes.data, status))
     raw_tr = tr.tobytes()
     return [(out[i].tobytes(), [int.from_bytes(raw_tr[32 * (i * tl + k):32 * (i * tl + k) + 32], "little") for k in range(tl)]) for i in range(K)]
+
+
+def _core_batch_args(provers, K, assignments, constants, who):
+    """what the two core batch calls share: the witness source (or None: the resident assignments) and the constants (or None)"""
+    Q, n = provers[0].Q, provers[0].n
+    src = keep = None
+    if assignments is not None:
+        if not isinstance(assignments, WitnessBatch):
+            assignments = list(assignments)
+            cols = [np.ascontiguousarray(np.stack([fr_array(getattr(a, k)) for a in assignments])) if assignments else np.zeros((0, n, 32), np.uint8) for k in ("aL", "aR", "aO")]
+            assignments = WitnessBatch(*cols)
+        if len(assignments) != K:
+            raise ValueError(f"{who}: one assignment per proof")
+        if K:
+            src, keep = _witness_src(assignments.aL, assignments.aR, assignments.aO, assignments.stream, n, K, [p.device for p in provers], who)
+    cs = None
+    if constants is not None:
+        constants = list(constants)
+        if len(constants) != K:
+            raise ValueError(f"{who}: one set of constants per proof")
+        cs = b"".join(_constants_bytes(c, Q, who) for c in constants) or bytes(32)
+    return (C.byref(src) if src is not None else None), cs, keep
+
+
+def prove_core_batch(provers, transcripts, assignments=None, constants=None) -> List[bytes]:
+    """K core proofs of one circuit over several prover handles (sonic_prove_batch_core_src; proof i on handle i % len(provers)).
+    transcripts: six values per proof; assignments: Assignment objects, a WitnessBatch, or None (the resident assignments);
+    constants: one cs per proof, or None."""
+    provers = list(provers)
+    K = len(transcripts)
+    tr = np.ascontiguousarray(np.stack([fr_array(t) for t in transcripts]) if K else np.zeros((0, 6, 32), np.uint8))
+    assert tr.shape[1] == 6
+    src, cs, _keep = _core_batch_args(provers, K, assignments, constants, "prove_core_batch")
+    out = np.zeros((max(K, 1), _lib.CORE_PROOF_SIZE), np.uint8)
+    status = (C.c_int * max(K, 1))()
+    _lib.check(_lib.lib().sonic_prove_batch_core_src(_handle_array(provers), len(provers), K, src, cs, tr.ctypes.data, out.ctypes.data, status))
+    return [out[i].tobytes() for i in range(K)]
+
+
+def prove_core_batch_fs(provers, digests, seeds, assignments=None, constants=None):
+    """K Fiat-Shamir core proofs (sonic_prove_batch_core_fs_src): [(proof bytes, y, z), ...]; digests, seeds, assignments, constants as
+    for prove_batch_fs"""
+    provers = list(provers)
+    digests, seeds = [bytes(d) for d in digests], [bytes(s) for s in seeds]
+    K = len(digests)
+    if len(seeds) != K or any(len(b) != 32 for b in digests + seeds):
+        raise ValueError("prove_core_batch_fs: one 32-byte circuit digest and one 32-byte seed per proof")
+    src, cs, _keep = _core_batch_args(provers, K, assignments, constants, "prove_core_batch_fs")
+    out = np.zeros((max(K, 1), _lib.CORE_PROOF_SIZE), np.uint8)
+    yz = np.zeros((max(K, 1), 64), np.uint8)
+    status = (C.c_int * max(K, 1))()
+    _lib.check(_lib.lib().sonic_prove_batch_core_fs_src(_handle_array(provers), len(provers), K, src, cs, b"".join(digests) or bytes(32),
+                                                        b"".join(seeds) or bytes(32), out.ctypes.data, yz.ctypes.data, status))
+    return [(out[i].tobytes(), int.from_bytes(yz[i, :32].tobytes(), "little"), int.from_bytes(yz[i, 32:].tobytes(), "little")) for i in range(K)]
 
 
 class _Statement(C.Structure):          # sonic_statement_t
@@ -853,6 +982,52 @@ def verify(srs: SRS, circuit: ArithCircuit, proof: Proof, y: int, z: int, yzs) -
     return bool(ok.value)
 
 
+def _core_bytes(proof) -> bytes:
+    """a core proof as its 576 bytes: a CoreProof, a Proof (its head), or bytes in either encoding"""
+    if isinstance(proof, Proof):
+        proof = proof.core()
+    if isinstance(proof, CoreProof):
+        return proof.to_bytes()
+    raw = bytes(proof)
+    return CoreProof.from_bytes(raw).to_bytes() if len(raw) == _lib.CORE_PROOF_SIZE_COMPRESSED else raw
+
+
+def verify_core(srs: SRS, circuit, proof, y: int, z: int) -> bool:
+    """the sound check of a proof's head (sonic_verify_core[_csr]): the proof's s must be s(z, y) of the circuit -- evaluated here, since
+    nothing in `verify` ties it down -- and the three pcV equations of R, T and their openings must hold.  proof: a CoreProof, its bytes,
+    or a Proof, whose head is checked: verify_core(proof, y, z) with the proof's own y, z (fs_challenges for a Fiat-Shamir proof) is the
+    sound verification of an existing full proof."""
+    n, Q, suffix, args, _keep = _circuit_args(circuit, "verify_core: ")
+    raw = _core_bytes(proof)
+    if len(raw) != _lib.CORE_PROOF_SIZE:
+        return False
+    ok = C.c_int(0)
+    _lib.check(getattr(_lib.lib(), "sonic_verify_core" + suffix)(srs._h, n, Q, *args, raw, fr_to_bytes(y), fr_to_bytes(z), C.byref(ok)))
+    return bool(ok.value)
+
+
+def verify_core_fs(srs: SRS, circuit, proof) -> bool:
+    """verify_core for a proof made by Prover.prove_core_fs: y, z are recomputed from the circuit and the proof (sonic_verify_core_fs[_csr])"""
+    n, Q, suffix, args, _keep = _circuit_args(circuit, "verify_core_fs: ")
+    raw = _core_bytes(proof)
+    if len(raw) != _lib.CORE_PROOF_SIZE:
+        return False
+    ok = C.c_int(0)
+    _lib.check(getattr(_lib.lib(), "sonic_verify_core_fs" + suffix)(srs._h, n, Q, *args, raw, C.byref(ok)))
+    return bool(ok.value)
+
+
+def fs_core_challenges(srs: SRS, circuit, proof):
+    """(y, z) of a Fiat-Shamir core proof (sonic_fs_core_challenges; host only)"""
+    n, Q = _circuit_args(circuit)[:2]
+    raw = _core_bytes(proof)
+    if len(raw) != _lib.CORE_PROOF_SIZE:
+        raise ValueError(f"fs_core_challenges: a core proof is {_lib.CORE_PROOF_SIZE} bytes")
+    out = C.create_string_buffer(64)
+    _lib.check(_lib.lib().sonic_fs_core_challenges(n, Q, srs.srsD, fs_circuit_digest(circuit), fs_srs_id(srs), raw, out))
+    return int.from_bytes(out.raw[:32], "little"), int.from_bytes(out.raw[32:], "little")
+
+
 class Verifier:
     """The batched verifier (sonic_verifier_* of the C ABI): the circuit resident in HBM, K proofs folded into ONE pairing product --
     four Miller loops and one final exponentiation per batch; point validation, s(u, v) and the G1 sums run on the GPU.  `circuit` is an
@@ -924,6 +1099,37 @@ class Verifier:
             return self._result(K, lambda ok, flags: call(self._h, K, raw, int(z == "_z"), cs, sd, ok, flags), each)
         call = getattr(_lib.lib(), "sonic_verifier_verify_fs_batch" + z)
         return self._result(K, lambda ok, flags: call(self._h, K, raw, sd, ok, flags), each)
+
+    def _core_proof_bytes(self, proofs):
+        """a batch of core proofs as one buffer and whether it is the compressed form (told apart by length)"""
+        raws = [p.core().to_bytes() if isinstance(p, Proof) else p.to_bytes() if isinstance(p, CoreProof) else bytes(p) for p in proofs]
+        if raws and all(len(r) == _lib.CORE_PROOF_SIZE_COMPRESSED for r in raws):
+            return b"".join(raws), 1
+        if not raws or any(len(r) != _lib.CORE_PROOF_SIZE for r in raws):
+            raise ValueError(f"Verifier: need at least one core proof, each of {_lib.CORE_PROOF_SIZE} bytes, or each of {_lib.CORE_PROOF_SIZE_COMPRESSED} compressed")
+        return b"".join(raws), 0
+
+    def verify_core_batch(self, proofs, yzs, seed=None, each: bool = False, constants=None):
+        """K core proofs in one pairing product (sonic_verifier_verify_core_batch): s(z_k, y_k) on the GPU held against each proof's s,
+        then the 3K checks of the heads folded.  proofs: CoreProof objects, Proofs (their heads), 576-byte or 336-byte (compressed) core
+        proofs; yzs: one (y, z) per proof; constants: None, or one cs per proof.  A proof whose s is not s(z, y) is a rejected proof."""
+        proofs, yzs = list(proofs), list(yzs)
+        if len(yzs) != len(proofs) or any(len(pair) != 2 for pair in yzs):
+            raise ValueError("verify_core_batch: one (y, z) pair per proof")
+        fr = lambda v: int(v).to_bytes(32, "little")     # noqa: E731  (as is: a non-canonical challenge rejects its proof)
+        (raw, z), yz, sd, K = self._core_proof_bytes(proofs), b"".join(fr(y) + fr(zz) for y, zz in yzs), self._seed(seed), len(proofs)
+        cs = self._constants(constants, K) if constants is not None else None
+        call = _lib.lib().sonic_verifier_verify_core_batch
+        return self._result(K, lambda ok, flags: call(self._h, K, raw, z, yz, cs, sd, ok, flags), each)
+
+    def verify_core_fs_batch(self, proofs, seed=None, each: bool = False, constants=None):
+        """the same for Fiat-Shamir core proofs (Prover.prove_core_fs): y_k, z_k recomputed from the circuit (with constants: from the
+        digest of proof k's own statement) and the proof"""
+        proofs = list(proofs)
+        (raw, z), sd, K = self._core_proof_bytes(proofs), self._seed(seed), len(proofs)
+        cs = self._constants(constants, K) if constants is not None else None
+        call = _lib.lib().sonic_verifier_verify_core_fs_batch
+        return self._result(K, lambda ok, flags: call(self._h, K, raw, z, cs, sd, ok, flags), each)
 
     def eval_s(self, uvs) -> List[int]:
         """s(u, v) of the circuit's s(X, Y) for every (u, v) of `uvs`, on the GPU (raises SonicError INEXACT_DIVISION for u = 0 or v = 0)"""
