@@ -64,6 +64,8 @@ module Sonic.HIP
   , WitnessSrc(..), setWitnessI64, proveBatchI64
     -- * core proofs
   , CoreProof(..), coreOf, decodeCoreProof, encodeCoreProof, proveCore, submitCore, collectCore, proveCoreFs, verifyCore, verifyCoreBatch
+    -- * Helped verification: one aggregate signature for K core proofs
+  , aggregateCore, fsWeightsDigest, verifyCoreBatchHelped
   ) where
 
 import Protolude hiding (check)
@@ -166,6 +168,9 @@ foreign import ccall safe   "sonic_prover_prove_core"     c_prover_prove_core ::
 foreign import ccall safe   "sonic_prover_submit_core"    c_prover_submit_core :: Ptr ProverHandle -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_prover_collect_core"   c_prover_collect_core :: Ptr ProverHandle -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_prover_prove_core_fs"  c_prover_prove_core_fs :: Ptr ProverHandle -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_fs_weights_digest"     c_fs_weights_digest :: Ptr Word8 -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_prover_aggregate_core" c_prover_aggregate_core :: Ptr ProverHandle -> Ptr Word8 -> Int64 -> Ptr Word8 -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_verifier_verify_core_batch_helped" c_verify_core_batch_helped :: Ptr VerifierHandle -> Int64 -> Ptr Word8 -> CInt -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_verify_core_csr"       c_verify_core_csr :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> IO CInt
 foreign import ccall safe   "sonic_verifier_verify_core_batch" c_verify_core_batch :: Ptr VerifierHandle -> Int64 -> Ptr Word8 -> CInt -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_verifier_verify_fs_batch_cs" c_verify_fs_batch_cs :: Ptr VerifierHandle -> Int64 -> Ptr Word8 -> CInt -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> Ptr Word8 -> IO CInt
@@ -961,6 +966,39 @@ verifyCoreBatch Verifier{..} sts = do
       withFrs (concat [ [y, z] | (_, (y, z), _) <- sts ]) $ \pyz -> withFrs (concat [ cs | (_, _, cs) <- sts ]) $ \pcs ->
         alloca $ \acc -> do
           each <- BSI.create k $ \out -> check =<< c_verify_core_batch v (fromIntegral k) ppf 0 pyz pcs nullPtr acc out
+          pure (map (/= 0) (BS.unpack each))
+
+-- | SHA-256 of the gate weights alone (sonic_fs_weights_digest over fsCircuitMidstate): what the transcript of an aggregate binds, since
+--   s(X, Y) does not depend on the constants
+fsWeightsDigest :: ArithCircuit Fr -> ByteString
+fsWeightsDigest circuit = unsafePerformIO $
+  withBytes (fsCircuitMidstate circuit) $ \pm -> BSI.create 32 $ \out -> check =<< c_fs_weights_digest pm out
+
+-- | the helper of helped verification (sonic_prover_aggregate_core): ONE signature of correct computation over the (y_k, z_k) of K core
+--   proofs of the handle's circuit -- an HscProof with m = K whose s_k is s(z_k, y_k), and whose u, v come from the aggregate's own
+--   transcript under the weights digest (fsWeightsDigest of the circuit)
+aggregateCore :: Prover -> ByteString -> [(Fr, Fr)] -> IO HscProof
+aggregateCore pr wdigest yzs
+  | BS.length wdigest /= 32 = panic "aggregateCore: a weights digest is 32 bytes"
+  | null yzs = panic "aggregateCore: at least one (y, z) pair"
+  | otherwise = withProverAlive pr $ \p -> withBytes wdigest $ \pw -> withFrs (concat [ [y, z] | (y, z) <- yzs ]) $ \pyz -> do
+      let k = length yzs
+      sz <- fromIntegral <$> c_hsc_proof_size (fromIntegral k)
+      bytes <- BSI.create sz $ \out -> check =<< c_prover_aggregate_core p pw (fromIntegral k) pyz out
+      pure (decodeHscProof k bytes)
+
+-- | verifyCoreBatch with a helper's aggregate over the same (y, z) (sonic_verifier_verify_core_batch_helped): proof k's s is held against
+--   the aggregate's s_k and s(u, v) is evaluated once per batch.  An aggregate that is malformed, not under its own transcript, or whose
+--   global check fails rejects every proof.
+verifyCoreBatchHelped :: Verifier -> [(CoreProof, (Fr, Fr), [Fr])] -> HscProof -> IO [Bool]
+verifyCoreBatchHelped _ [] _ = pure []
+verifyCoreBatchHelped Verifier{..} sts agg = do
+  let k = length sts
+  withForeignPtr verifierHandle $ \v ->
+    withBytes (BS.concat [ encodeCoreProof pf | (pf, _, _) <- sts ]) $ \ppf ->
+      withFrs (concat [ [y, z] | (_, (y, z), _) <- sts ]) $ \pyz -> withFrs (concat [ cs | (_, _, cs) <- sts ]) $ \pcs ->
+        withBytes (encodeHscProof agg) $ \pagg -> alloca $ \acc -> do
+          each <- BSI.create k $ \out -> check =<< c_verify_core_batch_helped v (fromIntegral k) ppf 0 pyz pcs pagg nullPtr acc out
           pure (map (/= 0) (BS.unpack each))
 
 deviceCount :: IO Int

@@ -105,7 +105,9 @@ typedef struct sonic_verifier sonic_verifier_t;
  * sonic_prover_prove_core, sonic_prover_submit_core, sonic_prover_collect_core, sonic_prover_prove_core_fs, sonic_fs_core_challenges,
  * sonic_prove_batch_core_src, sonic_prove_batch_core_fs_src, sonic_verify_core[_csr], sonic_verify_core_fs[_csr],
  * sonic_verifier_verify_core_batch, sonic_verifier_verify_core_fs_batch, sonic_verify_core_batch_digest, sonic_core_proof_compress,
- * sonic_core_proof_decompress */
+ * sonic_core_proof_decompress; still 7, additions only: helped verification -- sonic_fs_weights_digest, sonic_fs_aggregate_challenges,
+ * sonic_prover_aggregate_core, sonic_verifier_verify_core_batch_helped, sonic_verifier_verify_core_fs_batch_helped,
+ * sonic_verify_core_helped_digest */
 int sonic_abi_version(void);
 int sonic_init(int device_ordinal);                 /* choose the DEFAULT GPU (first call wins) and make it the thread's HIP device; idempotent */
 int sonic_device_count(int* out);                   /* GPUs this process can see; SONIC_ERR_NO_DEVICE (and 0) without one */
@@ -737,6 +739,65 @@ int sonic_verify_core_batch_digest(int64_t n, int64_t Q, int64_t d, const uint8_
                                    const uint8_t* proofs, const uint8_t* yz, const uint8_t* cs, uint8_t out[32]);
 int sonic_core_proof_compress(const uint8_t* proof, uint8_t* out);
 int sonic_core_proof_decompress(const uint8_t* proof_z, uint8_t* out_proof);
+
+/* ---- Helped verification: one aggregate signature for K core proofs (ABI 7, additions only) ----
+ * A core proof carries no signature of correct computation, so its verifier evaluates s(z_k, y_k) itself: O(nnz + n) per proof.  Sonic's
+ * helped mode moves that cost to an untrusted HELPER, which proves all K values s(z_k, y_k) with ONE signature (Signature.hs:38-72 with
+ * m = K), after which a verifier needs s(u, v) at one point per batch.
+ *
+ * The aggregate for K pairs (y_k, z_k) is exactly an HscProof with m = K in the layout sonic_prover_hsc_prove writes --
+ * [S_j, s_j, W_j]_j, [s'_j, W'_j, Q_j]_j, Q_v, C, u, v: sonic_hsc_proof_size(K) bytes -- so sonic_hsc_verify(m = K) accepts a correct one
+ * and sonic_prover_hsc_prove(K, yzs, u, v) reproduces it byte for byte.  Its s_k is s(z_k, y_k): proof k's s must equal it.
+ * u and v are not the helper's to choose.  They come from a transcript with a label of its own (absorb / challenge: sonic_amd/csrc/fs.hpp):
+ *     st0 = SHA256("sonic-hip/fs-agg/v1" || le64 n || le64 Q || le64 d || weights digest || srs id)
+ *     absorb("pairs", le64 K || K x (y_k || z_k))
+ *     absorb("hscS", [S_j || s_j || W_j]_j)          -> u = challenge("u", 0)
+ *     absorb("hscW", C || [s'_j || W'_j || Q_j]_j)   -> v = challenge("v", 0)
+ * u follows every S_j, s_j, W_j and v follows C and every s'_j, W'_j, Q_j: a helper that knew u before it committed S_j (or v before C)
+ * could commit to a polynomial that agrees with s at that one point only.
+ * s(X, Y) depends on the gate weights only, and one circuit serves many statements with their own constants, so the transcript binds
+ *     weights digest = SHA256("sonic-hip/weights/v1" || the SONIC_FS_MIDSTATE_SIZE bytes of sonic_fs_circuit_midstate[_csr])
+ * and not the circuit digest, which ends in cs.
+ *
+ *   fs_weights_digest          that digest from a midstate (the bytes are hashed as they are); no device needed.
+ *   fs_aggregate_challenges    u || v (64 bytes) that the bytes of an aggregate determine; no device needed.  yz: K x 64, y_k || z_k.
+ *   prover_aggregate_core      the helper, on a prover handle (dense or CSR, prepared or not, over an SRS view too; no assignment needed).
+ *                   Blocking; three passes with a host hash between them: S_j, s_j, W_j -> u -> C, s'_j, W'_j, Q_j -> v -> Q_v.  The
+ *                   polynomials s(X, y_j) of up to 8 pairs come from one launch that reads the circuit once, their 16 MSMs run as one
+ *                   chain, and the tiles of 8 are dealt over the handle's lanes.  Pass 2 reads the polynomials of pass 1 again: they are
+ *                   kept when K (3n + 1) 32 bytes fit 4 GiB and recomputed per tile otherwise (SONIC_AGG_KEEP=0 / 1 forces either), so
+ *                   device memory is bounded by that budget, not by K.  out: sonic_hsc_proof_size(K) bytes.
+ *                   A zero y_k or z_k: SONIC_ERR_INEXACT_DIVISION before anything is launched.  A proof in flight, a handle in share
+ *                   mode, K < 1: SONIC_ERR_INVALID_ARG (a flight stays intact).  A non-canonical y_k or z_k: SONIC_ERR_BAD_ENCODING.
+ *   verifier_verify_core_batch_helped / _core_fs_batch_helped   K core proofs and the aggregate over their (y_k, z_k) on a sonic_verifier_t
+ *                   handle (the _fs form recomputes y_k, z_k per proof as sonic_verifier_verify_core_fs_batch does).  proofs, compressed, yz,
+ *                   cs, seed, all_accepted, each: as sonic_verifier_verify_core_batch's; aggregate: sonic_hsc_proof_size(K) bytes.  Steps:
+ *                     1. the proofs' 5K points (compressed = 1: decompressed) and the aggregate's 4K + 2 points are validated on the GPU;
+ *                     2. u, v are recomputed from the transcript: the aggregate's own must match, and neither may be zero;
+ *                     3. proof k's s must equal the aggregate's s_k, as bytes;
+ *                     4. s(u, v) is evaluated ONCE (where the unhelped batch evaluates s(z_k, y_k) K times);
+ *                     5. the 3K checks of the heads and the 3K + 1 of the signature are folded into the same four Miller loops, under
+ *                        randomizers derived from the digest D below: check index 3k + i for the heads, 3K + (position in the
+ *                        signature's list: S_j at z_j, S_j at u, C at y_j for j = 0 .., then C at v) for the signature.
+ *                   Verdicts: a bad input is a rejected proof, not a failed call.  An aggregate that is malformed, whose u, v are not
+ *                   its transcript's, or whose global check (C at v against s(u, v)) fails rejects EVERY proof: each[k] = 0 for all k, and
+ *                   sonic_last_error names the aggregate.  Otherwise proof k is accepted iff it is well-formed, its s equals s_k, its
+ *                   three head checks hold and the three signature checks of j = k hold: when the whole fold fails, the global check is
+ *                   folded alone, then each k's six checks alone, and the others' verdicts stand.
+ *                   The handle computes the weights digest from what it holds, once, on the first helped call.
+ *   verify_core_helped_digest  the digest a helped batch derives its randomizers from (as sonic_verify_batch_randomizers'); no device needed:
+ *                     D = SHA-256("sonic-hip/batch-digest/helped/v1" || le64 n || le64 Q || le64 d || weights digest || srs id || le64 K ||
+ *                                 K x (576 proof bytes || y_k || z_k || cs_k) || aggregate bytes) */
+int sonic_fs_weights_digest(const uint8_t midstate[SONIC_FS_MIDSTATE_SIZE], uint8_t out[32]);
+int sonic_fs_aggregate_challenges(int64_t n, int64_t Q, int64_t d, const uint8_t weights_digest[32], const uint8_t srs_id[32], int64_t K, const uint8_t* yz,
+                                  const uint8_t* aggregate, uint8_t out_uv[64]);
+int sonic_prover_aggregate_core(sonic_prover_t* p, const uint8_t weights_digest[32], int64_t K, const uint8_t* yz, uint8_t* out);
+int sonic_verifier_verify_core_batch_helped(sonic_verifier_t* v, int64_t K, const uint8_t* proofs, int compressed, const uint8_t* yz, const uint8_t* cs,
+                                            const uint8_t* aggregate, const uint8_t seed[32], int* all_accepted, uint8_t* each);
+int sonic_verifier_verify_core_fs_batch_helped(sonic_verifier_t* v, int64_t K, const uint8_t* proofs, int compressed, const uint8_t* cs,
+                                               const uint8_t* aggregate, const uint8_t seed[32], int* all_accepted, uint8_t* each);
+int sonic_verify_core_helped_digest(int64_t n, int64_t Q, int64_t d, const uint8_t weights_digest[32], const uint8_t srs_id[32], int64_t K,
+                                    const uint8_t* proofs, const uint8_t* yz, const uint8_t* cs, const uint8_t* aggregate, uint8_t out[32]);
 
 /* ---- device memory for callers without a HIP binding ---- */
 int sonic_dev_alloc(size_t bytes, void** out);                       /* on the default device */

@@ -33,7 +33,8 @@ from .protocol import fs_circuit_midstate, fs_circuit_digest_resume  # noqa: F40
 from .protocol import prove_batch_fs  # noqa: F401,E402
 from .protocol import WitnessBatch  # noqa: F401,E402
 from .protocol import CoreProof, prove_core_batch, prove_core_batch_fs, verify_core, verify_core_fs, fs_core_challenges  # noqa: F401,E402
+from .protocol import aggregate_core, fs_weights_digest, fs_aggregate_challenges  # noqa: F401,E402
 from .compressed import g1_compress, g1_decompress, g2_compress, g2_decompress, proof_compress, proof_decompress  # noqa: F401,E402
 
-__all__ = ["CoreProof", "prove_core_batch", "prove_core_batch_fs", "verify_core", "verify_core_fs", "fs_core_challenges", "WitnessBatch", "Verifier", "verify_batch", "prove_batch_fs", "fs_circuit_midstate", "fs_circuit_digest_resume", "g1_compress", "g1_decompress", "g2_compress", "g2_decompress", "proof_compress", "proof_decompress", "SRS", "commit_poly", "open_poly", "pc_v", "msm_g1", "MsmLane", "prove", "verify", "prove_fs", "verify_fs", "fs_challenges", "fs_circuit_digest", "hsc_prove", "hsc_verify", "hsc_prove_poly", "hsc_verify_poly", "Proof", "HscProof", "RndOracle", "Prover", "ProverPipeline",
+__all__ = ["aggregate_core", "fs_weights_digest", "fs_aggregate_challenges", "CoreProof", "prove_core_batch", "prove_core_batch_fs", "verify_core", "verify_core_fs", "fs_core_challenges", "WitnessBatch", "Verifier", "verify_batch", "prove_batch_fs", "fs_circuit_midstate", "fs_circuit_digest_resume", "g1_compress", "g1_decompress", "g2_compress", "g2_decompress", "proof_compress", "proof_decompress", "SRS", "commit_poly", "open_poly", "pc_v", "msm_g1", "MsmLane", "prove", "verify", "prove_fs", "verify_fs", "fs_challenges", "fs_circuit_digest", "hsc_prove", "hsc_verify", "hsc_prove_poly", "hsc_verify_poly", "Proof", "HscProof", "RndOracle", "Prover", "ProverPipeline",
            "ArithCircuit", "SparseCircuit", "Assignment", "GateWeights", "SonicError"]

@@ -192,6 +192,12 @@ def lib() -> C.CDLL:
         "sonic_verify_core_batch_digest": [i64, i64, i64, cp, cp, i64, vp, vp, vp, vp],
         "sonic_core_proof_compress": [cp, cp],
         "sonic_core_proof_decompress": [cp, cp],
+        "sonic_fs_weights_digest": [cp, vp],
+        "sonic_fs_aggregate_challenges": [i64, i64, i64, cp, cp, i64, vp, vp, vp],
+        "sonic_prover_aggregate_core": [vp, cp, i64, vp, vp],
+        "sonic_verify_core_helped_digest": [i64, i64, i64, cp, cp, i64, vp, vp, vp, vp, vp],
+        "sonic_verifier_verify_core_batch_helped": [vp, i64, vp, i32, vp, vp, vp, cp, C.POINTER(i32), vp],
+        "sonic_verifier_verify_core_fs_batch_helped": [vp, i64, vp, i32, vp, vp, cp, C.POINTER(i32), vp],
         "sonic_dev_alloc": [C.c_size_t, C.POINTER(vp)],
         "sonic_dev_free": [vp],
         "sonic_dev_upload": [vp, vp, C.c_size_t],
@@ -295,6 +301,8 @@ EXPORTED = [
     "sonic_prover_prove_core", "sonic_prover_submit_core", "sonic_prover_collect_core", "sonic_prover_prove_core_fs", "sonic_fs_core_challenges",
     "sonic_prove_batch_core_src", "sonic_prove_batch_core_fs_src", "sonic_verify_core", "sonic_verify_core_csr", "sonic_verify_core_fs", "sonic_verify_core_fs_csr",
     "sonic_verifier_verify_core_batch", "sonic_verifier_verify_core_fs_batch", "sonic_verify_core_batch_digest", "sonic_core_proof_compress", "sonic_core_proof_decompress",
+    "sonic_fs_weights_digest", "sonic_fs_aggregate_challenges", "sonic_prover_aggregate_core", "sonic_verify_core_helped_digest",
+    "sonic_verifier_verify_core_batch_helped", "sonic_verifier_verify_core_fs_batch_helped",
 ]
 
 

@@ -269,4 +269,79 @@ inline void fs_batch_digest_v2(int64_t n, int64_t Q, int64_t d, const uint8_t di
   h.finish(out);
 }
 
+// ---- helped verification (include/sonic_hip.h, "Helped verification"): one aggregate signature over the (y_k, z_k) of K core proofs ----
+// s(X, Y) depends on the gate weights only, and one circuit serves many statements with their own cs_k, so the aggregate's transcript
+// binds a digest of the weights, not the circuit digest (which ends in cs):
+//   weights digest = SHA256("sonic-hip/weights/v1" || the FS_MIDSTATE_SIZE bytes of the circuit's midstate, above)
+// An aggregate is an HscProof with m = K in the layout every HscProof has ([S_j, s_j, W_j]_j, [s'_j, W'_j, Q_j]_j, Q_v, C, u, v), whose
+// u and v are NOT the helper's to choose:
+//   st_0 = SHA256("sonic-hip/fs-agg/v1" || le64 n || le64 Q || le64 d || weights digest || srs id)
+//   absorb("pairs", le64 K || K x (y_k || z_k))
+//   absorb("hscS", [S_j || s_j || W_j]_j)          -> u = challenge("u", 0)
+//   absorb("hscW", C || [s'_j || W'_j || Q_j]_j)   -> v = challenge("v", 0)
+// u follows every S_j, s_j, W_j: S_j is checked against C at the point u, so a helper that knew u before it committed S_j could commit
+// to a polynomial that agrees with s(X, y_j) at u only.  v follows C and every s'_j, W'_j, Q_j for the same reason one variable on:
+// C is checked against s(u, v), which the verifier evaluates itself, at the point v.
+constexpr const char* FS_AGG_LABEL = "sonic-hip/fs-agg/v1";
+inline void fs_weights_digest(const uint8_t mid[FS_MIDSTATE_SIZE], uint8_t out[32]) {
+  Sha256 h;
+  h.update("sonic-hip/weights/v1", 20);
+  h.update(mid, FS_MIDSTATE_SIZE);
+  h.finish(out);
+}
+// where the parts of an aggregate for K pairs lie
+struct AggLayout {
+  int64_t K;
+  size_t hscS() const { return 0; }
+  size_t hscW() const { return 224 * (size_t)K; }
+  size_t Qv() const { return 448 * (size_t)K; }
+  size_t C() const { return Qv() + 96; }
+  size_t u() const { return Qv() + 192; }
+  size_t v() const { return Qv() + 224; }
+  size_t bytes() const { return Qv() + 256; }
+};
+// the transcript in the three steps the helper walks it in (aggregate.hip); fs_aggregate_challenges is the three in a row
+inline void fs_agg_begin(FsTranscript& t, int64_t n, int64_t Q, int64_t d, const uint8_t weights_digest[32], const uint8_t srs_id[32], int64_t K, const uint8_t* yz) {
+  t.init(n, Q, d, weights_digest, srs_id, FS_AGG_LABEL);
+  std::string w(8, '\0');
+  for (int i = 0; i < 8; i++) w[(size_t)i] = (char)(uint8_t)((uint64_t)K >> (8 * i));
+  w.append(reinterpret_cast<const char*>(yz), 64 * (size_t)K);
+  t.absorb("pairs", reinterpret_cast<const uint8_t*>(w.data()), w.size());
+}
+inline void fs_agg_u(FsTranscript& t, int64_t K, const uint8_t* hscS, uint8_t out_u[32]) {
+  t.absorb("hscS", hscS, 224 * (size_t)K);
+  t.challenge("u", 0, out_u);
+}
+inline void fs_agg_v(FsTranscript& t, int64_t K, const uint8_t* Cc, const uint8_t* hscW, uint8_t out_v[32]) {
+  std::string w(reinterpret_cast<const char*>(Cc), 96);
+  w.append(reinterpret_cast<const char*>(hscW), 224 * (size_t)K);
+  t.absorb("hscW", reinterpret_cast<const uint8_t*>(w.data()), w.size());
+  t.challenge("v", 0, out_v);
+}
+// u || v (64 bytes) that the bytes of an aggregate determine: what the verifier recomputes and compares with the aggregate's own
+inline void fs_aggregate_challenges(int64_t n, int64_t Q, int64_t d, const uint8_t weights_digest[32], const uint8_t srs_id[32], int64_t K, const uint8_t* yz,
+                                    const uint8_t* aggregate, uint8_t out_uv[64]) {
+  const AggLayout A{K};
+  FsTranscript t;
+  fs_agg_begin(t, n, Q, d, weights_digest, srs_id, K, yz);
+  fs_agg_u(t, K, aggregate + A.hscS(), out_uv);
+  fs_agg_v(t, K, aggregate + A.C(), aggregate + A.hscW(), out_uv + 32);
+}
+// The digest of a helped batch, from which its randomizers are derived as for the other batches (check index 3k + i for the heads,
+// 3K + the position in hsc_checks' order for the signature):
+//   D = SHA-256("sonic-hip/batch-digest/helped/v1" || le64 n || le64 Q || le64 d || weights digest || srs id || le64 K ||
+//               K x (576 proof bytes || y_k || z_k || cs_k) || aggregate bytes)
+inline void fs_core_helped_digest(int64_t n, int64_t Q, int64_t d, const uint8_t weights_digest[32], const uint8_t srs_id[32], int64_t K, const uint8_t* proofs,
+                                  const uint8_t* yz, const uint8_t* cs, const uint8_t* aggregate, uint8_t out[32]) {
+  const size_t ksz = 32 * (size_t)Q;
+  Sha256 h;
+  h.update("sonic-hip/batch-digest/helped/v1", 32);
+  FsTranscript::le64(h, n); FsTranscript::le64(h, Q); FsTranscript::le64(h, d);
+  h.update(weights_digest, 32); h.update(srs_id, 32);
+  FsTranscript::le64(h, K);
+  for (int64_t k = 0; k < K; k++) { h.update(proofs + 576 * (size_t)k, 576); h.update(yz + 64 * (size_t)k, 64); h.update(cs + ksz * (size_t)k, ksz); }
+  h.update(aggregate, AggLayout{K}.bytes());
+  h.finish(out);
+}
+
 }  // namespace sonic

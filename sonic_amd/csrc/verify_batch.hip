@@ -173,6 +173,8 @@ struct sonic_verifier {
   uint8_t digest[32], srs_id[32];
   uint8_t midstate[FS_MIDSTATE_SIZE];   // the circuit digest before the constants (fs.hpp): each statement's digest from it (the `_cs` calls)
   std::vector<uint8_t> cs;
+  uint8_t weights_digest[32];           // of the midstate (fs.hpp, "helped verification"): made by the first helped call, not when the handle is
+  bool have_weights_digest = false;
   std::mutex mu;                        // one call at a time per handle
   hipStream_t st = nullptr;
   MsmWorkspace ws;
@@ -594,10 +596,9 @@ int verify_core_proofs_batch(sonic_verifier* v, long K, const uint8_t* proofs, c
 }
 
 // the Fiat-Shamir form: y_k, z_k from each proof's own transcript (fs.hpp, "core proofs"), proof k's from the digest of ITS statement
-int verify_core_proofs_fs_batch(sonic_verifier* v, long K, const uint8_t* proofs, const uint8_t* cs_each, const uint8_t* seed, int* all_accepted, uint8_t* each,
-                                const std::vector<uint8_t>* accepted) {
+void core_fs_challenges_batch(sonic_verifier* v, long K, const uint8_t* proofs, const uint8_t* cs_each, std::vector<uint8_t>& yz) {
   const long Q = v->Q;
-  std::vector<uint8_t> yz(64 * (size_t)K);
+  yz.resize(64 * (size_t)K);
   for (int64_t k = 0; k < K; k++) {
     uint8_t dk[32];
     memcpy(dk, v->digest, 32);
@@ -605,7 +606,246 @@ int verify_core_proofs_fs_batch(sonic_verifier* v, long K, const uint8_t* proofs
     if (cs_each && fs_circuit_digest_resume(v->midstate, cs_each + 32 * (size_t)(k * Q), dk) != 0) memcpy(dk, v->digest, 32);
     fs_core_challenges_of_proof(v->n, Q, v->d, dk, v->srs_id, proofs + ProofLayout::core_proof_bytes() * (size_t)k, &yz[64 * (size_t)k]);
   }
+}
+int verify_core_proofs_fs_batch(sonic_verifier* v, long K, const uint8_t* proofs, const uint8_t* cs_each, const uint8_t* seed, int* all_accepted, uint8_t* each,
+                                const std::vector<uint8_t>* accepted) {
+  std::vector<uint8_t> yz;
+  core_fs_challenges_batch(v, K, proofs, cs_each, yz);
   return verify_core_proofs_batch(v, K, proofs, yz.data(), cs_each, seed, all_accepted, each, accepted);
+}
+
+// ---- helped verification (include/sonic_hip.h, "Helped verification"): K core proofs and ONE aggregate signature over their (y_k, z_k) --------
+// The aggregate vouches for s_k = s(z_k, y_k), so the verifier holds proof k's s against s_k as bytes and evaluates s(u, v) ONCE, at the
+// aggregate's own point, instead of K times.  The 3K checks of the heads (core_checks) and the 3K + 1 of the signature (hsc_checks) fold
+// into the same four Miller loops.  Points: proof k's five at 5k .., the aggregate's S_k, W_k, W'_k, Q_k at 5K + 4k .., then Q_v and C at
+// 9K and 9K + 1 -- the proofs first, because that is where decompress_core_device leaves the points of compressed ones.  Q_v and C belong to
+// no proof: their scalars are kept on the host, so that the global check (C at v against s(u, v)) and any proof's six checks can be folded
+// on their own when the whole fold fails.
+struct Helped {
+  sonic_verifier* v;
+  long K;
+  std::vector<char> good;               // proof k: well-formed, y_k, z_k != 0, and its s is the aggregate's s_k
+  std::vector<Fr> gv, rho_c;            // per proof: sum rho val over its six checks; the rho of its check on C (Montgomery)
+  Fr g_glob, rho_glob, rho_z_glob;      // the global check: rho s(u, v), rho, rho v
+  G1Affine Qv, C;
+  size_t N() const { return 9 * (size_t)K + 2; }
+  const Fr* scal(int which) const { return v->scalars.as<Fr>() + (size_t)which * N(); }
+};
+
+G1XYZZ span_msm(const Helped& b, int which, size_t at, long count) {
+  sonic_verifier* v = b.v;
+  uint8_t part[192];
+  msm_blocking(v->st, v->ws, msm_plan(count), PointArray::packed(v->pts.as<G1Affine>() + at), b.scal(which) + at, count, false, nullptr, part);
+  G1XYZZ s;
+  memcpy(&s, part, sizeof s);
+  return s;
+}
+// the G1 side of the fold over the six checks of each proof in [k0, k1) and, with `glob`, the global check
+Sums helped_sums(const Helped& b, long k0, long k1, bool glob) {
+  const long K = b.K;
+  auto part = [&](int which) {
+    if (k1 <= k0) return G1XYZZ::inf();
+    if (k0 == 0 && k1 == K) return span_msm(b, which, 0, 9 * K);
+    return g1_add(span_msm(b, which, (size_t)(5 * k0), 5 * (k1 - k0)), span_msm(b, which, (size_t)(5 * K + 4 * k0), 4 * (k1 - k0)));
+  };
+  Fr g = glob ? b.g_glob : Fr::zero(), rc = glob ? b.rho_glob : Fr::zero();
+  for (long k = k0; k < k1; k++) if (b.good[(size_t)k]) { g = fp_add(g, b.gv[(size_t)k]); rc = fp_add(rc, b.rho_c[(size_t)k]); }
+  Sums s;
+  G1XYZZ A = part(0), B = g1_add(g1_mul_fr(g1_gen_host(), fp_from_mont(g)), g1_neg(part(1)));
+  if (glob) { A = g1_add(A, g1_mul_fr(b.Qv, fp_from_mont(b.rho_glob))); B = g1_add(B, g1_neg(g1_mul_fr(b.Qv, fp_from_mont(b.rho_z_glob)))); }
+  s.A = g1_to_affine(A); s.B = g1_to_affine(B);
+  for (size_t c = 0; c < b.v->ms.size(); c++) {
+    G1XYZZ F = part(2 + (int)c);
+    if (b.v->ms[c] == b.v->d) F = g1_add(F, g1_mul_fr(b.C, fp_from_mont(rc)));      // every check on C has max = d
+    s.C.push_back(g1_neg(g1_to_affine(F)));
+  }
+  return s;
+}
+
+// encodings validated into v->pts[at ..]; the buffers hold 9K + 2 points already (ensured by the caller, so that nothing moves)
+void validate_span(sonic_verifier* v, const uint8_t* enc, size_t at, size_t M, uint8_t* flags_out) {
+  hipStream_t st = v->st;
+  HIP_OK(hipMemcpyAsync(v->raw.as<uint8_t>() + 96 * at, enc, 96 * M, hipMemcpyHostToDevice, st));
+  g1_validate_enqueue(st, v->raw.as<uint8_t>() + 96 * at, v->pts.as<G1Affine>() + at, v->flags.as<uint8_t>() + at, (long)M);
+  HIP_OK(hipMemcpyAsync(flags_out, v->flags.as<uint8_t>() + at, M, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+}
+void helped_reserve(sonic_verifier* v, long K) {
+  const size_t N = 9 * (size_t)K + 2;
+  v->raw.ensure(96 * N); v->zraw.ensure(48 * 5 * (size_t)K); v->pts.ensure(sizeof(G1Affine) * N); v->flags.ensure(N);
+}
+
+// proofs: K x 576 bytes; yz: K x (y_k, z_k); cs_each: K x Q constants or null; aggregate: sonic_hsc_proof_size(K) bytes; accepted: null, or
+// the flags of the proofs' 5K points, which decompress_core_device has validated into v->pts (helped_reserve called before it)
+int verify_core_helped(sonic_verifier* v, long K, const uint8_t* proofs, const uint8_t* yz, const uint8_t* cs_each, const uint8_t* aggregate, const uint8_t* seed_in,
+                       int* all_accepted, uint8_t* each, const std::vector<uint8_t>* accepted = nullptr) {
+  const long Q = v->Q;
+  const size_t psz = ProofLayout::core_proof_bytes();
+  const AggLayout A{K};
+  uint8_t seed[32];
+  if (seed_in) memcpy(seed, seed_in, 32);
+  else if (getrandom(seed, 32, 0) != 32) { set_error("sonic_verifier_verify_core_batch_helped: the operating system gave no random bytes for the seed"); return SONIC_ERR_INVALID_ARG; }
+  if (!v->have_weights_digest) { fs_weights_digest(v->midstate, v->weights_digest); v->have_weights_digest = true; }
+  double t0 = now_ms();
+  auto reject_all = [&] { *all_accepted = 0; for (long k = 0; each && k < K; k++) each[k] = 0; return SONIC_OK; };
+
+  // 1. decode: the proofs as the unhelped batch does, the aggregate into indices of the same staging buffer
+  Helped b{v, K, std::vector<char>((size_t)K, 0), std::vector<Fr>((size_t)K, Fr::zero()), std::vector<Fr>((size_t)K, Fr::zero()), Fr::zero(), Fr::zero(), Fr::zero(), G1Affine::inf(), G1Affine::inf()};
+  const size_t N = b.N();
+  std::vector<ProofViewT<int32_t>> views((size_t)K);
+  std::vector<Fr> yms((size_t)K), zms((size_t)K);
+  std::vector<uint8_t> stage(96 * N, 0);
+  long first_bad = -1, first_zero = -1, first_unbound = -1;
+  for (long k = 0; k < K; k++) {
+    int32_t idx = 0;
+    uint8_t* dst = &stage[96 * (size_t)(5 * k)];
+    auto take = [&](const uint8_t* enc, int32_t& o) { o = (int32_t)(5 * k) + idx++; memcpy(dst + 96 * (size_t)(o - 5 * k), enc, 96); return true; };
+    b.good[(size_t)k] = parse_core_proof(proofs + psz * (size_t)k, yz + 64 * (size_t)k, yz + 64 * (size_t)k + 32, views[(size_t)k], yms[(size_t)k], zms[(size_t)k], take) ? 1 : 0;
+    for (long q = 0; cs_each && q < Q && b.good[(size_t)k]; q++) { Fr c; if (!load_fr(cs_each + 32 * (size_t)(k * Q + q), c)) b.good[(size_t)k] = 0; }
+    if (!b.good[(size_t)k] && first_bad < 0) first_bad = k;
+  }
+  HscProofViewT<int32_t> h;
+  // the pairs as the aggregate's view holds them: a pair that is no pair of field elements stands as (1, 1) -- its proof is malformed, and
+  // the checks of j = k are left out with it
+  std::vector<uint8_t> yz_ok(yz, yz + 64 * (size_t)K);
+  for (long k = 0; k < K; k++) {
+    Fr t;
+    if (!load_fr(yz + 64 * (size_t)k, t) || !load_fr(yz + 64 * (size_t)k + 32, t)) { memset(&yz_ok[64 * (size_t)k], 0, 64); yz_ok[64 * (size_t)k] = yz_ok[64 * (size_t)k + 32] = 1; }
+  }
+  long seen = 0;
+  auto take_agg = [&](const uint8_t* enc, int32_t& o) {
+    // parse_hsc visits S_j, W_j (j = 0 ..), then W'_j, Q_j, then Q_v, C
+    const long c = seen++;
+    const long at = c < 2 * K ? 4 * (c / 2) + c % 2 : (c < 4 * K ? 4 * ((c - 2 * K) / 2) + 2 + c % 2 : c);
+    o = (int32_t)(5 * K + at);
+    memcpy(&stage[96 * (size_t)o], enc, 96);
+    return true;
+  };
+  bool agg_ok = parse_hsc(aggregate, K, yz_ok.data(), h, take_agg);
+  host_phase("verify_core_helped:host_decode", now_ms() - t0);
+
+  // 2. the points: the proofs' 5K (unless they came compressed and are validated already) and the aggregate's 4K + 2
+  std::vector<uint8_t> flags(N, 0);
+  if (accepted) { memcpy(flags.data(), accepted->data(), 5 * (size_t)K); validate_span(v, &stage[96 * 5 * (size_t)K], 5 * (size_t)K, 4 * (size_t)K + 2, &flags[5 * (size_t)K]); }
+  else validate_span(v, stage.data(), 0, N, flags.data());
+  for (long k = 0; k < K; k++) {
+    bool ok = true;
+    for (long j = 0; j < 5; j++) ok = ok && flags[(size_t)(5 * k + j)];
+    if (!ok) { b.good[(size_t)k] = 0; if (first_bad < 0 || k < first_bad) first_bad = k; }
+  }
+  for (size_t i = 5 * (size_t)K; i < N; i++) agg_ok = agg_ok && flags[i];
+  if (!agg_ok) {
+    set_error("verify_core_batch_helped: the aggregate is malformed (non-canonical field element, or point off the curve or outside the order-r subgroup): every proof is rejected");
+    return reject_all();
+  }
+  // 3. u, v are the transcript's, and not zero
+  uint8_t uv[64];
+  fs_aggregate_challenges(v->n, Q, v->d, v->weights_digest, v->srs_id, K, yz, aggregate, uv);
+  if (memcmp(uv, aggregate + A.u(), 64) != 0 || h.u.is_zero() || h.v.is_zero()) {
+    set_error("verify_core_batch_helped: the aggregate's u, v are not the ones its transcript determines for these pairs: every proof is rejected");
+    return reject_all();
+  }
+  // 4. proof k's s is the aggregate's s_k, as bytes; y_k, z_k are invertible
+  for (long k = 0; k < K; k++) {
+    if (!b.good[(size_t)k]) continue;
+    if (yms[(size_t)k].is_zero() || zms[(size_t)k].is_zero()) { b.good[(size_t)k] = 0; if (first_zero < 0) first_zero = k; }
+    else if (memcmp(proofs + psz * (size_t)k + 544, aggregate + A.hscS() + 224 * (size_t)k + 96, 32) != 0) { b.good[(size_t)k] = 0; if (first_unbound < 0) first_unbound = k; }
+  }
+  if (first_bad >= 0) set_error("verify_core_batch_helped: proof %ld is malformed (non-canonical field element in the proof, its challenges or its constants, or point off the curve or "
+                                "outside the order-r subgroup)", first_bad);
+  else if (first_zero >= 0 && (first_unbound < 0 || first_zero < first_unbound)) set_error("verify_core_batch_helped: proof %ld has y or z zero", first_zero);
+  else if (first_unbound >= 0) set_error("verify_core_batch_helped: the s of proof %ld is not the aggregate's s_k", first_unbound);
+  const bool any_bad = first_bad >= 0 || first_zero >= 0 || first_unbound >= 0;
+  {
+    G1Affine g[2];
+    HIP_OK(hipMemcpy(g, v->pts.as<G1Affine>() + 9 * (size_t)K, sizeof g, hipMemcpyDeviceToHost));
+    b.Qv = g[0]; b.C = g[1];
+  }
+  // 5. s(u, v), once
+  std::vector<Fr> svs;
+  std::vector<uint8_t> sok;
+  eval_s_device(v, 1, std::vector<Fr>{h.u}, std::vector<Fr>{h.v}, svs, sok);
+  if (!sok[0]) { set_error("verify_core_batch_helped: the aggregate's u or v is zero: every proof is rejected"); return reject_all(); }
+
+  // 6. the digest the randomizers bind, and the scalars of the fold: rho on W, rho z on W, rho on F by class of max
+  t0 = now_ms();
+  uint8_t D[32];
+  std::vector<uint8_t> cs_all;
+  if (!cs_each) { cs_all.resize(32 * (size_t)(K * Q)); for (long k = 0; k < K; k++) memcpy(&cs_all[32 * (size_t)(k * Q)], v->cs.data(), 32 * (size_t)Q); }
+  fs_core_helped_digest(v->n, Q, v->d, v->weights_digest, v->srs_id, K, proofs, yz, cs_each ? cs_each : cs_all.data(), aggregate, D);
+  const size_t nclass = v->ms.size();
+  std::vector<Fr> sc((2 + nclass) * N, Fr::zero());          // Montgomery while they are summed
+  std::vector<PcvCheckT<int32_t>> sig;
+  hsc_checks<int32_t>(v->d, h, svs[0], sig);                   // 3K + 1, in the order the randomizers number them from 3K on
+  const size_t local = 9 * (size_t)K;
+  // check c of proof k (k < 0: the global check) under randomizer number `index`
+  auto add = [&](long k, const PcvCheckT<int32_t>& c, int64_t index) {
+    uint8_t rho[16];
+    batch_randomizers(seed, D, index, 1, rho);
+    Fr r = Fr::zero();
+    memcpy(r.l, rho, 16);
+    r = fp_to_mont(r);
+    const Fr rz = fp_mul(r, c.z), rv = fp_mul(r, c.val);
+    if ((size_t)c.W < local) { sc[(size_t)c.W] = fp_add(sc[(size_t)c.W], r); sc[N + (size_t)c.W] = fp_add(sc[N + (size_t)c.W], rz); }
+    else { b.rho_glob = r; b.rho_z_glob = rz; }               // (W = Q_v: the global check only)
+    if (k >= 0) b.gv[(size_t)k] = fp_add(b.gv[(size_t)k], rv); else b.g_glob = rv;
+    if ((size_t)c.F < local) {
+      size_t cls = 0;
+      while (v->ms[cls] != c.maxm) cls++;
+      sc[(2 + cls) * N + (size_t)c.F] = fp_add(sc[(2 + cls) * N + (size_t)c.F], r);
+    } else if (k >= 0) b.rho_c[(size_t)k] = fp_add(b.rho_c[(size_t)k], r);      // (F = C; the global check's own rho on C is rho_glob)
+  };
+  CircuitView cview{v->n, Q, v->cs.data(), true, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (long k = 0; k < K; k++) {
+    if (!b.good[(size_t)k]) continue;
+    Fr t;
+    if (cs_each) cview.cs = cs_each + 32 * (size_t)(k * Q);
+    proof_t(cview, views[(size_t)k], yms[(size_t)k], t);
+    const auto head = core_checks<int32_t>(v->n, v->d, views[(size_t)k], yms[(size_t)k], zms[(size_t)k], t);
+    for (long i = 0; i < 3; i++) add(k, head[(size_t)i], 3 * k + i);
+    for (long i = 0; i < 3; i++) add(k, sig[(size_t)(3 * k + i)], 3 * K + 3 * k + i);
+  }
+  add(-1, sig[3 * (size_t)K], 6 * K);
+  for (auto& x : sc) x = fp_from_mont(x);
+  v->scalars.ensure(sizeof(Fr) * sc.size());
+  HIP_OK(hipMemcpyAsync(v->scalars.p, sc.data(), sizeof(Fr) * sc.size(), hipMemcpyHostToDevice, v->st));
+  HIP_OK(hipStreamSynchronize(v->st));
+  host_phase("verify_core_helped:host_scalars", now_ms() - t0);
+
+  // 7. the fold: every well-formed proof's six checks and the global check in one pairing product
+  t0 = now_ms();
+  const Sums all = helped_sums(b, 0, K, true);
+  host_phase("verify_core_helped:msm", now_ms() - t0);
+  t0 = now_ms();
+  const bool fold_ok = fold_accepts(v, all, true);
+  host_phase("verify_core_helped:host_pairing", now_ms() - t0);
+  *all_accepted = (fold_ok && !any_bad) ? 1 : 0;
+  if (fold_ok) { for (long k = 0; each && k < K; k++) each[k] = b.good[(size_t)k] ? 1 : 0; return SONIC_OK; }
+  // it failed: the global check on its own says whether the aggregate is to blame -- then every proof is rejected -- and if it is not, each
+  // well-formed proof's six checks are folded on their own, and the others' verdicts stand
+  t0 = now_ms();
+  if (!fold_accepts(v, helped_sums(b, 0, 0, true), true)) {
+    set_error("verify_core_batch_helped: the aggregate's C does not open to s(u, v) at v: every proof is rejected");
+    return reject_all();
+  }
+  if (!any_bad) set_error("verify_core_batch_helped: an equation of a proof or of its part of the aggregate does not hold");
+  if (!each) return SONIC_OK;
+  std::vector<Sums> sums((size_t)K);
+  for (long k = 0; k < K; k++) { each[k] = 0; if (b.good[(size_t)k]) sums[(size_t)k] = helped_sums(b, k, k + 1, false); }
+  const int nt = (int)std::min<long>(K, 16);
+  auto work = [&](int w) { for (long k = w; k < K; k += nt) if (b.good[(size_t)k]) each[k] = fold_accepts(v, sums[(size_t)k], false) ? 1 : 0; };
+  {
+    ThreadGroup th;
+    int started = 1;
+    try {
+      for (; started < nt; started++) th.emplace_back(work, started);
+    } catch (const std::system_error&) {}
+    work(0);
+    for (int w = started; w < nt; w++) work(w);
+    th.join();
+  }
+  host_phase("verify_core_helped:each", now_ms() - t0);
+  return SONIC_OK;
 }
 
 int verifier_new(const char* who, const sonic_srs_t* srs, const CircuitView& c, sonic_verifier_t** out) {
@@ -814,6 +1054,31 @@ int sonic_verifier_verify_core_fs_batch(sonic_verifier_t* v, int64_t K, const ui
   decompress_core_device(v, (long)K, proofs, full, accepted);
   return verify_core_proofs_fs_batch(v, (long)K, full.data(), cs, seed, all_accepted, each, &accepted);
   API_CATCH
+}
+// K core proofs and the aggregate signature over their (y_k, z_k): yz = K x (y_k, z_k), or null -- the Fiat-Shamir form, y_k, z_k from each
+// proof's own transcript
+static int verify_core_helped_entry(const char* who, sonic_verifier_t* v, int64_t K, const uint8_t* proofs, int compressed, const uint8_t* yz, bool fs, const uint8_t* cs,
+                                    const uint8_t* aggregate, const uint8_t seed[32], int* all_accepted, uint8_t* each) {
+  if (all_accepted) *all_accepted = 0;
+  API_BEGIN_ON(v ? v->device : -1)                      // (first: without a device the answer is SONIC_ERR_NO_DEVICE whatever the arguments are)
+  if (!v || !proofs || (!fs && !yz) || !aggregate || !all_accepted || (compressed != 0 && compressed != 1)) { set_error("%s: bad argument", who); return SONIC_ERR_INVALID_ARG; }
+  int rc = batch_size_ok(who, v, K);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> g(v->mu);
+  helped_reserve(v, (long)K);
+  std::vector<uint8_t> full, accepted, yzs;
+  if (compressed) { decompress_core_device(v, (long)K, proofs, full, accepted); proofs = full.data(); }
+  if (fs) { core_fs_challenges_batch(v, (long)K, proofs, cs, yzs); yz = yzs.data(); }
+  return verify_core_helped(v, (long)K, proofs, yz, cs, aggregate, seed, all_accepted, each, compressed ? &accepted : nullptr);
+  API_CATCH
+}
+int sonic_verifier_verify_core_batch_helped(sonic_verifier_t* v, int64_t K, const uint8_t* proofs, int compressed, const uint8_t* yz, const uint8_t* cs,
+                                            const uint8_t* aggregate, const uint8_t seed[32], int* all_accepted, uint8_t* each) {
+  return verify_core_helped_entry("sonic_verifier_verify_core_batch_helped", v, K, proofs, compressed, yz, false, cs, aggregate, seed, all_accepted, each);
+}
+int sonic_verifier_verify_core_fs_batch_helped(sonic_verifier_t* v, int64_t K, const uint8_t* proofs, int compressed, const uint8_t* cs, const uint8_t* aggregate,
+                                               const uint8_t seed[32], int* all_accepted, uint8_t* each) {
+  return verify_core_helped_entry("sonic_verifier_verify_core_fs_batch_helped", v, K, proofs, compressed, nullptr, true, cs, aggregate, seed, all_accepted, each);
 }
 // the digest of a batch of core proofs on its own (host only; fs.hpp)
 int sonic_verify_core_batch_digest(int64_t n, int64_t Q, int64_t d, const uint8_t circuit_digest[32], const uint8_t srs_id[32], int64_t K, const uint8_t* proofs,

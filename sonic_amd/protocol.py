@@ -299,6 +299,8 @@ class Prover:
     def __init__(self, srs: SRS, circuit: ArithCircuit, prepare: bool = True):
         self.n, self.Q, suffix, args, _keep = _circuit_args(circuit)
         self._srs = srs
+        self._circuit = circuit          # (aggregate_core: the weights digest, made on first use)
+        self._weights_digest = None
         self._h = C.c_void_p()
         _lib.check(getattr(_lib.lib(), "sonic_prover_new" + suffix)(srs._h, self.n, self.Q, *args, C.byref(self._h)))
         if prepare:     # a handle exists to prove repeatedly: commit the constraint rows once (sonic_prover_prepare)
@@ -469,6 +471,25 @@ class Prover:
         out = C.create_string_buffer(_lib.lib().sonic_hsc_proof_size(len(yzs)))
         _lib.check(_lib.lib().sonic_prover_hsc_prove(self._h, len(yzs), flat.ctypes.data, fr_to_bytes(u), fr_to_bytes(v), out))
         return _hsc_from_bytes(out.raw, len(yzs))
+
+    def aggregate_core(self, yzs, weights_digest: Optional[bytes] = None) -> bytes:
+        """the helper of helped verification (sonic_prover_aggregate_core): ONE signature of correct computation over the (y_k, z_k) of K
+        core proofs of this handle's circuit -- the bytes of an HscProof with m = K whose s_k is s(z_k, y_k) and whose u, v come from the
+        aggregate's own transcript (fs_aggregate_challenges).  weights_digest: fs_weights_digest of the circuit (default: computed from
+        the circuit the handle was made with, once).  Needs no assignment."""
+        yzs = list(yzs)
+        if not yzs or any(len(pair) != 2 for pair in yzs):
+            raise ValueError("aggregate_core: yzs must hold at least one (y_k, z_k) pair")
+        if weights_digest is None:
+            if self._weights_digest is None:
+                self._weights_digest = fs_weights_digest(self._circuit)
+            weights_digest = self._weights_digest
+        if len(bytes(weights_digest)) != 32:
+            raise ValueError("aggregate_core: a weights digest is 32 bytes")
+        flat = fr_array([x for pair in yzs for x in pair])
+        out = C.create_string_buffer(_lib.lib().sonic_hsc_proof_size(len(yzs)))
+        _lib.check(_lib.lib().sonic_prover_aggregate_core(self._h, bytes(weights_digest), len(yzs), flat.ctypes.data, out))
+        return out.raw
 
     def close(self):
         if self._h:
@@ -1028,6 +1049,44 @@ def fs_core_challenges(srs: SRS, circuit, proof):
     return int.from_bytes(out.raw[:32], "little"), int.from_bytes(out.raw[32:], "little")
 
 
+def fs_weights_digest(circuit) -> bytes:
+    """SHA-256 of the gate weights alone (sonic_fs_weights_digest over fs_circuit_midstate; host only): what the transcript of an aggregate
+    binds, since s(X, Y) does not depend on the constants.  circuit: an ArithCircuit, a SparseCircuit, or the 112 bytes of a midstate."""
+    mid = bytes(circuit) if isinstance(circuit, (bytes, bytearray)) else fs_circuit_midstate(circuit)
+    if len(mid) != _lib.FS_MIDSTATE_SIZE:
+        raise ValueError(f"fs_weights_digest: a midstate is {_lib.FS_MIDSTATE_SIZE} bytes")
+    out = C.create_string_buffer(32)
+    _lib.check(_lib.lib().sonic_fs_weights_digest(mid, out))
+    return out.raw
+
+
+def fs_aggregate_challenges(srs: SRS, circuit, yzs, aggregate: bytes, weights_digest: Optional[bytes] = None):
+    """(u, v) that the bytes of an aggregate for the pairs yzs determine (sonic_fs_aggregate_challenges; host only): a verifier compares
+    them with the aggregate's own last 64 bytes"""
+    n, Q = _circuit_args(circuit)[:2]
+    yzs = list(yzs)
+    aggregate = bytes(aggregate)
+    if not yzs or len(aggregate) != _lib.lib().sonic_hsc_proof_size(len(yzs)):
+        raise ValueError("fs_aggregate_challenges: an aggregate for K >= 1 pairs is sonic_hsc_proof_size(K) bytes")
+    flat = fr_array([x for pair in yzs for x in pair])
+    out = C.create_string_buffer(64)
+    wd = weights_digest if weights_digest is not None else fs_weights_digest(circuit)
+    _lib.check(_lib.lib().sonic_fs_aggregate_challenges(n, Q, srs.srsD, bytes(wd), fs_srs_id(srs), len(yzs), flat.ctypes.data, aggregate, out))
+    return int.from_bytes(out.raw[:32], "little"), int.from_bytes(out.raw[32:], "little")
+
+
+def aggregate_core(prover: "Prover", proofs, yzs):
+    """what a helper ships for K core proofs: (aggregate, mismatched) -- Prover.aggregate_core over their (y_k, z_k), and the k whose proof's
+    s is not the aggregate's s_k = s(z_k, y_k): no verifier will accept those, so the helper can drop them first"""
+    yzs = list(yzs)
+    raws = [_core_bytes(p) for p in proofs]
+    if len(raws) != len(yzs):
+        raise ValueError("aggregate_core: one (y_k, z_k) pair per proof")
+    agg = prover.aggregate_core(yzs)
+    mismatched = [k for k, raw in enumerate(raws) if len(raw) != _lib.CORE_PROOF_SIZE or raw[544:576] != agg[224 * k + 96:224 * k + 128]]
+    return agg, mismatched
+
+
 class Verifier:
     """The batched verifier (sonic_verifier_* of the C ABI): the circuit resident in HBM, K proofs folded into ONE pairing product --
     four Miller loops and one final exponentiation per batch; point validation, s(u, v) and the G1 sums run on the GPU.  `circuit` is an
@@ -1130,6 +1189,34 @@ class Verifier:
         cs = self._constants(constants, K) if constants is not None else None
         call = _lib.lib().sonic_verifier_verify_core_fs_batch
         return self._result(K, lambda ok, flags: call(self._h, K, raw, z, cs, sd, ok, flags), each)
+
+    def _aggregate(self, aggregate, K):
+        aggregate = _hsc_to_bytes(aggregate) if isinstance(aggregate, HscProof) else bytes(aggregate)
+        if len(aggregate) != _lib.lib().sonic_hsc_proof_size(K):
+            raise ValueError(f"Verifier: an aggregate for {K} proofs is {_lib.lib().sonic_hsc_proof_size(K)} bytes")
+        return aggregate
+
+    def verify_core_batch_helped(self, proofs, yzs, aggregate, seed=None, each: bool = False, constants=None):
+        """verify_core_batch with a helper's aggregate signature over the same (y_k, z_k) (Prover.aggregate_core;
+        sonic_verifier_verify_core_batch_helped): each proof's s is held against the aggregate's s_k, s(u, v) is evaluated once for the
+        batch instead of s(z_k, y_k) per proof, and the 6K + 1 checks fold into the same four Miller loops.  An aggregate that is
+        malformed, not under its own transcript, or fails its global check rejects every proof."""
+        proofs, yzs = list(proofs), list(yzs)
+        if len(yzs) != len(proofs) or any(len(pair) != 2 for pair in yzs):
+            raise ValueError("verify_core_batch_helped: one (y, z) pair per proof")
+        fr = lambda v: int(v).to_bytes(32, "little")     # noqa: E731  (as is: a non-canonical challenge rejects its proof)
+        (raw, z), yz, sd, K = self._core_proof_bytes(proofs), b"".join(fr(y) + fr(zz) for y, zz in yzs), self._seed(seed), len(proofs)
+        cs = self._constants(constants, K) if constants is not None else None
+        agg, call = self._aggregate(aggregate, K), _lib.lib().sonic_verifier_verify_core_batch_helped
+        return self._result(K, lambda ok, flags: call(self._h, K, raw, z, yz, cs, agg, sd, ok, flags), each)
+
+    def verify_core_fs_batch_helped(self, proofs, aggregate, seed=None, each: bool = False, constants=None):
+        """the same for Fiat-Shamir core proofs: y_k, z_k recomputed per proof as verify_core_fs_batch does; the aggregate is over those"""
+        proofs = list(proofs)
+        (raw, z), sd, K = self._core_proof_bytes(proofs), self._seed(seed), len(proofs)
+        cs = self._constants(constants, K) if constants is not None else None
+        agg, call = self._aggregate(aggregate, K), _lib.lib().sonic_verifier_verify_core_fs_batch_helped
+        return self._result(K, lambda ok, flags: call(self._h, K, raw, z, cs, agg, sd, ok, flags), each)
 
     def eval_s(self, uvs) -> List[int]:
         """s(u, v) of the circuit's s(X, Y) for every (u, v) of `uvs`, on the GPU (raises SonicError INEXACT_DIVISION for u = 0 or v = 0)"""
