@@ -45,6 +45,7 @@ module Sonic.HIP
   , gNegativeX, gPositiveX, gNegativeAlphaX, gPositiveAlphaX
   , hNegativeX, hPositiveX, hNegativeAlphaX, hPositiveAlphaX, srsPairing
   , saveSRS, loadSRS, srsForCircuit, loadSrsForCircuit
+  , checkSrs, updateSrs, verifySrsUpdate
     -- * Sonic.CommitmentScheme
   , commitPoly, openPoly, pcV
     -- * Sonic.Protocol
@@ -113,6 +114,10 @@ foreign import ccall safe   "sonic_srs_save"          c_srs_save         :: Ptr 
 foreign import ccall safe   "sonic_srs_load"          c_srs_load         :: CString -> Ptr (Ptr SrsHandle) -> IO CInt
 foreign import ccall safe   "sonic_srs_for_circuit"   c_srs_for_circuit  :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr (Ptr SrsHandle) -> IO CInt
 foreign import ccall safe   "sonic_srs_load_for_circuit" c_srs_load_for_circuit :: CString -> Int64 -> Int64 -> Ptr (Ptr SrsHandle) -> IO CInt
+-- the updatable half (ABI 7): structure check, contribution, verification of a contribution
+foreign import ccall safe   "sonic_srs_check"         c_srs_check        :: Ptr SrsHandle -> Ptr Word8 -> Ptr CInt -> IO CInt
+foreign import ccall safe   "sonic_srs_update"        c_srs_update       :: Ptr SrsHandle -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr (Ptr SrsHandle) -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_srs_verify_update" c_srs_verify_update :: Ptr SrsHandle -> Ptr SrsHandle -> Ptr Word8 -> CInt -> Ptr CInt -> IO CInt
 
 foreign import ccall safe   "sonic_commit_poly"       c_commit_poly      :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_open_poly"         c_open_poly        :: Ptr SrsHandle -> Ptr Word8 -> Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> IO CInt
@@ -371,6 +376,32 @@ loadSrsForCircuit :: FilePath -> Int -> Int -> IO SRS
 loadSrsForCircuit path n q = libraryReady `seq` withCString path (\cp -> alloca $ \out -> do
   check =<< c_srs_load_for_circuit cp (fromIntegral n) (fromIntegral q) out
   wrapSRS out)
+
+-- | whether the handle's points ARE a reference string (include/sonic_hip.h, "Updatable SRS": relations R0 .. R4 under random 128-bit
+-- weights drawn from the operating system).  Right (): it passes; Left mask: bit i set when Ri fails.  Run it on every string that
+-- comes from outside: loading validates each point on its own and nothing else.
+checkSrs :: SRS -> IO (Either Int ())
+checkSrs (SRS h) = withForeignPtr h $ \p -> alloca $ \failed -> do
+  check =<< c_srs_check p nullPtr failed
+  m <- peek failed
+  pure (if m == 0 then Right () else Left (fromIntegral m))
+
+-- | a contribution with shares x1, alpha1 (non-zero): the string of trapdoor (x x1, alpha alpha1) as a NEW handle on the same GPU, and
+-- the 448-byte proof that the contributor knew the shares.  The source is untouched.  Nonces come from the operating system.
+updateSrs :: SRS -> Fr -> Fr -> IO (SRS, ByteString)
+updateSrs (SRS h) x1 alpha1 = withForeignPtr h $ \p -> withFr x1 $ \px -> withFr alpha1 $ \pa ->
+  alloca $ \out -> allocaBytes 448 $ \proof -> do
+    check =<< c_srs_update p px pa nullPtr out proof
+    (,) <$> wrapSRS out <*> packed proof 448
+
+-- | whether the second string is the first updated by someone who knew the shares behind the proof; the new string's structure is
+-- checked as well (checkSrs).  A malformed proof is False.
+verifySrsUpdate :: SRS -> SRS -> ByteString -> IO Bool
+verifySrsUpdate (SRS old) (SRS new') proof
+  | BS.length proof /= 448 = pure False
+  | otherwise = withForeignPtr old $ \po -> withForeignPtr new' $ \pn -> withBytes proof $ \pp -> alloca $ \ok -> do
+      check =<< c_srs_verify_update po pn pp 1 ok
+      (/= 0) <$> peek ok
 
 -- ---------------------------------------------------------------------------------------------------------------------
 -- Sonic.CommitmentScheme

@@ -107,7 +107,7 @@ typedef struct sonic_verifier sonic_verifier_t;
  * sonic_verifier_verify_core_batch, sonic_verifier_verify_core_fs_batch, sonic_verify_core_batch_digest, sonic_core_proof_compress,
  * sonic_core_proof_decompress; still 7, additions only: helped verification -- sonic_fs_weights_digest, sonic_fs_aggregate_challenges,
  * sonic_prover_aggregate_core, sonic_verifier_verify_core_batch_helped, sonic_verifier_verify_core_fs_batch_helped,
- * sonic_verify_core_helped_digest */
+ * sonic_verify_core_helped_digest; still 7, additions only: the updatable SRS -- sonic_srs_check, sonic_srs_update, sonic_srs_verify_update */
 int sonic_abi_version(void);
 int sonic_init(int device_ordinal);                 /* choose the DEFAULT GPU (first call wins) and make it the thread's HIP device; idempotent */
 int sonic_device_count(int* out);                   /* GPUs this process can see; SONIC_ERR_NO_DEVICE (and 0) without one */
@@ -798,6 +798,55 @@ int sonic_verifier_verify_core_fs_batch_helped(sonic_verifier_t* v, int64_t K, c
                                                const uint8_t* aggregate, const uint8_t seed[32], int* all_accepted, uint8_t* each);
 int sonic_verify_core_helped_digest(int64_t n, int64_t Q, int64_t d, const uint8_t weights_digest[32], const uint8_t srs_id[32], int64_t K,
                                     const uint8_t* proofs, const uint8_t* yz, const uint8_t* cs, const uint8_t* aggregate, uint8_t out[32]);
+
+/* ---- Updatable SRS: check a string, contribute to it, verify a contribution (ABI 7, additions only) ----
+ * Notation: G0[e] = basis 0, G1[e] = basis 1 (slot e = 0 empty), H0[e], H1[e] the G2 bases, e in [-d, d]; g, h the fixed generators.
+ * All three calls take whole strings: a circuit-sized view is SONIC_ERR_INVALID_ARG.
+ *
+ *   srs_check       whether the points of a handle ARE a reference string: the consecutive powers of one x over g and h, with the alpha
+ *                   basis and the G2 half belonging to them.  (Loading checks every point on its own -- canonical, on the curve, in the
+ *                   subgroup -- and nothing else: a file with one wrong element, or with bases of two trapdoors, loads.)  Run it on
+ *                   every string that comes from outside, before the first prover or verifier is made over it.
+ *                   The handle needs its G2 half (one that can still generate it does so first; none: SONIC_ERR_INVALID_ARG).
+ *                   With randomizers rho_e the string passes iff
+ *                     R0  G0[0] == g and H0[0] == h, as bytes
+ *                     R1  e(P, H0[1]) = e(P+, h),          P = sum_{e=-d}^{d-1} rho_e G0[e],  P+ = sum_{e=-d}^{d-1} rho_e G0[e+1]
+ *                     R2  e(A, h) = e(A0, H1[0]),          A = sum_{e!=0} rho_e G1[e],        A0 = sum_{e!=0} rho_e G0[e]
+ *                     R3  e(g, B) = e(sum_e rho_e G0[e], h),          B = sum_e rho_e H0[e]
+ *                     R4  e(g, C) = e(sum_e rho_e G0[e], H1[0]),      C = sum_e rho_e H1[e]   (every element, e = 0 included)
+ *                   *failed is the bit mask of the relations that do not hold (SONIC_SRS_CHECK_R0 .. R4), 0 for a string that passes.
+ *                   The return value is SONIC_OK either way: errors are bad arguments and HIP failures only.
+ *                   rho_e = the first 16 bytes of SHA-256("sonic-hip/srs-check/v1" || seed || le64 (e + d)) as a little-endian integer,
+ *                   1 in place of 0; a wrong string passes with probability <= 2^-128 per relation.  seed = NULL draws 32 bytes from the
+ *                   operating system (none to be had: SONIC_ERR_HIP).  The string is fixed before the seed is drawn, so the seed need not bind the string.  A
+ *                   caller-supplied seed is for reproducible tests only: whoever knows the seed before choosing the string can defeat the check.
+ *   srs_update      a contribution: a NEW handle on the same GPU with G0'[e] = x1^e G0[e], G1'[e] = alpha1 x1^e G1[e], H0'[e] = x1^e H0[e],
+ *                   H1'[e] = alpha1 x1^e H1[e] -- the string of trapdoor (x x1, alpha alpha1) -- with its own tables.  The source handle
+ *                   is untouched (provers hold it).  The new handle holds no trapdoor.  proof: 448 bytes,
+ *                     X = x1 g (96) || A = alpha1 g (96) || Rx = kx g (96) || Ra = ka g (96) || sx (32) || sa (32),
+ *                   two Schnorr proofs under one challenge that binds d and the Fiat-Shamir id of the OLD string
+ *                   (sonic_amd/csrc/srs_update.hpp has the normative text).  seed = NULL: nonces from the operating system; a seed
+ *                   derives them from the seed, the shares and the old id, for tests.
+ *                   A share that is zero: SONIC_ERR_INVALID_ARG; not below r: SONIC_ERR_BAD_ENCODING; a source without a G2 half:
+ *                   SONIC_ERR_INVALID_ARG -- each before anything is launched.  The library's named host copies of the shares, their
+ *                   inverse and the nonces are wiped before the call returns, on every path.  Not wiped: what the compiler and the HIP
+ *                   runtime copy on their own (stack temporaries of the field arithmetic, the kernels' argument buffers), and x1 and
+ *                   alpha1 themselves, which are the caller's.  An operating system that gives no random bytes: SONIC_ERR_HIP.
+ *   srs_verify_update   *ok = 1 iff new is old updated by someone who knew the shares behind the proof: the same d; the proof's four
+ *                   points canonical, on the curve, in the subgroup, not infinity, its two scalars canonical; sx g = Rx + c X and
+ *                   sa g = Ra + c A; e(G0'[1], h) = e(X, H0[1]); e(g, H1'[0]) = e(A, H1[0]); and, with check_new != 0, the new string
+ *                   passes sonic_srs_check.  Without that check the two pairing equations say nothing about the other 8d + 2 points: pass
+ *                   check_new = 0 only for a string that is checked elsewhere.  A malformed proof gives *ok = 0, not an error.  Both
+ *                   handles need their G2 halves. */
+#define SONIC_SRS_CHECK_R0 1
+#define SONIC_SRS_CHECK_R1 2
+#define SONIC_SRS_CHECK_R2 4
+#define SONIC_SRS_CHECK_R3 8
+#define SONIC_SRS_CHECK_R4 16
+#define SONIC_SRS_UPDATE_PROOF_SIZE 448
+int sonic_srs_check(const sonic_srs_t* srs, const uint8_t seed[32], int* failed);
+int sonic_srs_update(const sonic_srs_t* srs, const uint8_t x1[32], const uint8_t alpha1[32], const uint8_t seed[32], sonic_srs_t** out, uint8_t proof[448]);
+int sonic_srs_verify_update(const sonic_srs_t* old_srs, const sonic_srs_t* new_srs, const uint8_t proof[448], int check_new, int* ok);
 
 /* ---- device memory for callers without a HIP binding ---- */
 int sonic_dev_alloc(size_t bytes, void** out);                       /* on the default device */

@@ -20,7 +20,7 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 from ._lib import SonicError, LIB_PATH  # noqa: F401,E402
 from .encoding import R_MODULUS, Q_MODULUS, fr_to_bytes, fr_from_bytes, g1_to_bytes, g1_from_bytes  # noqa: F401,E402
-from .srs import SRS  # noqa: F401,E402
+from .srs import SRS, srs_verify_update  # noqa: F401,E402
 from .commitment import commit_poly, open_poly, pc_v, msm_g1, MsmLane  # noqa: F401,E402
 from .protocol import hsc_prove_poly, hsc_verify_poly  # noqa: F401,E402
 from .protocol import prove_fs, verify_fs, fs_challenges, fs_circuit_digest, fs_srs_id  # noqa: F401,E402
@@ -36,5 +36,5 @@ from .protocol import CoreProof, prove_core_batch, prove_core_batch_fs, verify_c
 from .protocol import aggregate_core, fs_weights_digest, fs_aggregate_challenges  # noqa: F401,E402
 from .compressed import g1_compress, g1_decompress, g2_compress, g2_decompress, proof_compress, proof_decompress  # noqa: F401,E402
 
-__all__ = ["aggregate_core", "fs_weights_digest", "fs_aggregate_challenges", "CoreProof", "prove_core_batch", "prove_core_batch_fs", "verify_core", "verify_core_fs", "fs_core_challenges", "WitnessBatch", "Verifier", "verify_batch", "prove_batch_fs", "fs_circuit_midstate", "fs_circuit_digest_resume", "g1_compress", "g1_decompress", "g2_compress", "g2_decompress", "proof_compress", "proof_decompress", "SRS", "commit_poly", "open_poly", "pc_v", "msm_g1", "MsmLane", "prove", "verify", "prove_fs", "verify_fs", "fs_challenges", "fs_circuit_digest", "hsc_prove", "hsc_verify", "hsc_prove_poly", "hsc_verify_poly", "Proof", "HscProof", "RndOracle", "Prover", "ProverPipeline",
+__all__ = ["aggregate_core", "fs_weights_digest", "fs_aggregate_challenges", "CoreProof", "prove_core_batch", "prove_core_batch_fs", "verify_core", "verify_core_fs", "fs_core_challenges", "WitnessBatch", "Verifier", "verify_batch", "prove_batch_fs", "fs_circuit_midstate", "fs_circuit_digest_resume", "g1_compress", "g1_decompress", "g2_compress", "g2_decompress", "proof_compress", "proof_decompress", "SRS", "srs_verify_update", "commit_poly", "open_poly", "pc_v", "msm_g1", "MsmLane", "prove", "verify", "prove_fs", "verify_fs", "fs_challenges", "fs_circuit_digest", "hsc_prove", "hsc_verify", "hsc_prove_poly", "hsc_verify_poly", "Proof", "HscProof", "RndOracle", "Prover", "ProverPipeline",
            "ArithCircuit", "SparseCircuit", "Assignment", "GateWeights", "SonicError"]

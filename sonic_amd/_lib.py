@@ -198,6 +198,9 @@ def lib() -> C.CDLL:
         "sonic_verify_core_helped_digest": [i64, i64, i64, cp, cp, i64, vp, vp, vp, vp, vp],
         "sonic_verifier_verify_core_batch_helped": [vp, i64, vp, i32, vp, vp, vp, cp, C.POINTER(i32), vp],
         "sonic_verifier_verify_core_fs_batch_helped": [vp, i64, vp, i32, vp, vp, cp, C.POINTER(i32), vp],
+        "sonic_srs_check": [vp, cp, C.POINTER(i32)],
+        "sonic_srs_update": [vp, cp, cp, cp, C.POINTER(vp), cp],
+        "sonic_srs_verify_update": [vp, vp, cp, i32, C.POINTER(i32)],
         "sonic_dev_alloc": [C.c_size_t, C.POINTER(vp)],
         "sonic_dev_free": [vp],
         "sonic_dev_upload": [vp, vp, C.c_size_t],
@@ -303,6 +306,7 @@ EXPORTED = [
     "sonic_verifier_verify_core_batch", "sonic_verifier_verify_core_fs_batch", "sonic_verify_core_batch_digest", "sonic_core_proof_compress", "sonic_core_proof_decompress",
     "sonic_fs_weights_digest", "sonic_fs_aggregate_challenges", "sonic_prover_aggregate_core", "sonic_verify_core_helped_digest",
     "sonic_verifier_verify_core_batch_helped", "sonic_verifier_verify_core_fs_batch_helped",
+    "sonic_srs_check", "sonic_srs_update", "sonic_srs_verify_update",
 ]
 
 

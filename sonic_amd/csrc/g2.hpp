@@ -108,6 +108,25 @@ HD G2Jac g2_add_mixed(const G2Jac& p, const G2Affine& q) {   // madd-2007-bl
   r.z = f2_sub(f2_sub(f2_sqr(f2_add(p.z, H)), Z1Z1), HH);
   return r;
 }
+// p + q, both Jacobian (add-2007-bl): the tree of the G2 sums (srs_g2.hip, k_g2_sum) and the host's additions of block totals
+HD G2Jac g2_add(const G2Jac& p, const G2Jac& q) {
+  if (q.is_inf()) return p;
+  if (p.is_inf()) return q;
+  Fq2 Z1Z1 = f2_sqr(p.z), Z2Z2 = f2_sqr(q.z);
+  Fq2 U1 = f2_mul(p.x, Z2Z2), U2 = f2_mul(q.x, Z1Z1);
+  Fq2 S1 = f2_mul(f2_mul(p.y, q.z), Z2Z2), S2 = f2_mul(f2_mul(q.y, p.z), Z1Z1);
+  if (U1 == U2) {
+    if (S1 == S2) return g2_dbl(p);
+    return G2Jac::inf();
+  }
+  Fq2 H = f2_sub(U2, U1), I = f2_sqr(f2_dbl(H)), J = f2_mul(H, I);
+  Fq2 rr = f2_dbl(f2_sub(S2, S1)), V = f2_mul(U1, I);
+  G2Jac r;
+  r.x = f2_sub(f2_sub(f2_sqr(rr), J), f2_dbl(V));
+  r.y = f2_sub(f2_mul(rr, f2_sub(V, r.x)), f2_dbl(f2_mul(S1, J)));
+  r.z = f2_mul(f2_sub(f2_sub(f2_sqr(f2_add(p.z, q.z)), Z1Z1), Z2Z2), H);
+  return r;
+}
 // r P == O for a finite point of the twist (E'(Fq2) has a large cofactor and the pairing is bilinear only on the order-r subgroup): the
 // literal double-and-add over the bits of r, shared by k_g2_points_from_bytes and k_g2_decompress
 HD bool g2_in_subgroup(const G2Affine& p) {

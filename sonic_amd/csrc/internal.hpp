@@ -136,6 +136,10 @@ struct G2Affine;
 void srs_generate_g2(hipStream_t st, long d, const Fr& x_std, const Fr& alpha_std, G2Affine* h0, G2Affine* h1);
 void g2_points_to_bytes_enqueue(hipStream_t st, const G2Affine* in, uint8_t* d_out, long n);
 void g2_points_from_bytes_enqueue(hipStream_t st, const uint8_t* d_in, G2Affine* out, long n, int* d_err);
+// updatable SRS (srs_g2.hip): sum_i rho[i] * pts[i] for the 128-bit randomizers of the structure check, as the 192 bytes of the header's G2
+// layout; and a contribution to both G2 bases, o0[i] = x^e * h0[i], o1[i] = alpha x^e * h1[i] (Montgomery scalars).  Both wait for the stream.
+void g2_weighted_sum(hipStream_t st, const G2Affine* pts, const Fr* d_rho, long n, uint8_t out192[192]);
+void srs_scale_g2(hipStream_t st, long d, const G2Affine* h0, const G2Affine* h1, const Fr& x, const Fr& xinv, const Fr& alpha, G2Affine* o0, G2Affine* o1);
 
 // compressed point encodings (compress.hip; the format: compress.hpp).  One thread per point; d_in at multiples of 48 / 96 bytes.
 // decompress: out (may be {nullptr}) gets the Montgomery affine point, d_bytes (may be null) its canonical 96 / 192 bytes, d_flags one

@@ -6,6 +6,7 @@
 // normalisation to affine, 64 points per inversion.
 #include "srs_handle.hpp"
 #include "endo.hpp"
+#include "srs_scale.hpp"
 
 namespace sonic {
 
@@ -206,6 +207,53 @@ void srs_build_tables(hipStream_t st, sonic_srs* s) {
     }
   }
   HIP_OK(hipStreamSynchronize(st));
+}
+
+// ---- updatable SRS (include/sonic_hip.h, "Updatable SRS"): a contribution scales every point by a scalar of its own ------------------
+// out[i] = k_i * in[i], one thread per point.  Slab slot i <-> exponent e = i - e_origin; k_i = x^e (times alpha where mul_alpha), derived
+// in the thread from x or its inverse as k_srs_points derives it, then walked bit by bit (srs_scale.hpp: the limb by constant-index
+// selects, nothing in scratch).  The result stays XYZZ for k_batch_affine.  An empty slot (basis 1, e = 0) stays empty.
+__global__ __launch_bounds__(256) void k_g1_scale_each(PointArray in, long e_origin, long m, Fr x, Fr xinv, Fr alpha, int mul_alpha, G1XYZZ* __restrict__ out) {
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  long e = i - e_origin;
+  Fr p = e >= 0 ? fp_pow_u64(x, (uint64_t)e) : fp_pow_u64(xinv, (uint64_t)(-e));
+  if (mul_alpha) p = fp_mul(p, alpha);
+  out[i] = g1_scale(in[i], fp_from_mont(p));
+}
+
+// dst's bases = src's, every point scaled: basis 0 by x^e, basis 1 by alpha x^e (x, xinv, alpha Montgomery).  Both handles hold the
+// whole string of one d.  A multiple of a subgroup point is a subgroup point: no walk over r here.  The caller builds dst's tables.
+void srs_scale_g1_enqueue(hipStream_t st, const sonic_srs* src, sonic_srs* dst, const Fr& x, const Fr& xinv, const Fr& alpha) {
+  const long d = src->d, n = 2 * d + 1;
+  const long SLAB = 1L << 20;
+  const long cap = n < SLAB ? n : SLAB;
+  DevBuf xs(sizeof(G1XYZZ) * cap), pref(sizeof(Fq) * cap);
+  for (int b = 0; b < 2; b++)
+    for (long base = 0; base < n; base += SLAB) {
+      const long m = n - base < SLAB ? n - base : SLAB;
+      LAUNCH(k_g1_scale_each, ceil_div(m, 256), 256, 0, st, src->basis(b) + base, d - base, m, x, xinv, alpha, b, xs.as<G1XYZZ>());
+      LAUNCH(k_batch_affine, ceil_div(ceil_div(m, 64), 64), 64, 0, st, (const G1XYZZ*)xs.as<G1XYZZ>(), dst->basis_mut(b) + base, pref.as<Fq>(), m);
+    }
+  HIP_OK(hipStreamSynchronize(st));
+}
+
+// the randomizers of sonic_srs_check (srs_scale.hpp, srs_check_rho): rho[i] for index i = e + d as a standard-form Fr whose upper four
+// limbs are zero -- what the MSMs over the G1 bases take as scalars and k_g2_scale_each reads the low 16 bytes of
+struct SrsCheckSeed { uint32_t w[8]; };
+__global__ __launch_bounds__(256) void k_srs_check_rho(SrsCheckSeed seed, long n, Fr* __restrict__ rho) {
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t r4[4];
+  srs_check_rho(seed.w, (uint64_t)i, r4);
+  Fr k = Fr::zero();
+  for (int j = 0; j < 4; j++) k.l[j] = r4[j];
+  rho[i] = k;
+}
+void srs_check_rho_enqueue(hipStream_t st, const uint8_t seed[32], long n, Fr* d_rho) {
+  SrsCheckSeed s;
+  for (int k = 0; k < 8; k++) s.w[k] = (uint32_t)seed[4 * k] << 24 | (uint32_t)seed[4 * k + 1] << 16 | (uint32_t)seed[4 * k + 2] << 8 | seed[4 * k + 3];
+  LAUNCH(k_srs_check_rho, ceil_div(n, 256), 256, 0, st, s, n, d_rho);
 }
 
 __global__ void k_fr_setup_x(const Fr* in_std, Fr* out) {  // out = {x, x^-1, alpha} Montgomery

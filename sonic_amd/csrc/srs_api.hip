@@ -171,8 +171,9 @@ int sonic_srs_get_points(const sonic_srs_t* srs, int basis, int64_t e0, int64_t 
   API_END
 }
 
+}  // extern "C"
 // makes sure the G2 half is resident; caller holds call_mutex
-static int srs_ensure_g2(const sonic_srs_t* srs, hipStream_t st, const char* who) {
+int sonic::srs_ensure_g2(const sonic_srs* srs, hipStream_t st, const char* who) {
   std::lock_guard<std::mutex> g2(srs->g2_mu);
   if (srs->h.p) return SONIC_OK;
   if (srs->is_view()) { set_error("%s: this view of the SRS has no G2 half (the string it was made from could not supply one)", who); return SONIC_ERR_INVALID_ARG; }
@@ -189,6 +190,7 @@ static int srs_ensure_g2(const sonic_srs_t* srs, hipStream_t st, const char* who
   srs->wipe_trapdoor();          // x and alpha have served their last purpose
   return SONIC_OK;
 }
+extern "C" {
 
 int sonic_srs_get_g2_points(const sonic_srs_t* srs, int basis, int64_t e0, int64_t n, uint8_t* out) {
   API_BEGIN_ON(srs_device(srs))

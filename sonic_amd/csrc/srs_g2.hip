@@ -6,6 +6,8 @@
 // scheme as the G1 side (byte table of the generator, 32 mixed additions per element, batched normalisation).
 #include "internal.hpp"
 #include "g2.hpp"
+#include "srs_scale.hpp"
+#include "compress.hpp"
 
 namespace sonic {
 
@@ -145,6 +147,85 @@ void srs_generate_g2(hipStream_t st, long d, const Fr& x_std, const Fr& alpha_st
     LAUNCH(k_g2_batch_affine, ceil_div(ceil_div(m, 64), 64), 64, 0, st, (const G2Jac*)x0.as<G2Jac>(), h0 + base, pref.as<Fq2>(), m);
     LAUNCH(k_g2_batch_affine, ceil_div(ceil_div(m, 64), 64), 64, 0, st, (const G2Jac*)x1.as<G2Jac>(), h1 + base, pref.as<Fq2>(), m);
   }
+  HIP_OK(hipStreamSynchronize(st));
+}
+
+// ---- updatable SRS (include/sonic_hip.h, "Updatable SRS"): every G2 point times a scalar of its own -----------------------------------
+// out[i] = k_i * in[i] (Jacobian, for k_g2_batch_affine or k_g2_sum), one thread per point.  rho == nullptr: slab slot i <-> exponent
+// e = i - e_origin and k_i = x^e (times alpha where mul_alpha), derived in the thread as k_g2_srs_points derives it -- a contribution.
+// Otherwise k_i = the low 128 bits of rho[i] -- the randomizers of the structure check -- and only 128 steps are walked.
+__global__ __launch_bounds__(256, 1) void k_g2_scale_each(const G2Affine* __restrict__ in, long e_origin, long m, Fr x, Fr xinv, Fr alpha, int mul_alpha,
+                                                          const Fr* __restrict__ rho, G2Jac* __restrict__ out) {
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  if (rho) { out[i] = g2_scale(in[i], rho[i], 4); return; }
+  long e = i - e_origin;
+  Fr p = e >= 0 ? fp_pow_u64(x, (uint64_t)e) : fp_pow_u64(xinv, (uint64_t)(-e));
+  if (mul_alpha) p = fp_mul(p, alpha);
+  out[i] = g2_scale(in[i], fp_from_mont(p));
+}
+
+// the sum of n Jacobian points as a block tree: every thread adds the points of its stride, the 64 threads of a block fold their sums
+// in LDS (64 x 288 B), and the block's total goes to tot[blockIdx.x] for the host to add
+constexpr int G2_SUM_BLOCK = 64, G2_SUM_MAX_BLOCKS = 256;
+__global__ __launch_bounds__(G2_SUM_BLOCK, 1) void k_g2_sum(const G2Jac* __restrict__ in, long n, G2Jac* __restrict__ tot) {
+  __shared__ G2Jac sh[G2_SUM_BLOCK];
+  const int t = threadIdx.x;
+  G2Jac acc = G2Jac::inf();
+  for (long i = (long)blockIdx.x * G2_SUM_BLOCK + t; i < n; i += (long)gridDim.x * G2_SUM_BLOCK) acc = g2_add(acc, in[i]);
+  sh[t] = acc;
+  __syncthreads();
+  for (int s = G2_SUM_BLOCK / 2; s > 0; s >>= 1) {
+    if (t < s) sh[t] = g2_add(sh[t], sh[t + s]);
+    __syncthreads();
+  }
+  if (t == 0) {
+    G2Jac r = sh[0];                  // leaves the device (lazy range)
+    r.x.c0 = fp_canonical(r.x.c0); r.x.c1 = fp_canonical(r.x.c1); r.y.c0 = fp_canonical(r.y.c0); r.y.c1 = fp_canonical(r.y.c1);
+    r.z.c0 = fp_canonical(r.z.c0); r.z.c1 = fp_canonical(r.z.c1);
+    tot[blockIdx.x] = r;
+  }
+}
+
+// sum_i rho[i] * pts[i] over n points (rho: 128-bit scalars in 32-byte elements) as the 192 canonical bytes sonic_srs_get_g2_points writes;
+// waits for the stream
+void g2_weighted_sum(hipStream_t st, const G2Affine* pts, const Fr* d_rho, long n, uint8_t out192[192]) {
+  const long SLAB = 1L << 19;
+  const long cap = n < SLAB ? n : SLAB;
+  const int slabs = ceil_div(n, SLAB);
+  DevBuf xs(sizeof(G2Jac) * cap), tot(sizeof(G2Jac) * (size_t)G2_SUM_MAX_BLOCKS * slabs);
+  std::vector<G2Jac> h;
+  const Fr none = Fr::zero();
+  long nt = 0;
+  for (long base = 0; base < n; base += SLAB) {
+    const long m = n - base < SLAB ? n - base : SLAB;
+    const int blocks = ceil_div(m, G2_SUM_BLOCK) < G2_SUM_MAX_BLOCKS ? ceil_div(m, G2_SUM_BLOCK) : G2_SUM_MAX_BLOCKS;
+    LAUNCH(k_g2_scale_each, ceil_div(m, 256), 256, 0, st, pts + base, 0L, m, none, none, none, 0, d_rho + base, xs.as<G2Jac>());
+    LAUNCH(k_g2_sum, blocks, G2_SUM_BLOCK, 0, st, (const G2Jac*)xs.as<G2Jac>(), m, tot.as<G2Jac>() + nt);
+    nt += blocks;
+  }
+  h.resize((size_t)nt);
+  HIP_OK(hipMemcpyAsync(h.data(), tot.p, sizeof(G2Jac) * (size_t)nt, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  G2Jac acc = G2Jac::inf();
+  for (long k = 0; k < nt; k++) acc = g2_add(acc, h[(size_t)k]);
+  uint32_t w[48];
+  g2_canonical_words(g2_to_affine(acc), w);
+  memcpy(out192, w, 192);
+}
+
+// o0[i] = x^e * h0[i], o1[i] = alpha x^e * h1[i] over the 2d + 1 points of each basis (x, xinv, alpha Montgomery); waits for the stream
+void srs_scale_g2(hipStream_t st, long d, const G2Affine* h0, const G2Affine* h1, const Fr& x, const Fr& xinv, const Fr& alpha, G2Affine* o0, G2Affine* o1) {
+  const long n = 2 * d + 1;
+  const long SLAB = 1L << 19;
+  const long cap = n < SLAB ? n : SLAB;
+  DevBuf xs(sizeof(G2Jac) * cap), pref(sizeof(Fq2) * cap);
+  for (int b = 0; b < 2; b++)
+    for (long base = 0; base < n; base += SLAB) {
+      const long m = n - base < SLAB ? n - base : SLAB;
+      LAUNCH(k_g2_scale_each, ceil_div(m, 256), 256, 0, st, (b ? h1 : h0) + base, d - base, m, x, xinv, alpha, b, (const Fr*)nullptr, xs.as<G2Jac>());
+      LAUNCH(k_g2_batch_affine, ceil_div(ceil_div(m, 64), 64), 64, 0, st, (const G2Jac*)xs.as<G2Jac>(), (b ? o1 : o0) + base, pref.as<Fq2>(), m);
+    }
   HIP_OK(hipStreamSynchronize(st));
 }
 

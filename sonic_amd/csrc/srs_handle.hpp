@@ -96,5 +96,12 @@ MsmPlan srs_msm_plan(const sonic_srs* s, long n);
 void srs_generate(hipStream_t st, sonic_srs* s, const Fr& x_std, const Fr& alpha_std);
 // fills window tables 1 .. W-1 of both bases from table 0, the running sums and the symmetric sums (srs.hip)
 void srs_build_tables(hipStream_t st, sonic_srs* s);
+// updatable SRS (srs.hip): dst's two bases = src's with every point scaled, basis 0 by x^e, basis 1 by alpha x^e (Montgomery scalars; both
+// handles whole strings of one d; waits for the stream; the caller builds dst's tables), and the randomizers of the structure check:
+// rho[i] for i = e + d in [0, n), standard form, upper four limbs zero (srs_scale.hpp)
+void srs_scale_g1_enqueue(hipStream_t st, const sonic_srs* src, sonic_srs* dst, const Fr& x, const Fr& xinv, const Fr& alpha);
+void srs_check_rho_enqueue(hipStream_t st, const uint8_t seed[32], long n, Fr* d_rho);
+// makes sure the G2 half is resident, generating it where the handle still can (srs_api.hip); the caller holds call_mutex
+int srs_ensure_g2(const sonic_srs* srs, hipStream_t st, const char* who);
 
 }  // namespace sonic

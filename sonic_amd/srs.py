@@ -6,7 +6,27 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .encoding import fr_to_bytes, g1_from_bytes
+from .encoding import R_MODULUS, fr_to_bytes, g1_from_bytes
+
+
+UPDATE_PROOF_SIZE = 448         # SONIC_SRS_UPDATE_PROOF_SIZE
+
+
+def check_names(failed: int) -> str:
+    """the relations a failed_mask of SRS.check names, as in 'R1, R3'"""
+    return ", ".join(f"R{i}" for i in range(5) if failed >> i & 1)
+
+
+def srs_verify_update(old: "SRS", new: "SRS", proof: bytes, check: bool = True) -> bool:
+    """whether `new` is `old` updated by someone who knew the shares behind `proof` (sonic_srs_verify_update): the proof's two Schnorr
+    equations, the two pairing equations that link the strings and -- with check, the default -- the structure check of the new string.
+    check=False is for a string that is checked elsewhere: the link equations alone say nothing about the other 8d + 2 points.
+    A malformed proof is False, not an error."""
+    if len(proof) != UPDATE_PROOF_SIZE:
+        return False
+    ok = C.c_int(0)
+    _lib.check(_lib.lib().sonic_srs_verify_update(old._h, new._h, bytes(proof), 1 if check else 0, C.byref(ok)))
+    return bool(ok.value)
 
 
 class SRS:
@@ -77,16 +97,54 @@ class SRS:
         _lib.check(save(self._h, str(path).encode(), 2 if g2 is None else (1 if g2 else 0)))
 
     @classmethod
-    def load(cls, path: str, device: int = -1, circuit=None) -> "SRS":
+    def load(cls, path: str, device: int = -1, circuit=None, check: bool = False) -> "SRS":
         """read either container.  circuit=(n, Q): a circuit-sized view (see for_circuit) made by reading only the byte ranges of its
-        windows, and the four G2 points where the file has a G2 half (sonic_srs_load_for_circuit_on)"""
+        windows, and the four G2 points where the file has a G2 half (sonic_srs_load_for_circuit_on).
+        check=True runs the structure check (see check) on the loaded string and raises SonicError(BAD_ENCODING) naming the relations
+        that fail: loading alone validates every point on its own and nothing else.  A view cannot be checked: check the whole string."""
+        if check and circuit is not None:
+            raise ValueError("SRS.load: check=True needs the whole string, not a circuit-sized view")
         h = C.c_void_p()
         if circuit is None:
             _lib.check(_lib.lib().sonic_srs_load_on(device, str(path).encode(), C.byref(h)))
         else:
             n, Q = circuit
             _lib.check(_lib.lib().sonic_srs_load_for_circuit_on(device, str(path).encode(), n, Q, C.byref(h)))
-        return cls(h, int(_lib.lib().sonic_srs_d(h)))
+        srs = cls(h, int(_lib.lib().sonic_srs_d(h)))
+        if check:
+            ok, failed = srs.check()
+            if not ok:
+                srs.close()
+                raise _lib.SonicError(3, f"SRS.load: {path} is no reference string: relations {check_names(failed)} fail")
+        return srs
+
+    def check(self, seed: bytes = None):
+        """(ok, failed_mask): whether the handle's points ARE a reference string -- the consecutive powers of one x over the fixed
+        generators, with the alpha basis and the G2 half belonging to them (sonic_srs_check: relations R0 .. R4 under 128-bit
+        randomizers, the G1 sums as MSMs, the G2 sums and the pairings beside them).  failed_mask has bit i set when Ri fails.
+        seed=None draws the randomizers' seed from the operating system; a 32-byte seed is for reproducible tests only."""
+        if seed is not None and len(seed) != 32:
+            raise ValueError("SRS.check: the seed is 32 bytes")
+        failed = C.c_int(0)
+        _lib.check(_lib.lib().sonic_srs_check(self._h, seed, C.byref(failed)))
+        return failed.value == 0, int(failed.value)
+
+    def update(self, x: int = None, alpha: int = None, seed: bytes = None):
+        """(new_srs, proof): a contribution to the string (sonic_srs_update).  The new handle holds the string of trapdoor
+        (x_old * x, alpha_old * alpha) on the same GPU; this handle is untouched.  proof: 448 bytes for srs_verify_update.
+        x=None / alpha=None: the share is drawn with `secrets` and never returned -- what a real contribution does.  seed: 32 bytes that
+        make the proof's nonces reproducible, for tests."""
+        import secrets
+        if seed is not None and len(seed) != 32:
+            raise ValueError("SRS.update: the seed is 32 bytes")
+        xs = [1 + secrets.randbelow(R_MODULUS - 1) if v is None else v for v in (x, alpha)]
+        for v in xs:
+            if not 0 <= v < 1 << 256:
+                raise ValueError("SRS.update: a share is a non-negative integer below 2^256")
+        h = C.c_void_p()
+        proof = C.create_string_buffer(UPDATE_PROOF_SIZE)
+        _lib.check(_lib.lib().sonic_srs_update(self._h, xs[0].to_bytes(32, "little"), xs[1].to_bytes(32, "little"), seed, C.byref(h), proof))
+        return SRS(h, self.srsD), proof.raw
 
     def for_circuit(self, n: int, Q: int) -> "SRS":
         """a circuit-sized VIEW of this string on the same GPU (sonic_srs_for_circuit): the same d, Fiat-Shamir id, commitments and
