@@ -45,7 +45,7 @@ module Sonic.HIP
   , gNegativeX, gPositiveX, gNegativeAlphaX, gPositiveAlphaX
   , hNegativeX, hPositiveX, hNegativeAlphaX, hPositiveAlphaX, srsPairing
   , saveSRS, loadSRS, srsForCircuit, loadSrsForCircuit
-  , checkSrs, updateSrs, verifySrsUpdate
+  , checkSrs, updateSrs, verifySrsUpdate, msmG2, msmG2Srs
     -- * Sonic.CommitmentScheme
   , commitPoly, openPoly, pcV
     -- * Sonic.Protocol
@@ -119,6 +119,8 @@ foreign import ccall safe   "sonic_srs_check"         c_srs_check        :: Ptr 
 foreign import ccall safe   "sonic_srs_update"        c_srs_update       :: Ptr SrsHandle -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr (Ptr SrsHandle) -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_srs_verify_update" c_srs_verify_update :: Ptr SrsHandle -> Ptr SrsHandle -> Ptr Word8 -> CInt -> Ptr CInt -> IO CInt
 
+foreign import ccall safe   "sonic_msm_g2"            c_msm_g2           :: Ptr Word8 -> Ptr Word8 -> Int64 -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_msm_g2_srs"        c_msm_g2_srs       :: Ptr SrsHandle -> CInt -> Int64 -> Ptr Word8 -> Int64 -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_commit_poly"       c_commit_poly      :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_open_poly"         c_open_poly        :: Ptr SrsHandle -> Ptr Word8 -> Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_pc_v"              c_pc_v             :: Ptr SrsHandle -> Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> IO CInt
@@ -243,6 +245,11 @@ g2FromBytes b
   | BS.all (== 0) b = O
   | otherwise       = A (toE [c 0, c 1]) (toE [c 2, c 3])
   where c i = fqFromBytes (BS.take 48 (BS.drop (48 * i) b))
+
+g2ToBytes :: G2 BLS12381 -> ByteString
+g2ToBytes O       = BS.replicate 192 0
+g2ToBytes (A x y) = BS.concat (map fqToBytes (coeffs x ++ coeffs y))
+  where coeffs e = take 2 (fromE e ++ repeat 0)             -- (a coefficient list may stop at the last non-zero one)
 
 -- | GT: the Fq12 element as its twelve Fq coefficients in tower order, c[i][j][k] at 48 (6 i + 2 j + k)
 --   (Fq12 = Fq6[w]/(w^2 - v), Fq6 = Fq2[v]/(v^3 - (1 + u)), Fq2 = Fq[u]/(u^2 + 1))
@@ -402,6 +409,23 @@ verifySrsUpdate (SRS old) (SRS new') proof
   | otherwise = withForeignPtr old $ \po -> withForeignPtr new' $ \pn -> withBytes proof $ \pp -> alloca $ \ok -> do
       check =<< c_srs_verify_update po pn pp 1 ok
       (/= 0) <$> peek ok
+
+-- | sum_i s_i P_i on the twist (include/sonic_hip.h, sonic_msm_g2): the points only have to be on the twist (O is the neutral element)
+-- and the sum is the literal multiple, whatever subgroup they lie in
+msmG2 :: [(G2 BLS12381, Fr)] -> IO (G2 BLS12381)
+msmG2 terms = libraryReady `seq`
+  withBytes (BS.concat (map (g2ToBytes . fst) terms)) $ \pp -> withFrs (map snd terms) $ \ps ->
+    allocaBytes 192 $ \out -> do
+      check =<< c_msm_g2 pp ps (fromIntegral (length terms)) out
+      g2FromBytes <$> packed out 192
+
+-- | sum_i s_i H[e0 + i] over the G2 half of the string: basis 0 is h^{x^e}, basis 1 h^{alpha x^e} (sonic_msm_g2_srs) -- a commitment in
+-- G2, e.g. to check a counterparty's polynomial against the string
+msmG2Srs :: SRS -> Int -> Int -> [Fr] -> IO (G2 BLS12381)
+msmG2Srs (SRS h) basis e0 scalars = withForeignPtr h $ \p -> withFrs scalars $ \ps ->
+  allocaBytes 192 $ \out -> do
+    check =<< c_msm_g2_srs p (fromIntegral basis) (fromIntegral e0) ps (fromIntegral (length scalars)) out
+    g2FromBytes <$> packed out 192
 
 -- ---------------------------------------------------------------------------------------------------------------------
 -- Sonic.CommitmentScheme

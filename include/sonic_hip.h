@@ -229,6 +229,25 @@ int sonic_msm_g1_srs_dev(const sonic_srs_t* srs, int basis, int64_t e0, const vo
 /* one rank's share of a range-sharded MSM: the un-normalised partial sum */
 int sonic_msm_g1_srs_partial_dev(const sonic_srs_t* srs, int basis, int64_t e0, const void* d_scalars,
                                  int64_t n, uint8_t out_partial[192]);
+/* ---- the same sums over G2 (the twist): a bucket-method MSM of its own (ABI 7 additions) ----
+ * Encodings are those of sonic_srs_get_g2_points: 192 bytes x.c0 || x.c1 || y.c0 || y.c1, little-endian, canonical; the result at
+ * infinity is 192 zero bytes.  n = 0 gives infinity and launches nothing.  Blocking; re-entrant as the G1 forms are.
+ *
+ * sonic_msm_g2: caller-supplied points.  Every point must be canonical and on the twist y^2 = x^3 + 4(u + 1), else
+ * SONIC_ERR_BAD_ENCODING (so is a scalar that is not < r).  An all-zero encoding is accepted as the point at infinity, the neutral
+ * element of the sum (no point of the twist has x = y = 0).  The order-r subgroup is NOT tested -- the twist has a large cofactor and a
+ * subgroup walk per point would cost more than the sum -- and the result is the literal sum_i s_i P_i for any point of the twist, as
+ * sonic_msm_g1's is for any point of the curve: (r - 1) P is r - 1 times P, not -P.
+ *
+ * sonic_msm_g2_srs[_dev]: the sum over exponents e0 .. e0+n-1 of a basis of the handle's G2 half (0: h^{x^e}, 1: h^{alpha x^e}), scalars
+ * on the host or resident in HBM (canonical 32-byte Fr).  A handle made by sonic_srs_new generates the half on first use; one without
+ * a G2 half is SONIC_ERR_INVALID_ARG.  A range outside [-d, d] is SONIC_ERR_SRS_INDEX.  A view holds four G2 elements and serves
+ * n = 1 at one of them; any other range is SONIC_ERR_INVALID_ARG with the range in sonic_last_error, never a wrong point. */
+int sonic_msm_g2(const uint8_t* points /* n x 192 */, const uint8_t* scalars /* n x 32 */, int64_t n, uint8_t out_g2[192]);
+int sonic_msm_g2_srs(const sonic_srs_t* srs, int basis, int64_t e0, const uint8_t* scalars, int64_t n, uint8_t out_g2[192]);
+int sonic_msm_g2_srs_dev(const sonic_srs_t* srs, int basis, int64_t e0, const void* d_scalars, int64_t n, uint8_t out_g2[192]);
+/* the longest run of additions one thread of the G2 bucket accumulation makes (longer buckets are cut into chunks); for tests */
+int sonic_msm_g2_walk_max(void);
 /* the same fold (CommitmentScheme.hs:26-29, 45-48 over an SRS slice, as sonic_msm_g1_srs_dev) in two halves on a lane of its
  * own (stream, bucket workspace, pinned result): submit queues it and returns,
  * collect waits and finishes it (out_g1: 96 canonical bytes, out_partial: 192-byte un-normalised sum; either may be NULL).

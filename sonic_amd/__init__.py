@@ -27,6 +27,7 @@ from .protocol import prove_fs, verify_fs, fs_challenges, fs_circuit_digest, fs_
 from .protocol import proof_from_shares, share_plan, from_x, from_y, biv_add  # noqa: F401,E402
 from .protocol import prove_shared, prove_batch, prove_many, device_count  # noqa: F401,E402
 from .commitment import msm_g1_srs_multi  # noqa: F401,E402
+from .commitment import msm_g2, msm_g2_srs  # noqa: F401,E402
 from .protocol import prove, verify, hsc_prove, hsc_verify, Proof, HscProof, RndOracle, Prover, ProverPipeline, ArithCircuit, SparseCircuit, Assignment, GateWeights  # noqa: F401,E402
 from .protocol import Verifier, verify_batch  # noqa: F401,E402
 from .protocol import fs_circuit_midstate, fs_circuit_digest_resume  # noqa: F401,E402
@@ -36,5 +37,5 @@ from .protocol import CoreProof, prove_core_batch, prove_core_batch_fs, verify_c
 from .protocol import aggregate_core, fs_weights_digest, fs_aggregate_challenges  # noqa: F401,E402
 from .compressed import g1_compress, g1_decompress, g2_compress, g2_decompress, proof_compress, proof_decompress  # noqa: F401,E402
 
-__all__ = ["aggregate_core", "fs_weights_digest", "fs_aggregate_challenges", "CoreProof", "prove_core_batch", "prove_core_batch_fs", "verify_core", "verify_core_fs", "fs_core_challenges", "WitnessBatch", "Verifier", "verify_batch", "prove_batch_fs", "fs_circuit_midstate", "fs_circuit_digest_resume", "g1_compress", "g1_decompress", "g2_compress", "g2_decompress", "proof_compress", "proof_decompress", "SRS", "srs_verify_update", "commit_poly", "open_poly", "pc_v", "msm_g1", "MsmLane", "prove", "verify", "prove_fs", "verify_fs", "fs_challenges", "fs_circuit_digest", "hsc_prove", "hsc_verify", "hsc_prove_poly", "hsc_verify_poly", "Proof", "HscProof", "RndOracle", "Prover", "ProverPipeline",
+__all__ = ["msm_g2", "msm_g2_srs", "aggregate_core", "fs_weights_digest", "fs_aggregate_challenges", "CoreProof", "prove_core_batch", "prove_core_batch_fs", "verify_core", "verify_core_fs", "fs_core_challenges", "WitnessBatch", "Verifier", "verify_batch", "prove_batch_fs", "fs_circuit_midstate", "fs_circuit_digest_resume", "g1_compress", "g1_decompress", "g2_compress", "g2_decompress", "proof_compress", "proof_decompress", "SRS", "srs_verify_update", "commit_poly", "open_poly", "pc_v", "msm_g1", "MsmLane", "prove", "verify", "prove_fs", "verify_fs", "fs_challenges", "fs_circuit_digest", "hsc_prove", "hsc_verify", "hsc_prove_poly", "hsc_verify_poly", "Proof", "HscProof", "RndOracle", "Prover", "ProverPipeline",
            "ArithCircuit", "SparseCircuit", "Assignment", "GateWeights", "SonicError"]

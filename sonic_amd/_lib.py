@@ -201,6 +201,10 @@ def lib() -> C.CDLL:
         "sonic_srs_check": [vp, cp, C.POINTER(i32)],
         "sonic_srs_update": [vp, cp, cp, cp, C.POINTER(vp), cp],
         "sonic_srs_verify_update": [vp, vp, cp, i32, C.POINTER(i32)],
+        "sonic_msm_g2": [vp, vp, i64, vp],
+        "sonic_msm_g2_srs": [vp, i32, i64, vp, i64, vp],
+        "sonic_msm_g2_srs_dev": [vp, i32, i64, vp, i64, vp],
+        "sonic_msm_g2_walk_max": [],
         "sonic_dev_alloc": [C.c_size_t, C.POINTER(vp)],
         "sonic_dev_free": [vp],
         "sonic_dev_upload": [vp, vp, C.c_size_t],
@@ -307,6 +311,7 @@ EXPORTED = [
     "sonic_fs_weights_digest", "sonic_fs_aggregate_challenges", "sonic_prover_aggregate_core", "sonic_verify_core_helped_digest",
     "sonic_verifier_verify_core_batch_helped", "sonic_verifier_verify_core_fs_batch_helped",
     "sonic_srs_check", "sonic_srs_update", "sonic_srs_verify_update",
+    "sonic_msm_g2", "sonic_msm_g2_srs", "sonic_msm_g2_srs_dev", "sonic_msm_g2_walk_max",
 ]
 
 

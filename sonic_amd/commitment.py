@@ -62,6 +62,32 @@ def msm_g1_srs(srs: SRS, basis: int, e0: int, scalars) -> bytes:
     return out.raw
 
 
+def msm_g2(points: np.ndarray, scalars) -> bytes:
+    """sum scalars[i] * points[i] on the twist (sonic_msm_g2): points uint8 [n, 192] in the layout of SRS.g2_points, canonical and on the
+    twist (192 zero bytes: the point at infinity); the order-r subgroup is not tested and the sum is the literal multiple.  scalars: ints
+    or uint8 [n, 32].  Returns the 192 canonical bytes, zeros for infinity."""
+    pts = np.ascontiguousarray(points, np.uint8)
+    sc = fr_array(scalars)
+    if pts.size != 192 * sc.shape[0]:
+        raise ValueError(f"msm_g2: {sc.shape[0]} scalars for {pts.size} bytes of points (192 per point)")
+    out = C.create_string_buffer(192)
+    _lib.check(_lib.lib().sonic_msm_g2(pts.ctypes.data, sc.ctypes.data, sc.shape[0], out))
+    return out.raw
+
+
+def msm_g2_srs(srs: SRS, basis: int, e0: int, scalars) -> bytes:
+    """sum_i scalars[i] * H[e0 + i] over the G2 half of the SRS, basis 0 (h^{x^e}) or 1 (h^{alpha x^e}) (sonic_msm_g2_srs).  scalars as in
+    msm_g2, or a (device pointer, n) pair of canonical 32-byte Fr resident on the SRS's GPU (sonic_msm_g2_srs_dev)."""
+    out = C.create_string_buffer(192)
+    if isinstance(scalars, tuple):
+        ptr, n = scalars
+        _lib.check(_lib.lib().sonic_msm_g2_srs_dev(srs._h, basis, e0, ptr, n, out))
+        return out.raw
+    sc = fr_array(scalars)
+    _lib.check(_lib.lib().sonic_msm_g2_srs(srs._h, basis, e0, sc.ctypes.data, sc.shape[0], out))
+    return out.raw
+
+
 def msm_g1_srs_multi(replicas, basis: int, e0: int, scalars, mode: int = 0, d_slices=None) -> bytes:
     """ONE MSM sum_i s_i B[e0 + i] over several SRS replicas -- one per GPU, all in this process (sonic_msm_g1_srs_multi[_dev]).
     mode 0: by term range (every GPU a whole MSM over its slice, the host adds the partial sums); mode 1: by bucket range (every GPU

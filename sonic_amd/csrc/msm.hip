@@ -126,6 +126,20 @@ MsmPlan msm_plan(long n, bool fold) {
   return p;
 }
 
+// No-table plan with the window width and the scalar width given: W = ceil(bits / c) windows of c bits, one bucket set each (the G2 MSM,
+// whose window rule is msm_g2_host.hpp's)
+MsmPlan msm_plan_windows(long n, int c, int bits, bool fold) {
+  MsmPlan p;
+  p.fold = fold;
+  p.bits = bits;
+  p.c = c;
+  p.W = (bits + c - 1) / c;
+  p.Wb = p.W;
+  p.table_stride = 0;
+  plan_finish(p, n);
+  return p;
+}
+
 // Fixed-base plan over precomputed window tables (tab[w][i] = 2^(c w) P_i): every window feeds ONE shared
 // set of 2^(c-1) buckets, so there is one running-sum reduction instead of W and no Horner tail, and c can
 // grow (fewer windows => fewer point additions) without multiplying the bucket count by W.
@@ -1133,37 +1147,22 @@ __global__ __launch_bounds__(256) void k_endo_split(const Fr* __restrict__ sc, l
   s1[i] = a; s2[i] = b;
 }
 
-void msm_enqueue_batch(hipStream_t st, MsmWorkspace& ws, const MsmPlan& pl, const MsmJob* jobs, int k, bool scalars_mont, G1XYZZ* ext_buckets) {
-  if (k < 1 || k > MSM_MAX_JOBS) throw std::runtime_error("msm_enqueue_batch: 1..MSM_MAX_JOBS jobs");
-  if (ext_buckets && (k != 1 || pl.Wb != 1)) throw std::runtime_error("msm_enqueue_batch: bucket hand-off needs one job over a shared bucket set");
-  if (k > 1 && !msm_can_batch(pl)) throw std::runtime_error("msm_enqueue_batch: plan cannot be batched");
-  MsmJob split_jobs[MSM_MAX_JOBS];
-  bool fold = pl.fold;
-  if (pl.endo) {
-    // every job becomes two device jobs over the same points: the halves s1, s2 of its scalars (endo.hpp); both sums land in the
-    // job's slot (the second at win[MSM_ENDO_SLOT_OFFSET ..]) and the host adds phi(second) to the first
-    if (ext_buckets) { set_error("the bucket hand-off of a bucket-sharded MSM needs the full window tables (this SRS holds endomorphism tables)"); throw HipFail{SONIC_ERR_INVALID_ARG}; }
-    if (2 * k > MSM_MAX_JOBS) {
-      const int h = MSM_MAX_JOBS / 2;
-      for (int j0 = 0; j0 < k; j0 += h) msm_enqueue_batch(st, ws, pl, jobs + j0, k - j0 < h ? k - j0 : h, scalars_mont, nullptr);
-      return;
-    }
-    long n_all = 0;
-    for (int j = 0; j < k; j++) n_all += jobs[j].n;
-    ws.endo_scalars.ensure(sizeof(Fr) * 2 * (size_t)(n_all > 0 ? n_all : 1));
-    Fr* halves = ws.endo_scalars.as<Fr>();
-    for (int j = 0; j < k; j++) {
-      Fr* s1 = halves; Fr* s2 = halves + jobs[j].n;
-      halves += 2 * jobs[j].n;
-      if (jobs[j].n > 0) LAUNCH(k_endo_split, ceil_div(jobs[j].n, 256), 256, 0, st, jobs[j].scalars, jobs[j].n, (int)scalars_mont, s1, s2);
-      split_jobs[2 * j] = MsmJob{jobs[j].points, s1, jobs[j].n, jobs[j].slot, jobs[j].table_stride};
-      split_jobs[2 * j + 1] = MsmJob{jobs[j].points, s2, jobs[j].n, jobs[j].slot, jobs[j].table_stride};
-    }
-    jobs = split_jobs;
-    k = 2 * k;
-    scalars_mont = false;
-    fold = false;             // the halves are non-negative and below 2^128: nothing to fold, no carry out of the 130 bits
-  }
+// exclusive scan of m words, in -> out; tmp holds scan_u32_tiles(m) + 1 words and the total is left in the last of them
+int scan_u32_tiles(size_t m) { return ceil_div((long)m + 1, 2048); }
+void scan_u32_enqueue(hipStream_t st, const uint32_t* in, size_t m, uint32_t* out, uint32_t* tmp) {
+  const int ht = scan_u32_tiles(m);
+  // (a single-launch chained scan with decoupled look-back was measured in round 3 and is not kept: 0.080 ms against 0.052 ms for
+  // these three launches on an empty chip, and no difference inside prove())
+  LAUNCH(k_scan_tile_sums, ht, 256, 0, st, in, m, tmp);
+  LAUNCH(k_scan_top, 1, 256, 0, st, tmp, ht, tmp + ht);
+  LAUNCH(k_scan_apply, ht, 256, 0, st, in, m, (const uint32_t*)tmp, out);
+}
+
+// The first phase of every bucket-method chain, G1 (msm_enqueue_batch) and G2 (msm_g2.hip) alike: the signed digits of the jobs' scalars
+// and their two-pass partition sort.  Fills `batch`; leaves ws.off (first entry of every (job, window, bucket), and the total at the end),
+// ws.entries (term index | sign << 31, with the window over tables) and the size classes of the buckets in the chain's header.  Reads
+// scalars only: a job's points may be null.
+static void sort_phase_enqueue(hipStream_t st, MsmWorkspace& ws, const MsmPlan& pl, const MsmJob* jobs, int k, bool scalars_mont, bool fold, MsmBatchDev& batch) {
   for (int j = 0; j < k; j++) {
     const bool tables = pl.table_stride != 0;
     if (jobs[j].n >= (tables ? MSM_TABLE_MAX_TERMS : MSM_MAX_TERMS) || (tables && pl.W > MSM_TABLE_MAX_WINDOWS) || pl.W > MSM_MAX_WINDOWS) {
@@ -1172,7 +1171,6 @@ void msm_enqueue_batch(hipStream_t st, MsmWorkspace& ws, const MsmPlan& pl, cons
       throw HipFail{SONIC_ERR_INVALID_ARG};
     }
   }
-  MsmBatchDev batch;
   memset(&batch, 0, sizeof batch);
   batch.k = k;
   batch.bits = pl.bits;
@@ -1189,13 +1187,10 @@ void msm_enqueue_batch(hipStream_t st, MsmWorkspace& ws, const MsmPlan& pl, cons
   }
   if (batch.tile0[k] == 0) for (int j = 1; j <= k; j++) batch.tile0[j] = 1;      // nothing to do: one idle workgroup keeps the chain uniform
   ws.reserve(n_total > 0 ? n_total : 1, pl, k);
-  G1XYZZ* const buckets = ext_buckets ? ext_buckets : ws.buckets.as<G1XYZZ>();
   const uint32_t jobstride = (uint32_t)pl.Wb * pl.NB;              // buckets per job
-  const size_t M = (size_t)k * jobstride;
   const int keystride = pl.Wb == 1 ? 0 : pl.NB;
   uint32_t* off = ws.off.as<uint32_t>();
   HeavyMeta* hm = ws.heavy_meta.as<HeavyMeta>();
-  HeavyRec* hrecs = reinterpret_cast<HeavyRec*>(hm + 1);
   HIP_OK(hipMemsetAsync(hm, 0, sizeof(HeavyMeta), st));
   uint32_t* tiles = ws.scan_tmp.as<uint32_t>();
   {
@@ -1204,15 +1199,10 @@ void msm_enqueue_batch(hipStream_t st, MsmWorkspace& ws, const MsmPlan& pl, cons
     const size_t hn = (size_t)P * pblk;
     uint32_t* hist = ws.count.as<uint32_t>();
     uint32_t* hbase = hist + hn + 1;
-    const int ht = ceil_div((long)hn + 1, 2048);
-    uint32_t* total = tiles + ht;
+    uint32_t* total = tiles + scan_u32_tiles(hn);
     const uint32_t pgrid = pblk < PASS1_GRID ? pblk : PASS1_GRID;
     LAUNCH(k_part_hist, pgrid, 256, P * 4, st, batch, pl.c, pl.W, keystride, (int)scalars_mont, (int)fold, P, hist);
-    // (a single-launch chained scan with decoupled look-back was measured in round 3 and is not kept: 0.080 ms against 0.052 ms for
-    // these three launches on an empty chip, and no difference inside prove())
-    LAUNCH(k_scan_tile_sums, ht, 256, 0, st, (const uint32_t*)hist, hn, tiles);
-    LAUNCH(k_scan_top, 1, 256, 0, st, tiles, ht, total);
-    LAUNCH(k_scan_apply, ht, 256, 0, st, (const uint32_t*)hist, hn, (const uint32_t*)tiles, hbase);
+    scan_u32_enqueue(st, hist, hn, hbase, tiles);
     // the LDS-staged passes need more dynamic LDS than the 64-KB default: asked for once per DEVICE (a function attribute belongs to the
     // device that is current when it is set; two threads racing here set the same values); a runtime that refuses keeps the direct
     // kernels instead of failing the MSM
@@ -1245,6 +1235,47 @@ void msm_enqueue_batch(hipStream_t st, MsmWorkspace& ws, const MsmPlan& pl, cons
     LAUNCH(k_part_sort, nparts < PART_SORT_GRID ? nparts : PART_SORT_GRID, PART_SORT_THREADS, (size_t)stage_cap * 4, st, batch, (const uint2*)ws.digits.as<uint2>(),
            (const uint32_t*)hbase, (const uint32_t*)total, hn, P, jobstride, off, ws.entries.as<uint32_t>(), hm->class_hist, stage_cap);
   }
+}
+
+void msm_enqueue_batch(hipStream_t st, MsmWorkspace& ws, const MsmPlan& pl, const MsmJob* jobs, int k, bool scalars_mont, G1XYZZ* ext_buckets) {
+  if (k < 1 || k > MSM_MAX_JOBS) throw std::runtime_error("msm_enqueue_batch: 1..MSM_MAX_JOBS jobs");
+  if (ext_buckets && (k != 1 || pl.Wb != 1)) throw std::runtime_error("msm_enqueue_batch: bucket hand-off needs one job over a shared bucket set");
+  if (k > 1 && !msm_can_batch(pl)) throw std::runtime_error("msm_enqueue_batch: plan cannot be batched");
+  MsmJob split_jobs[MSM_MAX_JOBS];
+  bool fold = pl.fold;
+  if (pl.endo) {
+    // every job becomes two device jobs over the same points: the halves s1, s2 of its scalars (endo.hpp); both sums land in the
+    // job's slot (the second at win[MSM_ENDO_SLOT_OFFSET ..]) and the host adds phi(second) to the first
+    if (ext_buckets) { set_error("the bucket hand-off of a bucket-sharded MSM needs the full window tables (this SRS holds endomorphism tables)"); throw HipFail{SONIC_ERR_INVALID_ARG}; }
+    if (2 * k > MSM_MAX_JOBS) {
+      const int h = MSM_MAX_JOBS / 2;
+      for (int j0 = 0; j0 < k; j0 += h) msm_enqueue_batch(st, ws, pl, jobs + j0, k - j0 < h ? k - j0 : h, scalars_mont, nullptr);
+      return;
+    }
+    long n_all = 0;
+    for (int j = 0; j < k; j++) n_all += jobs[j].n;
+    ws.endo_scalars.ensure(sizeof(Fr) * 2 * (size_t)(n_all > 0 ? n_all : 1));
+    Fr* halves = ws.endo_scalars.as<Fr>();
+    for (int j = 0; j < k; j++) {
+      Fr* s1 = halves; Fr* s2 = halves + jobs[j].n;
+      halves += 2 * jobs[j].n;
+      if (jobs[j].n > 0) LAUNCH(k_endo_split, ceil_div(jobs[j].n, 256), 256, 0, st, jobs[j].scalars, jobs[j].n, (int)scalars_mont, s1, s2);
+      split_jobs[2 * j] = MsmJob{jobs[j].points, s1, jobs[j].n, jobs[j].slot, jobs[j].table_stride};
+      split_jobs[2 * j + 1] = MsmJob{jobs[j].points, s2, jobs[j].n, jobs[j].slot, jobs[j].table_stride};
+    }
+    jobs = split_jobs;
+    k = 2 * k;
+    scalars_mont = false;
+    fold = false;             // the halves are non-negative and below 2^128: nothing to fold, no carry out of the 130 bits
+  }
+  MsmBatchDev batch;
+  sort_phase_enqueue(st, ws, pl, jobs, k, scalars_mont, fold, batch);
+  G1XYZZ* const buckets = ext_buckets ? ext_buckets : ws.buckets.as<G1XYZZ>();
+  const uint32_t jobstride = (uint32_t)pl.Wb * pl.NB;              // buckets per job
+  const size_t M = (size_t)k * jobstride;
+  const uint32_t* off = ws.off.as<uint32_t>();
+  HeavyMeta* hm = ws.heavy_meta.as<HeavyMeta>();
+  HeavyRec* hrecs = reinterpret_cast<HeavyRec*>(hm + 1);
   LAUNCH(k_border_place, ceil_div((long)M, 2048), 256, 0, st, (const uint32_t*)off, (uint32_t)M, (const uint32_t*)hm->class_hist, hm->class_cursor,
          ws.order.as<uint32_t>());
   const int accum_block = (pl.accum_block == 64 || pl.accum_block == 128) ? pl.accum_block : 256;
@@ -1341,6 +1372,13 @@ void msm_enqueue(hipStream_t st, MsmWorkspace& ws, const MsmPlan& pl, PointArray
                  long n, bool scalars_mont, MsmSlot* d_slot) {
   MsmJob job{d_points, d_scalars, n, d_slot};
   msm_enqueue_batch(st, ws, pl, &job, 1, scalars_mont);
+}
+
+void msm_sort_enqueue(hipStream_t st, MsmWorkspace& ws, const MsmPlan& pl, const Fr* d_scalars, long n, bool scalars_mont) {
+  if (pl.Wb != pl.W || pl.table_stride != 0) throw std::runtime_error("msm_sort_enqueue: a no-table plan, one bucket set per window");
+  MsmJob job{PointArray{nullptr, 0}, d_scalars, n, nullptr};
+  MsmBatchDev batch;
+  sort_phase_enqueue(st, ws, pl, &job, 1, scalars_mont, pl.fold, batch);
 }
 
 }  // namespace sonic

@@ -50,6 +50,8 @@ struct MsmPlan {
 };
 MsmPlan msm_plan(long n, bool fold = true);
 MsmPlan msm_plan_tables(long n, int c, int W, long table_stride, bool endo = false);
+// no tables, W = ceil(bits / c) windows of c bits with a bucket set each; `bits` counts the room for the recoding's carry (scalars < 2^(bits-1))
+MsmPlan msm_plan_windows(long n, int c, int bits, bool fold);
 // Trade latency for work in the bucket running sums: K buckets per segment.  A standalone MSM wants the shortest
 // dependent chain (K = 8); inside prove() the reduction of one MSM hides under the accumulation of others, so fewer,
 // longer segments cost less MAD issue overall: 2 + 2 / K additions per bucket over shared bucket sets, whose segments hand their runs
@@ -64,6 +66,9 @@ constexpr long MSM_MAX_TERMS = 1L << 31;
 
 struct MsmWorkspace {
   DevBuf count, off, digits, entries, buckets, segres, scan_tmp, order, heavy_meta, heavy_partial, endo_scalars;
+  // the G2 MSM's own stages behind the shared sort (msm_g2.hip): chunk counts and their scan, partial sums, buckets, segment results,
+  // block totals and window sums
+  DevBuf g2_nchunk, g2_chunk_off, g2_scan_tmp, g2_partial, g2_buckets, g2_segres, g2_sum_tmp, g2_wsum;
   // n = total terms over the k jobs of a batch
   void reserve(long n, const MsmPlan& pl, int k = 1);
 };
@@ -90,6 +95,15 @@ void msm_enqueue_batch(hipStream_t st, MsmWorkspace& ws, const MsmPlan& pl, cons
 // reduces them with the range's weights into d_slot (one window sum).  len and base are multiples of MSM_SLICE_QUANTUM.
 constexpr long MSM_SLICE_QUANTUM = 16384;     // = 2048 segments: whole 256-segment groups and wave-uniform segment bits
 void msm_reduce_slices_enqueue(hipStream_t st, MsmWorkspace& ws, const G1XYZZ* d_slices, int k, long len, long base, int c, MsmSlot* d_slot);
+
+// The first phase of a chain alone, for one job under a no-table plan (Wb = W): signed digits and the two-pass sort.  Leaves in ws.off the
+// first entry of bucket (w, i) at [w * NB + i - 1] (digit magnitude i = 1 .. NB) with the number of entries at [W * NB], and in ws.entries
+// the entries, term index | sign << 31.  Reads scalars only.  msm_enqueue_batch runs the same function; the G2 MSM (msm_g2.hip) walks
+// its own points over what this leaves.
+void msm_sort_enqueue(hipStream_t st, MsmWorkspace& ws, const MsmPlan& pl, const Fr* d_scalars, long n, bool scalars_mont);
+// exclusive scan of m words (in != out); tmp: scan_u32_tiles(m) + 1 words, the total in the last
+int scan_u32_tiles(size_t m);
+void scan_u32_enqueue(hipStream_t st, const uint32_t* in, size_t m, uint32_t* out, uint32_t* tmp);
 
 // canonical 96-byte encodings on the host: g1_host.hpp
 int msm_window_override();

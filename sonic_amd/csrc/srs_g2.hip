@@ -166,11 +166,14 @@ __global__ __launch_bounds__(256, 1) void k_g2_scale_each(const G2Affine* __rest
 }
 
 // the sum of n Jacobian points as a block tree: every thread adds the points of its stride, the 64 threads of a block fold their sums
-// in LDS (64 x 288 B), and the block's total goes to tot[blockIdx.x] for the host to add
+// in LDS (64 x 288 B), and the block's total goes to tot[blockIdx.x] for the host to add.  blockIdx.y counts independent ranges of n points,
+// range_stride apart (the segment results of the windows of a G2 MSM, msm_g2.hip): range y's totals follow those of range y - 1
 constexpr int G2_SUM_BLOCK = 64, G2_SUM_MAX_BLOCKS = 256;
-__global__ __launch_bounds__(G2_SUM_BLOCK, 1) void k_g2_sum(const G2Jac* __restrict__ in, long n, G2Jac* __restrict__ tot) {
+__global__ __launch_bounds__(G2_SUM_BLOCK, 1) void k_g2_sum(const G2Jac* __restrict__ in, long n, G2Jac* __restrict__ tot, long range_stride) {
   __shared__ G2Jac sh[G2_SUM_BLOCK];
   const int t = threadIdx.x;
+  in += (size_t)blockIdx.y * range_stride;
+  tot += (size_t)blockIdx.y * gridDim.x;
   G2Jac acc = G2Jac::inf();
   for (long i = (long)blockIdx.x * G2_SUM_BLOCK + t; i < n; i += (long)gridDim.x * G2_SUM_BLOCK) acc = g2_add(acc, in[i]);
   sh[t] = acc;
@@ -187,6 +190,15 @@ __global__ __launch_bounds__(G2_SUM_BLOCK, 1) void k_g2_sum(const G2Jac* __restr
   }
 }
 
+// `ranges` sums of n Jacobian points each, range_stride apart, into tot[0 .. ranges) (canonical limbs): one launch of a block per range
+// up to G2_SUM_BLOCK points, else a launch of up to G2_SUM_BLOCK blocks per range into `tmp` (ranges x G2_SUM_BLOCK points) and one over those
+void g2_sum_ranges_enqueue(hipStream_t st, const G2Jac* in, long n, int ranges, long range_stride, G2Jac* tmp, G2Jac* tot) {
+  const int blocks = ceil_div(n, G2_SUM_BLOCK) < G2_SUM_BLOCK ? ceil_div(n, G2_SUM_BLOCK) : G2_SUM_BLOCK;
+  if (blocks <= 1) { LAUNCH(k_g2_sum, dim3(1, ranges), G2_SUM_BLOCK, 0, st, in, n, tot, range_stride); return; }
+  LAUNCH(k_g2_sum, dim3(blocks, ranges), G2_SUM_BLOCK, 0, st, in, n, tmp, range_stride);
+  LAUNCH(k_g2_sum, dim3(1, ranges), G2_SUM_BLOCK, 0, st, (const G2Jac*)tmp, (long)blocks, tot, (long)blocks);
+}
+
 // sum_i rho[i] * pts[i] over n points (rho: 128-bit scalars in 32-byte elements) as the 192 canonical bytes sonic_srs_get_g2_points writes;
 // waits for the stream
 void g2_weighted_sum(hipStream_t st, const G2Affine* pts, const Fr* d_rho, long n, uint8_t out192[192]) {
@@ -201,7 +213,7 @@ void g2_weighted_sum(hipStream_t st, const G2Affine* pts, const Fr* d_rho, long 
     const long m = n - base < SLAB ? n - base : SLAB;
     const int blocks = ceil_div(m, G2_SUM_BLOCK) < G2_SUM_MAX_BLOCKS ? ceil_div(m, G2_SUM_BLOCK) : G2_SUM_MAX_BLOCKS;
     LAUNCH(k_g2_scale_each, ceil_div(m, 256), 256, 0, st, pts + base, 0L, m, none, none, none, 0, d_rho + base, xs.as<G2Jac>());
-    LAUNCH(k_g2_sum, blocks, G2_SUM_BLOCK, 0, st, (const G2Jac*)xs.as<G2Jac>(), m, tot.as<G2Jac>() + nt);
+    LAUNCH(k_g2_sum, blocks, G2_SUM_BLOCK, 0, st, (const G2Jac*)xs.as<G2Jac>(), m, tot.as<G2Jac>() + nt, 0L);
     nt += blocks;
   }
   h.resize((size_t)nt);

@@ -4,8 +4,10 @@
 // check are the library's MSMs over the handle; the pairings stay on the host.
 #include <string.h>
 #include <memory>
+#include <stdlib.h>
 #include "srs_handle.hpp"
 #include "g2.hpp"
+#include "msm_g2.hpp"
 #include "srs_update.hpp"
 
 using namespace sonic;
@@ -73,8 +75,17 @@ int sonic_srs_check(const sonic_srs_t* srs, const uint8_t seed[32], int* failed)
     else if (!srs_update::os_random(sd, 32)) { set_error("sonic_srs_check: the operating system gave no random bytes for the seed"); return SONIC_ERR_HIP; }
     rho.alloc(sizeof(Fr) * (size_t)n);
     srs_check_rho_enqueue(st, sd, (long)n, rho.as<Fr>());
-    g2_weighted_sum(st, srs->h.as<G2Affine>(), rho.as<Fr>(), (long)n, Bb);          // B = sum_e rho_e H0[e]
-    g2_weighted_sum(st, srs->ha.as<G2Affine>(), rho.as<Fr>(), (long)n, Cb);         // C = sum_e rho_e H1[e]
+    // B = sum_e rho_e H0[e], C = sum_e rho_e H1[e]: the G2 MSM over 129 bits (128-bit randomizers and the recoding's carry), or with
+    // SONIC_G2_MSM=0, read per call, the walk over all 128 bits of every randomizer (for comparing the two in one process)
+    const char* knob = getenv("SONIC_G2_MSM");
+    if (knob && atoi(knob) == 0) {
+      g2_weighted_sum(st, srs->h.as<G2Affine>(), rho.as<Fr>(), (long)n, Bb);
+      g2_weighted_sum(st, srs->ha.as<G2Affine>(), rho.as<Fr>(), (long)n, Cb);
+    } else {
+      CallLease lease;          // (for its workspace: the chains run on the stream the randomizers were queued on)
+      g2_msm_blocking(st, lease.ws(), srs->h.as<G2Affine>(), rho.as<Fr>(), (long)n, 129, true, Bb);
+      g2_msm_blocking(st, lease.ws(), srs->ha.as<G2Affine>(), rho.as<Fr>(), (long)n, 129, true, Cb);
+    }
   }
   // R0: the string stands over the fixed generators
   uint8_t b0[96], gb[96], h0[192], hb[192];
