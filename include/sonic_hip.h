@@ -299,7 +299,9 @@ int sonic_poly_mul_fr_dev(const void* d_a, int64_t na, const void* d_b, int64_t 
 /* bytes between consecutive points of an SRS basis / window table in HBM (128: one HBM line per 96-byte point); what a bucket walk
  * reads per (term, window) by design */
 int sonic_srs_point_bytes(void);
-/* MSM tuning knob for tests: window bits (0 = automatic) */
+/* MSM tuning knob for tests: window bits c = 4 .. 16 (0 = automatic).  Process-wide, not thread-safe.  Honoured
+ * by the G1 MSMs (which then run without the window tables), by the G2 MSM (sonic_msm_g2, sonic_msm_g2_srs, sonic_msm_g2_srs_dev: every
+ * slab at that c instead of floor(log2 n) - 4) and by the G2 sums of sonic_srs_check, whose 129-bit plan then has ceil(129 / c) windows */
 int sonic_msm_set_window(int c);
 /* what an n-term MSM over this SRS will run as: window bits, number of windows, and bucket sets
  * (1 = all windows share one bucket set over the precomputed window tables, else one set per window) */

@@ -12,6 +12,9 @@ Sizes, and what each crosses (window width c = floor(log2 n) - 4, at least 4; NB
   n = 16401           d = 8200, the whole basis: c = 10, 512 buckets per window, 26 windows: more buckets than one workgroup
   n = 3 WALK_MAX + 5  equal scalars: one bucket per window with n entries, cut into four chunks
   n = 2^19 + 17       one term more than a slab and then some: two chains, the second at c = 4
+Every c = 4 .. 16 by override, degenerate strings (x = 1, r - 1, roots of unity) through every stage with the exceptional branch each
+case reaches asserted from an integer mirror, the check over those strings and G1 / G2 chains in turn on one workspace:
+tests/test_gpu_msm_g2_paths.py.
 """
 import ctypes as C
 import random

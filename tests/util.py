@@ -179,3 +179,150 @@ def valued_scalars(rng: np.random.Generator, pyr: random.Random, n: int, pairs: 
     idx = rng.integers(0, len(vals), size=n)
     table = fr_bytes(vals)
     return table[idx], vals, idx
+
+
+# ---- the G2 MSM replayed on integers (tests/test_msm_g2_mirror.py, tests/test_gpu_msm_g2_paths.py) -------------------------------------
+G2_MIRROR_STAGES = ("accum", "combine", "seg_run", "seg_acc", "seg_mul", "seg_join", "range", "range_tree", "range2", "range2_tree", "fold")
+G2_SUM_BLOCK = 64                          # srs_g2.hip: threads of a k_g2_sum block, and the most blocks per range of g2_sum_ranges_enqueue
+
+
+class G2Mirror:
+    """what g2_msm_mirror returns: the total, per stage a Counter of addition kinds, whether the accumulate / combine counts hold for
+    every order of a bucket's entries, and the window sums"""
+
+    def __init__(self, total, events, order_free, windows, plan):
+        self.total, self.events, self.order_free, self.windows, self.plan = total, events, order_free, windows, plan
+
+    def __getitem__(self, stage):
+        return self.events[stage]
+
+
+def g2_msm_mirror(ks, scalars, c: int, bits: int, fold: bool, walk_max: int, mod=R) -> G2Mirror:
+    """One chain of g2_msm_blocking (sonic_amd/csrc/msm_g2.hip) over points that are known multiples ks[i] of one point, replayed on
+    integers: modulo `mod` (r, for multiples of h), or over plain integers with mod = None (a point whose order is not known to divide
+    anything: equal integers are equal points, and the replay claims no more).  ks[i] = 0 is the point at infinity.
+
+    Digits: util.digit_stream with widths [c] * W, W = ceil(bits / c); digit d of window w goes to bucket d - 1 of that window's NB =
+    2^(c-1) (msm.hip, key = w NB + d - 1), zero digits make no entry.  Buckets are cut into chunks of walk_max entries
+    (k_g2_bucket_accum, mixed additions from infinity), a bucket's partial sums are added from infinity (k_g2_bucket_combine), segments of
+    K = min(NB, 8) buckets run `run += B_j; acc += run` from the top and add (s K) run by double-and-add over c - 1 bits
+    (k_g2_bucket_segments), the nseg segment results of a window are summed by k_g2_sum (thread-stride sums, a 64-leaf LDS tree, and a
+    second launch over the block totals once nseg > 64: g2_sum_ranges_enqueue), and the host folds the window sums by Horner.
+
+    Every addition p + q is counted once under its stage as one of
+      both_inf, p_inf, q_inf   an operand at infinity (the branch the code returns from first)
+      dbl                      equal operands: the doubling branch
+      neg                      opposite operands: the result is infinity
+      add                      the generic formula
+    and the doublings of seg_mul and fold as dbl_of_inf or dbl_op.
+
+    The sort of msm.hip does not keep the order of a bucket's entries (its placement is by atomic counters), so the accum and combine
+    counts are those of the entries in index order and hold for the device only where order_free is true: every bucket has at most two
+    entries or holds one value throughout.  The counts from seg_run on depend on the buckets' sums alone."""
+    from collections import Counter
+    W = -(-bits // c)
+    NB = 1 << (c - 1)
+    K = min(NB, 8)
+    nseg = NB // K
+    widths = [c] * W
+    assert len(ks) == len(scalars) and 0 < len(ks) <= 1 << 19, "one slab"
+    norm = (lambda v: v % mod) if mod else (lambda v: v)
+    ev = {st: Counter() for st in G2_MIRROR_STAGES}
+
+    def add(st, p, q):
+        if q == 0 or p == 0:
+            ev[st]["both_inf" if p == 0 and q == 0 else ("p_inf" if p == 0 else "q_inf")] += 1
+            return p if q == 0 else q
+        if p == q:
+            ev[st]["dbl"] += 1
+        elif norm(p + q) == 0:
+            ev[st]["neg"] += 1
+        else:
+            ev[st]["add"] += 1
+        return norm(p + q)
+
+    def dbl(st, p):
+        ev[st]["dbl_op" if p else "dbl_of_inf"] += 1
+        return norm(2 * p)
+
+    entries = {}
+    for k, s in zip(ks, scalars):
+        digs, _, (carry, rest) = digit_stream(s, widths, fold)
+        assert carry == 0 and rest == 0, "the recoding stays inside the W windows"
+        for w, (dg, sg) in enumerate(digs):
+            if dg:
+                entries.setdefault((w, dg - 1), []).append(norm(-k if sg else k))
+    order_free = all(len(v) <= 2 or len(set(v)) == 1 for v in entries.values())
+
+    buckets = {}
+    for key, vals in entries.items():
+        partial = []
+        for at in range(0, len(vals), walk_max):
+            acc = 0
+            for v in vals[at:at + walk_max]:
+                acc = add("accum", acc, v)
+            partial.append(acc)
+        acc = 0
+        for p in partial:
+            acc = add("combine", acc, p)
+        buckets[key] = acc
+
+    live = {(w, b // K) for (w, b) in buckets}
+    windows = []
+    for w in range(W):
+        seg = [0] * nseg
+        idle = 0
+        for s in range(nseg):
+            if (w, s) not in live:
+                idle += 1
+                continue
+            run = acc = 0
+            for j in range(K - 1, -1, -1):
+                run = add("seg_run", run, buckets.get((w, s * K + j), 0))
+                acc = add("seg_acc", acc, run)
+            m = s * K
+            if m:
+                up = 0
+                for bit in range(c - 2, -1, -1):
+                    up = dbl("seg_mul", up)
+                    if m >> bit & 1:
+                        up = add("seg_mul", up, run)
+                acc = add("seg_join", acc, up)
+            seg[s] = acc
+        # segments without an entry: every operand at infinity
+        ev["seg_run"]["both_inf"] += idle * K
+        ev["seg_acc"]["both_inf"] += idle * K
+        for s in range(nseg):
+            if s and (w, s) not in live:
+                ev["seg_mul"]["dbl_of_inf"] += c - 1
+                ev["seg_mul"]["both_inf"] += bin(s * K).count("1")
+                ev["seg_join"]["both_inf"] += 1
+
+        def block_sum(st, vals, b, nblocks):
+            sh = []
+            for t in range(G2_SUM_BLOCK):
+                acc = 0
+                for i in range(b * G2_SUM_BLOCK + t, len(vals), nblocks * G2_SUM_BLOCK):
+                    acc = add(st, acc, vals[i])
+                sh.append(acc)
+            h = G2_SUM_BLOCK // 2
+            while h:
+                for t in range(h):
+                    sh[t] = add(st + "_tree", sh[t], sh[t + h])
+                h //= 2
+            return sh[0]
+
+        blocks = min(-(-nseg // G2_SUM_BLOCK), G2_SUM_BLOCK)
+        if blocks <= 1:
+            windows.append(block_sum("range", seg, 0, 1))
+        else:
+            tmp = [block_sum("range", seg, b, blocks) for b in range(blocks)]
+            windows.append(block_sum("range2", tmp, 0, 1))
+
+    acc = 0
+    for w in range(W - 1, -1, -1):
+        if w + 1 < W:
+            for _ in range(c):
+                acc = dbl("fold", acc)
+        acc = add("fold", acc, windows[w])
+    return G2Mirror(acc, ev, order_free, windows, dict(c=c, W=W, NB=NB, K=K, nseg=nseg, blocks=blocks))
