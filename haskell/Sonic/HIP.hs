@@ -46,6 +46,7 @@ module Sonic.HIP
   , hNegativeX, hPositiveX, hNegativeAlphaX, hPositiveAlphaX, srsPairing
   , saveSRS, loadSRS, srsForCircuit, loadSrsForCircuit
   , checkSrs, updateSrs, verifySrsUpdate, msmG2, msmG2Srs
+  , g1SubgroupCheck, g2SubgroupCheck
     -- * Sonic.CommitmentScheme
   , commitPoly, openPoly, pcV
     -- * Sonic.Protocol
@@ -121,6 +122,9 @@ foreign import ccall safe   "sonic_srs_verify_update" c_srs_verify_update :: Ptr
 
 foreign import ccall safe   "sonic_msm_g2"            c_msm_g2           :: Ptr Word8 -> Ptr Word8 -> Int64 -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_msm_g2_srs"        c_msm_g2_srs       :: Ptr SrsHandle -> CInt -> Int64 -> Ptr Word8 -> Int64 -> Ptr Word8 -> IO CInt
+-- subgroup membership on its own (ABI 7); method 0: the endomorphism test of the loaders, 1: r P = O by double-and-add
+foreign import ccall safe   "sonic_g1_subgroup_check" c_g1_subgroup_check :: Ptr Word8 -> Int64 -> CInt -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_g2_subgroup_check" c_g2_subgroup_check :: Ptr Word8 -> Int64 -> CInt -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_commit_poly"       c_commit_poly      :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_open_poly"         c_open_poly        :: Ptr SrsHandle -> Ptr Word8 -> Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_pc_v"              c_pc_v             :: Ptr SrsHandle -> Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> IO CInt
@@ -426,6 +430,21 @@ msmG2Srs (SRS h) basis e0 scalars = withForeignPtr h $ \p -> withFrs scalars $ \
   allocaBytes 192 $ \out -> do
     check =<< c_msm_g2_srs p (fromIntegral basis) (fromIntegral e0) ps (fromIntegral (length scalars)) out
     g2FromBytes <$> packed out 192
+
+-- | whether each point lies in the order-r subgroup (include/sonic_hip.h, "Subgroup membership": phi(P) = lambda P on the GPU, one thread
+-- per point; O is a member).  Values of the curve's type are canonical and on the curve, so False means: outside the subgroup.
+g1SubgroupCheck :: [G1 BLS12381] -> IO [Bool]
+g1SubgroupCheck pts = libraryReady `seq`
+  withBytes (BS.concat (map g1ToBytes pts)) $ \pp -> allocaBytes (max 1 (length pts)) $ \fl -> do
+    check =<< c_g1_subgroup_check pp (fromIntegral (length pts)) 0 fl
+    map (== 0) . BS.unpack <$> packed fl (length pts)
+
+-- | the same over the twist (psi(P) = z P): run it over the operands of msmG2 when they come from outside
+g2SubgroupCheck :: [G2 BLS12381] -> IO [Bool]
+g2SubgroupCheck pts = libraryReady `seq`
+  withBytes (BS.concat (map g2ToBytes pts)) $ \pp -> allocaBytes (max 1 (length pts)) $ \fl -> do
+    check =<< c_g2_subgroup_check pp (fromIntegral (length pts)) 0 fl
+    map (== 0) . BS.unpack <$> packed fl (length pts)
 
 -- ---------------------------------------------------------------------------------------------------------------------
 -- Sonic.CommitmentScheme

@@ -107,7 +107,9 @@ typedef struct sonic_verifier sonic_verifier_t;
  * sonic_verifier_verify_core_batch, sonic_verifier_verify_core_fs_batch, sonic_verify_core_batch_digest, sonic_core_proof_compress,
  * sonic_core_proof_decompress; still 7, additions only: helped verification -- sonic_fs_weights_digest, sonic_fs_aggregate_challenges,
  * sonic_prover_aggregate_core, sonic_verifier_verify_core_batch_helped, sonic_verifier_verify_core_fs_batch_helped,
- * sonic_verify_core_helped_digest; still 7, additions only: the updatable SRS -- sonic_srs_check, sonic_srs_update, sonic_srs_verify_update */
+ * sonic_verify_core_helped_digest; still 7, additions only: the updatable SRS -- sonic_srs_check, sonic_srs_update, sonic_srs_verify_update;
+ * still 7, additions only: the G2 sums -- sonic_msm_g2, sonic_msm_g2_srs[_dev], sonic_msm_g2_walk_max; subgroup membership --
+ * sonic_g1_subgroup_check, sonic_g2_subgroup_check */
 int sonic_abi_version(void);
 int sonic_init(int device_ordinal);                 /* choose the DEFAULT GPU (first call wins) and make it the thread's HIP device; idempotent */
 int sonic_device_count(int* out);                   /* GPUs this process can see; SONIC_ERR_NO_DEVICE (and 0) without one */
@@ -237,7 +239,8 @@ int sonic_msm_g1_srs_partial_dev(const sonic_srs_t* srs, int basis, int64_t e0, 
  * SONIC_ERR_BAD_ENCODING (so is a scalar that is not < r).  An all-zero encoding is accepted as the point at infinity, the neutral
  * element of the sum (no point of the twist has x = y = 0).  The order-r subgroup is NOT tested -- the twist has a large cofactor and a
  * subgroup walk per point would cost more than the sum -- and the result is the literal sum_i s_i P_i for any point of the twist, as
- * sonic_msm_g1's is for any point of the curve: (r - 1) P is r - 1 times P, not -P.
+ * sonic_msm_g1's is for any point of the curve: (r - 1) P is r - 1 times P, not -P.  A caller who needs the test runs
+ * sonic_g2_subgroup_check over the points first.
  *
  * sonic_msm_g2_srs[_dev]: the sum over exponents e0 .. e0+n-1 of a basis of the handle's G2 half (0: h^{x^e}, 1: h^{alpha x^e}), scalars
  * on the host or resident in HBM (canonical 32-byte Fr).  A handle made by sonic_srs_new generates the half on first use; one without
@@ -514,6 +517,27 @@ int sonic_verifier_eval_s(sonic_verifier_t* v, int64_t K, const uint8_t* uv, uin
 int sonic_g1_validate(const uint8_t* points, int64_t n, uint8_t* flags);
 /* host only, no device: rho_0 .. rho_{count-1} of a batch with digest D (out: count x 16 bytes, little-endian) */
 int sonic_verify_batch_randomizers(const uint8_t seed[32], const uint8_t batch_digest[32], int64_t count, uint8_t* out);
+
+/* ---- Subgroup membership (ABI 7 additions) ----
+ * Every point that enters the library is tested for membership of the order-r subgroup, and these two calls run that test on its own,
+ * on the GPU, one thread per point.  The criteria: a finite point P of the curve is in G1 iff phi(P) = lambda P, with phi(x, y) =
+ * (beta x, y), beta a cube root of unity in Fq and lambda = z^2 - 1 for the BLS parameter z = -0xd201000000010000 (phi^2 + phi + 1 = 0
+ * on the whole curve and lambda^2 + lambda + 1 = r, so phi(P) = lambda P forces r P = O); a finite point P of the twist is in G2 iff
+ * psi(P) = z P, with psi = twist . Frobenius . untwist, psi(x, y) = (conj(x) (1 + u)^(-(q-1)/3), conj(y) (1 + u)^(-(q-1)/2)) (psi^2 -
+ * (z + 1) psi + q = 0 on the whole twist, so psi(P) = z P forces (q - z) P = O, and q - z = h1 r with h1 prime to the twist's cofactor).
+ * Both walks are short -- z^2 has 128 bits, |z| has 64 -- where the definition, r P = O by double-and-add, walks 255.
+ *
+ * points: n encodings, 96 bytes as sonic_g1_validate reads them, 192 bytes as sonic_srs_get_g2_points writes them.  flags[i] = 0 for an
+ * accepted point -- the all-zero encoding is the point at infinity and is accepted -- otherwise the error bits of the loaders: 1 a
+ * non-canonical coordinate, 2 off the curve or twist, 4 outside the subgroup.  method: SONIC_SUBGROUP_DEFAULT is the endomorphism test,
+ * the one every loader, validator and decompressor of the library runs; SONIC_SUBGROUP_WALK is the definition, kept for differential
+ * tests and A/B measurements -- the two give the same flags on every input.  The call returns SONIC_OK whatever the verdicts are; n = 0 is
+ * SONIC_OK and launches nothing; a NULL pointer with n > 0, n < 0, n > 2^26 (the bound of the batched verifier's validation stage) or an
+ * unknown method is SONIC_ERR_INVALID_ARG. */
+#define SONIC_SUBGROUP_DEFAULT 0   /* the endomorphism test */
+#define SONIC_SUBGROUP_WALK    1   /* [r]P == O by double-and-add: the definition */
+int sonic_g1_subgroup_check(const uint8_t* points96,  int64_t n, int method, uint8_t* flags);
+int sonic_g2_subgroup_check(const uint8_t* points192, int64_t n, int method, uint8_t* flags);
 
 /* ---- Compressed encodings ----
  * The compressed form of the Zcash / IETF pairing-friendly-curves serialization, the default wire format of other BLS12-381 libraries.

@@ -1,6 +1,6 @@
 """Bulk conversion between the 96- / 192-byte encodings of the C ABI and the compressed 48- / 96-byte ones, on the GPU (sonic_g1_compress
-and its kin, include/sonic_hip.h "Compressed encodings"), and one proof's re-encoding on the host.  Single points as Python integers:
-encoding.py."""
+and its kin, include/sonic_hip.h "Compressed encodings"), one proof's re-encoding on the host, and the subgroup test of the loaders on its
+own (g1_subgroup_check, g2_subgroup_check).  Single points as Python integers: encoding.py."""
 from __future__ import annotations
 
 import ctypes as C
@@ -44,6 +44,30 @@ def g2_compress(points) -> np.ndarray:
 def g2_decompress(points, check_subgroup: bool = True, flags: bool = False):
     """uint8 [n, 96] -> uint8 [n, 192]; flags as for g1_decompress"""
     return _expand("sonic_g2_decompress", points, 96, 192, check_subgroup, flags)
+
+
+_SUBGROUP_METHODS = {"endo": _lib.SUBGROUP_DEFAULT, "walk": _lib.SUBGROUP_WALK}
+
+
+def _subgroup_check(name: str, points, in_bytes: int, method: str) -> np.ndarray:
+    if method not in _SUBGROUP_METHODS:
+        raise ValueError(f"method {method!r}: 'endo' (the endomorphism test) or 'walk' (r P = O by double-and-add)")
+    a = np.ascontiguousarray(points, np.uint8).reshape(-1, in_bytes)
+    fl = np.zeros(a.shape[0], np.uint8)
+    _lib.check(getattr(_lib.lib(), name)(a.ctypes.data, a.shape[0], _SUBGROUP_METHODS[method], fl.ctypes.data))
+    return fl
+
+
+def g1_subgroup_check(points, method: str = "endo") -> np.ndarray:
+    """uint8 [n, 96] -> uint8 [n]: 0 for a point of the order-r subgroup (infinity included), else bits 1 non-canonical, 2 off the curve,
+    4 outside the subgroup (sonic_g1_subgroup_check, include/sonic_hip.h "Subgroup membership").  'endo' is the test every loader runs,
+    'walk' the definition; both give the same flags"""
+    return _subgroup_check("sonic_g1_subgroup_check", points, 96, method)
+
+
+def g2_subgroup_check(points, method: str = "endo") -> np.ndarray:
+    """uint8 [n, 192] -> uint8 [n]; flags and methods as for g1_subgroup_check"""
+    return _subgroup_check("sonic_g2_subgroup_check", points, 192, method)
 
 
 def proof_compress(proof: bytes, Q: int) -> bytes:

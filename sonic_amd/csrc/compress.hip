@@ -10,7 +10,7 @@ namespace sonic {
 namespace {
 
 // 48 bytes -> the affine point for an MSM or a basis array, its canonical 96 bytes and a verdict (compress.hpp); a refused point is
-// written as infinity, as k_g1_validate does.  The walk is the shared one (g1_in_subgroup).
+// written as infinity, as k_g1_validate does.  The subgroup test is the shared one (g1_in_subgroup: the endomorphism test).
 __global__ __launch_bounds__(256) void k_g1_decompress(const uint8_t* __restrict__ in, PointArrayMut out, uint8_t* __restrict__ bytes96, uint8_t* __restrict__ flags,
                                                        long n, int check_subgroup) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -22,7 +22,7 @@ __global__ __launch_bounds__(256) void k_points_from_bytes(const uint8_t* __rest
   if (fp_sqr(p.y) != fp_add(fp_mul(fp_sqr(p.x), p.x), four)) { atomicOr(err, 2); out[i] = G1Affine::inf(); return; }
   out[i] = p;
 }
-// r P == O for every point (literal double-and-add over the bits of r): SRS elements must lie in the order-r subgroup because
+// r P == O for every point, by the endomorphism test (g1_in_subgroup, g1.hpp): SRS elements must lie in the order-r subgroup because
 // MSMs over an SRS fold scalars with r P = O (msm.hpp).  Sets err bit 4 otherwise.
 __global__ __launch_bounds__(256) void k_points_subgroup_check(PointArray in, long n, int* err) {
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;

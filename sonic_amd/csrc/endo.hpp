@@ -19,7 +19,7 @@ namespace sonic {
 
 #define ENDO_LAMBDA {0xffffffffu, 0x00000000u, 0x0001a402u, 0xac45a401u}
 #define ENDO_MU {0xf6cfee30u, 0x63f6e522u, 0xe01faaddu, 0x7c6becf1u, 0x00000001u}
-#define ENDO_BETA_MONT {0x8671f071u, 0xcd03c9e4u, 0x1fcda5d2u, 0x5dab2246u, 0xd3851b95u, 0x587042afu, 0x01bacb9eu, 0x8eb60ebeu, 0x83d050d2u, 0x03f97d6eu, 0x54638741u, 0x18f02065u}
+// ENDO_BETA_MONT: constants.hpp (g1.hpp's subgroup test multiplies by it too)
 constexpr int ENDO_BITS = 130;          // what the windows of an endomorphism plan cover: 128 bits + room for the signed recoding's carry
 
 // s (standard form, < r) -> s1 = s mod lambda, s2 = s div lambda, both as Fr-sized standard-form integers (upper four limbs zero)
@@ -92,11 +92,8 @@ HD void endo_split(const Fr& s, Fr& s1, Fr& s2) {
 
 // phi on an XYZZ point: x = X / ZZ, so (beta X, Y, ZZ, ZZZ)
 HD G1XYZZ g1_endo(const G1XYZZ& p) {
-  constexpr uint32_t b[12] = ENDO_BETA_MONT;
-  Fq beta;
-  for (int i = 0; i < 12; i++) beta.l[i] = b[i];
   G1XYZZ r = p;
-  r.x = fp_mul(p.x, beta);
+  r.x = fp_mul(p.x, g1_endo_beta());
   return r;
 }
 

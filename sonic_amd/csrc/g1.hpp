@@ -117,10 +117,10 @@ HD G1XYZZ g1_add_mixed(const G1XYZZ& acc, const G1Affine& q) {
   return r;
 }
 
-// r P == O for a finite affine point, by the literal double-and-add over the bits of r: the membership test of every G1 input (E(Fq) has
-// cofactor points, e.g. (0, 2) of order 3).  ONE copy, shared by the kernels that validate points (k_points_subgroup_check, k_g1_validate,
-// k_g1_decompress).
-HD bool g1_in_subgroup(const G1Affine& p) {
+// r P == O for a finite affine point of the curve, by the literal double-and-add over the bits of r: the DEFINITION of membership (E(Fq)
+// has cofactor points, e.g. (0, 2) of order 3) -- 254 doublings and about 127 additions.  Kept as the differential reference of the
+// test below (sonic_g1_subgroup_check with SONIC_SUBGROUP_WALK); no loader runs it.
+HD bool g1_in_subgroup_walk(const G1Affine& p) {
   constexpr uint32_t rl[8] = FR_P;
   G1XYZZ acc = G1XYZZ::from_affine(p);       // top bit (254) of r
 #pragma unroll 1
@@ -132,6 +132,42 @@ HD bool g1_in_subgroup(const G1Affine& p) {
     if ((wd >> (b & 31)) & 1u) acc = g1_add_mixed(acc, p);
   }
   return acc.is_inf();
+}
+
+// beta: the cube root of unity in Fq with phi(x, y) = (beta x, y) = lambda (x, y) on G1, lambda = z^2 - 1 (endo.hpp splits MSM scalars by it)
+HD Fq g1_endo_beta() {
+  constexpr uint32_t b[12] = ENDO_BETA_MONT;
+  Fq beta;
+  for (int i = 0; i < 12; i++) beta.l[i] = b[i];
+  return beta;
+}
+
+// The membership test of every G1 input: a finite point P of the curve is in the order-r subgroup iff phi(P) = lambda P.  phi^2 + phi + 1 = 0
+// on all of E(Fq), so phi(P) = lambda P gives (lambda^2 + lambda + 1) P = r P = O; and lambda is phi's eigenvalue on the subgroup
+// (DESIGN.md section 7).  lambda P = z^2 P - P, and z^2 has 128 bits of which 17 are set: 127 doublings and 18 additions.  The bits are
+// compile-time constants, so the walk is runs of doublings up to the next set bit -- no scalar limb is read per bit.  The additions are
+// the general ones: from a point of small order the accumulator does pass through P, -P and infinity.  The comparison is made in the
+// accumulator's coordinates (x = X / ZZ, y = Y / ZZZ), without an inversion.  ONE copy, shared by the kernels that validate points
+// (k_points_subgroup_check, k_g1_validate, k_g1_decompress, k_g1_subgroup) and by the host's load_g1.
+HD bool g1_in_subgroup(const G1Affine& p) {
+  G1XYZZ acc = G1XYZZ::from_affine(p);       // top bit (127) of z^2
+#pragma unroll 1
+  for (int k = 0; k < 2; k++) {
+    uint64_t w = k == 0 ? ENDO_Z2_HI << 1 : ENDO_Z2_LO;      // the bits of this word still to walk, left-aligned
+    int left = k == 0 ? 63 : 64;
+#pragma unroll 1
+    while (left > 0) {
+      const int run = w ? __builtin_clzll(w) + 1 : left;      // up to and including the next set bit, or to the end of the word
+#pragma unroll 1
+      for (int i = 0; i < run; i++) acc = g1_dbl(acc);
+      if (w) acc = g1_add_mixed(acc, p);
+      w = run < 64 ? w << run : 0;
+      left -= run;
+    }
+  }
+  acc = g1_add_mixed(acc, g1_neg(p));        // lambda P = z^2 P - P
+  if (acc.is_inf()) return false;            // phi(P) is finite
+  return fp_mul(fp_mul(p.x, g1_endo_beta()), acc.zz) == acc.x && fp_mul(p.y, acc.zzz) == acc.y;
 }
 
 // The same addition for the bucket walks: on the device the whole formula is one generated asm statement around ten calls of

@@ -128,8 +128,9 @@ HD G2Jac g2_add(const G2Jac& p, const G2Jac& q) {
   return r;
 }
 // r P == O for a finite point of the twist (E'(Fq2) has a large cofactor and the pairing is bilinear only on the order-r subgroup): the
-// literal double-and-add over the bits of r, shared by k_g2_points_from_bytes and k_g2_decompress
-HD bool g2_in_subgroup(const G2Affine& p) {
+// literal double-and-add over the bits of r, the DEFINITION of membership and the differential reference of the test below
+// (sonic_g2_subgroup_check with SONIC_SUBGROUP_WALK); no loader runs it.
+HD bool g2_in_subgroup_walk(const G2Affine& p) {
   constexpr uint32_t rl[8] = FR_P;
   G2Jac acc; acc.x = p.x; acc.y = p.y; acc.z = Fq2::one();       // top bit (254) of r
 #pragma unroll 1
@@ -141,6 +142,42 @@ HD bool g2_in_subgroup(const G2Affine& p) {
     if ((word >> (bit & 31)) & 1u) acc = g2_add_mixed(acc, p);
   }
   return acc.is_inf();
+}
+// psi = twist . Frobenius . untwist on E'(Fq2): psi(x, y) = (conj(x) c_x, conj(y) c_y), c_x = (1 + u)^(-(q-1)/3), c_y = (1 + u)^(-(q-1)/2)
+HD G2Affine g2_psi(const G2Affine& p) {
+  constexpr uint32_t x0[12] = G2_PSI_CX_C0_MONT, x1[12] = G2_PSI_CX_C1_MONT, y0[12] = G2_PSI_CY_C0_MONT, y1[12] = G2_PSI_CY_C1_MONT;
+  Fq2 cx, cy;
+  for (int i = 0; i < 12; i++) { cx.c0.l[i] = x0[i]; cx.c1.l[i] = x1[i]; cy.c0.l[i] = y0[i]; cy.c1.l[i] = y1[i]; }
+  Fq2 xb = p.x, yb = p.y;
+  xb.c1 = fp_neg(xb.c1); yb.c1 = fp_neg(yb.c1);
+  G2Affine r;
+  r.x = f2_mul(xb, cx);
+  r.y = f2_mul(yb, cy);
+  return r;
+}
+// The membership test of every G2 input: a finite point P of the twist is in the order-r subgroup iff psi(P) = z P.  psi^2 - t psi + q = 0
+// on E'(Fq2) with t = z + 1, so psi(P) = z P gives (z^2 - (z + 1) z + q) P = (q - z) P = O; q - z = h1 r, and the order of P divides
+// #E'(Fq2) = h2 r with gcd(h1, h2) = 1, so it divides r.  z is negative: the comparison is against -(|z| P), in the
+// accumulator's Jacobian coordinates (x = X / Z^2, y = Y / Z^3), without an inversion.  |z| has 64 bits of which 6 are set: 63 doublings
+// and 5 additions, walked as g1_in_subgroup walks z^2, with the general addition.  Shared by k_g2_points_from_bytes, k_g2_decompress and
+// k_g2_subgroup.
+HD bool g2_in_subgroup(const G2Affine& p) {
+  G2Jac acc; acc.x = p.x; acc.y = p.y; acc.z = Fq2::one();       // top bit (63) of |z|
+  uint64_t w = BLS_Z_ABS << 1;                                    // the bits still to walk, left-aligned
+  int left = 63;
+#pragma unroll 1
+  while (left > 0) {
+    const int run = w ? __builtin_clzll(w) + 1 : left;            // up to and including the next set bit, or to the end
+#pragma unroll 1
+    for (int i = 0; i < run; i++) acc = g2_dbl(acc);
+    if (w) acc = g2_add_mixed(acc, p);
+    w = run < 64 ? w << run : 0;
+    left -= run;
+  }
+  if (acc.is_inf()) return false;                                 // psi(P) is finite
+  const G2Affine s = g2_psi(p);
+  const Fq2 z2 = f2_sqr(acc.z);
+  return f2_mul(s.x, z2) == acc.x && f2_mul(f2_neg(s.y), f2_mul(z2, acc.z)) == acc.y;
 }
 // on the twist y^2 = x^3 + 4 (u + 1): the right-hand side for an x (Montgomery)
 HD Fq2 g2_curve_rhs(const Fq2& x) {

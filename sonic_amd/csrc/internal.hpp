@@ -151,6 +151,10 @@ void g1_compress_enqueue(hipStream_t st, PointArray in, uint8_t* d_out48, long n
 void g2_compress_enqueue(hipStream_t st, const G2Affine* in, uint8_t* d_out96, long n);
 // k_g1_validate (verify_batch.hip): 96-byte encodings -> affine points and flags, 1 = what load_g1 accepts
 void g1_validate_enqueue(hipStream_t st, const uint8_t* d_in96, G1Affine* out, uint8_t* d_flags, long n);
+// k_g1_subgroup (verify_batch.hip), k_g2_subgroup (srs_g2.hip): encodings -> one verdict per point, 0 accepted, else 1 non-canonical, 2 off
+// the curve, 4 outside the subgroup by the test `method` names (SONIC_SUBGROUP_DEFAULT / SONIC_SUBGROUP_WALK)
+void g1_subgroup_enqueue(hipStream_t st, const uint8_t* d_in96, uint8_t* d_flags, long n, int method);
+void g2_subgroup_enqueue(hipStream_t st, const uint8_t* d_in192, uint8_t* d_flags, long n, int method);
 
 // NTT (ntt.hip).  Data in Montgomery form, in place.  forward: natural -> bit-reversed;
 // inverse: bit-reversed -> natural, scaled by 1/n.

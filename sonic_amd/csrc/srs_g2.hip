@@ -99,8 +99,9 @@ __global__ __launch_bounds__(256) void k_g2_points_to_bytes(const G2Affine* __re
 }
 
 // Caller-supplied G2 elements (an SRS file, sonic_srs_set_g2_points): canonical coordinates, on the twist
-// y^2 = x^3 + 4(u + 1), and r P = O (E'(Fq2) has a large cofactor and the pairing is bilinear only on the order-r
-// subgroup).  err bits as on the G1 side: 1 non-canonical, 2 off the curve, 4 outside the subgroup, 8 the point at infinity.
+// y^2 = x^3 + 4(u + 1), and r P = O by the endomorphism test, g2_in_subgroup (E'(Fq2) has a large cofactor and the pairing is
+// bilinear only on the order-r subgroup).  err bits as on the G1 side: 1 non-canonical, 2 off the curve, 4 outside the
+// subgroup, 8 the point at infinity.
 __global__ __launch_bounds__(64, 1) void k_g2_points_from_bytes(const uint8_t* __restrict__ in, G2Affine* __restrict__ out, long n, int* err) {
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -122,6 +123,28 @@ __global__ __launch_bounds__(64, 1) void k_g2_points_from_bytes(const uint8_t* _
 }
 void g2_points_from_bytes_enqueue(hipStream_t st, const uint8_t* d_in, G2Affine* out, long n, int* d_err) {
   if (n > 0) LAUNCH(k_g2_points_from_bytes, ceil_div(n, 64), 64, 0, st, d_in, out, n, d_err);
+}
+// sonic_g2_subgroup_check: the same tests with one verdict per point (0 accepted, infinity included; 1 non-canonical, 2 off the twist,
+// 4 outside the subgroup) and the membership test named by METHOD: the endomorphism test every loader runs, or the definition.
+template <int METHOD>
+__global__ __launch_bounds__(64, 1) void k_g2_subgroup(const uint8_t* __restrict__ in, uint8_t* __restrict__ flags, long n) {
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(in + 192 * i);
+  G2Affine p;
+  for (int k = 0; k < 12; k++) { p.x.c0.l[k] = w[k]; p.x.c1.l[k] = w[12 + k]; p.y.c0.l[k] = w[24 + k]; p.y.c1.l[k] = w[36 + k]; }
+  uint32_t nz = 0;
+  for (int k = 0; k < 48; k++) nz |= w[k];
+  if (!nz) { flags[i] = 0; return; }
+  if (!fp_is_canonical(p.x.c0) || !fp_is_canonical(p.x.c1) || !fp_is_canonical(p.y.c0) || !fp_is_canonical(p.y.c1)) { flags[i] = 1; return; }
+  p.x.c0 = fp_to_mont(p.x.c0); p.x.c1 = fp_to_mont(p.x.c1); p.y.c0 = fp_to_mont(p.y.c0); p.y.c1 = fp_to_mont(p.y.c1);
+  if (!(f2_sqr(p.y) == g2_curve_rhs(p.x))) { flags[i] = 2; return; }
+  flags[i] = (METHOD == SONIC_SUBGROUP_WALK ? g2_in_subgroup_walk(p) : g2_in_subgroup(p)) ? 0 : 4;
+}
+void g2_subgroup_enqueue(hipStream_t st, const uint8_t* d_in192, uint8_t* d_flags, long n, int method) {
+  if (n <= 0) return;
+  if (method == SONIC_SUBGROUP_WALK) LAUNCH(k_g2_subgroup<SONIC_SUBGROUP_WALK>, ceil_div(n, 64), 64, 0, st, d_in192, d_flags, n);
+  else LAUNCH(k_g2_subgroup<SONIC_SUBGROUP_DEFAULT>, ceil_div(n, 64), 64, 0, st, d_in192, d_flags, n);
 }
 
 // fills h0 / h1 (2d+1 affine points each)

@@ -8,7 +8,7 @@
 namespace sonic {
 
 // limb j of a scalar.  The limbs live in registers, and a register array indexed by a run-time value goes to scratch: the limb is
-// picked by eight constant-index selects instead (as g1_in_subgroup reads r), once per 32 bits.
+// picked by eight constant-index selects instead (as g1_in_subgroup_walk reads r), once per 32 bits.
 HD uint32_t fr_limb(const Fr& k, int j) {
   uint32_t wd = 0;
 #pragma unroll

@@ -33,8 +33,8 @@ namespace {
 // ---- kernels --------------------------------------------------------------------------------------------------------------------
 
 // M points from their 96-byte encodings -> affine Montgomery points for the MSM and one flag per point: 1 = what load_g1 accepts (both
-// coordinates canonical; the encoding of infinity, or on the curve and r P = O by the literal double-and-add over the bits of r).  A
-// refused point is written as infinity, so that nothing downstream ever adds a point outside the subgroup.
+// coordinates canonical; the encoding of infinity, or on the curve and in the order-r subgroup by the endomorphism test, g1_in_subgroup).
+// A refused point is written as infinity, so that nothing downstream ever adds a point outside the subgroup.
 __global__ __launch_bounds__(256) void k_g1_validate(const uint8_t* __restrict__ in, G1Affine* __restrict__ out, uint8_t* __restrict__ flags, long n) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -51,6 +51,22 @@ __global__ __launch_bounds__(256) void k_g1_validate(const uint8_t* __restrict__
   ok = ok && g1_in_subgroup(p);
   out[i] = ok ? p : G1Affine::inf();
   flags[i] = ok ? 1 : 0;
+}
+// sonic_g1_subgroup_check: the same tests with the loaders' bits as the verdict (0 accepted, infinity included; 1 non-canonical, 2 off the
+// curve, 4 outside the subgroup) and the membership test named by METHOD: the endomorphism test every loader runs, or the definition.
+template <int METHOD>
+__global__ __launch_bounds__(256) void k_g1_subgroup(const uint8_t* __restrict__ in, uint8_t* __restrict__ flags, long n) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(in + 96 * i);
+  G1Affine p;
+  for (int k = 0; k < 12; k++) { p.x.l[k] = w[k]; p.y.l[k] = w[12 + k]; }
+  if (p.is_inf()) { flags[i] = 0; return; }
+  if (!fp_is_canonical(p.x) || !fp_is_canonical(p.y)) { flags[i] = 1; return; }
+  p.x = fp_to_mont(p.x); p.y = fp_to_mont(p.y);
+  const Fq four = fp_dbl(fp_dbl(Fq::one()));
+  if (fp_sqr(p.y) != fp_add(fp_mul(fp_sqr(p.x), p.x), four)) { flags[i] = 2; return; }
+  flags[i] = (METHOD == SONIC_SUBGROUP_WALK ? g1_in_subgroup_walk(p) : g1_in_subgroup(p)) ? 0 : 4;
 }
 
 // The resident circuit: the 3Q rows as CSR (values Montgomery) and the work items the s-kernel's threads take -- at most S_ITEM entries of
@@ -128,6 +144,11 @@ __global__ __launch_bounds__(S_BLOCK) void k_s_of_uv_finish(const Fr* __restrict
 }  // namespace
 void g1_validate_enqueue(hipStream_t st, const uint8_t* d_in96, G1Affine* out, uint8_t* d_flags, long n) {
   if (n > 0) LAUNCH(k_g1_validate, ceil_div(n, 256), 256, 0, st, d_in96, out, d_flags, n);
+}
+void g1_subgroup_enqueue(hipStream_t st, const uint8_t* d_in96, uint8_t* d_flags, long n, int method) {
+  if (n <= 0) return;
+  if (method == SONIC_SUBGROUP_WALK) LAUNCH(k_g1_subgroup<SONIC_SUBGROUP_WALK>, ceil_div(n, 256), 256, 0, st, d_in96, d_flags, n);
+  else LAUNCH(k_g1_subgroup<SONIC_SUBGROUP_DEFAULT>, ceil_div(n, 256), 256, 0, st, d_in96, d_flags, n);
 }
 namespace {
 
@@ -919,6 +940,13 @@ int batch_size_ok(const char* who, const sonic_verifier* v, int64_t K) {
   return SONIC_OK;
 }
 
+// the arguments of sonic_g1_subgroup_check / sonic_g2_subgroup_check; the bound is the one of the batched verifier's validation stage
+int subgroup_args_ok(const char* who, const uint8_t* points, int64_t n, int method, const uint8_t* flags) {
+  if (n >= 0 && n <= MSM_TABLE_MAX_TERMS && (n == 0 || (points && flags)) && (method == SONIC_SUBGROUP_DEFAULT || method == SONIC_SUBGROUP_WALK)) return SONIC_OK;
+  set_error("%s: bad argument (n = %lld of at most 2^26, method = %d)", who, (long long)n, method);
+  return SONIC_ERR_INVALID_ARG;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1120,6 +1148,37 @@ int sonic_g1_validate(const uint8_t* points, int64_t n, uint8_t* flags) {
   DevBuf raw(96 * (size_t)n), pts(sizeof(G1Affine) * (size_t)n), fl((size_t)n);
   HIP_OK(hipMemcpyAsync(raw.p, points, 96 * (size_t)n, hipMemcpyHostToDevice, st));
   g1_validate_enqueue(st, raw.as<uint8_t>(), pts.as<G1Affine>(), fl.as<uint8_t>(), (long)n);
+  HIP_OK(hipMemcpyAsync(flags, fl.p, (size_t)n, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  return SONIC_OK;
+  API_CATCH
+}
+
+// ---- subgroup membership on its own (include/sonic_hip.h, "Subgroup membership") ----
+int sonic_g1_subgroup_check(const uint8_t* points96, int64_t n, int method, uint8_t* flags) {
+  if (int rc = subgroup_args_ok("sonic_g1_subgroup_check", points96, n, method, flags)) return rc;
+  if (n == 0) return SONIC_OK;
+  API_BEGIN
+  CallLease lease;
+  hipStream_t st = lease.st();
+  DevBuf raw(96 * (size_t)n), fl((size_t)n);
+  HIP_OK(hipMemcpyAsync(raw.p, points96, 96 * (size_t)n, hipMemcpyHostToDevice, st));
+  g1_subgroup_enqueue(st, raw.as<uint8_t>(), fl.as<uint8_t>(), (long)n, method);
+  HIP_OK(hipMemcpyAsync(flags, fl.p, (size_t)n, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  return SONIC_OK;
+  API_CATCH
+}
+
+int sonic_g2_subgroup_check(const uint8_t* points192, int64_t n, int method, uint8_t* flags) {
+  if (int rc = subgroup_args_ok("sonic_g2_subgroup_check", points192, n, method, flags)) return rc;
+  if (n == 0) return SONIC_OK;
+  API_BEGIN
+  CallLease lease;
+  hipStream_t st = lease.st();
+  DevBuf raw(192 * (size_t)n), fl((size_t)n);
+  HIP_OK(hipMemcpyAsync(raw.p, points192, 192 * (size_t)n, hipMemcpyHostToDevice, st));
+  g2_subgroup_enqueue(st, raw.as<uint8_t>(), fl.as<uint8_t>(), (long)n, method);
   HIP_OK(hipMemcpyAsync(flags, fl.p, (size_t)n, hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));
   return SONIC_OK;
