@@ -46,7 +46,7 @@ module Sonic.HIP
   , hNegativeX, hPositiveX, hNegativeAlphaX, hPositiveAlphaX, srsPairing
   , saveSRS, loadSRS, srsForCircuit, loadSrsForCircuit
   , checkSrs, updateSrs, verifySrsUpdate, msmG2, msmG2Srs
-  , g1SubgroupCheck, g2SubgroupCheck
+  , g1SubgroupCheck, g2SubgroupCheck, pairingCheck
     -- * Sonic.CommitmentScheme
   , commitPoly, openPoly, pcV
     -- * Sonic.Protocol
@@ -125,6 +125,8 @@ foreign import ccall safe   "sonic_msm_g2_srs"        c_msm_g2_srs       :: Ptr 
 -- subgroup membership on its own (ABI 7); method 0: the endomorphism test of the loaders, 1: r P = O by double-and-add
 foreign import ccall safe   "sonic_g1_subgroup_check" c_g1_subgroup_check :: Ptr Word8 -> Int64 -> CInt -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_g2_subgroup_check" c_g2_subgroup_check :: Ptr Word8 -> Int64 -> CInt -> Ptr Word8 -> IO CInt
+-- products of pairings checked in groups (ABI 7); where 0: the library's rule, 1: host threads, 2: the GPU
+foreign import ccall safe   "sonic_pairing_check"     c_pairing_check    :: Ptr Word8 -> Ptr Word8 -> Int64 -> Ptr Int64 -> Int64 -> CInt -> Ptr Word8 -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_commit_poly"       c_commit_poly      :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_open_poly"         c_open_poly        :: Ptr SrsHandle -> Ptr Word8 -> Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_pc_v"              c_pc_v             :: Ptr SrsHandle -> Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> IO CInt
@@ -445,6 +447,18 @@ g2SubgroupCheck pts = libraryReady `seq`
   withBytes (BS.concat (map g2ToBytes pts)) $ \pp -> allocaBytes (max 1 (length pts)) $ \fl -> do
     check =<< c_g2_subgroup_check pp (fromIntegral (length pts)) 0 fl
     map (== 0) . BS.unpack <$> packed fl (length pts)
+
+-- | one verdict per group of pairs: whether the product of the group's pairings is one (include/sonic_hip.h, "Pairing": KZG openings,
+-- batches of BLS signatures, the links of an SRS ceremony).  Values of the curves' types are canonical and on the curve; a point outside
+-- the order-r subgroup makes its group False.  An empty group is True.
+pairingCheck :: [[(G1 BLS12381, G2 BLS12381)]] -> IO [Bool]
+pairingCheck groups = libraryReady `seq`
+  let pairs = concat groups
+      ends  = drop 1 (scanl (+) 0 (map length groups))
+  in withBytes (BS.concat (map (g1ToBytes . fst) pairs)) $ \p1 -> withBytes (BS.concat (map (g2ToBytes . snd) pairs)) $ \p2 ->
+       withArrayLen (map fromIntegral ends :: [Int64]) $ \ng pe -> allocaBytes (max 1 ng) $ \vd -> do
+         check =<< c_pairing_check p1 p2 (fromIntegral (length pairs)) pe (fromIntegral ng) 0 vd nullPtr
+         map (== 0) . BS.unpack <$> packed vd ng
 
 -- ---------------------------------------------------------------------------------------------------------------------
 -- Sonic.CommitmentScheme

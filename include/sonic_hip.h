@@ -109,7 +109,7 @@ typedef struct sonic_verifier sonic_verifier_t;
  * sonic_prover_aggregate_core, sonic_verifier_verify_core_batch_helped, sonic_verifier_verify_core_fs_batch_helped,
  * sonic_verify_core_helped_digest; still 7, additions only: the updatable SRS -- sonic_srs_check, sonic_srs_update, sonic_srs_verify_update;
  * still 7, additions only: the G2 sums -- sonic_msm_g2, sonic_msm_g2_srs[_dev], sonic_msm_g2_walk_max; subgroup membership --
- * sonic_g1_subgroup_check, sonic_g2_subgroup_check */
+ * sonic_g1_subgroup_check, sonic_g2_subgroup_check; pairings -- sonic_pairing_check */
 int sonic_abi_version(void);
 int sonic_init(int device_ordinal);                 /* choose the DEFAULT GPU (first call wins) and make it the thread's HIP device; idempotent */
 int sonic_device_count(int* out);                   /* GPUs this process can see; SONIC_ERR_NO_DEVICE (and 0) without one */
@@ -538,6 +538,36 @@ int sonic_verify_batch_randomizers(const uint8_t seed[32], const uint8_t batch_d
 #define SONIC_SUBGROUP_WALK    1   /* [r]P == O by double-and-add: the definition */
 int sonic_g1_subgroup_check(const uint8_t* points96,  int64_t n, int method, uint8_t* flags);
 int sonic_g2_subgroup_check(const uint8_t* points192, int64_t n, int method, uint8_t* flags);
+
+/* ---- Pairing (ABI 7 additions) ----
+ * Products of pairings checked in groups: the equations of KZG openings, of batches of BLS signatures, of the links of an SRS
+ * ceremony.  The pairing is the verifier's own (one copy of the formulas for the host and the device, so both give the same bytes):
+ * the ate Miller loop over |z| and the exponent 3 (q^12 - 1) / r.
+ *
+ * n_pairs pairs (g1: 96 bytes each, g2: 192 bytes each, the encodings of sonic_msm_g1 / sonic_msm_g2; all zeros is the point at
+ * infinity, and a pair with one contributes 1), cut into n_groups groups: group g is pairs [group_end[g-1], group_end[g]), group_end
+ * non-decreasing, group_end[n_groups-1] == n_pairs; an empty group's product is 1.
+ * verdict[g]: 0 the product of the group's pairings is one; 1 it is not; otherwise the OR over the group's points of
+ * 2 non-canonical, 4 off the curve / twist, 8 outside the subgroup (such a group's product is not computed).
+ * gt (may be NULL): n_groups x 576 bytes, the value in the layout of sonic_srs_pairing -- e^3 of the textbook ate pairing,
+ * since the exponent is 3 (q^12 - 1) / r; zeros for a group with a bad point.
+ *
+ * Every point is validated (canonical, on the curve, in the order-r subgroup), by the device's validators or the host's.  A bad point
+ * is a verdict, not an error: the call returns SONIC_OK whatever the verdicts are.  SONIC_ERR_INVALID_ARG: a NULL array that is needed,
+ * n_pairs or n_groups outside 0 .. 2^26, a group_end that decreases or does not end at n_pairs, an unknown `where`.  n_pairs == 0 with
+ * n_groups empty groups is valid: verdict 0 for each.
+ *
+ * where: SONIC_PAIRING_HOST runs on up to 16 host threads, SONIC_PAIRING_GPU on the default device (one thread per pair, then one per
+ * group), SONIC_PAIRING_AUTO by the library's rule: the device from the number of groups upward at which it was measured to win
+ * (256 groups; README, "Pairing").  The environment's SONIC_PAIRING_GPU, read per call, overrides the rule -- 0: AUTO is the
+ * host, 1: AUTO is the device -- and does the same for the per-proof verdicts of the batched verifiers (`each` after a failed fold).
+ * AUTO decides by size alone and, like every device call of the library, does not fall back: where it picks the device and the process
+ * has none, the call returns SONIC_ERR_NO_DEVICE (a HIP failure: SONIC_ERR_HIP).  SONIC_PAIRING_HOST is the one form that needs no GPU. */
+#define SONIC_PAIRING_AUTO 0   /* the library's rule */
+#define SONIC_PAIRING_HOST 1   /* pairing.hpp on host threads */
+#define SONIC_PAIRING_GPU  2   /* the kernels of pairing.hip */
+int sonic_pairing_check(const uint8_t* g1, const uint8_t* g2, int64_t n_pairs, const int64_t* group_end, int64_t n_groups,
+                        int where, uint8_t* verdict, uint8_t* gt);
 
 /* ---- Compressed encodings ----
  * The compressed form of the Zcash / IETF pairing-friendly-curves serialization, the default wire format of other BLS12-381 libraries.

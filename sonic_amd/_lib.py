@@ -207,6 +207,7 @@ def lib() -> C.CDLL:
         "sonic_msm_g2_walk_max": [],
         "sonic_g1_subgroup_check": [vp, i64, i32, vp],
         "sonic_g2_subgroup_check": [vp, i64, i32, vp],
+        "sonic_pairing_check": [vp, vp, i64, vp, i64, i32, vp, vp],
         "sonic_dev_alloc": [C.c_size_t, C.POINTER(vp)],
         "sonic_dev_free": [vp],
         "sonic_dev_upload": [vp, vp, C.c_size_t],
@@ -273,6 +274,7 @@ FS_MIDSTATE_SIZE = 112   # SONIC_FS_MIDSTATE_SIZE
 WIT_FR32, WIT_I64 = 0, 1  # SONIC_WIT_*
 CORE_PROOF_SIZE, CORE_PROOF_SIZE_COMPRESSED = 576, 336   # SONIC_CORE_PROOF_SIZE[_COMPRESSED]
 SUBGROUP_DEFAULT, SUBGROUP_WALK = 0, 1  # SONIC_SUBGROUP_*
+PAIRING_AUTO, PAIRING_HOST, PAIRING_GPU = 0, 1, 2  # SONIC_PAIRING_*
 
 
 class WitnessSrc(C.Structure):          # sonic_witness_src_t
@@ -316,6 +318,7 @@ EXPORTED = [
     "sonic_srs_check", "sonic_srs_update", "sonic_srs_verify_update",
     "sonic_msm_g2", "sonic_msm_g2_srs", "sonic_msm_g2_srs_dev", "sonic_msm_g2_walk_max",
     "sonic_g1_subgroup_check", "sonic_g2_subgroup_check",
+    "sonic_pairing_check",
 ]
 
 

@@ -18,6 +18,7 @@
 // 2 + 2Q challenges)) and i = k (3Q + 4) + (index of the check in proof_checks' order).  D binds everything the verdict depends on, so even
 // a fixed public seed leaves a cheating prover no rho to aim at.
 #include <string.h>
+#include <stdlib.h>
 #include <sys/random.h>
 #include <algorithm>
 #include <chrono>
@@ -26,6 +27,8 @@
 #include "verify_host.hpp"
 #include "srs_handle.hpp"
 #include "proof_layout.hpp"
+#include "srs_scale.hpp"
+#include "pairing_device.hpp"
 
 namespace sonic {
 namespace {
@@ -141,6 +144,44 @@ __global__ __launch_bounds__(S_BLOCK) void k_s_of_uv_finish(const Fr* __restrict
   if (threadIdx.x == 0) { out[k] = sum; ok[k] = refused ? 0 : 1; }
 }
 
+// ---- the per-proof fold on the device (`each` after a failed fold; fold_each_device below) ----
+// Proof k's sums are sum_j scal(s)[k NP + j] * pts[k NP + j] for the S = 2 + (classes of max) scalar arrays s, the very sums fold_sums
+// takes from range_msm one proof at a time.  Here every term is a thread: a double-and-add of its scalar (g1_scale, the walk of
+// k_g1_scale_each), infinity at once for a zero scalar.  Slot NP of array 1 is the generator's term gv_k * g.  good[i] is the proof of group i.
+__global__ __launch_bounds__(256) void k_each_terms(const G1Affine* __restrict__ pts, const Fr* __restrict__ scalars, const Fr* __restrict__ gv, const int32_t* __restrict__ good,
+                                                    long groups, int S, long NP, long N, G1Affine gen, G1XYZZ* __restrict__ terms) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x, T = NP + 1;
+  if (t >= groups * S * T) return;
+  const long i = t / (S * T), j = t % T;
+  const int s = (int)((t / T) % S);
+  const long k = good[i];
+  G1XYZZ r = G1XYZZ::inf();
+  if (j < NP) {
+    const Fr sc = scalars[(size_t)s * (size_t)N + (size_t)(k * NP + j)];
+    if (!sc.is_zero()) r = g1_scale(pts[k * NP + j], sc);
+  } else if (s == 1) {
+    r = g1_scale(gen, gv[k]);
+  }
+  terms[t] = r;
+}
+// one thread per (proof, sum): the terms added, negated where fold_sums negates -- A = sum_0, B = gv g - sum_1, C_c = -sum_{2+c} -- and
+// made affine, beside the G2 element it is paired with (h2: h^{alpha x}, h^alpha, h^{x^{m-d}} per class)
+__global__ __launch_bounds__(64) void k_each_sums(const G1XYZZ* __restrict__ terms, long groups, int S, long NP, const G2Affine* __restrict__ h2,
+                                                  G1Affine* __restrict__ P, G2Affine* __restrict__ Qo) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x, T = NP + 1;
+  if (t >= groups * S) return;
+  const int s = (int)(t % S);
+  const G1XYZZ* mine = terms + t * T;
+  G1XYZZ acc = G1XYZZ::inf();
+#pragma unroll 1
+  for (long j = 0; j < NP; j++) acc = g1_add(acc, mine[j]);
+  if (s == 1) acc = g1_add(mine[NP], g1_neg(acc));
+  G1Affine a = g1_to_affine(acc);
+  if (s >= 2 && !a.is_inf()) a = g1_neg(a);
+  P[t] = a;
+  Qo[t] = h2[s];
+}
+
 }  // namespace
 void g1_validate_enqueue(hipStream_t st, const uint8_t* d_in96, G1Affine* out, uint8_t* d_flags, long n) {
   if (n > 0) LAUNCH(k_g1_validate, ceil_div(n, 256), 256, 0, st, d_in96, out, d_flags, n);
@@ -203,6 +244,10 @@ struct sonic_verifier {
   DevBuf row_ptr, col, val, item_row, item_begin;
   // per call, grown on demand: K (4Q + 7) encodings, points and flags; K pairs, s-values and flags; K nblk partial sums; the scalars
   DevBuf raw, zraw, pts, flags, uv, sv, sok, partial, scalars;      // (zraw: the compressed encodings of the `_z` calls)
+  // the per-proof fold on the device (fold_each_device): h^{alpha x}, h^alpha, hm[] uploaded by the first such call; per call the terms,
+  // the pairs, the generator's scalars, the proofs of the groups, the groups' ends and verdicts
+  DevBuf each_g2, each_terms, each_P, each_Q, each_gv, each_good, each_end, each_one;
+  bool have_each_g2 = false;
 };
 
 namespace {
@@ -261,6 +306,57 @@ bool fold_accepts(const sonic_verifier* v, const Sums& s, bool threads) {
   F12 prod = f[0];
   for (size_t i = 1; i < L; i++) prod = f12_mul(prod, f[i]);
   return final_exponentiation(prod).is_one();
+}
+
+// `each` after a failed fold, on the device: every well-formed proof folded on its own -- k_each_terms, k_each_sums, then one group of
+// 2 + (classes) pairs per proof through pairing_groups_device.  The sums are fold_sums' sums (the same group elements, so the same affine
+// coordinates) and the pairing is fold_accepts' pairing (one copy of the formulas), so each[k] is what the host form gives.
+void fold_each_device(const Batch& b, uint8_t* each) {
+  sonic_verifier* v = b.v;
+  hipStream_t st = v->st;
+  const int S = 2 + (int)v->ms.size();
+  const long NP = b.NP, T = NP + 1;
+  std::vector<int32_t> good;
+  for (long k = 0; k < b.K; k++) if (b.good[(size_t)k]) good.push_back((int32_t)k);
+  const long groups = (long)good.size();
+  if (groups == 0) return;
+  if (!v->have_each_g2) {
+    std::vector<G2Affine> h2{v->vk.h_alpha_x, v->vk.h_alpha};
+    h2.insert(h2.end(), v->hm.begin(), v->hm.end());
+    v->each_g2.ensure(sizeof(G2Affine) * h2.size());
+    HIP_OK(hipMemcpyAsync(v->each_g2.p, h2.data(), sizeof(G2Affine) * h2.size(), hipMemcpyHostToDevice, st));
+    HIP_OK(hipStreamSynchronize(st));
+    v->have_each_g2 = true;
+  }
+  std::vector<Fr> gv((size_t)b.K);
+  for (long k = 0; k < b.K; k++) gv[(size_t)k] = fp_from_mont(b.gv[(size_t)k]);
+  // in slices of proofs whose terms fit EACH_TERMS_BYTES: the handle keeps its buffers, and a batch of any size must not pin more than that
+  constexpr size_t EACH_TERMS_BYTES = (size_t)64 << 20;
+  long slice = std::max<long>(1, (long)(EACH_TERMS_BYTES / (sizeof(G1XYZZ) * (size_t)S * (size_t)T)));
+  if (const char* e = getenv("SONIC_EACH_SLICE")) { const long want = atol(e); if (want >= 1 && want < slice) slice = want; }      // (tests: several slices at a small K)
+  slice = std::min(slice, groups);
+  std::vector<int64_t> ends((size_t)slice);
+  for (long i = 0; i < slice; i++) ends[(size_t)i] = (i + 1) * S;
+  const size_t cap = (size_t)slice * (size_t)S;
+  v->each_terms.ensure(sizeof(G1XYZZ) * cap * (size_t)T);
+  v->each_P.ensure(sizeof(G1Affine) * cap); v->each_Q.ensure(sizeof(G2Affine) * cap);
+  v->each_gv.ensure(sizeof(Fr) * gv.size()); v->each_good.ensure(sizeof(int32_t) * good.size());
+  v->each_end.ensure(sizeof(int64_t) * ends.size()); v->each_one.ensure((size_t)slice);
+  HIP_OK(hipMemcpyAsync(v->each_gv.p, gv.data(), sizeof(Fr) * gv.size(), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(v->each_good.p, good.data(), sizeof(int32_t) * good.size(), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(v->each_end.p, ends.data(), sizeof(int64_t) * ends.size(), hipMemcpyHostToDevice, st));
+  std::vector<uint8_t> one((size_t)slice);
+  for (long g0 = 0; g0 < groups; g0 += slice) {
+    const long m = std::min(slice, groups - g0), pairs = m * S;          // the first m entries of ends are this slice's
+    LAUNCH(k_each_terms, ceil_div(pairs * T, 256), 256, 0, st, (const G1Affine*)v->pts.as<G1Affine>(), (const Fr*)v->scalars.as<Fr>(), (const Fr*)v->each_gv.as<Fr>(),
+           (const int32_t*)v->each_good.as<int32_t>() + g0, m, S, NP, (long)b.N(), g1_gen_host(), v->each_terms.as<G1XYZZ>());
+    LAUNCH(k_each_sums, ceil_div(pairs, 64), 64, 0, st, (const G1XYZZ*)v->each_terms.as<G1XYZZ>(), m, S, NP, (const G2Affine*)v->each_g2.as<G2Affine>(),
+           v->each_P.as<G1Affine>(), v->each_Q.as<G2Affine>());
+    pairing_groups_device(st, v->each_P.as<G1Affine>(), v->each_Q.as<G2Affine>(), pairs, v->each_end.as<int64_t>(), m, v->each_one.as<uint8_t>(), nullptr);
+    HIP_OK(hipMemcpyAsync(one.data(), v->each_one.p, (size_t)m, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    for (long i = 0; i < m; i++) each[good[(size_t)(g0 + i)]] = one[(size_t)i] ? 1 : 0;
+  }
 }
 
 // s(u_k, v_k) for K pairs (standard-form pairs on the host, canonical) on the handle's stream: Montgomery values and per-pair flags
@@ -387,6 +483,13 @@ int fold_batch(Batch& b, const uint8_t seed[32], const uint8_t D[32], bool any_b
   for (long k = 0; k < K; k++) each[k] = (fold_ok && b.good[(size_t)k]) ? 1 : 0;
   if (fold_ok || good_count == 0) return SONIC_OK;
   t0 = now_ms();
+  // the device form from the measured size upward (pairing_device.hpp); SONIC_PAIRING_GPU = 0 / 1: never / always
+  const int knob = pairing_gpu_knob();
+  if (knob == 1 || (knob < 0 && K >= EACH_GPU_MIN_PROOFS)) {
+    fold_each_device(b, each);
+    host_phase("verify_batch:each_gpu", now_ms() - t0);
+    return SONIC_OK;
+  }
   std::vector<Sums> sums((size_t)K);
   for (long k = 0; k < K; k++) if (b.good[(size_t)k]) sums[(size_t)k] = fold_sums(b, k, k + 1);
   const int nt = (int)std::min<long>(K, 16);
