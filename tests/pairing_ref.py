@@ -5,8 +5,11 @@ so the coefficient of w^i is (c_i + c_{i+6}) + c_{i+6} u, and w^i sits at [i % 2
 is 3 (q^12 - 1) / r: its value is the oracle's `pairing` cubed."""
 import functools
 
+import numpy as np
+
 from oracle import pairing as pr
-from oracle.sonic_ref import G1_GEN, Q, R
+from oracle.sonic_ref import G1_GEN, Q, R, g1_mul
+from sonic_amd.encoding import g1_to_bytes, g2_to_bytes
 
 GT_ONE = (1).to_bytes(48, "little") + bytes(528)
 
@@ -43,4 +46,59 @@ def oracle_value(pairs) -> bytes:
     return gt_bytes(cube(pr.f12_pow(f, pr.FINAL_EXP)))
 
 
-__all__ = ["GT_ONE", "gt_bytes", "gt_from_bytes", "cube", "oracle_value", "G1_GEN", "Q", "R"]
+# ---- pairs with a known value ---------------------------------------------------------------------------------------------------------
+# Pair i is (a_i G1_GEN, b_i G2_GEN) for integers a_i, b_i, so by bilinearity a group's value is E^(sum a_i b_i mod r) with E the value of
+# (G1_GEN, G2_GEN): one pairing of the oracle and one f12_pow per distinct exponent, whatever the group's size.  The pools hold the
+# scalars at which a Miller loop or a scalar walk changes behaviour (z is the curve's parameter, |z| the loop count).
+Z_ABS = 0xd201000000010000
+G1_POOL = (1, 2, R - 1, Z_ABS, Z_ABS + 1, R - Z_ABS, pow(2, 254, R), 3, 5, 7, 11, 13, 0x1234567)
+G2_POOL = (1, R - 1, Z_ABS, (R - 1) // 2, 5, 0xabcdef0123)          # 13 and 6 entries: index j walks all 78 combinations
+
+
+@functools.lru_cache(maxsize=None)
+def g1_row(a: int) -> bytes:
+    """the 96 bytes of a G1_GEN, a in [0, r) (zeros, the point at infinity, for 0)"""
+    return g1_to_bytes(g1_mul(G1_GEN, a)) if a else bytes(96)
+
+
+@functools.lru_cache(maxsize=None)
+def g2_row(b: int) -> bytes:
+    """the 192 bytes of b G2_GEN, b in [0, r)"""
+    return g2_to_bytes(pr.g2_mul(pr.G2_GEN, b)) if b else bytes(192)
+
+
+def pool_pairs(m: int, shift: int = 0):
+    """m scalar pairs (a, b) cycling through the pools from index `shift`"""
+    return [(G1_POOL[(shift + j) % len(G1_POOL)], G2_POOL[(shift + j) % len(G2_POOL)]) for j in range(m)]
+
+
+def exponent(pairs) -> int:
+    return sum(a * b for a, b in pairs) % R
+
+
+def closed(pairs, off: int = 0):
+    """the pairs and one more, (-(sum a_i b_i) G1_GEN, G2_GEN), that closes the group to one; with `off` that pair's scalar is off by it
+    and the group's exponent is `off`"""
+    return list(pairs) + [((off - exponent(pairs)) % R, 1)]
+
+
+def build(groups):
+    """groups: a list of lists of scalar pairs -> (g1 uint8 [n, 96], g2 uint8 [n, 192], group_end int64 [G], the groups' exponents)"""
+    flat = [(a % R, b % R) for grp in groups for a, b in grp]
+    g1 = np.frombuffer(b"".join(g1_row(a) for a, _ in flat), np.uint8).reshape(-1, 96).copy()
+    g2 = np.frombuffer(b"".join(g2_row(b) for _, b in flat), np.uint8).reshape(-1, 192).copy()
+    ends = np.cumsum(np.array([len(grp) for grp in groups], np.int64)).astype(np.int64)
+    return g1, g2, ends, [exponent(grp) for grp in groups]
+
+
+@functools.lru_cache(maxsize=None)
+def expected(e: int) -> bytes:
+    """the 576 bytes of a group whose exponent is e: E^e from the oracle's one pairing, GT_ONE for 0"""
+    e %= R
+    if e == 0:
+        return GT_ONE
+    return gt_bytes(pr.f12_pow(gt_from_bytes(oracle_value(((G1_GEN, pr.G2_GEN),))), e))
+
+
+__all__ = ["GT_ONE", "gt_bytes", "gt_from_bytes", "cube", "oracle_value", "G1_GEN", "Q", "R", "Z_ABS", "G1_POOL", "G2_POOL", "g1_row", "g2_row",
+           "pool_pairs", "exponent", "closed", "build", "expected"]

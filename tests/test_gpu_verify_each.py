@@ -7,7 +7,8 @@ import os
 
 import pytest
 
-from test_gpu_verify_batch import SEED, World, g1_shift, layout, put
+from test_gpu_verify_batch import SEED, World, _damages, g1_shift, layout, put
+from util import R
 
 pytestmark = pytest.mark.gpu
 
@@ -182,3 +183,74 @@ def test_the_device_fold_in_several_slices(sonic, ref, world, monkeypatch):
     monkeypatch.setenv("SONIC_EACH_SLICE", "64")
     got, names, loops = profiled(lambda: v.verify_batch(proofs, trs, seed=SEED, each=True))
     assert got == want and loops == 2
+
+
+# ---- the device form field by field: k_each_terms reads scalars[s * N + k * NP + j] over S arrays and NP + 1 slots, k_each_sums negates by s ----
+def cycle(world, K):
+    return [world.proofs[k % 3] for k in range(K)], [world.trs[k % 3] for k in range(K)]
+
+
+@pytest.mark.parametrize("form", ["dense", "csr"])
+def test_one_damaged_field_per_proof_in_one_batch(sonic, ref, world, form):
+    """one proof per field of the record: proof k has its k-th G1 field + g, then its Fr fields + 1 in turn, the last proof is intact.
+    each[k] is what sonic_verify says of proof k alone, under both forms: a slot or an array indexed wrongly moves a rejection to
+    another proof or loses it"""
+    g1, fr, _size = layout(Q)
+    K = len(g1) + len(fr) + 1
+    assert (len(g1), len(fr)) == (4 * Q + 7, 2 * Q + 5)
+    proofs, trs = cycle(world, K)
+    for k, off in enumerate(g1):
+        proofs[k] = g1_shift(ref, proofs[k], off, ref.G1_GEN)
+    for k, off in enumerate(fr, len(g1)):
+        proofs[k] = put(proofs[k], off, ((int.from_bytes(proofs[k][off:off + 32], "little") + 1) % R).to_bytes(32, "little"))
+    want = [world.yard(sonic, p, t, form) for p, t in zip(proofs, trs)]
+    assert not all(want[:len(g1)]) and not all(want[len(g1):K - 1]) and want[K - 1]
+    v = world.verifier(sonic, form)
+    assert both(lambda: v.verify_batch(proofs, trs, seed=SEED, each=True)) == (False, want)
+
+
+def test_damaged_challenges_under_both_forms(sonic, ref, world):
+    """y, z, y_j and z_j of one proof of four off by one: the scalars of that proof's slots alone change"""
+    K, at = 4, 2
+    v = world.verifier(sonic, "dense")
+    seen = []
+    for what, raw, tr in _damages(ref, world.proofs[at], world.trs[at], Q):
+        if what.startswith("every"):
+            continue
+        proofs, trs = cycle(world, K)
+        proofs[at], trs[at] = raw, tr
+        want = [world.yard(sonic, p, t) for p, t in zip(proofs, trs)]
+        assert want == [k != at for k in range(K)], what
+        assert both(lambda: v.verify_batch(proofs, trs, seed=SEED, each=True)) == (False, want), what
+        seen.append(what)
+    assert seen == ["y", "z", "y_0", "z_0", "y_1", "z_1"]
+
+
+def test_infinity_as_a_proof_point_under_both_forms(sonic, ref, world):
+    """R, then W_0, as the encoding of infinity in one proof of three: whatever sonic_verify says of it; once more beside a false proof,
+    so that the per-proof fold runs whatever that verdict is and k_each_terms / k_each_sums meet the point"""
+    g1, _fr, _size = layout(Q)
+    v = world.verifier(sonic, "dense")
+    for off in (g1[0], g1[6]):                       # R; W_0 of the first hsc list (R T Wa Wb Wt S_0 W_0)
+        bad = put(world.proofs[1], off, bytes(96))
+        want = world.yard(sonic, bad, world.trs[1])
+        proofs = [world.proofs[0], bad, world.proofs[2]]
+        assert both(lambda: v.verify_batch(proofs, world.trs, seed=SEED, each=True)) == (want, [True, want, True]), off
+        proofs = [false_proof(ref, world.proofs[0]), bad, world.proofs[2]]
+        assert both(lambda: v.verify_batch(proofs, world.trs, seed=SEED, each=True)) == (False, [False, want, True]), off
+
+
+def test_258_proofs_are_one_slice_of_258_groups(sonic, ref, world, monkeypatch):
+    """one group per proof gives k_gt_plan more groups than it has threads (per = 2, trailing empty slices); false proofs at 0 and at
+    255, 256, 257"""
+    K, bad = 258, (0, 255, 256, 257)
+    proofs, trs = cycle(world, K)
+    for k in bad:
+        proofs[k] = false_proof(ref, proofs[k])
+    want = (False, [k not in bad for k in range(K)])
+    v = world.verifier(sonic, "dense")
+    monkeypatch.delenv("SONIC_EACH_SLICE", raising=False)
+    assert both(lambda: v.verify_batch(proofs, trs, seed=SEED, each=True)) == want
+    monkeypatch.setenv(KNOB, "1")
+    got, names, loops = profiled(lambda: v.verify_batch(proofs, trs, seed=SEED, each=True))
+    assert got == want and "verify_batch:each_gpu" in names and loops == 1

@@ -56,14 +56,32 @@ def test_generated_frobenius_constants_are_their_definition(drivers, build):
     assert "FrobeniusConstants" not in hdr and "static const" not in hdr          # no run-time table, no function-local static
 
 
+def cycled(G, sizes=(0, 1, 2, 17, 16, 3)):
+    return " ".join(str(sizes[g % len(sizes)]) for g in range(G))
+
+
+# the layouts of tests/test_gpu_pairing_shapes.py and their pass counts: four passes (n >= 4097, also as 4096 + 1: the passes come from
+# n), every chunk edge, a launch bound beyond the buffers (G > 15 n / 16 over three passes), more groups than k_gt_plan has threads with
+# per = 2 and 3 groups a thread and uneven slices, and one long group behind 255 empty ones
+SHAPES = [("4097", 4), ("4096 1", 4), ("16 17 32 33 255 256 257 0 15", 3), ("257" + " 0" * 999, 3),
+          ("257 " + " ".join("1" if g in (1, 255, 256, 257, 999) or g % 29 == 27 else "0" for g in range(1, 1000)), 3),
+          (cycled(255), 3), (cycled(256), 3), (cycled(257), 3), (cycled(513), 3), (" ".join(str(g % 4) for g in range(600)), 3),
+          ("0 " * 255 + "4097" + " 1" * 10, 4)]
+
+
 @pytest.mark.parametrize("build", BUILDS)
 def test_segmented_product_equals_the_straight_loop(drivers, build):
     cases = ["0 1 2 3 17 300", "0", "0 0 0", "1", "16", "17", "16 16 0 17", "300", "257 0 1"]
-    got = run_driver(drivers[build], ["segments " + c for c in cases])
+    got = run_driver(drivers[build], ["segments " + c for c in cases + [c for c, _ in SHAPES]])
+    got, shaped = got[:len(cases)], got[len(cases):]
     assert len(got) == len(cases) and all(g.startswith("ok passes=") for g in got), got
     passes = [int(re.match(r"ok passes=(\d+)", g).group(1)) for g in got]
     # chunks of 16: 323 -> (<= 21 + 6) -> ... ; one pass while no group exceeds a chunk, three at 300
     assert passes[0] == 3 and passes[1] == 1 and passes[3] == 1 and passes[4] == 1 and passes[5] == 2 and passes[7] == 3
+    assert len(shaped) == len(SHAPES)
+    for (case, want), line in zip(SHAPES, shaped):
+        m = re.match(r"ok passes=(\d+) values=(\d+)$", line)
+        assert m and int(m.group(1)) == want and int(m.group(2)) == sum(int(x) for x in case.split()), (case[:60], line)
 
 
 @pytest.mark.parametrize("build", BUILDS)
