@@ -109,7 +109,7 @@ typedef struct sonic_verifier sonic_verifier_t;
  * sonic_prover_aggregate_core, sonic_verifier_verify_core_batch_helped, sonic_verifier_verify_core_fs_batch_helped,
  * sonic_verify_core_helped_digest; still 7, additions only: the updatable SRS -- sonic_srs_check, sonic_srs_update, sonic_srs_verify_update;
  * still 7, additions only: the G2 sums -- sonic_msm_g2, sonic_msm_g2_srs[_dev], sonic_msm_g2_walk_max; subgroup membership --
- * sonic_g1_subgroup_check, sonic_g2_subgroup_check; pairings -- sonic_pairing_check */
+ * sonic_g1_subgroup_check, sonic_g2_subgroup_check; pairings -- sonic_pairing_check; the opening chain alone -- sonic_open_batch_dense */
 int sonic_abi_version(void);
 int sonic_init(int device_ordinal);                 /* choose the DEFAULT GPU (first call wins) and make it the thread's HIP device; idempotent */
 int sonic_device_count(int* out);                   /* GPUs this process can see; SONIC_ERR_NO_DEVICE (and 0) without one */
@@ -297,6 +297,13 @@ int sonic_g1_sum_dev_partials(const uint8_t* blobs, int k, uint8_t out_g1[96]);
 int sonic_ntt_fr(uint8_t* data, int log2n, int inverse);
 /* dense product of two coefficient arrays (the `*` at Constraints.hs:61): out has na+nb-1 Fr */
 int sonic_poly_mul_fr(const uint8_t* a, int64_t na, const uint8_t* b, int64_t nb, uint8_t* out);
+/* the opening chain of prove() on caller-supplied dense polynomials, without the MSM: k (1 .. 16) openings over ONE exponent range
+ * [lo, lo + len), lo <= 0 <= lo + len - 1.  polys: k pointers to len canonical Fr each (coefficient of X^(lo + i) at i; equal pointers are
+ * allowed and share one device array); zs: k points, none zero (SONIC_ERR_INEXACT_DIVISION).  out_fz: the k values f_k(z_k); out_q (used
+ * when quotient != 0): k pointers to len - 1 Fr each, the coefficients of (f_k(X) - f_k(z_k)) / (X - z_k) over [lo, lo + len - 2].
+ * chunk: coefficients per GPU thread, 0 = what prove() takes at this length; 2 .. 16 force one (tests of the tile edges at small sizes) */
+int sonic_open_batch_dense(int k, const uint8_t* const* polys, int64_t lo, int64_t len, const uint8_t* zs, int quotient, int chunk,
+                           uint8_t* out_fz, uint8_t* const* out_q);
 /* the same with operands and result resident in HBM (device pointers to canonical Fr; d_out: na + nb - 1 elements) */
 int sonic_poly_mul_fr_dev(const void* d_a, int64_t na, const void* d_b, int64_t nb, void* d_out);
 /* bytes between consecutive points of an SRS basis / window table in HBM (128: one HBM line per 96-byte point); what a bucket walk

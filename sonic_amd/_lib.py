@@ -111,6 +111,7 @@ def lib() -> C.CDLL:
         "sonic_ntt_fr": [vp, i32, i32],
         "sonic_poly_mul_fr": [vp, i64, vp, i64, vp],
         "sonic_poly_mul_fr_dev": [vp, i64, vp, i64, vp],
+        "sonic_open_batch_dense": [i32, vp, i64, i64, vp, i32, i32, vp, vp],
         "sonic_msm_set_window": [i32],
         "sonic_srs_point_bytes": [],
         "sonic_msm_plan": [vp, i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)],
@@ -319,6 +320,7 @@ EXPORTED = [
     "sonic_msm_g2", "sonic_msm_g2_srs", "sonic_msm_g2_srs_dev", "sonic_msm_g2_walk_max",
     "sonic_g1_subgroup_check", "sonic_g2_subgroup_check",
     "sonic_pairing_check",
+    "sonic_open_batch_dense",
 ]
 
 

@@ -11,8 +11,11 @@
 //
 // Quotient identity: for e > 0, (X^e - z^e)/(X - z) = sum_{k<e} X^k z^{e-1-k}; for e < 0,
 // (X^e - z^e)/(X - z) = -sum_{m=1..|e|} X^{-m} z^{e+m-1}.  Collecting the coefficient of X^j gives
-// the two prefix-sum forms above, so openPoly is one elementwise pass, one additive scan and one
-// more elementwise pass -- no sequential Horner chain.
+// the two prefix-sum forms above, so the stand-alone openPoly (open_job) is one elementwise pass, one
+// additive scan and one more elementwise pass.  The openings of a proof (open_batch_enqueue) use the
+// same identity as two Horner recurrences cut into per-thread chunks -- see "Horner sweeps" below: a
+// chunked Horner chain is no more sequential than a thread's p = p * step, and needs no power of z per
+// coefficient.
 #include "internal.hpp"
 #include "poly.hpp"
 #include "csr.hpp"
@@ -20,8 +23,9 @@
 namespace sonic {
 
 // Elements per thread of k_scale_powers.  A thread pays ~45 products for its starting power x^(e0 + i) and x^256 and then 2 per
-// element, i.e. (45 + 2 PER) / PER products per element: 7.6 at PER = 8, 3.4 at 32.  These kernels touch ~77 n elements per proof
-// (two passes per opening), so at 8 they were ~5 % of a proof's instruction count -- which is what streamed proofs pay for.
+// element, i.e. (45 + 2 PER) / PER products per element: 7.6 at PER = 8, 3.4 at 32.  (Until round 8 a proof's openings ran through
+// these kernels too, two passes over ~38 n coefficients: at 8 they were ~5 % of a proof's instruction count.  The openings now take
+// the Horner sweeps below; the stand-alone openPoly, the aggregate and the power tables of prove.hip still come here.)
 #ifndef SONIC_SCALE_PER
 #define SONIC_SCALE_PER 32
 #endif
@@ -148,96 +152,164 @@ void poly_prefix_sum_enqueue(hipStream_t st, Fr* d, long n, DevBuf& tmp) {
   }
 }
 
-// ---- the same three steps for several openings at once (blockIdx.y = opening) -----------------
-// Prefix sums over tiles of 256 * EPT coefficients (EPT = 4 or 16: a tile per workgroup, fewer and fatter workgroups for long arrays -- see
-// scale_per); the tile offsets are added by the quotient kernel as it reads the prefixes, so there is no separate "apply" pass.
-template <int MODE>
-__global__ __launch_bounds__(256) void k_scale_powers_b(const OpenBatch b, long n, long e0, long lo_q, long nF, int PER, int tile_log) {
-  const int y = blockIdx.y;
-  const long base = (long)blockIdx.x * (256 * PER) + threadIdx.x;
-  // MODE 0: D = poly * z^(e0 + i);  MODE 2: q = numerator(P) * (z^-1)^(e0 + i), P = D + its tile's offset (the prefix sums), F = P[nF - 1]
-  const Fr* __restrict__ in = MODE == 0 ? b.poly[y] : b.D[y];
-  const Fr* __restrict__ tiles = b.tiles[y];
-  Fr* __restrict__ out = MODE == 0 ? b.D[y] : b.q[y];
-  Fr F;
-  if (MODE == 2) {
-    F = in[nF - 1];
-    if (((nF - 1) >> tile_log) > 0) F = fp_add(F, tiles[(nF - 1) >> tile_log]);
-    if (blockIdx.x == 0 && threadIdx.x == 0) *b.fz[y] = F;      // f(z): the last prefix
-  }
-  if (base >= n) return;
-  const Fr x = MODE == 0 ? b.zpair[y][0] : b.zpair[y][1], xinv = MODE == 0 ? b.zpair[y][1] : b.zpair[y][0];
-  const long e = e0 + base;
-  Fr p = e >= 0 ? fp_pow_u64(x, (uint64_t)e) : fp_pow_u64(xinv, (uint64_t)(-e));
-  const Fr step = fp_pow_u64(x, 256);
+// ---- Horner sweeps: several openings at once, without the power tables and without D (blockIdx.y = opening) ---------------------------
+// The quotient identity above, written as recurrences over the coefficient index i (X^0 at i0 = -lo, w = the quotient):
+//   below X^0, upward     w_i = z^-1 (w_{i-1} - f_i),   w_{-1} = 0          (i < i0)
+//   from X^0 on, downward w_i = f_{i+1} + z w_{i+1},    w_{len-1} = 0       (i >= i0)
+//   f(z) = f_{i0} + z w_{i0} - w_{i0-1}
+// Each side is a sequence x_t = step(x_{t-1}, a_t), t = 0 .. M - 1 (upward: a_t = f_t; downward: a_t = f_{len-1-t}), and every step is an
+// affine map of x with the same multiplier m (z^-1 or z).  A thread owns a chunk of L consecutive t.  k_sweep_chunks_b runs every chunk
+// from x = 0 (L products) and scans the chunk values over the workgroup's tile: chunks compose as x -> m^L x + b, so level o of the scan
+// multiplies by the one power m^(L o) (8 products a thread).  It leaves the carry into every chunk of a tile that itself starts from 0, and
+// the tile's value.  k_sweep_carries_b scans the tile values the same way (multiplier m^tile), which gives the carry into every tile and,
+// from the two sides' end values, f(z).  k_sweep_quotient_b repeats the recurrence from the true carry -- the chunk's carry within its tile
+// plus (m^L)^t times the tile's carry, the power read from a table of 256 -- and stores w (L + 1 products).  That is 2 + 9/L products per
+// coefficient and opening (plus 16 on the first wave of a workgroup for the scan's multipliers) instead of 4 + 90/PER, and the polynomial
+// read twice and the quotient written once instead of seven passes.  A sequential chain of L products per thread is what k_scale_powers'
+// p = p * step already is.
+// A side is padded IN FRONT to whole tiles (t < 0: no coefficient; x stays 0 there under both recurrences), so that every chunk that
+// carries anything is full and the last tile's inclusive value is the side's end value.
+// Threads take L consecutive 32-byte coefficients, loaded four at a time: one 128-byte line per lane and group of loads.
+// Openings that share their polynomial read it once each (through L2): one read feeding k recurrences would hold k x 8 registers of
+// state next to the four loaded coefficients and the product's temporaries, and OPEN_BATCH_MAX = 16 of them do not fit without scratch.
+struct SweepShape {
+  long len, i0;        // coefficients; index of X^0
+  int L;               // coefficients per thread (open_sweep_chunk)
+  long M[2], nb[2], pad[2];   // per side (0: below X^0, 1: from X^0 on): elements, tiles, padding in front
+};
+static SweepShape sweep_shape(long lo, long len, int chunk) {
+  SweepShape s;
+  s.len = len; s.i0 = -lo; s.L = chunk ? chunk : open_sweep_chunk(len);
+  const long tile = (long)SWEEP_BLOCK * s.L;
+  s.M[0] = s.i0; s.M[1] = len - 1 - s.i0;
+  for (int r = 0; r < 2; r++) { s.nb[r] = ceil_div(s.M[r], tile); s.pad[r] = s.nb[r] * tile - s.M[r]; }
+  return s;
+}
+// OpenBatch::tiles of one opening, NB = nb[0] + nb[1] tiles (side 0's first):
+//   [tile * 256 + t]          the carry into chunk t of the tile when the tile starts from 0
+//   [NB * 256 + tile]         the tile's value from 0 (k_sweep_chunks_b), then the carry into the tile (k_sweep_carries_b)
+//   [NB * 257 + side * 257 + t]  (m^L)^t for t < 256, and m^(256 L) at t = 256 (written only for a side of more than one tile)
+template <bool UP>
+__device__ __forceinline__ Fr sweep_step(const Fr& x, const Fr& a, const Fr& m) {
+  return UP ? fp_mul(fp_sub(x, a), m) : fp_add(a, fp_mul(x, m));
+}
+// elements t0 .. t0 + L - 1 of a side from the carry x; `top` = len - 1 (downward side: a_t = f[top - t], w goes to q[top - 1 - t])
+template <bool UP, bool STORE>
+__device__ __forceinline__ Fr sweep_chunk(const Fr* __restrict__ f, Fr* __restrict__ q, long t0, int L, long top, Fr x, const Fr& m) {
 #pragma unroll 1
-  for (int k = 0; k < PER; k++) {
-    const long i = base + (long)k * 256;
-    if (i >= n) break;
-    Fr v;
-    if (MODE == 0) v = fp_mul(in[i], p);
-    else {
-      Fr P = in[i];
-      if ((i >> tile_log) > 0) P = fp_add(P, tiles[i >> tile_log]);
-      v = fp_mul((lo_q + i >= 0) ? fp_sub(F, P) : fp_neg(P), p);
+  for (int g = 0; g < L; g += 4) {
+    Fr a[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const long t = t0 + g + j;
+      a[j] = (g + j < L && t >= 0) ? f[UP ? t : top - t] : Fr::zero();
     }
-    out[i] = v;
-    p = fp_mul(p, step);
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const long t = t0 + g + j;
+      if (g + j < L && t >= 0) {
+        x = sweep_step<UP>(x, a[j], m);
+        if (STORE) q[UP ? t : top - 1 - t] = x;
+      }
+    }
   }
+  return x;
 }
-template <int EPT>
-__global__ __launch_bounds__(256) void k_prefix_tiles_b(const OpenBatch b, long n) {
-  __shared__ Fr sh[256];
-  Fr* __restrict__ d = b.D[blockIdx.y];
-  const long base = (long)blockIdx.x * (256 * EPT) + threadIdx.x * EPT;
-  Fr s = Fr::zero();
-  // (two passes over the thread's EPT consecutive elements instead of EPT live values: 16 x 8 registers would not leave room for the scan)
-  for (int k = 0; k < EPT; k++) if (base + k < n) s = fp_add(s, d[base + k]);
-  Fr incl = block_inclusive_scan_fr(s, sh);
-  Fr run = fp_sub(incl, s);
-  for (int k = 0; k < EPT; k++) if (base + k < n) { run = fp_add(run, d[base + k]); d[base + k] = run; }
-  if (threadIdx.x == 255) b.tiles[blockIdx.y][blockIdx.x] = incl;
-}
-__global__ __launch_bounds__(256) void k_prefix_top_b(const OpenBatch b, long ntiles) {
-  __shared__ Fr sh[256];
-  __shared__ Fr carry_sh;
-  Fr* __restrict__ tile_sums = b.tiles[blockIdx.x];
-  if (threadIdx.x == 0) carry_sh = Fr::zero();
+__global__ __launch_bounds__(SWEEP_BLOCK) void k_sweep_chunks_b(const OpenBatch b, const SweepShape s) {
+  __shared__ Fr sh[SWEEP_BLOCK];
+  __shared__ Fr mu[9];                                   // m^(L 2^k)
+  const int y = blockIdx.y, t = threadIdx.x;
+  const int r = (long)blockIdx.x >= s.nb[0];
+  const long tile = (long)blockIdx.x - (r ? s.nb[0] : 0), NB = s.nb[0] + s.nb[1];
+  const Fr m = b.zpair[y][r ? 0 : 1];
+  Fr* __restrict__ base = b.tiles[y];
+  if (t < 64) {                                          // the first wave: the scan's multipliers, once per workgroup
+    Fr p = fp_pow_u64(m, (uint64_t)s.L);
+    for (int k = 0; k < 9; k++) {
+      if (t == 0) mu[k] = p;
+      if (k < 8) p = fp_mul(p, p);
+    }
+  }
+  const long t0 = (tile * SWEEP_BLOCK + t) * s.L - s.pad[r];
+  sh[t] = r == 0 ? sweep_chunk<true, false>(b.poly[y], nullptr, t0, s.L, 0, Fr::zero(), m)
+                 : sweep_chunk<false, false>(b.poly[y], nullptr, t0, s.L, s.len - 1, Fr::zero(), m);
   __syncthreads();
-  for (long base = 0; base < ntiles; base += 256) {
-    long idx = base + threadIdx.x;
-    Fr v = idx < ntiles ? tile_sums[idx] : Fr::zero();
-    Fr incl = block_inclusive_scan_fr(v, sh);
-    Fr carry = carry_sh;
-    if (idx < ntiles) tile_sums[idx] = fp_add(fp_sub(incl, v), carry);   // exclusive
+  for (int k = 0, o = 1; o < SWEEP_BLOCK; o <<= 1, k++) {
+    const Fr x = t >= o ? sh[t - o] : Fr::zero();
     __syncthreads();
-    if (threadIdx.x == 255) carry_sh = fp_add(carry, incl);
+    sh[t] = fp_add(sh[t], fp_mul(x, mu[k]));
     __syncthreads();
   }
+  base[(long)blockIdx.x * SWEEP_BLOCK + t] = t > 0 ? sh[t - 1] : Fr::zero();
+  if (t == SWEEP_BLOCK - 1) base[NB * SWEEP_BLOCK + blockIdx.x] = sh[t];
+  if (tile == 0 && s.nb[r] > 1) {                        // the tile carries' power table, by the side's first workgroup
+    Fr p = Fr::one();
+    for (int k = 0; k < 8; k++) if ((t >> k) & 1) p = fp_mul(p, mu[k]);
+    Fr* __restrict__ pw = base + NB * (SWEEP_BLOCK + 1) + r * (SWEEP_BLOCK + 1);
+    pw[t] = p;
+    if (t == 0) pw[SWEEP_BLOCK] = mu[8];
+  }
 }
-// fz_k = the last prefix, for a batch whose quotients are not wanted (an evaluation only)
-__global__ void k_last_prefix_b(const OpenBatch b, long len, int tile_log) {
-  const int y = blockIdx.x;
-  Fr F = b.D[y][len - 1];
-  if (((len - 1) >> tile_log) > 0) F = fp_add(F, b.tiles[y][(len - 1) >> tile_log]);
-  *b.fz[y] = F;
+// one workgroup per opening, a half of it per side: the carries into the tiles, in blocks of 256 tiles (the carry of a block enters the
+// next block's first tile before the scan), the sides' end values, and f(z)
+__global__ __launch_bounds__(2 * SWEEP_BLOCK) void k_sweep_carries_b(const OpenBatch b, const SweepShape s) {
+  __shared__ Fr sh[2][SWEEP_BLOCK];
+  __shared__ Fr fin[2];
+  const int y = blockIdx.x, r = threadIdx.x / SWEEP_BLOCK, u = threadIdx.x % SWEEP_BLOCK;
+  const long NB = s.nb[0] + s.nb[1], nt = s.nb[r], most = s.nb[0] > s.nb[1] ? s.nb[0] : s.nb[1];
+  Fr* __restrict__ base = b.tiles[y];
+  Fr* __restrict__ tt = base + NB * SWEEP_BLOCK + (r ? s.nb[0] : 0);
+  Fr last = Fr::zero();
+  if (most <= 1) {                                       // (a single tile starts from 0, and its value is the side's end value)
+    if (nt == 1) last = tt[0];
+  } else {
+    const Fr muT = nt > 1 ? base[NB * (SWEEP_BLOCK + 1) + r * (SWEEP_BLOCK + 1) + SWEEP_BLOCK] : Fr::zero();
+    Fr carry = Fr::zero();
+    for (long bs = 0; bs < most; bs += SWEEP_BLOCK) {
+      const long idx = bs + u;
+      Fr v = idx < nt ? tt[idx] : Fr::zero();
+      if (u == 0) v = fp_add(v, fp_mul(carry, muT));
+      sh[r][u] = v;
+      __syncthreads();
+      Fr mu = muT;
+      for (int o = 1; o < SWEEP_BLOCK; o <<= 1) {
+        const Fr x = u >= o ? sh[r][u - o] : Fr::zero();
+        __syncthreads();
+        sh[r][u] = fp_add(sh[r][u], fp_mul(x, mu));
+        __syncthreads();
+        mu = fp_mul(mu, mu);
+      }
+      if (idx < nt) tt[idx] = u > 0 ? sh[r][u - 1] : carry;
+      if (nt - 1 >= bs && nt - 1 < bs + SWEEP_BLOCK) last = sh[r][nt - 1 - bs];
+      carry = sh[r][SWEEP_BLOCK - 1];
+      __syncthreads();
+    }
+  }
+  if (u == 0) fin[r] = last;
+  __syncthreads();
+  if (threadIdx.x == 0) *b.fz[y] = fp_sub(fp_add(b.poly[y][s.i0], fp_mul(b.zpair[y][0], fin[1])), fin[0]);
 }
-void open_batch_enqueue(hipStream_t st, const OpenBatch& b, long lo, long len, bool quotient) {
+__global__ __launch_bounds__(SWEEP_BLOCK) void k_sweep_quotient_b(const OpenBatch b, const SweepShape s) {
+  const int y = blockIdx.y, t = threadIdx.x;
+  const int r = (long)blockIdx.x >= s.nb[0];
+  const long tile = (long)blockIdx.x - (r ? s.nb[0] : 0), NB = s.nb[0] + s.nb[1];
+  const long t0 = (tile * SWEEP_BLOCK + t) * s.L - s.pad[r];
+  if (t0 + s.L <= 0) return;                             // all padding
+  const Fr m = b.zpair[y][r ? 0 : 1];
+  const Fr* __restrict__ base = b.tiles[y];
+  Fr x = base[(long)blockIdx.x * SWEEP_BLOCK + t];
+  if (tile > 0) x = fp_add(x, fp_mul(base[NB * (SWEEP_BLOCK + 1) + r * (SWEEP_BLOCK + 1) + t], base[NB * SWEEP_BLOCK + blockIdx.x]));
+  if (r == 0) sweep_chunk<true, true>(b.poly[y], b.q[y], t0, s.L, 0, x, m);
+  else sweep_chunk<false, true>(b.poly[y], b.q[y], t0, s.L, s.len - 1, x, m);
+}
+void open_batch_enqueue(hipStream_t st, const OpenBatch& b, long lo, long len, bool quotient, int chunk) {
   if (b.k <= 0 || len <= 0) return;
   const unsigned k = (unsigned)b.k;
-  const int tile_log = len >= 65536 ? 12 : 10;           // 4096- or 1024-coefficient tiles (OpenBatch::tiles holds len / 1024 + 2 entries)
-  const int per = scale_per(len);
-  LAUNCH(k_scale_powers_b<0>, dim3((unsigned)ceil_div(len, 256L * per), k), 256, 0, st, b, len, lo, 0L, 0L, per, tile_log);
-  const long ntiles = (len + (1L << tile_log) - 1) >> tile_log;
-  if (tile_log == 12) LAUNCH(k_prefix_tiles_b<16>, dim3((unsigned)ntiles, k), 256, 0, st, b, len);
-  else LAUNCH(k_prefix_tiles_b<4>, dim3((unsigned)ntiles, k), 256, 0, st, b, len);
-  if (ntiles > 1) LAUNCH(k_prefix_top_b, k, 256, 0, st, b, ntiles);
-  if (!quotient) { LAUNCH(k_last_prefix_b, k, 1, 0, st, b, len, tile_log); return; }
-  // (quotient exponents [lo, lo + len - 2]: z^{-1-j} = (z^-1)^{1 + j}; the launch also writes f(z) = the last prefix.  A polynomial of
-  // ONE coefficient has an empty quotient: the launch then only writes f(z))
-  const long qn = len > 1 ? len - 1 : 1;
-  const int per2 = scale_per(qn);
-  LAUNCH(k_scale_powers_b<2>, dim3((unsigned)ceil_div(qn, 256L * per2), k), 256, 0, st, b, len - 1 > 0 ? len - 1 : 0, 1 + lo, lo, len, per2, tile_log);
+  const SweepShape s = sweep_shape(lo, len, chunk);
+  const unsigned NB = (unsigned)(s.nb[0] + s.nb[1]);     // (a polynomial of ONE coefficient has no tiles and an empty quotient: only f(z) = f_0)
+  if (NB) LAUNCH(k_sweep_chunks_b, dim3(NB, k), SWEEP_BLOCK, 0, st, b, s);
+  LAUNCH(k_sweep_carries_b, k, 2 * SWEEP_BLOCK, 0, st, b, s);
+  if (quotient && NB) LAUNCH(k_sweep_quotient_b, dim3(NB, k), SWEEP_BLOCK, 0, st, b, s);
 }
 
 // ---- prover-specific builders ----------------------------------------------------------------

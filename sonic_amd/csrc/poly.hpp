@@ -31,20 +31,35 @@ void fr_mul_scalar_enqueue(hipStream_t st, const Fr* a, const Fr* b, Fr* out);
 void scale_terms_enqueue(hipStream_t st, const int64_t* e, const Fr* c, long nt, const Fr* pair, Fr* out);
 void sparse_to_dense_enqueue(hipStream_t st, const int64_t* exps, const Fr* coeffs, long nt, long lo, Fr* dense);
 
-// Several openings of polynomials over ONE exponent range [lo, lo + len) as one launch per step (round 6): D_k[i] = poly_k[i] z_k^(lo + i),
-// inclusive prefix sums of every D_k, fz_k = the last prefix, q_k = the quotient (f_k(X) - f_k(z_k)) / (X - z_k) over [lo, lo + len - 2].
-// What poly_scale_powers / poly_prefix_sum / poly_quotient do for one opening in six launches, for up to OPEN_BATCH_MAX openings in
-// five: the openings of a group (r(X,1) at z and yz; s(X,y_j) at z_j and u; s(u,Y) at y_1 .. y_Q and v) share their polynomial.
+// Several openings of polynomials over ONE exponent range [lo, lo + len), lo <= 0 <= lo + len - 1, as one launch per step: fz_k = f_k(z_k)
+// and q_k = the quotient (f_k(X) - f_k(z_k)) / (X - z_k) over [lo, lo + len - 2], by two Horner sweeps per side of X^0 (poly.hip, "Horner
+// sweeps") -- what poly_scale_powers / poly_prefix_sum / poly_quotient do for one opening in six launches and seven array passes, for up to
+// OPEN_BATCH_MAX openings in three launches and three passes.  The openings of a group (r(X,1) at z and yz; s(X,y_j) at z_j and u;
+// s(u,Y) at y_1 .. y_Q and v) share their polynomial.
 constexpr int OPEN_BATCH_MAX = 16;
+constexpr int SWEEP_BLOCK = 256;    // threads of a sweep workgroup: a tile is SWEEP_BLOCK chunks of open_sweep_chunk(len) coefficients
+// Coefficients per thread (a chunk).  16 for arrays long enough to fill the chip with such threads; a short array keeps ~64 workgroups
+// (see scale_per in poly.hip: n = 2^14 would otherwise run on 12 of them), never below 2
+constexpr int SWEEP_CHUNK_MAX = 16;
+inline int open_sweep_chunk(long len) {
+  const long L = len / ((long)SWEEP_BLOCK * 64);
+  return (int)(L > SWEEP_CHUNK_MAX ? SWEEP_CHUNK_MAX : (L < 2 ? 2 : L));
+}
+// Entries of OpenBatch::tiles: for at most len / tile + 2 tiles over the two sides of X^0 (tile = SWEEP_BLOCK * chunk coefficients), the
+// carry into each of a tile's SWEEP_BLOCK chunks and one tile value; then, per side, the SWEEP_BLOCK powers (z^+-chunk)^t and z^+-tile
+// (chunk: 0 = open_sweep_chunk(len), what prove() runs; 2 .. SWEEP_CHUNK_MAX: that chunk at any length, for tests of the tile edges)
+inline long open_sweep_entries(long len, int chunk = 0) {
+  const long tile = (long)SWEEP_BLOCK * (chunk ? chunk : open_sweep_chunk(len));
+  return (len / tile + 2) * (SWEEP_BLOCK + 1) + 2 * (SWEEP_BLOCK + 1);
+}
 struct OpenBatch {
   int k;
-  const Fr* poly[OPEN_BATCH_MAX];
-  Fr* D[OPEN_BATCH_MAX];            // len + 1 entries each
-  Fr* q[OPEN_BATCH_MAX];            // len + 1 entries each
-  Fr* tiles[OPEN_BATCH_MAX];        // ceil(len / 1024) + 1 entries each
-  const Fr* zpair[OPEN_BATCH_MAX];  // {z, z^-1}
+  const Fr* poly[OPEN_BATCH_MAX];   // len entries each; equal pointers are fine
+  Fr* q[OPEN_BATCH_MAX];            // len + 1 entries each (unused when quotient = false)
+  Fr* tiles[OPEN_BATCH_MAX];        // open_sweep_entries(len, chunk) entries each: chunk carries, tile values, power tables
+  const Fr* zpair[OPEN_BATCH_MAX];  // {z, z^-1}, z != 0
   Fr* fz[OPEN_BATCH_MAX];           // where f(z) goes (never null)
 };
-void open_batch_enqueue(hipStream_t st, const OpenBatch& b, long lo, long len, bool quotient = true);      // quotient = false: only the evaluations fz_k
+void open_batch_enqueue(hipStream_t st, const OpenBatch& b, long lo, long len, bool quotient = true, int chunk = 0);      // quotient = false: only the evaluations fz_k
 
 }  // namespace sonic

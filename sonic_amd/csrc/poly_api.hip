@@ -276,6 +276,56 @@ int sonic_poly_mul_fr(const uint8_t* a, int64_t na, const uint8_t* b, int64_t nb
   API_END
 }
 
+// The batched opening chain of prove() (poly.hip, open_batch_enqueue) on caller-supplied dense polynomials: k openings over ONE exponent
+// range [lo, lo + len), lo <= 0 <= lo + len - 1.  Equal pointers in `polys` are uploaded once and share their device array, as the
+// openings of a group in a proof do.  chunk: coefficients per thread, 0 for what prove() takes at that length.  Upload, the chain,
+// download; no MSM.
+int sonic_open_batch_dense(int k, const uint8_t* const* polys, int64_t lo, int64_t len, const uint8_t* zs, int quotient, int chunk,
+                           uint8_t* out_fz, uint8_t* const* out_q) {
+  API_BEGIN
+  if (k < 1 || k > OPEN_BATCH_MAX || (chunk != 0 && (chunk < 2 || chunk > SWEEP_CHUNK_MAX)) || !polys || !zs || !out_fz || len < 1 || lo > 0 || lo + len - 1 < 0 || (quotient && len > 1 && !out_q))
+    return SONIC_ERR_INVALID_ARG;
+  for (int i = 0; i < k; i++) {
+    if (!polys[i] || (quotient && len > 1 && !out_q[i])) return SONIC_ERR_INVALID_ARG;
+    if (bytes_are_zero(zs + 32 * i, 32)) { set_error("sonic_open_batch_dense: z_%d = 0 (the chain divides by z)", i); return SONIC_ERR_INEXACT_DIVISION; }
+  }
+  std::lock_guard<std::mutex> g(call_mutex());
+  hipStream_t st = default_stream();
+  DevBuf flags(4), zin(sizeof(Fr) * k), zpair(2 * sizeof(Fr) * k), fz(sizeof(Fr) * k);
+  std::vector<DevBuf> f((size_t)k), q((size_t)k), tiles((size_t)k);
+  HIP_OK(hipMemsetAsync(flags.p, 0, 4, st));
+  HIP_OK(hipMemcpyAsync(zin.p, zs, 32 * (size_t)k, hipMemcpyHostToDevice, st));
+  fr_to_mont_enqueue(st, zin.as<Fr>(), k, flags.as<int>());
+  fr_with_inverse_enqueue(st, zin.as<Fr>(), k, zpair.as<Fr>());
+  OpenBatch b;
+  memset(&b, 0, sizeof b);
+  b.k = k;
+  for (int i = 0; i < k; i++) {
+    int same = -1;
+    for (int j = 0; j < i && same < 0; j++) if (polys[j] == polys[i]) same = j;
+    if (same < 0) {
+      f[i].alloc(sizeof(Fr) * len);
+      HIP_OK(hipMemcpyAsync(f[i].p, polys[i], 32 * (size_t)len, hipMemcpyHostToDevice, st));
+      fr_to_mont_enqueue(st, f[i].as<Fr>(), len, flags.as<int>());
+      b.poly[i] = f[i].as<Fr>();
+    } else {
+      b.poly[i] = b.poly[same];
+    }
+    q[i].alloc(sizeof(Fr) * (len + 1));
+    tiles[i].alloc(sizeof(Fr) * open_sweep_entries(len, chunk));
+    b.q[i] = q[i].as<Fr>(); b.tiles[i] = tiles[i].as<Fr>();
+    b.zpair[i] = zpair.as<Fr>() + 2 * i; b.fz[i] = fz.as<Fr>() + i;
+  }
+  open_batch_enqueue(st, b, lo, len, quotient != 0, chunk);
+  fr_from_mont_enqueue(st, fz.as<Fr>(), k);
+  if (quotient) for (int i = 0; i < k; i++) fr_from_mont_enqueue(st, q[i].as<Fr>(), len - 1);
+  int fl = read_flags(st, flags);
+  if (fl) return flags_to_status(fl, "sonic_open_batch_dense");
+  HIP_OK(hipMemcpy(out_fz, fz.p, 32 * (size_t)k, hipMemcpyDeviceToHost));
+  if (quotient && len > 1) for (int i = 0; i < k; i++) HIP_OK(hipMemcpy(out_q[i], q[i].p, 32 * (size_t)(len - 1), hipMemcpyDeviceToHost));
+  API_END
+}
+
 // the same product with both operands and the result resident in HBM (canonical Fr, device pointers; d_out: na + nb - 1
 // elements): what bench.py times for the NTT roofline -- the three transforms and the pointwise product alone on the chip
 int sonic_poly_mul_fr_dev(const void* d_a, int64_t na, const void* d_b, int64_t nb, void* d_out) {

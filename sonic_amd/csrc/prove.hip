@@ -151,9 +151,10 @@ MsmJob open_job_at_zero(hipStream_t st, const sonic_srs* srs, const Fr* poly, lo
 struct PendingOpen { const Fr* poly; long lo, len; const Fr* zp; Fr* fz; MsmSlot* slot; long slot_index; Scratch* sc; };
 // entry i of a batch: the opening of `poly` (len coefficients) at zp = {z, z^-1}, worked in `sc`, grown to fit; fz null: f(z) is not kept
 static void open_batch_set(OpenBatch& b, int i, Scratch& sc, const Fr* poly, long len, const Fr* zp, Fr* fz) {
-  sc.reserve(len);
-  sc.scan.ensure(sizeof(Fr) * (len / 1024 + 2));
-  b.poly[i] = poly; b.D[i] = sc.D.as<Fr>(); b.q[i] = sc.q.as<Fr>(); b.tiles[i] = sc.scan.as<Fr>();
+  sc.q.ensure(sizeof(Fr) * (len + 1));                   // (no D: the sweeps read the polynomial itself)
+  sc.fz_discard.ensure(sizeof(Fr));
+  sc.scan.ensure(sizeof(Fr) * open_sweep_entries(len));
+  b.poly[i] = poly; b.q[i] = sc.q.as<Fr>(); b.tiles[i] = sc.scan.as<Fr>();
   b.zpair[i] = zp; b.fz[i] = fz ? fz : sc.fz_discard.as<Fr>();
 }
 static void open_jobs_batched(hipStream_t st, const sonic_srs* srs, const PendingOpen* ops, int k, int* d_flags, MsmJob* jobs_out) {
