@@ -68,6 +68,8 @@ module Sonic.HIP
   , CoreProof(..), coreOf, decodeCoreProof, encodeCoreProof, proveCore, submitCore, collectCore, proveCoreFs, verifyCore, verifyCoreBatch
     -- * Helped verification: one aggregate signature for K core proofs
   , aggregateCore, fsWeightsDigest, verifyCoreBatchHelped
+    -- * R1CS front end
+  , R1CS(..), R1csMatrix(..), newR1cs, r1csCircuit, r1csAssignI64
   ) where
 
 import Protolude hiding (check)
@@ -187,6 +189,12 @@ foreign import ccall safe   "sonic_verifier_verify_core_batch_helped" c_verify_c
 foreign import ccall safe   "sonic_verify_core_csr"       c_verify_core_csr :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> IO CInt
 foreign import ccall safe   "sonic_verifier_verify_core_batch" c_verify_core_batch :: Ptr VerifierHandle -> Int64 -> Ptr Word8 -> CInt -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_verifier_verify_fs_batch_cs" c_verify_fs_batch_cs :: Ptr VerifierHandle -> Int64 -> Ptr Word8 -> CInt -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> Ptr Word8 -> IO CInt
+-- R1CS front end (ABI 7, additions): A, B, C resident on one GPU, compiled to a Sonic CSR, witnesses turned into assignments
+foreign import ccall safe   "sonic_r1cs_new"              c_r1cs_new       :: Int64 -> Int64 -> Int64 -> Ptr R1csMatrix -> Ptr R1csMatrix -> Ptr R1csMatrix -> Ptr (Ptr R1csHandle) -> IO CInt
+foreign import ccall safe   "&sonic_r1cs_free"            p_r1cs_free      :: FunPtr (Ptr R1csHandle -> IO ())
+foreign import ccall safe   "sonic_r1cs_shape"            c_r1cs_shape     :: Ptr R1csHandle -> Ptr Int64 -> IO CInt
+foreign import ccall safe   "sonic_r1cs_circuit"          c_r1cs_circuit   :: Ptr R1csHandle -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_r1cs_assign"           c_r1cs_assign    :: Ptr R1csHandle -> Int64 -> Ptr () -> CInt -> CInt -> Int64 -> Ptr () -> Ptr () -> Ptr () -> Ptr () -> Int64 -> Ptr Word8 -> Ptr Int64 -> IO CInt
 
 -- ---------------------------------------------------------------------------------------------------------------------
 -- status codes -> the reference's failure behaviour (it panics: Protocol.hs:55, CommitmentScheme.hs:70-73, :44)
@@ -930,6 +938,65 @@ proveBatchI64 ps@(p0 : _) asgs = do
         BSI.create (psz * k) $ \out ->
           check =<< c_prove_batch_src arr np (fromIntegral k) src nullPtr ptr out nullPtr
   pure (zip (map (decodeProof q) (chunks psz bytes)) (map snd drawn))
+
+-- ---------------------------------------------------------------------------------------------------------------------
+-- R1CS front end (include/sonic_hip.h, "R1CS front end"): three CSR matrices A, B, C with <A_i, z> <B_i, z> = <C_i, z>, column 0 the
+-- constant one and columns 1..nPub the public inputs, compiled under layout 1 to a Sonic constraint system of n = m + N / 2 gates and
+-- Q = 3m + nPub linear constraints.  Prove such circuits with core proofs: Q is of the order of n.
+-- ---------------------------------------------------------------------------------------------------------------------
+data R1csHandle
+
+-- | sonic_r1cs_matrix_t: 24 bytes -- row_ptr (m + 1 int64), col (int64), val (32-byte canonical Fr) at 0, 8, 16
+data R1csMatrix = R1csMatrix { rmRowPtr :: Ptr Int64, rmCol :: Ptr Int64, rmVal :: Ptr Word8 }
+
+instance Storable R1csMatrix where
+  sizeOf _    = 24
+  alignment _ = 8
+  peek p = R1csMatrix <$> peekByteOff p 0 <*> peekByteOff p 8 <*> peekByteOff p 16
+  poke p R1csMatrix{..} = do pokeByteOff p 0 rmRowPtr; pokeByteOff p 8 rmCol; pokeByteOff p 16 rmVal
+
+-- | the handle and its shape: gates, linear constraints, entries of the Sonic CSR, variable gates
+data R1CS = R1CS { r1csHandle :: ForeignPtr R1csHandle, r1csN, r1csQ, r1csNnz, r1csG :: Int }
+
+-- | sonic_r1cs_new over rows given as [(column, coefficient)] with strictly increasing columns
+newR1cs :: Int -> Int -> [[(Int, Fr)]] -> [[(Int, Fr)]] -> [[(Int, Fr)]] -> IO R1CS
+newR1cs bigN nPub as bs cs = libraryReady `seq` withMat as (\pa -> withMat bs (\pb -> withMat cs (\pc -> alloca $ \out -> allocaArray 4 $ \shp -> do
+    check =<< c_r1cs_new (fromIntegral (length as)) (fromIntegral bigN) (fromIntegral nPub) pa pb pc out
+    fp <- newForeignPtr p_r1cs_free =<< peek out
+    withForeignPtr fp $ \h -> check =<< c_r1cs_shape h shp
+    [n, q, z, g] <- map fromIntegral <$> mapM (peekElemOff shp) [0 .. 3 :: Int]
+    pure R1CS { r1csHandle = fp, r1csN = n, r1csQ = q, r1csNnz = z, r1csG = g })))
+  where
+    withMat :: [[(Int, Fr)]] -> (Ptr R1csMatrix -> IO a) -> IO a
+    withMat rows f =
+      withArray (scanl (+) 0 (map (fromIntegral . length) rows) :: [Int64]) $ \prp ->
+        withArray (map (fromIntegral . fst) (concat rows) :: [Int64]) $ \pcol ->
+          withFrs (map snd (concat rows)) $ \pval -> with (R1csMatrix prp pcol pval) f
+
+-- | the compiled Sonic CSR (sonic_r1cs_circuit): row_ptr (3Q + 1), col, val, and the constants with the public slots zero
+r1csCircuit :: R1CS -> IO ([Int64], [Int64], [Fr], [Fr])
+r1csCircuit R1CS{..} = withForeignPtr r1csHandle $ \h ->
+  allocaArray (3 * r1csQ + 1) $ \prp -> allocaArray (max 1 r1csNnz) $ \pcol ->
+   allocaBytes (32 * max 1 r1csNnz) $ \pval -> allocaBytes (32 * r1csQ) $ \pcs -> do
+    check =<< c_r1cs_circuit h prp pcol pval pcs
+    vb <- BS.packCStringLen (castPtr pval, 32 * r1csNnz)
+    csb <- BS.packCStringLen (castPtr pcs, 32 * r1csQ)
+    rp <- mapM (peekElemOff prp) [0 .. 3 * r1csQ]
+    cl <- mapM (peekElemOff pcol) [0 .. r1csNnz - 1]
+    pure (rp, cl, map frFromBytes (take r1csNnz (chunks 32 vb)), map frFromBytes (chunks 32 csb))
+
+-- | K witnesses of N machine integers each, on the host (sonic_r1cs_assign, SONIC_WIT_I64): the planes are written to three device
+--   buffers of K n 32 bytes on the handle's GPU, packed; the result is each witness's constants and its (broken gates, first or -1)
+r1csAssignI64 :: R1CS -> [[Int64]] -> Ptr () -> Ptr () -> Ptr () -> IO [([Fr], (Int64, Int64))]
+r1csAssignI64 R1CS{..} zs dL dR dO = withForeignPtr r1csHandle $ \h -> do
+  let k = length zs
+  withArray (concat zs) $ \pz -> allocaArray (2 * k) $ \pbad -> do
+    csb <- BSI.create (32 * r1csQ * k) $ \pcs ->
+      check =<< c_r1cs_assign h (fromIntegral k) (castPtr pz) 1 0 0 nullPtr dL dR dO 0 pcs pbad
+    bad <- mapM (peekElemOff pbad) [0 .. 2 * k - 1]
+    let pairs (a : b : r) = (a, b) : pairs r
+        pairs _ = []
+    pure (zip (map (map frFromBytes . chunks 32) (chunks (32 * r1csQ) csb)) (pairs bad))
 
 -- | the batched verifier's handle (sonic_verifier_new_csr): the circuit resident on the GPU; keeps the SRS alive as long as the handle
 data Verifier = Verifier { verifierHandle :: ForeignPtr VerifierHandle, verifierSrs :: SRS, verifierQ :: Int }

@@ -930,6 +930,65 @@ int sonic_srs_check(const sonic_srs_t* srs, const uint8_t seed[32], int* failed)
 int sonic_srs_update(const sonic_srs_t* srs, const uint8_t x1[32], const uint8_t alpha1[32], const uint8_t seed[32], sonic_srs_t** out, uint8_t proof[448]);
 int sonic_srs_verify_update(const sonic_srs_t* old_srs, const sonic_srs_t* new_srs, const uint8_t proof[448], int check_new, int* ok);
 
+/* ---- R1CS front end (ABI 7, additions only) ----
+ * A layer in front of the entry points above for callers who arrive with a rank-1 constraint system: three sparse matrices A, B, C and
+ * witness vectors z with <A_i, z> <B_i, z> = <C_i, z> for every row i.  A handle compiles the matrices into a Sonic constraint system (the
+ * CSR that sonic_prover_new_csr takes) and turns K witness vectors into K assignments and their constants on the GPU: a batched sparse
+ * matrix-vector product over Fr whose result lies in device memory, where a witness source reads it.
+ *
+ * The mapping ("layout 1", normative).
+ *   Input.  A, B, C: m >= 1 rows over N >= 1 columns, each canonical CSR as the gate-weight CSR is: row_ptr has m + 1 int64 entries,
+ *   starts at 0 and does not decrease; col lies in [0, N) and strictly increases within a row; val is 32-byte canonical Fr; explicit zeros
+ *   are allowed and stay entries.  Column 0 is the constant one (z[0] = 1), columns 1..n_pub are the public inputs (0 <= n_pub <= N - 1),
+ *   the rest are private.
+ *   Gates.  n = m + g with g = N / 2 (rounded down); columns are 0-based.  Constraint gate i < m: aL[i] = <A_i, z>, aR[i] = <B_i, z>,
+ *   aO[i] = <C_i, z> -- the C side, not the product, so an unsatisfied row is a broken multiplication gate i.  Variable j >= 1 has the
+ *   home(j) = (wL if j - 1 is even, else wR; gate m + (j - 1) / 2): aL and aR of a variable gate hold its two variables (a missing partner,
+ *   N even, is 0) and aO their product.
+ *   Linear constraints.  Q = 3m + n_pub:
+ *     row i            aL[i] - sum_{j >= 1} A_ij home(j) = A_i0        cs = A_i0 (0 if absent)
+ *     row m + i        the same for B over aR[i]                       cs = B_i0
+ *     row 2m + i       the same for C over aO[i]                       cs = C_i0
+ *     row 3m + k - 1   home(k) = z[k],  k = 1..n_pub                   cs = z[k]
+ *   In the stacked CSR of 3Q rows (wL rows, wR rows, wO rows) the weight 1 sits at (wL, q, i) for A rows, (wR, q, i) for B rows, (wO, q, i)
+ *   for C rows and at home(k) for the public rows; the weight r - A_ij (0 for an explicit zero) at (wL or wR by home(j), q, home gate).
+ *   Within a row every column is distinct and increasing; no entries are merged:
+ *     nnz = nnz(A) + nnz(B) + nnz(C) - (entries in column 0) + 3m + n_pub.
+ *   Constants.  The first 3m entries of cs depend on the circuit alone, the last n_pub are the public inputs: the split that
+ *   sonic_prover_set_constants and the batches' cs serve.
+ *
+ *   r1cs_new[_on]   validates (a structure violation, n_pub > N - 1, or n, N or an entry count beyond 32 bits: SONIC_ERR_INVALID_ARG with a
+ *                   message that names matrix and row; a value >= r: SONIC_ERR_BAD_ENCODING) and uploads A, B, C to one GPU.
+ *   r1cs_shape      out = {n, Q, nnz of the Sonic CSR, g}.
+ *   r1cs_circuit    host only: row_ptr[3Q + 1], col[nnz], val[32 nnz] and cs_fixed[32 Q] (public slots zero).
+ *   r1cs_assign     K witnesses z_k (N elements each; kind SONIC_WIT_FR32 or SONIC_WIT_I64, on_device, z_stride in bytes with 0 = packed,
+ *                   hip_stream: all as a witness source's, with its alignment, ordering and device rules) -> the three planes d_aL, d_aR,
+ *                   d_aO (device pointers on the handle's GPU, 32-byte aligned; witness k at k * out_stride bytes, out_stride a multiple
+ *                   of 32 and at least 32 n, 0 = packed; n x 32 canonical bytes each), out_cs (host, K x Q x 32 bytes, or NULL) and
+ *                   out_bad (host, K pairs {the number of constraint gates with aL aR != aO, the smallest such gate or -1}, or NULL).
+ *                   A non-canonical element: SONIC_ERR_BAD_ENCODING; a witness with z[0] != 1: SONIC_ERR_INVALID_ARG naming the first
+ *                   such k; an output pointer that is host memory or lies on another GPU, a misaligned pointer: SONIC_ERR_INVALID_ARG.
+ *                   Every refusal leaves the outputs untouched.  Witnesses pass through staging in chunks, so K is not bounded by device
+ *                   memory; SONIC_R1CS_STAGE=<k> (read per call) caps the witnesses per chunk, with the same results.  Blocking.
+ *   r1cs_row_chunk  rows of at most this many entries are summed by one thread each, longer rows by one block each.
+ *
+ * Costs to know.  A circuit made here has Q = 3m + n_pub, of the order of n.  A prover handle allocates Q buffers of 3n + 1 field elements
+ * when it is made, and the circuit digest hashes 96 Q n bytes: prove such circuits with core proofs and helped verification, on handles
+ * that are not prepared. */
+typedef struct sonic_r1cs sonic_r1cs_t;
+typedef struct sonic_r1cs_matrix { const int64_t* row_ptr; const int64_t* col; const uint8_t* val; } sonic_r1cs_matrix_t;
+int sonic_r1cs_new(int64_t m, int64_t N, int64_t n_pub, const sonic_r1cs_matrix_t* A, const sonic_r1cs_matrix_t* B, const sonic_r1cs_matrix_t* C,
+                   sonic_r1cs_t** out);
+int sonic_r1cs_new_on(int device, int64_t m, int64_t N, int64_t n_pub, const sonic_r1cs_matrix_t* A, const sonic_r1cs_matrix_t* B,
+                      const sonic_r1cs_matrix_t* C, sonic_r1cs_t** out);
+void sonic_r1cs_free(sonic_r1cs_t* r);
+int sonic_r1cs_device(const sonic_r1cs_t* r);
+int sonic_r1cs_shape(const sonic_r1cs_t* r, int64_t out[4]);
+int sonic_r1cs_circuit(const sonic_r1cs_t* r, int64_t* row_ptr, int64_t* col, uint8_t* val, uint8_t* cs_fixed);
+int sonic_r1cs_assign(sonic_r1cs_t* r, int64_t K, const void* z, int kind, int on_device, int64_t z_stride, void* hip_stream, void* d_aL,
+                      void* d_aR, void* d_aO, int64_t out_stride, uint8_t* out_cs, int64_t* out_bad);
+int sonic_r1cs_row_chunk(void);
+
 /* ---- device memory for callers without a HIP binding ---- */
 int sonic_dev_alloc(size_t bytes, void** out);                       /* on the default device */
 int sonic_dev_alloc_on(int device, size_t bytes, void** out);         /* free / upload / download find the pointer's device themselves */

@@ -209,6 +209,13 @@ def lib() -> C.CDLL:
         "sonic_g1_subgroup_check": [vp, i64, i32, vp],
         "sonic_g2_subgroup_check": [vp, i64, i32, vp],
         "sonic_pairing_check": [vp, vp, i64, vp, i64, i32, vp, vp],
+        "sonic_r1cs_new": [i64, i64, i64, vp, vp, vp, C.POINTER(vp)],
+        "sonic_r1cs_new_on": [i32, i64, i64, i64, vp, vp, vp, C.POINTER(vp)],
+        "sonic_r1cs_device": [vp],
+        "sonic_r1cs_shape": [vp, C.POINTER(i64)],
+        "sonic_r1cs_circuit": [vp, vp, vp, vp, vp],
+        "sonic_r1cs_assign": [vp, i64, vp, i32, i32, i64, vp, vp, vp, vp, i64, vp, vp],
+        "sonic_r1cs_row_chunk": [],
         "sonic_dev_alloc": [C.c_size_t, C.POINTER(vp)],
         "sonic_dev_free": [vp],
         "sonic_dev_upload": [vp, vp, C.c_size_t],
@@ -231,6 +238,8 @@ def lib() -> C.CDLL:
     L.sonic_prover_free.restype = None
     L.sonic_verifier_free.argtypes = [vp]
     L.sonic_verifier_free.restype = None
+    L.sonic_r1cs_free.argtypes = [vp]
+    L.sonic_r1cs_free.restype = None
     L.sonic_msm_lane_free.argtypes = [vp]
     L.sonic_msm_lane_free.restype = None
     L.sonic_srs_d.argtypes = [vp]
@@ -278,6 +287,10 @@ SUBGROUP_DEFAULT, SUBGROUP_WALK = 0, 1  # SONIC_SUBGROUP_*
 PAIRING_AUTO, PAIRING_HOST, PAIRING_GPU = 0, 1, 2  # SONIC_PAIRING_*
 
 
+class R1csMatrix(C.Structure):          # sonic_r1cs_matrix_t
+    _fields_ = [("row_ptr", C.c_void_p), ("col", C.c_void_p), ("val", C.c_void_p)]
+
+
 class WitnessSrc(C.Structure):          # sonic_witness_src_t
     _fields_ = [("aL", C.c_void_p), ("aR", C.c_void_p), ("aO", C.c_void_p), ("kind", C.c_int32), ("on_device", C.c_int32),
                 ("stride", C.c_int64), ("hip_stream", C.c_void_p)]
@@ -321,6 +334,7 @@ EXPORTED = [
     "sonic_g1_subgroup_check", "sonic_g2_subgroup_check",
     "sonic_pairing_check",
     "sonic_open_batch_dense",
+    "sonic_r1cs_new", "sonic_r1cs_new_on", "sonic_r1cs_free", "sonic_r1cs_device", "sonic_r1cs_shape", "sonic_r1cs_circuit", "sonic_r1cs_assign", "sonic_r1cs_row_chunk",
 ]
 
 
