@@ -70,6 +70,9 @@ module Sonic.HIP
   , aggregateCore, fsWeightsDigest, verifyCoreBatchHelped
     -- * R1CS front end
   , R1CS(..), R1csMatrix(..), newR1cs, r1csCircuit, r1csAssignI64
+    -- * circuits with Q ~ n: weights digest v2, circuit digest v2
+  , fsWeightsDigestV2, fsCircuitDigestV2, proverWeightsDigestV2, verifierWeightsDigestV2, newVerifierDigest, verifierDigestKind
+  , proverDeviceBytes
   ) where
 
 import Protolude hiding (check)
@@ -184,6 +187,13 @@ foreign import ccall safe   "sonic_prover_submit_core"    c_prover_submit_core :
 foreign import ccall safe   "sonic_prover_collect_core"   c_prover_collect_core :: Ptr ProverHandle -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_prover_prove_core_fs"  c_prover_prove_core_fs :: Ptr ProverHandle -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_fs_weights_digest"     c_fs_weights_digest :: Ptr Word8 -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_fs_weights_digest_v2_csr" c_fs_weights_digest_v2 :: Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_fs_circuit_digest_v2"  c_fs_circuit_digest_v2 :: Ptr Word8 -> Int64 -> Ptr Word8 -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_prover_weights_digest_v2" c_prover_weights_digest_v2 :: Ptr ProverHandle -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_verifier_weights_digest_v2" c_verifier_weights_digest_v2 :: Ptr VerifierHandle -> Ptr Word8 -> IO CInt
+foreign import ccall safe   "sonic_verifier_new_digest"   c_verifier_new_digest :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> CInt -> Ptr (Ptr VerifierHandle) -> IO CInt
+foreign import ccall safe   "sonic_verifier_digest_kind"  c_verifier_digest_kind :: Ptr VerifierHandle -> IO CInt
+foreign import ccall safe   "sonic_prover_device_bytes"   c_prover_device_bytes :: Ptr ProverHandle -> Ptr Int64 -> IO CInt
 foreign import ccall safe   "sonic_prover_aggregate_core" c_prover_aggregate_core :: Ptr ProverHandle -> Ptr Word8 -> Int64 -> Ptr Word8 -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_verifier_verify_core_batch_helped" c_verify_core_batch_helped :: Ptr VerifierHandle -> Int64 -> Ptr Word8 -> CInt -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_verify_core_csr"       c_verify_core_csr :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> IO CInt
@@ -1007,6 +1017,50 @@ newVerifier srs@(SRS h) circuit =
     check =<< c_verifier_new_csr p n q prp pcol pval pcs out
     fp <- newForeignPtr p_verifier_free =<< peek out
     pure Verifier { verifierHandle = fp, verifierSrs = srs, verifierQ = fromIntegral q }
+
+-- ---------------------------------------------------------------------------------------------------------------------
+-- Circuits with Q ~ n: weights digest v2 and circuit digest v2 hash the CSR ENTRIES (a SHA-256 tree, O(nnz)) where v1 hashes the
+-- 96 Q n dense bytes; an explicit zero is an entry.  The prover's Fiat-Shamir calls take the digest they are given, so proofs for a
+-- verifier of digest kind 2 are made under fsCircuitDigestV2 (proveCoreFs, submitFs) and aggregates under the v2 weights digest.
+-- ---------------------------------------------------------------------------------------------------------------------
+-- | weights digest v2 of the circuit's CSR (sonic_fs_weights_digest_v2_csr; host only): 32 bytes
+fsWeightsDigestV2 :: ArithCircuit Fr -> ByteString
+fsWeightsDigestV2 circuit = unsafePerformIO $
+  withCircuitCsr circuit $ \n q prp pcol pval _ -> BSI.create 32 $ \out ->
+    check =<< c_fs_weights_digest_v2 n q prp pcol pval out
+
+-- | circuit digest v2 of one statement (sonic_fs_circuit_digest_v2; host only): weights digest v2, then the constants
+fsCircuitDigestV2 :: ByteString -> [Fr] -> ByteString
+fsCircuitDigestV2 wd cs = unsafePerformIO $
+  withBytes wd $ \pw -> withFrs cs $ \pcs -> BSI.create 32 $ \out ->
+    check =<< c_fs_circuit_digest_v2 pw (fromIntegral (length cs)) pcs out
+
+-- | weights digest v2 from the prover handle's resident CSR, computed on the GPU (sonic_prover_weights_digest_v2)
+proverWeightsDigestV2 :: Prover -> IO ByteString
+proverWeightsDigestV2 pr = withProverAlive pr $ \p -> BSI.create 32 (check <=< c_prover_weights_digest_v2 p)
+
+-- | the same from a verifier handle (sonic_verifier_weights_digest_v2)
+verifierWeightsDigestV2 :: Verifier -> IO ByteString
+verifierWeightsDigestV2 Verifier{..} = withForeignPtr verifierHandle $ \v -> BSI.create 32 (check <=< c_verifier_weights_digest_v2 v)
+
+-- | newVerifier with the digest kind chosen (sonic_verifier_new_digest): 1 is newVerifier; 2 derives circuit digest v2 and hashes
+--   nothing dense when the handle is made
+newVerifierDigest :: Int -> SRS -> ArithCircuit Fr -> IO Verifier
+newVerifierDigest kind srs@(SRS h) circuit =
+  withForeignPtr h $ \p -> withCircuitCsr circuit $ \n q prp pcol pval pcs -> alloca $ \out -> do
+    check =<< c_verifier_new_digest p n q prp pcol pval pcs (fromIntegral kind) out
+    fp <- newForeignPtr p_verifier_free =<< peek out
+    pure Verifier { verifierHandle = fp, verifierSrs = srs, verifierQ = fromIntegral q }
+
+-- | 1 or 2 (sonic_verifier_digest_kind)
+verifierDigestKind :: Verifier -> IO Int
+verifierDigestKind Verifier{..} = withForeignPtr verifierHandle $ \v -> fromIntegral <$> c_verifier_digest_kind v
+
+-- | the device memory the prover handle owns now (sonic_prover_device_bytes): the pairs' buffers appear with the first full proof
+proverDeviceBytes :: Prover -> IO Int64
+proverDeviceBytes pr = withProverAlive pr $ \p -> alloca $ \out -> do
+  check =<< c_prover_device_bytes p out
+  peek out
 
 -- | K proofs of K statements of the handle's circuit in one pairing product (sonic_verifier_verify_batch_cs): proof k against cs_k with
 --   its RndOracle; the per-proof verdicts (a malformed proof is a rejected proof).  The library draws the seed of the randomizers.

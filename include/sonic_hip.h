@@ -109,7 +109,9 @@ typedef struct sonic_verifier sonic_verifier_t;
  * sonic_prover_aggregate_core, sonic_verifier_verify_core_batch_helped, sonic_verifier_verify_core_fs_batch_helped,
  * sonic_verify_core_helped_digest; still 7, additions only: the updatable SRS -- sonic_srs_check, sonic_srs_update, sonic_srs_verify_update;
  * still 7, additions only: the G2 sums -- sonic_msm_g2, sonic_msm_g2_srs[_dev], sonic_msm_g2_walk_max; subgroup membership --
- * sonic_g1_subgroup_check, sonic_g2_subgroup_check; pairings -- sonic_pairing_check; the opening chain alone -- sonic_open_batch_dense */
+ * sonic_g1_subgroup_check, sonic_g2_subgroup_check; pairings -- sonic_pairing_check; the opening chain alone -- sonic_open_batch_dense;
+ * still 7, additions only: circuits with Q ~ n -- sonic_fs_weights_digest_v2_csr, sonic_fs_circuit_digest_v2, sonic_prover_weights_digest_v2,
+ * sonic_verifier_weights_digest_v2, sonic_verifier_new_digest, sonic_verifier_digest_kind, sonic_prover_device_bytes */
 int sonic_abi_version(void);
 int sonic_init(int device_ordinal);                 /* choose the DEFAULT GPU (first call wins) and make it the thread's HIP device; idempotent */
 int sonic_device_count(int* out);                   /* GPUs this process can see; SONIC_ERR_NO_DEVICE (and 0) without one */
@@ -972,9 +974,9 @@ int sonic_srs_verify_update(const sonic_srs_t* old_srs, const sonic_srs_t* new_s
  *                   memory; SONIC_R1CS_STAGE=<k> (read per call) caps the witnesses per chunk, with the same results.  Blocking.
  *   r1cs_row_chunk  rows of at most this many entries are summed by one thread each, longer rows by one block each.
  *
- * Costs to know.  A circuit made here has Q = 3m + n_pub, of the order of n.  A prover handle allocates Q buffers of 3n + 1 field elements
- * when it is made, and the circuit digest hashes 96 Q n bytes: prove such circuits with core proofs and helped verification, on handles
- * that are not prepared. */
+ * Costs to know.  A circuit made here has Q = 3m + n_pub, of the order of n.  A FULL proof needs Q buffers of 3n + 1 field elements (the
+ * handle makes them on the first one) and circuit digest v1 hashes 96 Q n bytes: prove such circuits with core proofs and helped
+ * verification under circuit digest v2 ("Circuits with Q ~ n", below), on handles that are not prepared. */
 typedef struct sonic_r1cs sonic_r1cs_t;
 typedef struct sonic_r1cs_matrix { const int64_t* row_ptr; const int64_t* col; const uint8_t* val; } sonic_r1cs_matrix_t;
 int sonic_r1cs_new(int64_t m, int64_t N, int64_t n_pub, const sonic_r1cs_matrix_t* A, const sonic_r1cs_matrix_t* B, const sonic_r1cs_matrix_t* C,
@@ -988,6 +990,56 @@ int sonic_r1cs_circuit(const sonic_r1cs_t* r, int64_t* row_ptr, int64_t* col, ui
 int sonic_r1cs_assign(sonic_r1cs_t* r, int64_t K, const void* z, int kind, int on_device, int64_t z_stride, void* hip_stream, void* d_aL,
                       void* d_aR, void* d_aO, int64_t out_stride, uint8_t* out_cs, int64_t* out_bad);
 int sonic_r1cs_row_chunk(void);
+
+/* ---- Circuits with Q ~ n: weights digest v2, circuit digest v2, per-pair prover state on first use ----
+ * Circuit digest v1 hashes the 96 Q n dense bytes the gate weights stand for, whichever form they come in.  With Q of the order of n that
+ * is seconds of hashing per handle.  Digest v2 hashes the ENTRIES of the stacked CSR, O(nnz), as a SHA-256 tree that the GPU computes from
+ * a handle's resident CSR.  The normative text (sonic_amd/csrc/fs.hpp), repeated:
+ *
+ *   input    the validated stacked CSR of 3Q rows ("gate weights as CSR"), AS GIVEN.  An explicit zero value is an entry: two CSRs of the
+ *            same matrix that differ in explicit zeros have DIFFERENT digests (v1 does not tell them apart).  Prover and verifier must
+ *            hold the same CSR, not merely the same matrix.
+ *   items    entry k (0 <= k < nnz, CSR order) is two items of 32 bytes: item 2k = le64 r || le64 c || 16 zero bytes (r in [0, 3Q) the
+ *            stacked row, c in [0, n) the column); item 2k + 1 = the 32 canonical little-endian bytes of val[k]
+ *   leaves   L = max(1, ceil(nnz / 16));  leaf_i = SHA256(H_leaf(i) || items 32 i .. min(32 (i+1), 2 nnz) - 1); nnz = 0: one leaf over zero items
+ *   nodes    as in witness digest v2: while a level has c > 1 digests the next has ceil(c / 32) nodes,
+ *            node_j = SHA256(H_node(level, j) || the digests 32 j .. min(32 (j+1), c) - 1 of the level below)
+ *   headers  64 bytes, those of witness digest v2 under the labels "sonic-hip/weights-leaf/v2" (zero-padded to 56 bytes, then le64 i) and
+ *            "sonic-hip/weights-node/v2" (zero-padded to 48 bytes, then le64 level -- 1 for the first level of nodes -- and le64 j)
+ *   root   = the single digest left (leaf_0 when L = 1)
+ *   weights digest v2 = SHA256("sonic-hip/weights/v2" || le64 n || le64 Q || le64 nnz || root)
+ *   circuit digest v2 = SHA256("sonic-hip/circuit/v2" || weights digest v2 || le64 Q || cs),   cs = Q x 32 canonical bytes
+ *
+ * A statement's digest costs 32 Q bytes of hashing from the weights digest (what midstate / resume gives v1).  The prover's Fiat-Shamir
+ * and helper calls take `circuit_digest` and `weights_digest` as arguments, so they work under either kind: pass v2 bytes.  A proof or an
+ * aggregate made under one kind is a REJECTED proof (not an error) on a verifier handle of the other.  The one-shot sonic_verify_core_fs[_csr]
+ * and sonic_fs_core_challenges keep v1.
+ *
+ *   sonic_fs_weights_digest_v2_csr    host only, no device.  Validation and errors are those of sonic_fs_circuit_midstate_csr.
+ *   sonic_fs_circuit_digest_v2        host only.  A cs[q] >= r: SONIC_ERR_BAD_ENCODING naming q.
+ *   sonic_prover_weights_digest_v2    on the GPU, from the resident CSR of a handle made by sonic_prover_new_csr; a handle with dense weights:
+ *                                     SONIC_ERR_INVALID_ARG (make the handle from CSR); a proof in flight: SONIC_ERR_INVALID_ARG.  Cached.
+ *   sonic_verifier_weights_digest_v2  the same on a verifier handle, which always holds CSR (made from dense weights: their non-zero entries).
+ *   sonic_verifier_new_digest         digest_kind 1: exactly sonic_verifier_new_csr.  digest_kind 2: no dense byte is hashed -- the GPU
+ *                                     computes weights digest v2; the handle's circuit digest is circuit digest v2 of (it, cs), in the `_cs`
+ *                                     batches proof k's is circuit digest v2 of (it, cs_k), and the helped calls bind it as the weights
+ *                                     digest.  Batch digests, randomizers, transcripts and checks are unchanged: they take the 32 bytes
+ *                                     they are given.  Any other kind: SONIC_ERR_INVALID_ARG.
+ *   sonic_verifier_digest_kind        1 or 2 (-1 for NULL).
+ *   sonic_prover_device_bytes         the device memory the handle owns now: all its buffers, lane workspaces included; not the SRS it borrows.
+ *
+ * Per-pair state on first use.  The Q buffers of 3n + 1 field elements for s(X, y_j) and their Q events belong to the signature.  A prover
+ * handle makes them on its first full proof, share or Fiat-Shamir proof; core proofs, sonic_prover_aggregate_core, eval_constraints, the
+ * witness calls and the digests never do, and a core proof does no per-pair work.  When that allocation fails the call returns SONIC_ERR_HIP
+ * with a message that names the size, and the handle remains good for core proofs.  Proof bytes are unchanged, in every order of calls. */
+int sonic_fs_weights_digest_v2_csr(int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val, uint8_t out[32]);
+int sonic_fs_circuit_digest_v2(const uint8_t weights_digest[32], int64_t Q, const uint8_t* cs, uint8_t out[32]);
+int sonic_prover_weights_digest_v2(sonic_prover_t* p, uint8_t out[32]);
+int sonic_verifier_weights_digest_v2(sonic_verifier_t* v, uint8_t out[32]);
+int sonic_verifier_new_digest(const sonic_srs_t* srs, int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val,
+                              const uint8_t* cs, int digest_kind, sonic_verifier_t** out);
+int sonic_verifier_digest_kind(const sonic_verifier_t* v);
+int sonic_prover_device_bytes(sonic_prover_t* p, int64_t* out);
 
 /* ---- device memory for callers without a HIP binding ---- */
 int sonic_dev_alloc(size_t bytes, void** out);                       /* on the default device */

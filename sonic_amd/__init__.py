@@ -35,11 +35,12 @@ from .protocol import prove_batch_fs  # noqa: F401,E402
 from .protocol import WitnessBatch  # noqa: F401,E402
 from .protocol import CoreProof, prove_core_batch, prove_core_batch_fs, verify_core, verify_core_fs, fs_core_challenges  # noqa: F401,E402
 from .protocol import aggregate_core, fs_weights_digest, fs_aggregate_challenges  # noqa: F401,E402
+from .protocol import fs_weights_digest_v2, fs_circuit_digest_v2  # noqa: F401,E402
 from .compressed import g1_compress, g1_decompress, g2_compress, g2_decompress, proof_compress, proof_decompress  # noqa: F401,E402
 from .compressed import g1_subgroup_check, g2_subgroup_check  # noqa: F401,E402
 from ._pairing import pairing_check, pairing  # noqa: F401,E402
 from .r1cs import R1CS  # noqa: F401,E402
 from . import r1cs_io  # noqa: F401,E402
 
-__all__ = ["R1CS", "r1cs_io", "pairing_check", "pairing", "g1_subgroup_check", "g2_subgroup_check", "msm_g2", "msm_g2_srs", "aggregate_core", "fs_weights_digest", "fs_aggregate_challenges", "CoreProof", "prove_core_batch", "prove_core_batch_fs", "verify_core", "verify_core_fs", "fs_core_challenges", "WitnessBatch", "Verifier", "verify_batch", "prove_batch_fs", "fs_circuit_midstate", "fs_circuit_digest_resume", "g1_compress", "g1_decompress", "g2_compress", "g2_decompress", "proof_compress", "proof_decompress", "SRS", "srs_verify_update", "commit_poly", "open_poly", "pc_v", "msm_g1", "MsmLane", "prove", "verify", "prove_fs", "verify_fs", "fs_challenges", "fs_circuit_digest", "hsc_prove", "hsc_verify", "hsc_prove_poly", "hsc_verify_poly", "Proof", "HscProof", "RndOracle", "Prover", "ProverPipeline",
+__all__ = ["fs_weights_digest_v2", "fs_circuit_digest_v2", "R1CS", "r1cs_io", "pairing_check", "pairing", "g1_subgroup_check", "g2_subgroup_check", "msm_g2", "msm_g2_srs", "aggregate_core", "fs_weights_digest", "fs_aggregate_challenges", "CoreProof", "prove_core_batch", "prove_core_batch_fs", "verify_core", "verify_core_fs", "fs_core_challenges", "WitnessBatch", "Verifier", "verify_batch", "prove_batch_fs", "fs_circuit_midstate", "fs_circuit_digest_resume", "g1_compress", "g1_decompress", "g2_compress", "g2_decompress", "proof_compress", "proof_decompress", "SRS", "srs_verify_update", "commit_poly", "open_poly", "pc_v", "msm_g1", "MsmLane", "prove", "verify", "prove_fs", "verify_fs", "fs_challenges", "fs_circuit_digest", "hsc_prove", "hsc_verify", "hsc_prove_poly", "hsc_verify_poly", "Proof", "HscProof", "RndOracle", "Prover", "ProverPipeline",
            "ArithCircuit", "SparseCircuit", "Assignment", "GateWeights", "SonicError"]

@@ -39,6 +39,29 @@
 //   witness digest v2 = SHA256("sonic-hip/witness/v2" || le64 n || root)
 // The 64-byte headers keep every message block aligned to whole field elements: one block is two elements, sixteen 32-bit limbs
 // byte-swapped.
+//
+// Weights digest v2 and circuit digest v2 (sonic_fs_weights_digest_v2_csr, sonic_fs_circuit_digest_v2, sonic_prover_weights_digest_v2,
+// sonic_verifier_weights_digest_v2, a verifier handle of digest kind 2): circuit digest v1 hashes the 96 Q n dense bytes the weights stand
+// for, which at Q ~ n (a compiled R1CS) is seconds of hashing; v2 hashes the ENTRIES, O(nnz), as a tree the GPU computes from the resident
+// CSR (weights_tree.hpp, weights_digest.hip).  The framing is exactly that of witness digest v2: a 64-byte header, then 1 .. 32 items of
+// 32 bytes, fan-out 32.
+//   input    the validated stacked CSR of 3Q rows (csr.hpp: wL rows 0 .. Q-1, wR rows Q .. 2Q-1, wO rows 2Q .. 3Q-1), AS GIVEN: an explicit
+//            zero value is an entry.  Two CSRs of the same matrix that differ in explicit zeros therefore have DIFFERENT digests (v1 does
+//            not tell them apart): prover and verifier must hold the same CSR, not merely the same matrix.
+//   items    entry k (0 <= k < nnz, CSR order) is two items: item 2k = le64 r || le64 c || 16 zero bytes, r in [0, 3Q) the stacked row,
+//            c in [0, n) the column; item 2k + 1 = the 32 canonical little-endian bytes of val[k]
+//   leaves   L = max(1, ceil(nnz / 16));  leaf_i = SHA256(H_leaf(i) || items 32 i .. min(32 (i+1), 2 nnz) - 1); nnz = 0: one leaf over
+//            zero items
+//   nodes    as in witness digest v2: while a level has c > 1 digests the next one has ceil(c / 32) nodes,
+//            node_j = SHA256(H_node(level, j) || the digests 32 j .. min(32 (j+1), c) - 1 of the level below)
+//   headers  H_leaf and H_node are the witness headers under the labels "sonic-hip/weights-leaf/v2" and "sonic-hip/weights-node/v2"
+//            (25 bytes each, like the witness labels)
+//   root   = the single digest left (leaf_0 when L = 1)
+//   weights digest v2 = SHA256("sonic-hip/weights/v2" || le64 n || le64 Q || le64 nnz || root)
+//   circuit digest v2 = SHA256("sonic-hip/circuit/v2" || weights digest v2 || le64 Q || cs),   cs = Q x 32 canonical bytes
+// so a statement's digest costs 32 Q bytes of hashing from the weights digest: the split that midstate / resume gives v1.  Every
+// transcript, batch digest and aggregate takes the 32 bytes of a circuit or weights digest as they are, so v2 bytes go wherever v1 bytes
+// went; a proof made under one kind is a rejected proof under the other.
 #pragma once
 #include <string>
 #include "field.hpp"
@@ -125,6 +148,30 @@ inline void fs_witness_digest_v2(int64_t n, const uint8_t root[32], uint8_t out3
   FsTranscript::le64(h, n);
   h.update(root, 32);
   h.finish(out32);
+}
+
+// weights digest v2 from the root of the tree over the CSR entries, and circuit digest v2 from it (above)
+inline void fs_weights_digest_v2(int64_t n, int64_t Q, int64_t nnz, const uint8_t root[32], uint8_t out32[32]) {
+  Sha256 h;
+  h.update("sonic-hip/weights/v2", 20);
+  FsTranscript::le64(h, n); FsTranscript::le64(h, Q); FsTranscript::le64(h, nnz);
+  h.update(root, 32);
+  h.finish(out32);
+}
+// 0 = done; 2 = cs[q] is not canonical (*bad_q = q): the codes of fs_circuit_digest_resume
+inline int fs_circuit_digest_v2(const uint8_t weights_digest[32], int64_t Q, const uint8_t* cs, uint8_t out32[32], int64_t* bad_q = nullptr) {
+  for (int64_t q = 0; q < Q; q++) {
+    Fr k;
+    memcpy(k.l, cs + 32 * q, 32);
+    if (!fp_is_canonical(k)) { if (bad_q) *bad_q = q; return 2; }
+  }
+  Sha256 h;
+  h.update("sonic-hip/circuit/v2", 20);
+  h.update(weights_digest, 32);
+  FsTranscript::le64(h, Q);
+  h.update(cs, (size_t)(32 * Q));
+  h.finish(out32);
+  return 0;
 }
 
 // The challenges a proof determines, in transcript order y, z, y_1..y_Q, z_1..z_Q, u, v (each 32 bytes), from the canonical proof

@@ -156,6 +156,10 @@ void g1_validate_enqueue(hipStream_t st, const uint8_t* d_in96, G1Affine* out, u
 void g1_subgroup_enqueue(hipStream_t st, const uint8_t* d_in96, uint8_t* d_flags, long n, int method);
 void g2_subgroup_enqueue(hipStream_t st, const uint8_t* d_in192, uint8_t* d_flags, long n, int method);
 
+// weights digest v2 (weights_digest.hip; fs.hpp): queues the SHA-256 tree over a resident CSR of R = 3Q rows and nnz entries (int32
+// indices, Montgomery values) into `tree` (grown to fit); returns where the root's eight state words will be
+const uint32_t* weights_tree_enqueue(hipStream_t st, const int32_t* row_ptr, const int32_t* col, const Fr* val, long R, long nnz, DevBuf& tree);
+
 // NTT (ntt.hip).  Data in Montgomery form, in place.  forward: natural -> bit-reversed;
 // inverse: bit-reversed -> natural, scaled by 1/n.
 struct NttTables {

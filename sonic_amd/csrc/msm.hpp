@@ -64,6 +64,7 @@ constexpr long MSM_TABLE_MAX_TERMS = 1L << 26;
 constexpr int MSM_TABLE_MAX_WINDOWS = 32;
 constexpr long MSM_MAX_TERMS = 1L << 31;
 
+// (sonic_prover_device_bytes, prove.hip, lists these buffers by name: a buffer added here must be added there)
 struct MsmWorkspace {
   DevBuf count, off, digits, entries, buckets, segres, scan_tmp, order, heavy_meta, heavy_partial, endo_scalars;
   // the G2 MSM's own stages behind the shared sort (msm_g2.hip): chunk counts and their scan, partial sums, buckets, segment results,

@@ -211,6 +211,7 @@ static void upload_i32(hipStream_t st, DevBuf& dst, const std::vector<int32_t>& 
 static void prover_upload_circuit(sonic_prover_t* p, hipStream_t st, int* d_flags) {
   const CircuitView& c = p->pend.view;
   const long n = p->n, Q = p->Q;
+  p->have_weights_digest_v2 = false;
   if (c.csr) {
     const CsrLayout& L = p->pend.layout;
     sonic_prover::CsrBufs& b = p->sp;
@@ -336,8 +337,7 @@ int prover_new_impl(const sonic_srs_t* srs, const CircuitView& c, sonic_prover_t
   p->fa.alloc(sizeof(Fr) * M); p->fb.alloc(sizeof(Fr) * M);
   p->r1.alloc(sizeof(Fr) * (3 * n + 5));
   p->sy0.alloc(sizeof(Fr) * (3 * n + 1));
-  p->syj.resize(Q);
-  for (auto& b : p->syj) b.alloc(sizeof(Fr) * (3 * n + 1));
+  // (syj, ev_syj: the Q buffers of 3n + 1 elements and Q events of the signature's pairs are made by ensure_pair_state, on first use)
   p->su.alloc(sizeof(Fr) * (2 * n + Q + 1));
   p->pw.alloc(sizeof(Fr) * (3 * n + Q + 2));
   p->kpow.alloc(sizeof(Fr) * Q);
@@ -357,8 +357,6 @@ int prover_new_impl(const sonic_srs_t* srs, const CircuitView& c, sonic_prover_t
   memset(p->h_slots, 0, sizeof(MsmSlot) * L.slots_total());
   auto mkev = [](hipEvent_t* e) { HIP_OK(hipEventCreateWithFlags(e, hipEventDisableTiming)); };
   mkev(&p->ev_r1); mkev(&p->ev_sy0); mkev(&p->ev_t); mkev(&p->ev_su);
-  p->ev_syj.resize(Q, nullptr);
-  for (auto& e : p->ev_syj) mkev(&e);
   mkev(&p->done); mkev(&p->ev_head); mkev(&p->ev_ts);
   // MSM workspaces and opening scratch grow on first use: every proof maps the same group of MSMs to the same lane
   if (p->small_plan) {
@@ -386,6 +384,37 @@ int prover_new_impl(const sonic_srs_t* srs, const CircuitView& c, sonic_prover_t
   }
   HIP_OK(hipStreamSynchronize(st));
   *out = p.release();
+  return SONIC_OK;
+}
+
+// The per-pair state of the signature (prover.hpp, have_pair_state), on first use: Q buffers of 3n + 1 elements for the s(X, y_j) and the
+// Q events that order their groups -- 32 Q (3n + 1) bytes, 9.5 GB for a compiled R1CS of m = 2^12, which a handle that makes core proofs
+// never needs.  Called by prove_enqueue, before anything of the proof is queued or captured, for every enqueue that is not a core
+// proof's.  A failed allocation frees what it had got and leaves the handle as it was: good for core proofs, and for another try.
+static int ensure_pair_state(sonic_prover_t* p) {
+  if (p->have_pair_state) return SONIC_OK;
+  const long n = p->n, Q = p->Q;
+  const size_t each = sizeof(Fr) * (size_t)(3 * n + 1);
+  bool made = false;
+  try {
+    p->syj.resize((size_t)Q);
+    for (auto& b : p->syj) b.alloc(each);
+    p->ev_syj.resize((size_t)Q, nullptr);
+    for (auto& e : p->ev_syj) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    made = true;
+  } catch (const HipFail&) {             // a device allocation or an event
+  } catch (const std::bad_alloc&) {      // the host vectors themselves
+  }
+  if (!made) {
+    p->syj.clear();
+    for (hipEvent_t e : p->ev_syj) if (e) (void)hipEventDestroy(e);
+    p->ev_syj.clear();
+    (void)hipGetLastError();      // (the failed hipMalloc must not surface as the next launch's error)
+    set_error("prove: no room for the signature's per-pair state: Q = %ld device buffers of %zu bytes, %.3f GB in all (core proofs need none of it)",
+              Q, each, (double)Q * (double)each / 1e9);
+    return SONIC_ERR_HIP;
+  }
+  p->have_pair_state = true;
   return SONIC_OK;
 }
 
@@ -600,7 +629,7 @@ struct ProofPass {
   const Fr* pair(long i) const { return PR + 2 * i; }
   ProofPass(sonic_prover_t* p, const GroupQueue& q)
       : n(p->n), Q(p->Q), d(p->srs->d), r_lo(ProofLayout::r_lo(n)), r_len(ProofLayout::r_len(n)), s_lo(ProofLayout::s_lo(n)), s_len(ProofLayout::s_len(n)),
-        t_lo(ProofLayout::t_lo(n)), t_len(ProofLayout::t_len(n)), u_lo(ProofLayout::u_lo(n)), u_len(q.L.u_len(n)), PR(p->PAIRS.as<Fr>()), need_j((size_t)Q, 0) {
+        t_lo(ProofLayout::t_lo(n)), t_len(ProofLayout::t_len(n)), u_lo(ProofLayout::u_lo(n)), u_len(q.L.u_len(n)), PR(p->PAIRS.as<Fr>()), need_j(p->core ? 0 : (size_t)Q, 0) {
     const ProofLayout& L = q.L;
     need_su = !p->core && (q.own(L.C()) || q.own(L.Qv()));
     for (long j = 0; j < Q && !p->core; j++) {      // (a core proof has no signature: none of its groups)
@@ -686,7 +715,9 @@ static void enqueue_polynomials(sonic_prover_t* p, GroupQueue& q, ProofPass& w) 
     HIP_OK(hipEventRecord(p->ev_t, ts));
   }
   // hscProve: s(X, y_j), s(u, Y)                                                     Signature.hs:41,51
-  for (long j = 0; j < Q; j++) {
+  // (no pair has a piece here -- a core proof, whose handle may not even have the pairs' buffers and events: no per-j work at all.  Nothing
+  // waits for an ev_syj[j] but the group of a j that is needed)
+  for (long j = 0; w.need_j_any && j < Q; j++) {
     if (w.need_j[(size_t)j] && q.on(PH_HSCS)) {
       poly_scale_powers_enqueue(ms, nullptr, pw, 2 * n + Q + 1, -n, w.pair(L.pYj(j)), w.pair(L.pYj(j)) + 1);
       // a prepared handle that has only a piece of S_j's diagonal part does not read s(X, y_j) itself
@@ -728,7 +759,7 @@ static void enqueue_groups(sonic_prover_t* p, GroupQueue& q, ProofPass& w) {
     p->fr_valid[(size_t)L.s] = 1;
   }
   enqueue_group0(p, q, w);
-  for (long j = 0; j < Q; j++) {
+  for (long j = 0; w.need_j_any && j < Q; j++) {
     if (!w.need_j[(size_t)j]) continue;
     Fr* syj = p->syj[j].as<Fr>();
     q.begin_group(p->ev_syj[j]);
@@ -898,6 +929,12 @@ static int prove_enqueue(sonic_prover_t* p, const uint8_t* transcript) {
   for (long k = L.n_blinders; k < L.transcript_len(); k++)
     if (bytes_are_zero(transcript + 32 * k, 32)) { set_error("prove: transcript element %ld is zero: Laurent evaluation at 0 divides by zero", k); return SONIC_ERR_INEXACT_DIVISION; }
   if (p->share_world > 1 && p->phases != PH_ALL) { set_error("prove: a shared proof runs with a caller-supplied transcript only"); return SONIC_ERR_INVALID_ARG; }
+  // (every enqueue of a proof that HAS a signature: its whole-proof enqueue, its share, each of its Fiat-Shamir passes -- those before
+  // PH_HSCS too, which still visit the pairs' groups; a core proof's enqueues never)
+  if (!p->core) {
+    const int rc_pairs = ensure_pair_state(p);
+    if (rc_pairs) return rc_pairs;
+  }
   decide_modes(p);
   share_replan_if_needed(p);
   memcpy(p->h_tr, transcript, 32 * L.transcript_len());
@@ -1744,6 +1781,36 @@ int sonic_prover_prepare(sonic_prover_t* p) {
 void sonic_prover_free(sonic_prover_t* p) {
   if (!p) return;
   try { DeviceScope scope(p->device); delete p; } catch (const HipFail&) { delete p; }
+}
+
+// The device memory the handle owns at this moment: every DevBuf of the handle, the workspaces and opening scratch of its lanes and
+// chains included, as the sizes they were allocated with.  Not counted: what the handle borrows -- the SRS, the device's shared NTT
+// tables and pooled streams -- and the temporaries of a call (prepare, hscProve, aggregate), which are gone when it returns.
+int sonic_prover_device_bytes(sonic_prover_t* p, int64_t* out) {
+  API_BEGIN_ON(p ? p->device : -1)
+  if (!p || !out) { set_error("sonic_prover_device_bytes: bad argument"); return SONIC_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> g(p->mu);
+  size_t total = 0;
+  auto add = [&total](const DevBuf& b) { total += b.bytes; };
+  auto add_ws = [&](const MsmWorkspace& w) {
+    for (const DevBuf* b : {&w.count, &w.off, &w.digits, &w.entries, &w.buckets, &w.segres, &w.scan_tmp, &w.order, &w.heavy_meta, &w.heavy_partial, &w.endo_scalars,
+                            &w.g2_nchunk, &w.g2_chunk_off, &w.g2_scan_tmp, &w.g2_partial, &w.g2_buckets, &w.g2_segres, &w.g2_sum_tmp, &w.g2_wsum}) add(*b);
+  };
+  auto add_sc = [&](const Scratch& s) { for (const DevBuf* b : {&s.D, &s.q, &s.scan, &s.fz_discard}) add(*b); };
+  auto add_lane = [&](const Lane& l) { add_ws(l.ws); for (const Scratch& s : l.sc) add_sc(s); };
+  for (const DevBuf* b : {&p->wL, &p->wR, &p->wO, &p->cs, &p->aL, &p->aR, &p->aO, &p->S, &p->PAIRS, &p->r1, &p->sy0, &p->su, &p->pw, &p->kpow, &p->fa, &p->fb, &p->slots,
+                          &p->frout, &p->flags, &p->tmp, &p->wit_raw, &p->frstd, &p->cq, &p->cq_tab, &p->wtree, &p->wdtree}) add(*b);
+  const sonic_prover::CsrBufs& sp = p->sp;
+  for (const DevBuf* b : {&sp.row_ptr, &sp.col, &sp.val, &sp.col_ptr, &sp.row, &sp.cval, &sp.chunk_row, &sp.chunk_begin, &sp.row_chunk, &sp.partial}) add(*b);
+  for (const DevBuf* b : {&p->stm.stage, &p->stm.partial, &p->stm.out, &p->stm.gates}) add(*b);
+  for (const Lane& l : p->lanes) add_lane(l);
+  for (const Lane& l : p->chain) add_lane(l);
+  add_ws(p->runs_ws);
+  for (const auto& r : p->runs) for (const DevBuf* b : {&r.masked, &r.val, &r.uniform, &r.scal, &r.pts}) add(*b);
+  for (const auto& s : p->fused_sc) add_sc(*s);
+  for (const std::vector<DevBuf>* v : {&p->syj, &p->diag, &p->yq}) for (const DevBuf& b : *v) add(b);
+  *out = (int64_t)total;
+  API_END
 }
 
 // hscProve :: SRS -> BiVLaurent Fr -> [(Fr, Fr)] -> m HscProof (Signature.hs:32-72) on its own, for the s(X,Y) of the handle's

@@ -43,6 +43,7 @@ enum { PH_R = 1,      // R                                   (blinders)
 // window tables of the per-circuit commitments C_q (sonic_prover_prepare): 29 windows of 9 / 8 bits over 256 shared buckets
 constexpr int CQ_TAB_W = 29, CQ_TAB_C = 9;
 constexpr long CQ_TAB_MAX_Q = 1L << 16;
+// (sonic_prover_device_bytes, prove.hip, lists these buffers by name: a buffer added here must be added there)
 struct Scratch {
   DevBuf D, q, scan, fz_discard;
   void reserve(long len) { D.ensure(sizeof(Fr) * (len + 1)); q.ensure(sizeof(Fr) * (len + 1)); fz_discard.ensure(sizeof(Fr)); }
@@ -89,6 +90,9 @@ struct FsWorker {
   std::vector<uint8_t> proof, transcript;
 };
 
+// Every DevBuf below -- directly, in CsrBufs, StatementBufs, RunBufs, the lanes and chains, the vectors -- is counted by
+// sonic_prover_device_bytes (prove.hip), which names them one by one: a device buffer added to the handle must be added to that list,
+// or the handle under-reports what it owns.
 struct sonic_prover {
   const sonic_srs* srs = nullptr;
   int device = 0;                            // the SRS's GPU: the handle's streams, buffers and every call on it live there
@@ -253,6 +257,15 @@ struct sonic_prover {
   DevBuf wtree;
   uint32_t* h_root = nullptr;
   void assignment_changed() { have_witness_digest = false; have_witness_digest_v2 = false; }
+  // weights digest v2 (fs.hpp): the SHA-256 tree over the entries of the resident CSR (weights_digest.hip) into `wdtree`, the root through
+  // h_root as well; cached until the circuit changes (prover_upload_circuit)
+  uint8_t weights_digest_v2[32] = {0};
+  bool have_weights_digest_v2 = false;
+  DevBuf wdtree;
+  // The per-pair state of the signature: s(X, y_j) for each of the Q pairs (syj: Q buffers of 3n + 1 elements, Q n-proportional) and the
+  // events that order their groups (ev_syj).  Made by ensure_pair_state (prove.hip) on the first enqueue whose phases include the
+  // signature; a handle that only ever makes core proofs, aggregates, digests or constraint evaluations never has it.
+  bool have_pair_state = false;
   // Lane N_LANES-1 carries the t(X,y) group (the largest, ready last); the other groups alternate over the rest, which
   // balances the point additions per lane (Q = 2: 55M / 51M / 48M) while one lane's sort and reduction phases run under
   // another lane's accumulation.  Streams beyond the 4 hardware queues would serialise behind each other.

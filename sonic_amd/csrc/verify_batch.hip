@@ -29,6 +29,7 @@
 #include "proof_layout.hpp"
 #include "srs_scale.hpp"
 #include "pairing_device.hpp"
+#include "weights_tree.hpp"
 
 namespace sonic {
 namespace {
@@ -237,6 +238,14 @@ struct sonic_verifier {
   std::vector<uint8_t> cs;
   uint8_t weights_digest[32];           // of the midstate (fs.hpp, "helped verification"): made by the first helped call, not when the handle is
   bool have_weights_digest = false;
+  // Which circuit digest the handle's Fiat-Shamir calls derive (sonic_verifier_new_digest): 1 = circuit digest v1 over the dense bytes the
+  // weights stand for (midstate + resume, O(Q n) hashing when the handle is made); 2 = circuit digest v2 over the CSR entries (fs.hpp):
+  // the GPU hashes the resident CSR into weights digest v2 when the handle is made -- `weights_digest`, have_weights_digest true from the
+  // start -- no dense byte is hashed and `midstate` is never filled.  Everything below the digests takes the 32 bytes it is given.
+  int digest_kind = 1;
+  DevBuf wdtree;                        // the tree of weights digest v2 (weights_digest.hip), all levels
+  bool have_wd2 = false;                // kind 1: weights digest v2 is made by the first sonic_verifier_weights_digest_v2, into wd2
+  uint8_t wd2[32];
   std::mutex mu;                        // one call at a time per handle
   hipStream_t st = nullptr;
   MsmWorkspace ws;
@@ -587,6 +596,13 @@ int verify_batch_core(sonic_verifier* v, long K, const uint8_t* proofs, const ui
   }, all_accepted, each);
 }
 
+// the digest of one statement of the handle's circuit, of the handle's kind: v1 resumes the midstate, v2 hashes the constants behind
+// weights digest v2 (fs.hpp).  Non-zero: cs is not canonical (dk is left alone)
+int statement_digest(const sonic_verifier* v, const uint8_t* cs, uint8_t dk[32]) {
+  if (v->digest_kind == 2) return fs_circuit_digest_v2(v->weights_digest, v->Q, cs, dk);
+  return fs_circuit_digest_resume(v->midstate, cs, dk);
+}
+
 // the Fiat-Shamir form: the challenges each proof determines (fs.hpp), in sonic_verify's order; a proof whose own u, v are not its
 // transcript's is rejected
 // cs_each (the `_cs` form): proof k's transcript starts from the digest of ITS statement, resume(midstate, cs_k); a cs_k that is not canonical has
@@ -601,7 +617,7 @@ int verify_fs_batch_core(sonic_verifier* v, long K, const uint8_t* proofs, const
     const uint8_t* proof = proofs + psz * (size_t)k;
     uint8_t dk[32];
     memcpy(dk, v->digest, 32);
-    if (cs_each && fs_circuit_digest_resume(v->midstate, cs_each + 32 * (size_t)(k * Q), dk) != 0) memcpy(dk, v->digest, 32);
+    if (cs_each && statement_digest(v, cs_each + 32 * (size_t)(k * Q), dk) != 0) memcpy(dk, v->digest, 32);
     fs_challenges_of_proof(v->n, Q, v->d, dk, v->srs_id, proof, ch.data());
     if (memcmp(proof + psz - 64, &ch[32 * (size_t)(2 + 2 * Q)], 64) != 0) { mine[(size_t)k] = 0; all_mine = false; }
     uint8_t* o = &chal[csz * (size_t)k];
@@ -727,7 +743,7 @@ void core_fs_challenges_batch(sonic_verifier* v, long K, const uint8_t* proofs, 
     uint8_t dk[32];
     memcpy(dk, v->digest, 32);
     // (a cs_k that is not canonical has no digest: the proof rides along under the handle's and is refused as malformed)
-    if (cs_each && fs_circuit_digest_resume(v->midstate, cs_each + 32 * (size_t)(k * Q), dk) != 0) memcpy(dk, v->digest, 32);
+    if (cs_each && statement_digest(v, cs_each + 32 * (size_t)(k * Q), dk) != 0) memcpy(dk, v->digest, 32);
     fs_core_challenges_of_proof(v->n, Q, v->d, dk, v->srs_id, proofs + ProofLayout::core_proof_bytes() * (size_t)k, &yz[64 * (size_t)k]);
   }
 }
@@ -972,9 +988,21 @@ int verify_core_helped(sonic_verifier* v, long K, const uint8_t* proofs, const u
   return SONIC_OK;
 }
 
-int verifier_new(const char* who, const sonic_srs_t* srs, const CircuitView& c, sonic_verifier_t** out) {
+// weights digest v2 of the handle's resident CSR, on the GPU (weights_digest.hip): the tree, 32 bytes back, the 76-byte hash over the root
+void verifier_weights_digest_v2(sonic_verifier* v, uint8_t out[32]) {
+  const uint32_t* root_d = weights_tree_enqueue(v->st, v->row_ptr.as<int32_t>(), v->col.as<int32_t>(), v->val.as<Fr>(), 3 * v->Q, v->cd.nnz, v->wdtree);
+  uint32_t words[8];
+  HIP_OK(hipMemcpyAsync(words, root_d, 32, hipMemcpyDeviceToHost, v->st));
+  HIP_OK(hipStreamSynchronize(v->st));
+  uint8_t root[32];
+  wt_digest_bytes(words, root);
+  fs_weights_digest_v2(v->n, v->Q, v->cd.nnz, root, out);
+}
+
+int verifier_new(const char* who, const sonic_srs_t* srs, const CircuitView& c, sonic_verifier_t** out, int digest_kind = 1) {
   if (!srs || !c.cs || !out) { set_error("%s: bad argument", who); return SONIC_ERR_INVALID_ARG; }
   *out = nullptr;
+  if (digest_kind != 1 && digest_kind != 2) { set_error("%s: digest_kind = %d, must be 1 (circuit digest v1) or 2 (circuit digest v2)", who, digest_kind); return SONIC_ERR_INVALID_ARG; }
   int rc = circuit_validate(who, c);
   if (rc) return rc;
   const long n = c.n, Q = c.Q, R = 3 * Q;
@@ -989,8 +1017,11 @@ int verifier_new(const char* who, const sonic_srs_t* srs, const CircuitView& c, 
   if (v->d != n) v->ms.push_back(v->d);
   v->hm.resize(v->ms.size());
   for (size_t i = 0; i < v->ms.size(); i++) { rc = pc_v_element(srs, v->ms[i], v->hm[i]); if (rc) return rc; }
-  circuit_midstate(c, v->midstate);
-  fs_circuit_digest_resume(v->midstate, c.cs, v->digest);
+  v->digest_kind = digest_kind;
+  if (digest_kind == 1) {
+    circuit_midstate(c, v->midstate);
+    fs_circuit_digest_resume(v->midstate, c.cs, v->digest);
+  }
   rc = sonic_fs_srs_id(srs, v->srs_id);
   if (rc) return rc;
   // the circuit as CSR, whichever form it came in (dense: the non-zero entries), values Montgomery
@@ -1032,6 +1063,15 @@ int verifier_new(const char* who, const sonic_srs_t* srs, const CircuitView& c, 
   } catch (...) { (void)hipStreamDestroy(v->st); throw; }
   cd.row_ptr = v->row_ptr.as<int32_t>(); cd.col = v->col.as<int32_t>(); cd.val = v->val.as<Fr>();
   cd.item_row = v->item_row.as<int32_t>(); cd.item_begin = v->item_begin.as<int32_t>();
+  if (digest_kind == 2) {
+    // (the constants were checked above: the digest of the handle's own statement cannot fail)
+    try {
+      verifier_weights_digest_v2(v.get(), v->weights_digest);
+    } catch (...) { (void)hipStreamDestroy(v->st); throw; }
+    v->have_weights_digest = true;
+    memcpy(v->wd2, v->weights_digest, 32); v->have_wd2 = true;
+    fs_circuit_digest_v2(v->weights_digest, Q, c.cs, v->digest);
+  }
   *out = v.release();
   return SONIC_OK;
 }
@@ -1065,6 +1105,21 @@ int sonic_verifier_new_csr(const sonic_srs_t* srs, int64_t n, int64_t Q, const i
   API_BEGIN_ON(srs_device(srs))
   return verifier_new("sonic_verifier_new_csr", srs, csr_view(n, Q, row_ptr, col, val, cs), out);
   API_CATCH
+}
+int sonic_verifier_new_digest(const sonic_srs_t* srs, int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val, const uint8_t* cs,
+                              int digest_kind, sonic_verifier_t** out) {
+  API_BEGIN_ON(srs_device(srs))
+  return verifier_new(digest_kind == 1 ? "sonic_verifier_new_csr" : "sonic_verifier_new_digest", srs, csr_view(n, Q, row_ptr, col, val, cs), out, digest_kind);
+  API_CATCH
+}
+int sonic_verifier_digest_kind(const sonic_verifier_t* v) { return v ? v->digest_kind : -1; }
+int sonic_verifier_weights_digest_v2(sonic_verifier_t* v, uint8_t out[32]) {
+  API_BEGIN_ON(v ? v->device : -1)
+  if (!v || !out) { set_error("sonic_verifier_weights_digest_v2: bad argument"); return SONIC_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> g(v->mu);
+  if (!v->have_wd2) { verifier_weights_digest_v2(v, v->wd2); v->have_wd2 = true; }
+  memcpy(out, v->wd2, 32);
+  API_END
 }
 void sonic_verifier_free(sonic_verifier_t* v) {
   if (!v) return;

@@ -51,12 +51,15 @@ HD void wt_compress(uint32_t s[8], uint32_t w[16]) {
 
 // H_leaf(i) (node = false: the label zero-padded to 56 bytes, then le64 i) and H_node(level, j) (the label zero-padded to 48 bytes, then
 // le64 level, le64 j), as message words.  Both labels are 25 bytes, and a leaf's bytes 48 .. 55 are padding: level = 0.
-HD void wt_header(bool node, uint64_t level, uint64_t index, uint32_t h[16]) {
-  const char* label = node ? "sonic-hip/witness-node/v2" : "sonic-hip/witness-leaf/v2";
+// (wt_header_of: the same header under another 25-byte label -- the tree of weights digest v2, weights_tree.hpp)
+HD void wt_header_of(const char* label, uint64_t level, uint64_t index, uint32_t h[16]) {
   for (int k = 0; k < 12; k++) h[k] = 0;
   for (int b = 0; b < 25; b++) h[b >> 2] |= (uint32_t)(uint8_t)label[b] << (24 - 8 * (b & 3));
   h[12] = wt_bswap((uint32_t)level); h[13] = wt_bswap((uint32_t)(level >> 32));
   h[14] = wt_bswap((uint32_t)index); h[15] = wt_bswap((uint32_t)(index >> 32));
+}
+HD void wt_header(bool node, uint64_t level, uint64_t index, uint32_t h[16]) {
+  wt_header_of(node ? "sonic-hip/witness-node/v2" : "sonic-hip/witness-leaf/v2", level, index, h);
 }
 
 // SHA-256(header || item 0 .. item count-1) as eight state words; item(k, w) writes item k as eight message words

@@ -449,6 +449,21 @@ class Prover:
         _lib.check(_lib.lib().sonic_prover_witness_digest_v2(self._h, out))
         return out.raw
 
+    def weights_digest_v2(self) -> bytes:
+        """weights digest v2 of the handle's circuit (sonic_prover_weights_digest_v2): the SHA-256 tree the GPU computes over the entries of
+        the resident CSR; cached.  A handle made from dense weights is refused: make it from a SparseCircuit."""
+        out = C.create_string_buffer(32)
+        _lib.check(_lib.lib().sonic_prover_weights_digest_v2(self._h, out))
+        return out.raw
+
+    @property
+    def device_bytes(self) -> int:
+        """the device memory the handle owns now (sonic_prover_device_bytes): every buffer of its own, lane workspaces included, not the
+        SRS it borrows.  The Q buffers of the signature's pairs appear with the first full proof; core proofs never make them."""
+        out = C.c_int64(0)
+        _lib.check(_lib.lib().sonic_prover_device_bytes(self._h, C.byref(out)))
+        return int(out.value)
+
     def submit_fs(self, circuit_digest: bytes, blinder_seed: bytes) -> None:
         """hand one Fiat-Shamir proof to the handle's host worker and return without waiting (sonic_prover_submit_fs); one proof in flight
         per handle.  The blinders come from witness digest v2, so the bytes differ from prove_fs's for the same seed."""
@@ -1060,6 +1075,36 @@ def fs_weights_digest(circuit) -> bytes:
     return out.raw
 
 
+def fs_weights_digest_v2(circuit) -> bytes:
+    """weights digest v2 (sonic_fs_weights_digest_v2_csr; host only): SHA-256 tree over the ENTRIES of the stacked CSR, O(nnz) where
+    fs_weights_digest hashes 96 Q n bytes.  circuit: a SparseCircuit, hashed as given -- an explicit zero is an entry, so two CSRs of one
+    matrix that differ in explicit zeros have different digests -- or an ArithCircuit, which goes through SparseCircuit.from_circuit
+    (its non-zero entries)."""
+    sp = circuit if isinstance(circuit, SparseCircuit) else SparseCircuit.from_circuit(circuit)
+    out = C.create_string_buffer(32)
+    _lib.check(_lib.lib().sonic_fs_weights_digest_v2_csr(sp.n, sp.Q, *sp._args(), out))
+    return out.raw
+
+
+def fs_circuit_digest_v2(weights_digest: bytes, cs) -> bytes:
+    """circuit digest v2 of one statement (sonic_fs_circuit_digest_v2; host only): SHA-256 over weights digest v2, Q and the constants
+    cs (ints or Q x 32 bytes) -- 32 Q bytes of hashing per statement.  What prove_core_fs and its batches take as `circuit_digest` for a
+    Verifier(..., digest=2)."""
+    weights_digest = bytes(weights_digest)
+    if len(weights_digest) != 32:
+        raise ValueError("fs_circuit_digest_v2: a weights digest is 32 bytes")
+    # (bytes as they are, ints without reduction: a non-canonical constant must reach the library, which refuses it)
+    if isinstance(cs, np.ndarray) and cs.dtype == np.uint8:
+        raw = cs.tobytes()
+    else:
+        raw = bytes(cs) if isinstance(cs, (bytes, bytearray, memoryview)) else b"".join(int(c).to_bytes(32, "little") for c in cs)
+    if not raw or len(raw) % 32:
+        raise ValueError("fs_circuit_digest_v2: need Q >= 1 constants of 32 bytes each")
+    out = C.create_string_buffer(32)
+    _lib.check(_lib.lib().sonic_fs_circuit_digest_v2(weights_digest, len(raw) // 32, raw, out))
+    return out.raw
+
+
 def fs_aggregate_challenges(srs: SRS, circuit, yzs, aggregate: bytes, weights_digest: Optional[bytes] = None):
     """(u, v) that the bytes of an aggregate for the pairs yzs determine (sonic_fs_aggregate_challenges; host only): a verifier compares
     them with the aggregate's own last 64 bytes"""
@@ -1092,11 +1137,34 @@ class Verifier:
     four Miller loops and one final exponentiation per batch; point validation, s(u, v) and the G1 sums run on the GPU.  `circuit` is an
     ArithCircuit or a SparseCircuit.  A malformed proof is a rejected proof (False), never an exception."""
 
-    def __init__(self, srs: SRS, circuit):
+    def __init__(self, srs: SRS, circuit, digest: int = 1):
+        """digest: which circuit digest the handle's Fiat-Shamir and helped calls derive.  1: circuit digest v1 (fs_circuit_digest; O(Q n)
+        hashing here).  2: circuit digest v2 (sonic_verifier_new_digest): the GPU hashes the CSR entries, nothing dense; proofs must be made
+        under fs_circuit_digest_v2(wd2, cs) and aggregates under weights_digest=wd2.  A dense circuit goes through
+        SparseCircuit.from_circuit first."""
+        if digest not in (1, 2):
+            raise ValueError("Verifier: digest must be 1 or 2")
+        if digest == 2 and not isinstance(circuit, SparseCircuit):
+            circuit = SparseCircuit.from_circuit(circuit)
         self.n, self.Q, suffix, args, _keep = _circuit_args(circuit, "Verifier: ")
         self._srs = srs                  # the handle borrows the SRS
         self._h = C.c_void_p()
-        _lib.check(getattr(_lib.lib(), "sonic_verifier_new" + suffix)(srs._h, self.n, self.Q, *args, C.byref(self._h)))
+        if digest == 2:
+            _lib.check(_lib.lib().sonic_verifier_new_digest(srs._h, self.n, self.Q, *args, 2, C.byref(self._h)))
+        else:
+            _lib.check(getattr(_lib.lib(), "sonic_verifier_new" + suffix)(srs._h, self.n, self.Q, *args, C.byref(self._h)))
+
+    @property
+    def digest_kind(self) -> int:
+        """1 or 2 (sonic_verifier_digest_kind)"""
+        return int(_lib.lib().sonic_verifier_digest_kind(self._h))
+
+    def weights_digest_v2(self) -> bytes:
+        """weights digest v2 of the handle's resident CSR, computed on the GPU (sonic_verifier_weights_digest_v2); a handle made from dense
+        weights holds their non-zero entries"""
+        out = C.create_string_buffer(32)
+        _lib.check(_lib.lib().sonic_verifier_weights_digest_v2(self._h, out))
+        return out.raw
 
     def _proof_bytes(self, proofs):
         """the batch as one buffer, and the suffix of the entry point that reads it: "" for proof bytes / Proof objects, "_z" when every
