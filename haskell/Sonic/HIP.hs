@@ -73,6 +73,7 @@ module Sonic.HIP
     -- * circuits with Q ~ n: weights digest v2, circuit digest v2
   , fsWeightsDigestV2, fsCircuitDigestV2, proverWeightsDigestV2, verifierWeightsDigestV2, newVerifierDigest, verifierDigestKind
   , proverDeviceBytes
+  , proverHostBytes
   ) where
 
 import Protolude hiding (check)
@@ -194,6 +195,7 @@ foreign import ccall safe   "sonic_verifier_weights_digest_v2" c_verifier_weight
 foreign import ccall safe   "sonic_verifier_new_digest"   c_verifier_new_digest :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> CInt -> Ptr (Ptr VerifierHandle) -> IO CInt
 foreign import ccall safe   "sonic_verifier_digest_kind"  c_verifier_digest_kind :: Ptr VerifierHandle -> IO CInt
 foreign import ccall safe   "sonic_prover_device_bytes"   c_prover_device_bytes :: Ptr ProverHandle -> Ptr Int64 -> IO CInt
+foreign import ccall safe   "sonic_prover_host_bytes"   c_prover_host_bytes :: Ptr ProverHandle -> Ptr Int64 -> IO CInt
 foreign import ccall safe   "sonic_prover_aggregate_core" c_prover_aggregate_core :: Ptr ProverHandle -> Ptr Word8 -> Int64 -> Ptr Word8 -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_verifier_verify_core_batch_helped" c_verify_core_batch_helped :: Ptr VerifierHandle -> Int64 -> Ptr Word8 -> CInt -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> Ptr Word8 -> IO CInt
 foreign import ccall safe   "sonic_verify_core_csr"       c_verify_core_csr :: Ptr SrsHandle -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr CInt -> IO CInt
@@ -1056,10 +1058,18 @@ newVerifierDigest kind srs@(SRS h) circuit =
 verifierDigestKind :: Verifier -> IO Int
 verifierDigestKind Verifier{..} = withForeignPtr verifierHandle $ \v -> fromIntegral <$> c_verifier_digest_kind v
 
--- | the device memory the prover handle owns now (sonic_prover_device_bytes): the pairs' buffers appear with the first full proof
+-- | the device memory the prover handle owns now (sonic_prover_device_bytes): the signature's state (MSM slots 5 and above, the pairs'
+--   buffers) appears with the first full proof
 proverDeviceBytes :: Prover -> IO Int64
 proverDeviceBytes pr = withProverAlive pr $ \p -> alloca $ \out -> do
   check =<< c_prover_device_bytes p out
+  peek out
+
+-- | the pinned host memory the prover handle owns now (sonic_prover_host_bytes): a core proof's staging until the first proof with a
+--   signature, whose MSM slots (5 Q + 8 of 12 304 bytes) then appear here and on the device
+proverHostBytes :: Prover -> IO Int64
+proverHostBytes pr = withProverAlive pr $ \p -> alloca $ \out -> do
+  check =<< c_prover_host_bytes p out
   peek out
 
 -- | K proofs of K statements of the handle's circuit in one pairing product (sonic_verifier_verify_batch_cs): proof k against cs_k with

@@ -111,7 +111,8 @@ typedef struct sonic_verifier sonic_verifier_t;
  * still 7, additions only: the G2 sums -- sonic_msm_g2, sonic_msm_g2_srs[_dev], sonic_msm_g2_walk_max; subgroup membership --
  * sonic_g1_subgroup_check, sonic_g2_subgroup_check; pairings -- sonic_pairing_check; the opening chain alone -- sonic_open_batch_dense;
  * still 7, additions only: circuits with Q ~ n -- sonic_fs_weights_digest_v2_csr, sonic_fs_circuit_digest_v2, sonic_prover_weights_digest_v2,
- * sonic_verifier_weights_digest_v2, sonic_verifier_new_digest, sonic_verifier_digest_kind, sonic_prover_device_bytes */
+ * sonic_verifier_weights_digest_v2, sonic_verifier_new_digest, sonic_verifier_digest_kind, sonic_prover_device_bytes,
+ * sonic_prover_host_bytes */
 int sonic_abi_version(void);
 int sonic_init(int device_ordinal);                 /* choose the DEFAULT GPU (first call wins) and make it the thread's HIP device; idempotent */
 int sonic_device_count(int* out);                   /* GPUs this process can see; SONIC_ERR_NO_DEVICE (and 0) without one */
@@ -991,7 +992,7 @@ int sonic_r1cs_assign(sonic_r1cs_t* r, int64_t K, const void* z, int kind, int o
                       void* d_aR, void* d_aO, int64_t out_stride, uint8_t* out_cs, int64_t* out_bad);
 int sonic_r1cs_row_chunk(void);
 
-/* ---- Circuits with Q ~ n: weights digest v2, circuit digest v2, per-pair prover state on first use ----
+/* ---- Circuits with Q ~ n: weights digest v2, circuit digest v2, the prover's signature state on first use ----
  * Circuit digest v1 hashes the 96 Q n dense bytes the gate weights stand for, whichever form they come in.  With Q of the order of n that
  * is seconds of hashing per handle.  Digest v2 hashes the ENTRIES of the stacked CSR, O(nnz), as a SHA-256 tree that the GPU computes from
  * a handle's resident CSR.  The normative text (sonic_amd/csrc/fs.hpp), repeated:
@@ -1028,10 +1029,25 @@ int sonic_r1cs_row_chunk(void);
  *   sonic_verifier_digest_kind        1 or 2 (-1 for NULL).
  *   sonic_prover_device_bytes         the device memory the handle owns now: all its buffers, lane workspaces included; not the SRS it borrows.
  *
- * Per-pair state on first use.  The Q buffers of 3n + 1 field elements for s(X, y_j) and their Q events belong to the signature.  A prover
- * handle makes them on its first full proof, share or Fiat-Shamir proof; core proofs, sonic_prover_aggregate_core, eval_constraints, the
- * witness calls and the digests never do, and a core proof does no per-pair work.  When that allocation fails the call returns SONIC_ERR_HIP
- * with a message that names the size, and the handle remains good for core proofs.  Proof bytes are unchanged, in every order of calls. */
+ *   sonic_prover_host_bytes           the pinned host memory the handle owns now (the staging of transcript, pairs, MSM slots, evaluations,
+ *                                     flags and digest root); same locking and errors as sonic_prover_device_bytes.
+ *
+ * Signature state on first use.  A prover handle is made with what a CORE proof reads: 8 MSM slots (of 12 304 bytes, on the device and in
+ * pinned host memory), 8 transcript elements, 5 evaluation-point pairs and 3 evaluations, whatever Q is.  Everything else a proof with a
+ * signature needs -- the other 5 Q slots on both sides, the transcript, pairs and evaluations beyond those prefixes, and the Q buffers of
+ * 3n + 1 field elements for s(X, y_j) with their Q events -- is made by the first enqueue of such a proof: a full proof, a share, every pass
+ * of sonic_prover_prove_fs / submit_fs, the batch calls over them.  Core proofs in every form (blocking, submit_core / collect_core,
+ * Fiat-Shamir, the batch calls), sonic_prover_aggregate_core, eval_constraints, the witness calls, the digests, sonic_prover_prepare and
+ * sonic_prover_hsc_prove (which work in buffers of the call) never make it.  It is made before anything of the proof is queued; when an
+ * allocation fails the call returns SONIC_ERR_HIP with a message that names the sizes, whatever it had got is freed, and the handle remains
+ * good for core proofs.  A core proof's enqueue and finish do no host work, allocation or copy that grows with Q beyond what its statement
+ * needs (the Q constants of a call that brings its own, and the Q-long device arrays of k(y) and s(X, y)).  Proof bytes are unchanged, in
+ * every order of calls.
+ *
+ * k(y) = sum_q cs[q] y^(n+1+q) runs in one block of 256 threads below a threshold of Q and over ceil(Q / span) blocks from it on (a second,
+ * one-block launch adds their partial sums; the sums are exact, so the proof's bytes do not depend on the form).  SONIC_K_OF_Y_SPLIT=<Q>
+ * sets the threshold (default 2^14, the smallest measured Q from which the split wins; 0: never split), SONIC_K_OF_Y_SPAN=<q per block> the
+ * span (default 2048); both are read per call. */
 int sonic_fs_weights_digest_v2_csr(int64_t n, int64_t Q, const int64_t* row_ptr, const int64_t* col, const uint8_t* val, uint8_t out[32]);
 int sonic_fs_circuit_digest_v2(const uint8_t weights_digest[32], int64_t Q, const uint8_t* cs, uint8_t out[32]);
 int sonic_prover_weights_digest_v2(sonic_prover_t* p, uint8_t out[32]);
@@ -1040,6 +1056,7 @@ int sonic_verifier_new_digest(const sonic_srs_t* srs, int64_t n, int64_t Q, cons
                               const uint8_t* cs, int digest_kind, sonic_verifier_t** out);
 int sonic_verifier_digest_kind(const sonic_verifier_t* v);
 int sonic_prover_device_bytes(sonic_prover_t* p, int64_t* out);
+int sonic_prover_host_bytes(sonic_prover_t* p, int64_t* out);
 
 /* ---- device memory for callers without a HIP binding ---- */
 int sonic_dev_alloc(size_t bytes, void** out);                       /* on the default device */

@@ -223,6 +223,7 @@ def lib() -> C.CDLL:
         "sonic_verifier_new_digest": [vp, i64, i64, vp, vp, vp, vp, i32, C.POINTER(vp)],
         "sonic_verifier_digest_kind": [vp],
         "sonic_prover_device_bytes": [vp, C.POINTER(i64)],
+        "sonic_prover_host_bytes": [vp, C.POINTER(i64)],
         "sonic_dev_alloc": [C.c_size_t, C.POINTER(vp)],
         "sonic_dev_free": [vp],
         "sonic_dev_upload": [vp, vp, C.c_size_t],
@@ -343,7 +344,7 @@ EXPORTED = [
     "sonic_open_batch_dense",
     "sonic_r1cs_new", "sonic_r1cs_new_on", "sonic_r1cs_free", "sonic_r1cs_device", "sonic_r1cs_shape", "sonic_r1cs_circuit", "sonic_r1cs_assign", "sonic_r1cs_row_chunk",
     "sonic_fs_weights_digest_v2_csr", "sonic_fs_circuit_digest_v2", "sonic_prover_weights_digest_v2", "sonic_verifier_weights_digest_v2",
-    "sonic_verifier_new_digest", "sonic_verifier_digest_kind", "sonic_prover_device_bytes",
+    "sonic_verifier_new_digest", "sonic_verifier_digest_kind", "sonic_prover_device_bytes", "sonic_prover_host_bytes",
 ]
 
 

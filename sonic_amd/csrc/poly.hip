@@ -589,8 +589,60 @@ __global__ __launch_bounds__(256) void k_sub_k_of_y(Fr* __restrict__ slot, const
     if (!v.is_zero()) atomicOr(flags, flag_bit);
   }
 }
-void sub_k_of_y_enqueue(hipStream_t st, Fr* slot, const Fr* cs, const Fr* ypow_nq, long Q, int* flags, int flag_bit) {
-  LAUNCH(k_sub_k_of_y, 1, 256, 0, st, slot, cs, ypow_nq, Q, flags, flag_bit);
+// The same over many blocks (k_of_y_plan.hpp), for circuits with Q of the order of n: a compiled R1CS of m = 2^18 has Q = 3 * 2^18, which is
+// ~3000 dependent products per thread of the one block above, on one CU, in front of the T commitment.  Stage 1: block b sums the terms
+// of its span into partial[b] (no atomics on field elements: every partial has one writer).  Stage 2: one block sums the partials --
+// looping when there are more than 256 -- subtracts from the slot and raises the flag exactly as k_sub_k_of_y does.  The sums are exact
+// field sums, so the slot's value does not depend on the plan.
+__global__ __launch_bounds__(K_OF_Y_BLOCK) void k_k_of_y_partials(const Fr* __restrict__ cs, const Fr* __restrict__ ypow_nq, long Q, KOfYPlan plan, Fr* __restrict__ partial) {
+  __shared__ Fr sh[K_OF_Y_BLOCK];
+  long lo, hi;
+  k_of_y_span(plan, Q, (long)blockIdx.x, &lo, &hi);
+  Fr acc = Fr::zero();
+  for (long q = lo + threadIdx.x; q < hi; q += K_OF_Y_BLOCK) acc = fp_add(acc, fp_mul(cs[q], ypow_nq[q]));
+  sh[threadIdx.x] = acc;
+  __syncthreads();
+  for (int o = K_OF_Y_BLOCK / 2; o >= 1; o >>= 1) {
+    if ((int)threadIdx.x < o) sh[threadIdx.x] = fp_add(sh[threadIdx.x], sh[threadIdx.x + o]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
+}
+__global__ __launch_bounds__(K_OF_Y_BLOCK) void k_k_of_y_finish(Fr* __restrict__ slot, const Fr* __restrict__ partial, long blocks, int* flags, int flag_bit) {
+  __shared__ Fr sh[K_OF_Y_BLOCK];
+  Fr acc = Fr::zero();
+  for (long b = threadIdx.x; b < blocks; b += K_OF_Y_BLOCK) acc = fp_add(acc, partial[b]);
+  sh[threadIdx.x] = acc;
+  __syncthreads();
+  for (int o = K_OF_Y_BLOCK / 2; o >= 1; o >>= 1) {
+    if ((int)threadIdx.x < o) sh[threadIdx.x] = fp_add(sh[threadIdx.x], sh[threadIdx.x + o]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    Fr v = fp_sub(*slot, sh[0]);
+    *slot = v;
+    if (!v.is_zero()) atomicOr(flags, flag_bit);
+  }
+}
+// Which form a proof over Q constraints takes: one block below the threshold (blocks = 0: small circuits launch exactly what they always
+// launched), spans of K_OF_Y_SPAN_DEFAULT terms from it on.  SONIC_K_OF_Y_SPLIT=<Q> sets the threshold (0: never split),
+// SONIC_K_OF_Y_SPAN=<q per block> the span: read per call like the SONIC_PROVE_* knobs, because the tests switch them inside one process.
+// The default threshold is K_OF_Y_SPLIT_DEFAULT (poly.hpp, with the measurement behind it).
+KOfYPlan k_of_y_choose(long Q) {
+  const char* te = getenv("SONIC_K_OF_Y_SPLIT");
+  const char* se = getenv("SONIC_K_OF_Y_SPAN");
+  const long threshold = te ? atol(te) : K_OF_Y_SPLIT_DEFAULT;
+  const long span = se && atol(se) >= 1 ? atol(se) : K_OF_Y_SPAN_DEFAULT;
+  if (threshold <= 0 || Q < threshold) return KOfYPlan();
+  return k_of_y_plan(Q, span);
+}
+void sub_k_of_y_enqueue(hipStream_t st, Fr* slot, const Fr* cs, const Fr* ypow_nq, long Q, int* flags, int flag_bit, const KOfYPlan& plan, Fr* partial) {
+  if (plan.blocks <= 0) {
+    LAUNCH(k_sub_k_of_y, 1, 256, 0, st, slot, cs, ypow_nq, Q, flags, flag_bit);
+    return;
+  }
+  LAUNCH(k_k_of_y_partials, (unsigned)plan.blocks, K_OF_Y_BLOCK, 0, st, cs, ypow_nq, Q, plan, partial);
+  LAUNCH(k_k_of_y_finish, 1, K_OF_Y_BLOCK, 0, st, slot, partial, plan.blocks, flags, flag_bit);
 }
 
 // flags |= bit if any of a[0..n) is non-zero

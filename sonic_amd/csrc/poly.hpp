@@ -3,6 +3,7 @@
 #include "common.hpp"
 #include "field.hpp"
 #include "g1.hpp"
+#include "k_of_y_plan.hpp"
 
 namespace sonic {
 
@@ -19,7 +20,14 @@ void s_of_u_csr_enqueue(hipStream_t st, const int32_t* row_ptr, const int32_t* c
 void csr_row_terms_enqueue(hipStream_t st, const int32_t* col, const Fr* val, const int32_t seg[6], long n, PointArray A, G1Affine* pts, Fr* scal);
 void add_into_enqueue(hipStream_t st, Fr* dst, const Fr* src, long n);
 void t_operands_enqueue(hipStream_t st, const Fr* r1, long r_len, long r_lo, const Fr* sy, long s_off, long s_len, const Fr* ypair, Fr* fa, Fr* fb, long M);
-void sub_k_of_y_enqueue(hipStream_t st, Fr* slot, const Fr* cs, const Fr* ypow_nq, long Q, int* flags, int flag_bit);
+// *slot -= k(y) = sum_q cs[q] ypow_nq[q], in one block (plan.blocks == 0) or over plan.blocks spans (k_of_y_plan.hpp; partial: one Fr per
+// block, the handle's).  k_of_y_choose: the form for Q constraints under the threshold and the knobs SONIC_K_OF_Y_SPLIT / SONIC_K_OF_Y_SPAN.
+// K_OF_Y_SPLIT_DEFAULT: the threshold when the knob is unset -- the smallest measured Q from which the split form wins by more than the
+// spread (us per proof's k(y), HIP events, one block / split at span 2048: Q = 2^10 9.9 / 17.2, 2^12 22.3 / 21.7 (spreads 5.0 / 3.8),
+// 2^14 69.1 / 23.3, 98 306 401 / 23.4, 786 434 3182 / 29.2; profiles/r23_core_scale.txt, part 3)
+constexpr long K_OF_Y_SPLIT_DEFAULT = 1L << 14;
+KOfYPlan k_of_y_choose(long Q);
+void sub_k_of_y_enqueue(hipStream_t st, Fr* slot, const Fr* cs, const Fr* ypow_nq, long Q, int* flags, int flag_bit, const KOfYPlan& plan, Fr* partial);
 void flag_nonzero_enqueue(hipStream_t st, const Fr* a, long n, int* flags, int bit);
 // runs of equal coefficients (poly.hip): tiles of RUN_TILE coefficients that hold one non-zero value are zeroed in `masked` and recorded;
 // run_terms turns the records into 2 * (len / RUN_TILE) (scalar, running-sum point) slots

@@ -58,6 +58,9 @@ struct ProofLayout {
   // a CORE proof (include/sonic_hip.h, "Core proofs"): the head of the record -- R, T, a, W_a, b, W_b, W_t, s -- and nothing of the
   // signature, whatever Q is: the slots 0 .. 4, the evaluations 0 .. 2, the transcript elements 0 .. 5 (4 blinders, y, z)
   static constexpr long core_K = 5, core_F = 3, core_transcript_len = 6;
+  // the pairs a core proof reads are pY, pZ, pYZ; it uploads the five-pair prefix (pU, pV as {1, 1}: never drawn, never read).  These
+  // prefixes are what ProofLayout{0} counts, and what a prover handle holds until its first proof with a signature (prover.hpp)
+  static constexpr long core_n_pairs = 5;
   static constexpr size_t core_proof_bytes() { return (size_t)(core_K * 96 + core_F * 32); }                  // 576
   static constexpr size_t core_proof_bytes_compressed() { return (size_t)(core_K * 48 + core_F * 32); }       // 336
 };

@@ -294,7 +294,11 @@ int prover_admits(const char* who, const sonic_srs* srs, const CircuitView& c) {
 // (an admitted circuit)
 int prover_new_impl(const sonic_srs_t* srs, const CircuitView& c, sonic_prover_t** out, bool own_streams) {
   const long n = c.n, Q = c.Q;
-  const ProofLayout L{Q};
+  // what a core proof reads of the transcript, the pairs, the slots and the evaluations: the counts of a proof without pairs.  The first
+  // proof with a signature re-creates these buffers for Q pairs (ensure_signature_state)
+  const ProofLayout L{0};
+  static_assert(ProofLayout{0}.transcript_len() >= ProofLayout::core_transcript_len && ProofLayout{0}.n_pairs() == ProofLayout::core_n_pairs &&
+                ProofLayout{0}.slots_total() >= ProofLayout::core_K && ProofLayout{0}.F() == ProofLayout::core_F, "a core proof's prefixes are ProofLayout{0}'s");
   for (long q = 0; c.csr && q < Q; q++) {
     Fr k; memcpy(k.l, c.cs + 32 * q, 32);
     if (!fp_is_canonical(k)) { set_error("sonic_prover_new_csr: non-canonical constant cs[%ld]", q); return SONIC_ERR_BAD_ENCODING; }
@@ -337,19 +341,23 @@ int prover_new_impl(const sonic_srs_t* srs, const CircuitView& c, sonic_prover_t
   p->fa.alloc(sizeof(Fr) * M); p->fb.alloc(sizeof(Fr) * M);
   p->r1.alloc(sizeof(Fr) * (3 * n + 5));
   p->sy0.alloc(sizeof(Fr) * (3 * n + 1));
-  // (syj, ev_syj: the Q buffers of 3n + 1 elements and Q events of the signature's pairs are made by ensure_pair_state, on first use)
+  // (syj, ev_syj: the Q buffers of 3n + 1 elements and Q events of the signature's pairs are made by ensure_signature_state, on first use)
   p->su.alloc(sizeof(Fr) * (2 * n + Q + 1));
   p->pw.alloc(sizeof(Fr) * (3 * n + Q + 2));
   p->kpow.alloc(sizeof(Fr) * Q);
   p->S.alloc(sizeof(Fr) * L.transcript_len()); p->PAIRS.alloc(sizeof(Fr) * 2 * L.n_pairs());
   p->slots.alloc(sizeof(MsmSlot) * L.slots_total());
-  HIP_OK(hipHostMalloc((void**)&p->h_tr, 32 * L.transcript_len(), hipHostMallocDefault));
-  HIP_OK(hipHostMalloc((void**)&p->h_pairs, sizeof(Fr) * 2 * L.n_pairs(), hipHostMallocDefault));
-  HIP_OK(hipHostMalloc((void**)&p->h_slots, sizeof(MsmSlot) * L.slots_total(), hipHostMallocDefault));
-  HIP_OK(hipHostMalloc((void**)&p->h_fr, 32 * L.F(), hipHostMallocDefault));
-  HIP_OK(hipHostMalloc((void**)&p->h_flags, 8, hipHostMallocDefault));
-  HIP_OK(hipHostMalloc((void**)&p->h_root, 32, hipHostMallocDefault));
+  p->pin_tr.alloc(32 * L.transcript_len()); p->pin_pairs.alloc(sizeof(Fr) * 2 * L.n_pairs());
+  p->pin_slots.alloc(sizeof(MsmSlot) * L.slots_total()); p->pin_fr.alloc(32 * L.F());
+  p->pin_flags.alloc(8); p->pin_root.alloc(32);
+  p->h_tr = p->pin_tr.as<uint8_t>(); p->h_pairs = p->pin_pairs.as<Fr>(); p->h_slots = p->pin_slots.as<MsmSlot>(); p->h_fr = p->pin_fr.as<uint8_t>();
+  p->h_flags = p->pin_flags.as<int>(); p->h_root = p->pin_root.as<uint32_t>();
   p->h_flags[0] = p->h_flags[1] = 0;
+  // (the partial sums of k(y) over many blocks, where the default plan of this Q has any: an enqueue then allocates nothing)
+  {
+    const KOfYPlan kp = k_of_y_choose(Q);
+    if (kp.blocks > 0) p->k_partial.alloc(sizeof(Fr) * (size_t)kp.blocks);
+  }
   p->frout.alloc(sizeof(Fr) * L.F());
   p->frstd.alloc(sizeof(Fr) * L.F());
   HIP_OK(hipMemsetAsync(p->frout.p, 0, sizeof(Fr) * L.F(), st));
@@ -377,7 +385,7 @@ int prover_new_impl(const sonic_srs_t* srs, const CircuitView& c, sonic_prover_t
   }
   if (p->small_plan) {
     // (the second chain stream is only used by proofs of more than MSM_MAX_JOBS MSMs: Q > 2)
-    for (int c = 0; c < (L.K() > MSM_MAX_JOBS ? 2 : 1); c++) {
+    for (int c = 0; c < (ProofLayout{Q}.K() > MSM_MAX_JOBS ? 2 : 1); c++) {
       mkstream(&p->chain[c].st, PoolRole::CHAIN, c);
       mkev(&p->chain[c].done);
     }
@@ -387,34 +395,61 @@ int prover_new_impl(const sonic_srs_t* srs, const CircuitView& c, sonic_prover_t
   return SONIC_OK;
 }
 
-// The per-pair state of the signature (prover.hpp, have_pair_state), on first use: Q buffers of 3n + 1 elements for the s(X, y_j) and the
-// Q events that order their groups -- 32 Q (3n + 1) bytes, 9.5 GB for a compiled R1CS of m = 2^12, which a handle that makes core proofs
-// never needs.  Called by prove_enqueue, before anything of the proof is queued or captured, for every enqueue that is not a core
-// proof's.  A failed allocation frees what it had got and leaves the handle as it was: good for core proofs, and for another try.
-static int ensure_pair_state(sonic_prover_t* p) {
-  if (p->have_pair_state) return SONIC_OK;
+// The signature state (prover.hpp, have_signature_state), on first use: everything a proof with a signature needs beyond a core proof's
+// prefixes.  The MSM slots 5 and above on the device and pinned on the host (5Q + 8 slots of sizeof(MsmSlot) = 12 304 bytes each: 6.2 GB
+// twice for a compiled R1CS of m = 2^15), the transcript, pairs and evaluations beyond 8, 5 and 3 elements, and the per-pair buffers: Q
+// buffers of 3n + 1 elements for the s(X, y_j) with the Q events that order their groups (32 Q (3n + 1) bytes).  Called by prove_enqueue,
+// before anything of the proof is queued or captured, for every enqueue that is not a core proof's: the handle is never in flight here
+// and nothing of an earlier proof is read afterwards, so the buffers are re-created, slots zeroed, as the constructor makes them.
+// Everything is acquired first and handed to the handle at the end: a failed allocation frees what it had got and leaves the handle as
+// it was, good for core proofs and for another try.
+static int ensure_signature_state(sonic_prover_t* p) {
+  if (p->have_signature_state) return SONIC_OK;
   const long n = p->n, Q = p->Q;
-  const size_t each = sizeof(Fr) * (size_t)(3 * n + 1);
+  const ProofLayout L{Q};
+  const size_t each = sizeof(Fr) * (size_t)(3 * n + 1), slot_bytes = sizeof(MsmSlot) * (size_t)L.slots_total();
+  DevBuf S, PAIRS, slots, frout, frstd;
+  PinnedBuf tr, pairs, hslots, hfr;
+  std::vector<DevBuf> syj;
+  std::vector<hipEvent_t> ev;
   bool made = false;
   try {
-    p->syj.resize((size_t)Q);
-    for (auto& b : p->syj) b.alloc(each);
-    p->ev_syj.resize((size_t)Q, nullptr);
-    for (auto& e : p->ev_syj) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    slots.alloc(slot_bytes);
+    hslots.alloc(slot_bytes);
+    S.alloc(sizeof(Fr) * (size_t)L.transcript_len()); PAIRS.alloc(sizeof(Fr) * 2 * (size_t)L.n_pairs());
+    frout.alloc(sizeof(Fr) * (size_t)L.F()); frstd.alloc(sizeof(Fr) * (size_t)L.F());
+    tr.alloc(32 * (size_t)L.transcript_len()); pairs.alloc(sizeof(Fr) * 2 * (size_t)L.n_pairs()); hfr.alloc(32 * (size_t)L.F());
+    syj.resize((size_t)Q);
+    for (auto& b : syj) b.alloc(each);
+    ev.resize((size_t)Q, nullptr);
+    for (auto& e : ev) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    p->slot_ran.reserve((size_t)L.slots_total());
+    p->fr_valid.reserve((size_t)L.F());
+    {
+      EnqueueLock enq(p);
+      HIP_OK(hipMemsetAsync(frout.p, 0, sizeof(Fr) * (size_t)L.F(), p->st));
+      HIP_OK(hipMemsetAsync(slots.p, 0, slot_bytes, p->st));      // W = 0: an empty sum until the slot's MSM has run
+      HIP_OK(hipStreamSynchronize(p->st));
+    }
+    memset(hslots.p, 0, slot_bytes);
     made = true;
-  } catch (const HipFail&) {             // a device allocation or an event
+  } catch (const HipFail&) {             // a device or pinned allocation, an event, a memset
   } catch (const std::bad_alloc&) {      // the host vectors themselves
   }
   if (!made) {
-    p->syj.clear();
-    for (hipEvent_t e : p->ev_syj) if (e) (void)hipEventDestroy(e);
-    p->ev_syj.clear();
-    (void)hipGetLastError();      // (the failed hipMalloc must not surface as the next launch's error)
-    set_error("prove: no room for the signature's per-pair state: Q = %ld device buffers of %zu bytes, %.3f GB in all (core proofs need none of it)",
-              Q, each, (double)Q * (double)each / 1e9);
-    return SONIC_ERR_HIP;
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    (void)hipGetLastError();      // (the failed allocation must not surface as the next launch's error)
+    set_error("prove: no room for the signature's state: %ld MSM slots of %zu bytes on the device and as many in pinned host memory (%.3f GB each), and Q = %ld "
+              "device buffers of %zu bytes, %.3f GB in all (core proofs need none of it)",
+              L.slots_total(), sizeof(MsmSlot), (double)slot_bytes / 1e9, Q, each, (double)Q * (double)each / 1e9);
+    return SONIC_ERR_HIP;      // (the locals release what they hold)
   }
-  p->have_pair_state = true;
+  p->S = std::move(S); p->PAIRS = std::move(PAIRS); p->slots = std::move(slots); p->frout = std::move(frout); p->frstd = std::move(frstd);
+  p->pin_tr = std::move(tr); p->pin_pairs = std::move(pairs); p->pin_slots = std::move(hslots); p->pin_fr = std::move(hfr);
+  p->h_tr = p->pin_tr.as<uint8_t>(); p->h_pairs = p->pin_pairs.as<Fr>(); p->h_slots = p->pin_slots.as<MsmSlot>(); p->h_fr = p->pin_fr.as<uint8_t>();
+  p->syj = std::move(syj);
+  p->ev_syj = std::move(ev);
+  p->have_signature_state = true;
   return SONIC_OK;
 }
 
@@ -468,8 +503,10 @@ struct GroupQueue {
       : p(p_), srs(p_->srs), L{p_->Q}, flags(p_->flags.as<int>()), slots(p_->slots.as<MsmSlot>()), frout(p_->frout.as<Fr>()),
         sh(p_->share_world > 1 ? p_->share.row(p_->share_rank) : nullptr) {
     p->next_lane = 0;
-    p->slot_ran.assign((size_t)L.slots_total(), 0);
-    p->fr_valid.assign((size_t)L.F(), 0);
+    // (a core proof's enqueue marks slots 0 .. 4 and evaluations 0 .. 2 only, and its finish reads neither vector: nothing Q long)
+    const ProofLayout V{p->core ? 0 : p->Q};
+    p->slot_ran.assign((size_t)V.slots_total(), 0);
+    p->fr_valid.assign((size_t)V.F(), 0);
   }
   bool on(int ph) const { return ((p->phases >> ph) & 1u) != 0; }
   bool own(long slot) const { return !sh || sh[slot].hi > sh[slot].lo; }
@@ -711,7 +748,7 @@ static void enqueue_polynomials(sonic_prover_t* p, GroupQueue& q, ProofPass& w) 
     ntt_forward_enqueue(ts, *p->ntt, fa, p->log2m);
     ntt_forward_enqueue(ts, *p->ntt, fb, p->log2m);
     ntt_inverse_of_product_enqueue(ts, *p->ntt, fa, fb, p->log2m);
-    sub_k_of_y_enqueue(ts, fa + (0 - w.t_lo), p->cs.as<Fr>(), p->kpow.as<Fr>(), Q, flags, 0);
+    sub_k_of_y_enqueue(ts, fa + (0 - w.t_lo), p->cs.as<Fr>(), p->kpow.as<Fr>(), Q, flags, 0, p->k_plan, p->k_partial.as<Fr>());
     HIP_OK(hipEventRecord(p->ev_t, ts));
   }
   // hscProve: s(X, y_j), s(u, Y)                                                     Signature.hs:41,51
@@ -821,9 +858,11 @@ static void enqueue_proof(sonic_prover_t* p) {
     p->asg_staged = false;
   } else HIP_OK(hipMemsetAsync(flags, 0, 8, st));
   Fr* S = p->S.as<Fr>();
-  HIP_OK(hipMemcpyAsync(S, p->h_tr, 32 * L.transcript_len(), hipMemcpyHostToDevice, st));
-  fr_to_mont_enqueue(st, S, L.transcript_len(), flags);
-  HIP_OK(hipMemcpyAsync(p->PAIRS.p, p->h_pairs, sizeof(Fr) * 2 * L.n_pairs(), hipMemcpyHostToDevice, st));
+  // (a core proof: its six transcript elements and the five-pair prefix, whatever Q is)
+  const long TL = p->core ? L.core_transcript_len : L.transcript_len(), NP = p->core ? L.core_n_pairs : L.n_pairs();
+  HIP_OK(hipMemcpyAsync(S, p->h_tr, 32 * TL, hipMemcpyHostToDevice, st));
+  fr_to_mont_enqueue(st, S, TL, flags);
+  HIP_OK(hipMemcpyAsync(p->PAIRS.p, p->h_pairs, sizeof(Fr) * 2 * NP, hipMemcpyHostToDevice, st));
   GroupQueue q(p);
   ProofPass w(p, q);
   enqueue_polynomials(p, q, w);
@@ -873,6 +912,13 @@ static void decide_modes(sonic_prover_t* p) {
     p->fused_jobs.clear();
     p->fused_sc_next = 0;
   }
+  // k(y) in one block or over many (poly.hip, k_of_y_choose).  The partial sums are the handle's; under the default plan they exist since
+  // the handle was made, so this grows them only when the knobs ask for more blocks -- here, before anything is queued or captured
+  // (a handle that replays a captured proof keeps the plan and the buffer the capture holds)
+  if (!p->graph) {
+    p->k_plan = k_of_y_choose(p->Q);
+    if (p->k_plan.blocks > 0) p->k_partial.ensure(sizeof(Fr) * (size_t)p->k_plan.blocks);
+  }
 }
 
 // a shared proof's plan, computed when the share or the prepared state changed since the last one
@@ -897,12 +943,19 @@ static void share_replan_if_needed(sonic_prover_t* p) {
 // {v, v^-1} for v = y, z, yz, u, v, y_1..y_Q, z_1..z_Q (Montgomery form), on the host with one shared inversion: the same
 // values cost a proof 0.35 ms of single-thread Fermat inversions on the device before its first polynomial could be built.
 // A non-canonical element is flagged by the device's conversion of the transcript; its pair here is then irrelevant.
+// A core proof's transcript ends with z: its pairs are y, z and yz, and the five-pair prefix it uploads is completed with {1, 1} for u and
+// v, which are never drawn (the values the padded transcript of earlier versions gave them; nothing reads them).
 static void challenge_pairs_host(sonic_prover_t* p, const uint8_t* transcript) {
-  const ProofLayout L{p->Q};
+  const ProofLayout L{p->core ? 0 : p->Q};
   const long np = L.n_pairs();
-  std::vector<Fr> v((size_t)np), pre((size_t)np);
+  Fr small[2 * ProofLayout::core_n_pairs];
+  std::vector<Fr> big(p->core ? 0 : 2 * (size_t)np);
+  Fr* v = p->core ? small : big.data();
+  Fr* pre = v + np;
   auto tr = [&](long k) { Fr a; memcpy(a.l, transcript + 32 * k, 32); return fp_to_mont(a); };
-  v[L.pY] = tr(L.y); v[L.pZ] = tr(L.z); v[L.pYZ] = fp_mul(v[L.pY], v[L.pZ]); v[L.pU] = tr(L.u()); v[L.pV] = tr(L.v());
+  v[L.pY] = tr(L.y); v[L.pZ] = tr(L.z); v[L.pYZ] = fp_mul(v[L.pY], v[L.pZ]);
+  if (p->core) v[L.pU] = v[L.pV] = Fr::one();
+  else { v[L.pU] = tr(L.u()); v[L.pV] = tr(L.v()); }
   for (long j = 0; j < L.Q; j++) { v[L.pYj(j)] = tr(L.y_j(j)); v[L.pZj(j)] = tr(L.z_j(j)); }
   Fr acc = Fr::one();
   for (long i = 0; i < np; i++) { pre[i] = acc; acc = fp_mul(acc, v[i].is_zero() ? Fr::one() : v[i]); }
@@ -926,18 +979,20 @@ static int prove_enqueue(sonic_prover_t* p, const uint8_t* transcript) {
   const ProofLayout L{p->Q};
   hipStream_t st = p->st;
   // evaluation points feed `pow x e` with negative e (Utils.hs:18, poly's eval): x = 0 has no inverse
-  for (long k = L.n_blinders; k < L.transcript_len(); k++)
+  // (p->core: `transcript` is the six elements of a core proof -- 4 blinders, y, z -- and nothing below reads past them)
+  const long TL = p->core ? L.core_transcript_len : L.transcript_len();
+  for (long k = L.n_blinders; k < TL; k++)
     if (bytes_are_zero(transcript + 32 * k, 32)) { set_error("prove: transcript element %ld is zero: Laurent evaluation at 0 divides by zero", k); return SONIC_ERR_INEXACT_DIVISION; }
   if (p->share_world > 1 && p->phases != PH_ALL) { set_error("prove: a shared proof runs with a caller-supplied transcript only"); return SONIC_ERR_INVALID_ARG; }
   // (every enqueue of a proof that HAS a signature: its whole-proof enqueue, its share, each of its Fiat-Shamir passes -- those before
   // PH_HSCS too, which still visit the pairs' groups; a core proof's enqueues never)
   if (!p->core) {
-    const int rc_pairs = ensure_pair_state(p);
-    if (rc_pairs) return rc_pairs;
+    const int rc_sig = ensure_signature_state(p);
+    if (rc_sig) return rc_sig;
   }
   decide_modes(p);
   share_replan_if_needed(p);
-  memcpy(p->h_tr, transcript, 32 * L.transcript_len());
+  memcpy(p->h_tr, transcript, 32 * TL);
   challenge_pairs_host(p, transcript);
   // Launch-bound sizes replay the whole multi-stream enqueue as one hipGraph: captured on the second proof of a handle (the
   // first one grows the workspaces), every address in it is owned by the handle.
@@ -1250,16 +1305,12 @@ int sonic_prover_collect(sonic_prover_t* p, uint8_t* out_proof) {
 
 // ---- core proofs (include/sonic_hip.h, "Core proofs") -----------------------------------------------------------------------------
 // The same enqueue with the phase mask PH_CORE: build_r1, s(X, y), the NTT product, group 0, the t group and s(z, y); no MSM of the
-// signature is queued and none of its polynomials built.  The six transcript elements of the caller are completed with 1 for the
-// challenges that are never drawn (as prove_fs_walk does), so that the head's bytes are those of sonic_prover_prove for every transcript
-// that starts with these six.
+// signature is queued and none of its polynomials built.  The enqueue reads the six transcript elements of the caller and nothing
+// behind them (prove_enqueue, enqueue_proof): no host work that grows with Q, and the head's bytes are those of sonic_prover_prove for
+// every transcript that starts with these six.
 static int prove_core_run(sonic_prover_t* p, const uint8_t* transcript6, uint32_t phases, int (*finish)(sonic_prover_t*, uint8_t*), uint8_t* out) {
-  const ProofLayout L{p->Q};
-  std::vector<uint8_t> tr(32 * (size_t)L.transcript_len(), 0);
-  memcpy(tr.data(), transcript6, 32 * (size_t)L.core_transcript_len);
-  for (long k = L.core_transcript_len; k < L.transcript_len(); k++) tr[32 * (size_t)k] = 1;
   p->phases = phases; p->core = true;
-  const int rc = prove_run(p, tr.data(), finish, out);
+  const int rc = prove_run(p, transcript6, finish, out);
   p->phases = PH_ALL; p->core = false;
   return rc;
 }
@@ -1324,8 +1375,10 @@ int sonic_prover_set_share(sonic_prover_t* p, int rank, int world) {
   p->share_planned = false;
   // slots and evaluations of pieces this rank no longer runs must not survive from an earlier proof
   EnqueueLock enq(p);
-  HIP_OK(hipMemsetAsync(p->slots.p, 0, sizeof(MsmSlot) * ProofLayout{p->Q}.C_extra(), p->st));      // (all but C's side slot, which a share never fills)
-  HIP_OK(hipMemsetAsync(p->frout.p, 0, sizeof(Fr) * ProofLayout{p->Q}.F(), p->st));
+  // (a handle without the signature state holds a core proof's slots and evaluations only: ProofLayout{0}'s)
+  const ProofLayout HL{p->have_signature_state ? p->Q : 0};
+  HIP_OK(hipMemsetAsync(p->slots.p, 0, sizeof(MsmSlot) * HL.C_extra(), p->st));      // (all but C's side slot, which a share never fills)
+  HIP_OK(hipMemsetAsync(p->frout.p, 0, sizeof(Fr) * HL.F(), p->st));
   HIP_OK(hipStreamSynchronize(p->st));
   API_END
 }
@@ -1435,11 +1488,13 @@ static int prove_fs_walk(sonic_prover_t* p, const uint8_t circuit_digest[32], co
   int rc;
   const long n = p->n, Q = p->Q, d = p->srs->d;
   const ProofLayout L{Q};
-  std::vector<uint8_t> tr(32 * (size_t)L.transcript_len(), 0), pf(sonic_proof_size(Q));
+  // (a core proof: its six transcript elements and its 576 bytes, nothing Q long)
+  const long TL = core ? L.core_transcript_len : L.transcript_len();
+  std::vector<uint8_t> tr(32 * (size_t)TL, 0), pf(core ? L.core_proof_bytes() : sonic_proof_size(Q));
   uint8_t srs_id[32];
   if ((rc = sonic_fs_srs_id(p->srs, srs_id))) return rc;
   for (long k = 0; k < L.n_blinders; k++) fs_blinder(blinder_seed, circuit_digest, srs_id, witness_digest, (uint32_t)k, &tr[32 * k]);
-  for (long k = L.n_blinders; k < L.transcript_len(); k++) tr[32 * k] = 1;               // not drawn yet: any invertible value (results that use it are not read)
+  for (long k = L.n_blinders; k < TL; k++) tr[32 * k] = 1;               // not drawn yet: any invertible value (results that use it are not read)
   FsTranscript t;
   if (core) t.init(n, Q, d, circuit_digest, srs_id, FS_CORE_LABEL);
   else t.init(n, Q, d, circuit_digest, srs_id);
@@ -1450,7 +1505,7 @@ static int prove_fs_walk(sonic_prover_t* p, const uint8_t circuit_digest[32], co
     p->phases = PH_ALL;
     return r;
   };
-  const uint8_t* R = pf.data(), * T = R + 96, * open = R + 192, * hscS = R + 576, * hscW = hscS + Q * 224, * Cc = hscW + Q * 224 + 96;
+  const uint8_t* R = pf.data(), * T = R + 96, * open = R + 192;
   if ((rc = pass(PH_R))) return rc;
   t.absorb("R", R, 96);
   t.challenge("y", 0, &tr[32 * L.y]);
@@ -1463,6 +1518,7 @@ static int prove_fs_walk(sonic_prover_t* p, const uint8_t circuit_digest[32], co
     if (out_transcript) memcpy(out_transcript, &tr[32 * L.y], 64);
     return SONIC_OK;
   }
+  const uint8_t* hscS = R + 576, * hscW = hscS + Q * 224, * Cc = hscW + Q * 224 + 96;
   t.absorb("open", open, 384);
   for (long j = 0; j < Q; j++) { t.challenge("yj", (uint32_t)j, &tr[32 * L.y_j(j)]); t.challenge("zj", (uint32_t)j, &tr[32 * L.z_j(j)]); }
   if ((rc = pass(PH_HSCS))) return rc;
@@ -1773,7 +1829,7 @@ int sonic_prover_prepare(sonic_prover_t* p) {
   p->diag.resize(Q); p->yq.resize(Q);
   for (auto& b : p->diag) b.alloc(sizeof(Fr) * n);
   for (auto& b : p->yq) b.alloc(sizeof(Fr) * Q);
-  p->slots.ensure(sizeof(MsmSlot) * ProofLayout{Q}.slots_total());
+  // (the rows' MSMs ran in slots of this call's own; the side slots of the S_j that a prepared proof fills belong to the signature state)
   p->prepared = true;
   API_END
 }
@@ -1799,7 +1855,7 @@ int sonic_prover_device_bytes(sonic_prover_t* p, int64_t* out) {
   auto add_sc = [&](const Scratch& s) { for (const DevBuf* b : {&s.D, &s.q, &s.scan, &s.fz_discard}) add(*b); };
   auto add_lane = [&](const Lane& l) { add_ws(l.ws); for (const Scratch& s : l.sc) add_sc(s); };
   for (const DevBuf* b : {&p->wL, &p->wR, &p->wO, &p->cs, &p->aL, &p->aR, &p->aO, &p->S, &p->PAIRS, &p->r1, &p->sy0, &p->su, &p->pw, &p->kpow, &p->fa, &p->fb, &p->slots,
-                          &p->frout, &p->flags, &p->tmp, &p->wit_raw, &p->frstd, &p->cq, &p->cq_tab, &p->wtree, &p->wdtree}) add(*b);
+                          &p->frout, &p->flags, &p->tmp, &p->wit_raw, &p->frstd, &p->cq, &p->cq_tab, &p->wtree, &p->wdtree, &p->k_partial}) add(*b);
   const sonic_prover::CsrBufs& sp = p->sp;
   for (const DevBuf* b : {&sp.row_ptr, &sp.col, &sp.val, &sp.col_ptr, &sp.row, &sp.cval, &sp.chunk_row, &sp.chunk_begin, &sp.row_chunk, &sp.partial}) add(*b);
   for (const DevBuf* b : {&p->stm.stage, &p->stm.partial, &p->stm.out, &p->stm.gates}) add(*b);
@@ -1809,6 +1865,19 @@ int sonic_prover_device_bytes(sonic_prover_t* p, int64_t* out) {
   for (const auto& r : p->runs) for (const DevBuf* b : {&r.masked, &r.val, &r.uniform, &r.scal, &r.pts}) add(*b);
   for (const auto& s : p->fused_sc) add_sc(*s);
   for (const std::vector<DevBuf>* v : {&p->syj, &p->diag, &p->yq}) for (const DevBuf& b : *v) add(b);
+  *out = (int64_t)total;
+  API_END
+}
+
+// The pinned host memory the handle owns at this moment, as the sizes it was allocated with: the staging of the transcript, the pairs,
+// the MSM slots and the evaluations (a core proof's prefixes until the signature state exists), the flags and the digest root.  Not
+// counted: pageable memory (the host vectors of the handle) and the temporaries of a call.
+int sonic_prover_host_bytes(sonic_prover_t* p, int64_t* out) {
+  API_BEGIN_ON(p ? p->device : -1)
+  if (!p || !out) { set_error("sonic_prover_host_bytes: bad argument"); return SONIC_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> g(p->mu);
+  size_t total = 0;
+  for (const PinnedBuf* b : {&p->pin_tr, &p->pin_pairs, &p->pin_slots, &p->pin_fr, &p->pin_flags, &p->pin_root}) total += b->bytes;
   *out = (int64_t)total;
   API_END
 }

@@ -19,6 +19,8 @@
 #include "share_plan.hpp"
 #include "csr.hpp"
 #include "witness_src.hpp"
+#include "k_of_y_plan.hpp"
+#include "proof_layout.hpp"
 
 
 namespace sonic {
@@ -60,6 +62,18 @@ bool bytes_are_zero(const uint8_t* p, size_t n);
 }  // namespace sonic
 
 using namespace sonic;
+
+// pinned host memory of a handle, counted by sonic_prover_host_bytes as the size it was allocated with (DevBuf's twin)
+struct PinnedBuf {
+  void* p = nullptr; size_t bytes = 0;
+  PinnedBuf() {}
+  PinnedBuf(const PinnedBuf&) = delete; PinnedBuf& operator=(const PinnedBuf&) = delete;
+  PinnedBuf& operator=(PinnedBuf&& o) noexcept { if (this != &o) { release(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; } return *this; }
+  ~PinnedBuf() { release(); }
+  void alloc(size_t n) { release(); HIP_OK(hipHostMalloc(&p, n, hipHostMallocDefault)); bytes = n; }
+  void release() { if (p) { (void)hipHostFree(p); p = nullptr; bytes = 0; } }
+  template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+};
 
 // One MSM "lane": its own stream, bucket workspace and opening scratch.  The MSMs of a proof that depend on the same
 // polynomial form a group (R, W_a, W_b | T, W_t | S_j, W_j, W'_j | C, Q_j.., Q_v) that runs on one lane as ONE batched
@@ -143,7 +157,9 @@ struct sonic_prover {
   DevBuf S, PAIRS, r1, sy0, su, pw, kpow, fa, fb, slots, frout, flags, tmp;
   std::vector<DevBuf> syj;
   // sonic_prover_prepare: Commit(P_q) per constraint row (affine, Montgomery) and per-j scalar buffers
-  // pinned host staging (fixed addresses: the whole enqueue of a proof can be captured once and replayed as a hipGraph)
+  // pinned host staging (fixed addresses: the whole enqueue of a proof can be captured once and replayed as a hipGraph).  The pointers
+  // below are views of these buffers, set where they are allocated (prove.hip: prover_new_impl, ensure_signature_state)
+  PinnedBuf pin_tr, pin_pairs, pin_slots, pin_fr, pin_flags, pin_root;
   uint8_t* h_tr = nullptr;
   Fr* h_pairs = nullptr;         // {v, v^-1} of the evaluation points, computed on the host (prove_enqueue)
   MsmSlot* h_slots = nullptr;
@@ -262,10 +278,17 @@ struct sonic_prover {
   uint8_t weights_digest_v2[32] = {0};
   bool have_weights_digest_v2 = false;
   DevBuf wdtree;
-  // The per-pair state of the signature: s(X, y_j) for each of the Q pairs (syj: Q buffers of 3n + 1 elements, Q n-proportional) and the
-  // events that order their groups (ev_syj).  Made by ensure_pair_state (prove.hip) on the first enqueue whose phases include the
-  // signature; a handle that only ever makes core proofs, aggregates, digests or constraint evaluations never has it.
-  bool have_pair_state = false;
+  // The signature state: everything a proof WITH a signature needs and a core proof does not.  A handle is made with S, PAIRS, slots,
+  // frout, frstd and their pinned twins (h_tr, h_pairs, h_slots, h_fr) sized for a core proof -- the counts of ProofLayout{0}: 8 transcript
+  // elements, 5 pairs, 8 slots, 3 evaluations -- and without the per-pair buffers: s(X, y_j) for each of the Q pairs (syj: Q buffers of
+  // 3n + 1 elements) and the events that order their groups (ev_syj).  ensure_signature_state (prove.hip) re-creates the former at the
+  // sizes of ProofLayout{Q} (5Q + 8 slots of sizeof(MsmSlot) bytes on the device and pinned, 8 + 2Q, 5 + 2Q, 3 + 2Q elements) and makes
+  // the latter, on the first enqueue whose proof has a signature; a handle that only ever makes core proofs, aggregates, digests or
+  // constraint evaluations never has it.  slot_ran and fr_valid are as long as the enqueue's own layout.
+  bool have_signature_state = false;
+  // k(y) over many blocks (poly.hip, k_of_y_plan.hpp): the plan of the enqueue in progress (decide_modes) and the blocks' partial sums
+  KOfYPlan k_plan;
+  DevBuf k_partial;
   // Lane N_LANES-1 carries the t(X,y) group (the largest, ready last); the other groups alternate over the rest, which
   // balances the point additions per lane (Q = 2: 55M / 51M / 48M) while one lane's sort and reduction phases run under
   // another lane's accumulation.  Streams beyond the 4 hardware queues would serialise behind each other.
@@ -305,7 +328,6 @@ struct sonic_prover {
     if (st && !pooled) (void)hipStreamDestroy(st);
     if (ts && !pooled) (void)hipStreamDestroy(ts);
     if (graph) (void)hipGraphExecDestroy(graph);
-    for (void* h : {(void*)h_tr, (void*)h_pairs, (void*)h_slots, (void*)h_fr, (void*)h_flags, (void*)h_root}) if (h) (void)hipHostFree(h);
   }
 };
 

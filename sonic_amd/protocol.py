@@ -459,9 +459,18 @@ class Prover:
     @property
     def device_bytes(self) -> int:
         """the device memory the handle owns now (sonic_prover_device_bytes): every buffer of its own, lane workspaces included, not the
-        SRS it borrows.  The Q buffers of the signature's pairs appear with the first full proof; core proofs never make them."""
+        SRS it borrows.  The signature's state -- the MSM slots 5 and above and the Q buffers of the pairs -- appears with the first full
+        proof; core proofs never make it."""
         out = C.c_int64(0)
         _lib.check(_lib.lib().sonic_prover_device_bytes(self._h, C.byref(out)))
+        return int(out.value)
+
+    @property
+    def host_bytes(self) -> int:
+        """the pinned host memory the handle owns now (sonic_prover_host_bytes): the staging of a core proof until the first full proof,
+        whose 5 Q + 8 MSM slots then have their pinned twins here"""
+        out = C.c_int64(0)
+        _lib.check(_lib.lib().sonic_prover_host_bytes(self._h, C.byref(out)))
         return int(out.value)
 
     def submit_fs(self, circuit_digest: bytes, blinder_seed: bytes) -> None:
